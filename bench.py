@@ -15,6 +15,10 @@ A "step" is one pass of the hot path over one resident batch:
            its shard, one RCCL all-gather of the hash shards, then each rank sweeps its share of the tile pairs;
            (-> `hamming_10m`): BASELINE config 5, strong scaling: 10 000 000 hashes split over the ranks, same steps.
 Inputs are generated on the device and resident in HBM before the timed regions.
+A plain run measures phase A alone (set-up, --warmup steps, --steps timed steps, the result line); --full adds everything else:
+phases C and B, the JPEG leg, the pure read stream of the roofline, the CPU baseline and the reference's own published cases.
+--dump-outputs DIR writes the hashes of phase A's last timed step as DIR/pdq_hash.npy (float32, one row of 32 bytes per image;
+DIR/pdq_hash_rank<R>.npy per rank when N > 1), so that two builds can be compared output for output on the same seeded images.
 One JSON line on rank 0.  Launch: python bench.py [--gpus N --steps K --warmup W].  For N > 1 either start it under
 torch.distributed.run (one process per GPU), or just run `python bench.py --gpus N`: with WORLD_SIZE unset it starts
 `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child BEFORE anything touches the GPU and exits
@@ -38,6 +42,8 @@ HBM_PEAK_GBS = 8000.0                          # MI355X_MICROARCH.md: 8.0 TB/s s
 VALU_LANE_OPS_PER_S = 256 * 4 * 32 * 2.4e9     # 256 CU x 4 SIMD x 32 lanes x 2.4 GHz = 78.6e12 (full-rate VOP2 ops only)
 MFMA_I8_OPS_PER_S = 256 * 4 * (32 * 32 * 32 * 2) / 32 * 2.4e9  # v_mfma_i32_32x32x32_i8: 65 536 ops / 32 clk / SIMD = 5.03e15
 HAMMING_HBM_BYTES_PER_PAIR = 64.0 / 1024       # 2 T 32 B / T^2 with T = 1024-hash tiles
+DUMP_BYTES = 64 << 20                          # --dump-outputs: at most this much over all ranks
+ALL_PHASES = {"pdq", "e2e", "hamming", "hamming_10m", "jpeg"}
 
 
 def cpu_inventory():
@@ -94,7 +100,19 @@ def parse_args():
     ap.add_argument("--jpeg-files", type=int, default=100_000, help="files per call of the JPEG leg (SURVEY 8f row N3; rank 0 at N = 1 only)")
     ap.add_argument("--jpeg-distinct", type=int, default=4096, help="distinct files of the JPEG leg (the first images of the synthetic sequence, repeated to --jpeg-files)")
     ap.add_argument("--no-jpeg", action="store_true", help="skip the JPEG leg")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="run every leg and check, not only the timed PDQ steps of the headline figure")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write the PDQ hashes of the last timed step under DIR as float32 .npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    only = set(p for p in args.only.split(",") if p)
+    if only - ALL_PHASES:
+        ap.error(f"--only: unknown phase(s) {sorted(only - ALL_PHASES)}")
+    if not args.full and only - {"pdq"}:
+        ap.error(f"--only {args.only} needs --full (a plain run times the PDQ phase alone)")
+    if args.dump_outputs and only and "pdq" not in only:
+        ap.error("--dump-outputs writes the PDQ phase's hashes: --only must include pdq")
+    return args
 
 
 def main():
@@ -111,7 +129,7 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run --nproc-per-node {args.gpus}")
-    phases = set(p for p in args.only.split(",") if p) or {"pdq", "e2e", "hamming", "hamming_10m", "jpeg"}
+    phases = set(p for p in args.only.split(",") if p) or (set(ALL_PHASES) if args.full else {"pdq"})
     if args.hashes_strong <= 0:
         phases.discard("hamming_10m")
     if args.no_e2e:
@@ -122,7 +140,7 @@ def main():
     # The CPU oracle (the checker and the cpu_baseline leg) is loaded BEFORE the GPU is initialised and is never built from
     # here: a `make` child of a process that holds the GPU (or runs under a profiler's preload) would be a forbidden exec.
     oracle = None
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_cpu = rank == 0 and world == 1 and args.full and not args.no_cpu_baseline
     if want_cpu:
         os.environ["RPH_ORACLE_NO_BUILD"] = "1"
         sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -226,9 +244,11 @@ def main():
         avg_kernel_ms = sum(kernel_ms) / len(kernel_ms)
         value = world * n_img * args.steps / elapsed
         achieved_gbs = ALGO_BYTES_PER_IMAGE * n_img / (avg_kernel_ms * 1e-3) / 1e9
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, hashes, rank, world, np)
         # what a pure read stream over the same resident images gets on this GPU (untimed part of the job; rank 0's figure is reported)
         read_gbs = None
-        if rank == 0:
+        if rank == 0 and args.full:
             eng.read_stream_dev(imgs.data_ptr(), n_img * IMG_BYTES, stream=stream)
             ra, rb = eng.event(), eng.event()
             eng.event_record(ra, stream)
@@ -240,7 +260,8 @@ def main():
             eng.event_destroy(ra)
             eng.event_destroy(rb)
         hash_checksum = int(hashes.to(torch.int64).sum().item())
-        pdq_sample = hashes[:min(n_img, 30_000)].cpu().numpy()  # every image the CPU baseline hashes is compared
+        if want_cpu:
+            pdq_sample = hashes[:min(n_img, 30_000)].cpu().numpy()  # every image the CPU baseline hashes is compared
 
         # L2 -> fabric read bytes per launch: rocprofv3 cannot run inside this process, so the figure is the PMC measurement of this
         # same kernel committed under profiles/ (FETCH_SIZE, corrected as MI355X_MICROARCH.md prescribes and calibrated on the read
@@ -495,7 +516,7 @@ def main():
             result["jpeg"] = {"skipped": str(e)}
 
     # ------------------------------------------------------------------ the reference's own published cases (rank 0, N = 1)
-    if rank == 0 and world == 1 and not args.no_reference_cases:
+    if rank == 0 and world == 1 and args.full and not args.no_reference_cases:
         result["reference_cases"] = reference_cases(eng, np)
 
     result["valid"] = valid
@@ -510,6 +531,20 @@ def main():
     eng.close()
     if not valid:
         sys.exit(1)
+
+
+def dump_outputs(out_dir, hashes, rank, world, np):
+    """The hashes a caller of the timed path receives, as float32 (the byte values, exact).  Beyond this rank's share of DUMP_BYTES
+    the rows are a fixed seeded sample, and their row numbers go beside them as pdq_hash_rows*.npy (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    h = hashes.cpu().numpy()
+    suffix = "" if world == 1 else f"_rank{rank}"
+    max_rows = DUMP_BYTES // world // (h.shape[1] * 4 + 8)
+    if len(h) > max_rows:
+        rows = np.sort(np.random.default_rng(0).choice(len(h), max_rows, replace=False))
+        np.save(os.path.join(out_dir, f"pdq_hash_rows{suffix}.npy"), rows.astype(np.float64))
+        h = h[rows]
+    np.save(os.path.join(out_dir, f"pdq_hash{suffix}.npy"), h.astype(np.float32))
 
 
 def jpeg_leg(eng, np, args, oracle):

@@ -26,7 +26,7 @@ pdq, ham, rs = pick("pdq_fused512"), pick("hamming_mfma"), pick("read_stream")
 N_IMG, IMG, PASSES = 30000, 786432, 7
 per = lambda k, c: k[c] / (k["_dispatches"] / PASSES)  # per launch: every pass runs the same launches, each counter lives in one pass
 out = [f"rocprofv3 --pmc passes ({tag}; tools/run_pmc.sh: one counter group per run, --kernel-trace only), command per pass:",
-       "  python3 bench.py --steps 2 --warmup 1 --images 30000 --hashes 1000000 --no-e2e --no-jpeg --hashes-strong 0 --no-cpu-baseline --no-reference-cases",
+       "  python3 bench.py --full --steps 2 --warmup 1 --images 30000 --hashes 1000000 --no-e2e --no-jpeg --hashes-strong 0 --no-cpu-baseline --no-reference-cases",
        f"Raw per-kernel sums: {tag}_pmc_raw.txt.  Per pass: 3 launches of the PDQ kernel (30000 images = 23.59 GB algorithmic read each), 3 sweeps of",
        "1 000 448 hashes at threshold 32, 4 launches of the read-stream kernel over the same 23.59 GB.  SQ_* cycle counters are in units of 4 clocks.", ""]
 # calibration of FETCH_SIZE on a known byte count

@@ -17,7 +17,7 @@ OUT=$R/gpurun_out/prof_$TAG
 rm -rf $OUT && mkdir -p $OUT
 run() {  # name, bench args...
   local name=$1; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$name -o run -- python3 $R/bench.py --no-cpu-baseline --no-reference-cases "$@" > $OUT/$name.json 2> $OUT/$name.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$name -o run -- python3 $R/bench.py --full --no-cpu-baseline --no-reference-cases "$@" > $OUT/$name.json 2> $OUT/$name.err
   python3 $R/tools/show_bench.py $OUT/$name.json
   grep -E "pdq_fused512|hamming_mfma|read_stream|jpeg_" $OUT/$name/run_kernel_stats.csv | cut -c1-200
 }
