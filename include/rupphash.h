@@ -396,6 +396,45 @@ int rph_jpeg_set_segments(rph_ctx *ctx, uint32_t min_stream_bytes, uint32_t segm
  * memory for the coefficients of the files in flight); this returns them.  The next call allocates again. */
 int rph_jpeg_release(rph_ctx *ctx);
 
+/* rph_jpeg_pdq_hash_batch + the pixel hash (rph_pixel_hash_batch, below) of every decoded file: pixel_hash32_out receives n x 32
+ * bytes.  The reference hashes the pixels before generate_pdq_features (scanner.rs:1393-1410), so an image below 5 px has its pixel
+ * hash (valid_out 0, status RPH_OK); a file that cannot be decoded gets status != RPH_OK and 32 zero bytes.  Colour files are
+ * reconstructed as Rgb8 (as rph_jpeg_decode does) instead of the luma-only fused kernel, and PDQ then hashes those pixels: the
+ * other outputs are byte-identical to rph_jpeg_pdq_hash_batch's, in every entropy mode. */
+int rph_jpeg_pdq_pixel_hash_batch(rph_ctx *ctx, const uint8_t *const *data, const size_t *len, uint32_t n, int flavour, uint32_t n_threads,
+                                  uint8_t *hash32_out, float *quality_out, float *coeffs_out, uint8_t *dihedral_out, uint8_t *valid_out,
+                                  int32_t *status_out, uint8_t *pixel_hash32_out);
+
+/* =====================================================================
+ * BLAKE3 identity hashes (blake3 crate 1.x, 32-byte output): the two exact hashes the reference computes next to the PDQ hash.
+ *   content hash  blake3::keyed_hash(content_key, file_bytes)                     scanner.rs:1343-1347 (the cache key)
+ *                 -> rph_blake3_host per file in the scan loop, or rph_blake3_batch(_dev) for a batch of files
+ *   pixel hash    blake3::hash of the decoded image's to_rgba16() as little-endian bytes (phdupes --pixel-hash, phdupes.rs:214,
+ *                 :850; scanner.rs:1393-1404) -> rph_pixel_hash_batch(_dev) on decoded pixels, or rph_jpeg_pdq_pixel_hash_batch
+ *                 for JPEG files (decode + PDQ + pixel hash in one call; the pixels never leave the device)
+ * analyze_group then puts bit-identical and pixel-identical files first (scanner.rs:1843-1864; rupphash_amd.scanner.identical_duplicates).
+ * Device layout: one lane per 1 KiB chunk, 64 chunks per wave folded across lanes into a 64 KiB subtree, a second kernel folds the
+ * subtrees per input.  From host memory rph_blake3_batch is bounded by PCIe and does not beat the host crate: it is the
+ * kernels' direct interface; the _dev form hashes bytes already on the device.
+ * ===================================================================== */
+/* BLAKE3 (hash, or keyed_hash when key32 != NULL: 32 key bytes) of n byte strings of any lengths (0 included) -> n x 32 bytes. */
+int rph_blake3_batch(rph_ctx *ctx, const uint8_t *const *data, const size_t *len, uint32_t n, const uint8_t *key32, uint8_t *digest32_out);
+/* The same on device memory: string i is d_data[d_offsets[i] .. d_offsets[i+1]) (n + 1 non-decreasing uint64 offsets, device memory).
+ * Reads back d_offsets[0] and d_offsets[n] to size its scratch (one synchronisation of `stream`), then runs asynchronously. */
+int rph_blake3_batch_dev(rph_ctx *ctx, const void *d_data, const void *d_offsets, uint32_t n, const uint8_t *key32, void *d_digest32,
+                         void *stream);
+/* One string on the host, no GPU call, no context (the same compression function as the kernels). */
+void rph_blake3_host(const uint8_t *data, size_t len, const uint8_t *key32, uint8_t *digest32_out);
+/* Pixel hash of scanner.rs:1393-1404: blake3::hash of to_rgba16() of n 8-bit images (channels 1 = Luma8, 3 = Rgb8, 4 = Rgba8;
+ * row_stride / image_stride as rph_pdq_hash_batch), little-endian.  Each u8 sample v becomes the u16 v * 257 (255 -> 65535), Luma8
+ * is copied into R, G and B, alpha is 65535 unless the input is Rgba8.  PARITY: that widening is the `image` crate's u8 -> u16
+ * conversion as published; the crate's source is not in the reference tree, so agreement with the Rust binary rests on it.
+ * The RGBA16 stream is built in registers, never in memory. */
+int rph_pixel_hash_batch(rph_ctx *ctx, const uint8_t *px, uint32_t n, uint32_t w, uint32_t h, uint32_t channels, size_t row_stride,
+                         size_t image_stride, uint8_t *hash32_out);
+int rph_pixel_hash_batch_dev(rph_ctx *ctx, const void *d_px, uint32_t n, uint32_t w, uint32_t h, uint32_t channels, size_t row_stride,
+                             size_t image_stride, void *d_hash32, void *stream);
+
 /* =====================================================================
  * 64-bit pHash bit operations (reference: src/phash.rs:137-255), host scalar
  * ===================================================================== */

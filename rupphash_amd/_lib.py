@@ -114,6 +114,13 @@ SIGNATURES = {
     "rph_jpeg_release": (C.c_int, [_vp]),
     "rph_jpeg_pdq_hash_batch": (C.c_int, [_vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_uint32, C.c_int, C.c_uint32, _u8p, _f32p, _f32p,
                                           _u8p, _u8p, _i32p]),
+    "rph_jpeg_pdq_pixel_hash_batch": (C.c_int, [_vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_uint32, C.c_int, C.c_uint32, _u8p, _f32p,
+                                                _f32p, _u8p, _u8p, _i32p, _u8p]),
+    "rph_blake3_batch": (C.c_int, [_vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_uint32, _u8p, _u8p]),
+    "rph_blake3_batch_dev": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _u8p, _vp, _vp]),
+    "rph_blake3_host": (None, [_u8p, _sz, _u8p, _u8p]),
+    "rph_pixel_hash_batch": (C.c_int, [_vp, _u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _sz, _sz, _u8p]),
+    "rph_pixel_hash_batch_dev": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _sz, _sz, _vp, _vp]),
     "rph_phash_rotate_90": (C.c_uint64, [C.c_uint64]),
     "rph_phash_rotate_180": (C.c_uint64, [C.c_uint64]),
     "rph_phash_rotate_270": (C.c_uint64, [C.c_uint64]),

@@ -52,7 +52,7 @@ struct Twin {
 
 constexpr size_t RES_BYTES = 32 + 4 + 1024 + 256 + 4;  // per image: hash, quality, coefficients, dihedral, valid + entropy status (padded)
 struct ResView {  // the per-image result arrays inside one buffer laid out for `images` images
-    uint8_t *hash, *quality, *coeffs, *dihedral, *valid, *status;
+    uint8_t *hash, *quality, *coeffs, *dihedral, *valid, *status, *pixel;
     ResView(uint8_t *p, size_t images)
     {
         hash = p;
@@ -61,6 +61,7 @@ struct ResView {  // the per-image result arrays inside one buffer laid out for 
         dihedral = coeffs + images * 1024;
         valid = dihedral + images * 256;
         status = valid + images;
+        pixel = p + images * RES_BYTES;  // pixel hashes (32 B per image) behind the rest, in slots reserved with room for them
     }
 };
 
@@ -78,6 +79,7 @@ struct Slot {
     Twin meta;              // descriptors (planes | images | tables | HImage | order | DeviceLut)
     Twin res;               // results
     size_t res_images = 0;
+    bool res_pixel = false;  // the results buffer has room for the pixel hashes (ResView::pixel)
     uint8_t *d_segwork = nullptr;  // device entropy, segmented streams: states | records of round 0 | out positions | segment -> file map
     size_t segwork_cap = 0;
     unsigned long long *d_pmask = nullptr;  // device entropy, progressive files: which coefficients are nonzero, one word per block
@@ -108,17 +110,18 @@ struct Slot {
         if (!done) RPH_HIP_CHECK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
         return RPH_OK;
     }
-    int reserve_res(size_t images)  // the caller has made sure nothing in flight still uses the slot's buffers
+    int reserve_res(size_t images, bool pixel)  // the caller has made sure nothing in flight still uses the slot's buffers
     {
-        if (res_images >= images) return RPH_OK;
+        if (res_images >= images && (res_pixel || !pixel)) return RPH_OK;
         RPH_HIP_CHECK(hipStreamSynchronize(stream));
         images += images / 4;
         // pinned host memory the kernels write into directly (32 B .. 1.3 KB per image cross PCIe as they are produced): a copy back at the
         // end of a chunk queued behind the other lanes' kernels and held the lane up for tens of milliseconds
         if (res.d == res.h) res.d = nullptr;
-        RPH_TRY(res.reserve(images * RES_BYTES, true, false));
+        RPH_TRY(res.reserve(images * (RES_BYTES + (pixel ? 32 : 0)), true, false));
         res.d = res.h;
         res_images = images;
+        res_pixel = pixel;
         return RPH_OK;
     }
 };
@@ -129,6 +132,9 @@ struct JpegPipe {
     // time per stream; each slot owns one pair
     uint8_t *d_planes[JPEG_LANES] = {}, *d_out[JPEG_LANES] = {};
     size_t recon_coef_bytes[JPEG_LANES] = {};
+    // pixel hashes: the group values of the images above 8192 px (allocated by the first call that asks for pixel hashes)
+    void *d_b3[JPEG_LANES] = {};
+    size_t b3_bytes[JPEG_LANES] = {};
     // device entropy: the chunk's coefficient buffer (one: chunks run back to back on one stream)
     int16_t *d_coef = nullptr;
     size_t d_coef_bytes = 0;
@@ -144,8 +150,10 @@ struct JpegPipe {
             slot[b].release();
             if (d_planes[b]) (void)hipFree(d_planes[b]);
             if (d_out[b]) (void)hipFree(d_out[b]);
+            if (d_b3[b]) (void)hipFree(d_b3[b]);
             d_planes[b] = d_out[b] = nullptr;
-            recon_coef_bytes[b] = 0;
+            d_b3[b] = nullptr;
+            recon_coef_bytes[b] = b3_bytes[b] = 0;
         }
         if (d_coef) (void)hipFree(d_coef);
         d_coef = nullptr;
@@ -164,6 +172,18 @@ struct JpegPipe {
         // packed pixels never exceed the coefficient bytes (4:2:0: both 3 w h; Luma8: w h against 2 w h), plus row / image padding
         RPH_HIP_CHECK(hipMalloc((void **)&d_out[b], coef_need + coef_need / 8 + 65536));
         recon_coef_bytes[b] = coef_need;
+        return RPH_OK;
+    }
+    int reserve_b3(int b, size_t bytes, hipStream_t s)
+    {
+        if (b3_bytes[b] >= bytes) return RPH_OK;
+        RPH_HIP_CHECK(hipStreamSynchronize(s));
+        if (d_b3[b]) (void)hipFree(d_b3[b]);
+        d_b3[b] = nullptr;
+        b3_bytes[b] = 0;
+        bytes += bytes / 4;
+        RPH_HIP_CHECK(hipMalloc(&d_b3[b], bytes));
+        b3_bytes[b] = bytes;
         return RPH_OK;
     }
 };
@@ -309,7 +329,7 @@ using Jobs = std::vector<Job>;
 // bytes of the chunk's stream buffer a file may need (prepare_stream: 32 zero bytes behind every scan)
 inline size_t stream_cap(const Job &j) { return align_up(j.len + 160 + (j.frame.progressive ? 32 * (size_t)rphj::MAX_PROG_SCANS : 0), 16); }
 
-// Channels of the pixels the device writes for a file: Rgb8 only where the caller reads RGB (rph_jpeg_decode); a colour file that
+// Channels of the pixels the device writes for a file: Rgb8 only where the caller reads RGB (rph_jpeg_decode, pixel hashes); a colour file that
 // only the hasher reads is written as its Rec.601 luma (a third of the bytes, and the PDQ paths start from luma anyway: Luma8 input
 // is borrowed as it is, pdqhash.rs:176; 512x512 Luma8 has its own form of the fused kernel)
 inline uint32_t out_channels(const rphj::Frame &f, bool rgb_wanted) { return (f.ncomp == 1 || !rgb_wanted) ? 1u : 3u; }
@@ -391,7 +411,9 @@ struct Outputs {
     uint8_t *valid = nullptr;
     int32_t *status = nullptr;
     uint8_t *pixels = nullptr;  // single-image decode: packed w * h * channels
+    uint8_t *pixel_hash = nullptr;  // n x 32: BLAKE3 of to_rgba16() of every decoded image (rph_jpeg_pdq_pixel_hash_batch)
     bool want_hash = true;
+    bool rgb_wanted() const { return pixels || pixel_hash; }  // colour files reconstructed as Rgb8 (no luma-only fused kernel)
 };
 
 // Descriptors of the chunk idx[first..last) and where they live in the slot's meta buffer (host and device at the same offsets)
@@ -521,17 +543,33 @@ int reconstruct_and_hash(rph_ctx *ctx, JpegPipe &P, int b, Slot &S, Jobs &jobs, 
         RPH_TRY(rph_jpeg_launch_color(flavour, max_groups, i1 - i0, s, P.d_planes[b], di, P.d_out[b]));
     }
     if (n_fused) RPH_TRY(rph_jpeg_launch_fused(flavour, max_tiles, i1 - i0, s, d_coef, dq, dp, di, P.d_out[b], D.d_refs, D.d_corr, D.d_dcbits));
-    if (!out.want_hash) return RPH_OK;
-    // hash runs of equal geometry where the pixels lie (generate_pdq_features, scanner.rs:1410)
     ResView R(S.res.d, S.res_images);
     const JImage *hi = reinterpret_cast<const JImage *>(S.meta.h + D.off_images);
+    // pixel hashes (scanner.rs:1393-1404, before generate_pdq_features: images below 5 px have one too), runs of equal geometry
+    for (size_t r = r0; out.pixel_hash && r < r1;) {
+        if (D.image_of[r] == UINT32_MAX) {
+            r++;
+            continue;
+        }
+        const rphj::Frame &f = jobs[idx[first + r]].frame;
+        const uint32_t och = out_channels(f, true);
+        size_t e = r + 1;
+        while (e < r1 && D.image_of[e] != UINT32_MAX && jobs[idx[first + e]].frame.w == f.w && jobs[idx[first + e]].frame.h == f.h && jobs[idx[first + e]].frame.ncomp == f.ncomp) e++;
+        const size_t scratch = rph_pixel_hash_scratch_bytes((uint32_t)(e - r), f.w, f.h);
+        if (scratch) RPH_TRY(P.reserve_b3(b, scratch, s));  // (runs of one stream follow each other: one buffer serves them all)
+        RPH_TRY(rph_launch_pixel_hash(P.d_out[b] + hi[D.image_of[r]].out_off, (uint32_t)(e - r), f.w, f.h, och, (size_t)och * align_up(f.w, 8), out_bytes_of(f, och),
+                                      R.pixel + r * 32, s, P.d_b3[b]));
+        r = e;
+    }
+    if (!out.want_hash) return RPH_OK;
+    // hash runs of equal geometry where the pixels lie (generate_pdq_features, scanner.rs:1410)
     for (size_t r = r0; r < r1;) {
         if (D.image_of[r] == UINT32_MAX) {
             r++;
             continue;
         }
         const rphj::Frame &f = jobs[idx[first + r]].frame;
-        const uint32_t och = out_channels(f, out.pixels != nullptr);
+        const uint32_t och = out_channels(f, out.rgb_wanted());
         size_t e = r + 1;
         while (e < r1 && D.image_of[e] != UINT32_MAX && jobs[idx[first + e]].frame.w == f.w && jobs[idx[first + e]].frame.h == f.h && jobs[idx[first + e]].frame.ncomp == f.ncomp) e++;
         RPH_TRY(rph_pdq_hash_batch_dev(ctx, P.d_out[b] + hi[D.image_of[r]].out_off, (uint32_t)(e - r), f.w, f.h, och, (size_t)och * align_up(f.w, 8), out_bytes_of(f, och),
@@ -555,6 +593,7 @@ void zero_results(Slot &S, size_t m, const Outputs &out)
     if (out.dihedral) memset(H.dihedral, 0, m * 256);
     memset(H.valid, 0, m);
     memset(H.status, 0, m);
+    if (out.pixel_hash) memset(H.pixel, 0, m * 32);
 }
 
 int fetch_results(Slot &S, size_t m, const Outputs &out, bool entropy_status)
@@ -577,6 +616,7 @@ void scatter_results(const Slot &S, Jobs &jobs, const std::vector<uint32_t> &idx
         if (out.coeffs) ok ? (void)memcpy(out.coeffs + (size_t)g * 256, R.coeffs + r * 1024, 1024) : (void)memset(out.coeffs + (size_t)g * 256, 0, 1024);
         if (out.dihedral) ok ? (void)memcpy(out.dihedral + (size_t)g * 256, R.dihedral + r * 256, 256) : (void)memset(out.dihedral + (size_t)g * 256, 0, 256);
         if (out.valid) out.valid[g] = ok ? R.valid[r] : 0;
+        if (out.pixel_hash) ok ? (void)memcpy(out.pixel_hash + (size_t)g * 32, R.pixel + r * 32, 32) : (void)memset(out.pixel_hash + (size_t)g * 32, 0, 32);
     }
 }
 
@@ -618,7 +658,7 @@ int run_host_entropy(rph_ctx *ctx, JpegPipe &P, Jobs &jobs, const std::vector<ui
             RPH_TRY(S.coef.reserve(coef_need));
         }
         RPH_TRY(P.reserve_recon(b, coef_need, S.stream));
-        RPH_TRY(S.reserve_res(std::max<size_t>(m, std::min<size_t>(n, CHUNK_MAX_IMAGES))));
+        RPH_TRY(S.reserve_res(std::max<size_t>(m, std::min<size_t>(n, CHUNK_MAX_IMAGES)), out.pixel_hash != nullptr));
         const size_t meta_need = std::max<size_t>(m, std::min<size_t>(n, CHUNK_MAX_IMAGES)) * (3 * sizeof(JPlane) + sizeof(JImage) + 3 * 128);
         if (S.meta.cap < meta_need) {
             RPH_HIP_CHECK(hipStreamSynchronize(S.stream));
@@ -643,7 +683,7 @@ int run_host_entropy(rph_ctx *ctx, JpegPipe &P, Jobs &jobs, const std::vector<ui
         RPH_JPEG_STAMP("lane %d: chunk %d buffers sized", b, k);
         ChunkDesc D;
         std::vector<size_t> subs;
-        RPH_TRY(build_descriptors(jobs, idx, first, last, flavour, out.pixels != nullptr, SIZE_MAX / 256, S.meta.h, 0, D, subs));
+        RPH_TRY(build_descriptors(jobs, idx, first, last, flavour, out.rgb_wanted(), SIZE_MAX / 256, S.meta.h, 0, D, subs));
         hipStream_t s = S.stream;
         zero_results(S, m, out);
         if (D.n_images) {
@@ -796,7 +836,7 @@ int run_device_entropy(rph_ctx *ctx, JpegPipe &P, Jobs &jobs, std::vector<uint32
         hipStream_t s = S.stream;
         int16_t *d_coef = P.d_coef + (size_t)b * (region / 2);  // (int16 elements: region bytes per lane)
         const size_t m = last - first;
-        RPH_TRY(S.reserve_res(m));
+        RPH_TRY(S.reserve_res(m, out.pixel_hash != nullptr));
         RPH_TRY(S.stream_bytes.reserve(file_bytes + 64));
         // ---- streams and scan plans (host threads: memchr + memcpy)
         const double t0 = now_ms();
@@ -1097,7 +1137,7 @@ int run_device_entropy(rph_ctx *ctx, JpegPipe &P, Jobs &jobs, std::vector<uint32
         }
         ChunkDesc D;
         std::vector<size_t> subs;
-        RPH_TRY(build_descriptors(jobs, idx, first, last, flavour, false, P.recon_coef_bytes[b], S.meta.h, 0, D, subs));
+        RPH_TRY(build_descriptors(jobs, idx, first, last, flavour, out.rgb_wanted(), P.recon_coef_bytes[b], S.meta.h, 0, D, subs));
         memcpy(S.meta.h + off_himg, himgs.data(), m * sizeof(HImage));
         memcpy(S.meta.h + off_items, items.data(), items.size() * sizeof(HItem));
         memcpy(S.meta.h + off_order, order.data(), order.size() * 4);
@@ -1545,6 +1585,28 @@ int rph_jpeg_pdq_hash_batch(rph_ctx *ctx, const uint8_t *const *data, const size
         o.dihedral = dihedral_out;
         o.valid = valid_out;
         o.status = status_out;
+        return run_batch(ctx, data, len, n, flavour, n_threads, o);
+    });
+}
+
+int rph_jpeg_pdq_pixel_hash_batch(rph_ctx *ctx, const uint8_t *const *data, const size_t *len, uint32_t n, int flavour, uint32_t n_threads,
+                                  uint8_t *hash32_out, float *quality_out, float *coeffs_out, uint8_t *dihedral_out, uint8_t *valid_out,
+                                  int32_t *status_out, uint8_t *pixel_hash32_out)
+{
+    return rph_guarded("rph_jpeg_pdq_pixel_hash_batch", [&]() -> int {
+        if (!ctx || (n && (!data || !len)) || !hash32_out || !pixel_hash32_out) {
+            rph_set_error("rph_jpeg_pdq_pixel_hash_batch: null argument");
+            return RPH_ERR_INVALID_ARG;
+        }
+        if (n == 0) return RPH_OK;
+        Outputs o;
+        o.hash = hash32_out;
+        o.quality = quality_out;
+        o.coeffs = coeffs_out;
+        o.dihedral = dihedral_out;
+        o.valid = valid_out;
+        o.status = status_out;
+        o.pixel_hash = pixel_hash32_out;
         return run_batch(ctx, data, len, n, flavour, n_threads, o);
     });
 }

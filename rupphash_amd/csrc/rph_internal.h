@@ -70,6 +70,7 @@ struct rph_ctx {
     bool jpeg_leader = false;
     std::vector<void *> jpeg_thread_buffers;  // the callers' pinned coefficient buffers (one per calling thread), freed with the context
     uint64_t serial = 0;                      // distinguishes this context from an earlier one at the same address
+    void *b3 = nullptr;                       // BLAKE3 scratch (blake3_kernels.hip): plan and group values, ordered between streams by an event
 };
 
 void rph_set_error(const char *fmt, ...);
@@ -122,6 +123,12 @@ int rph_launch_synth_images(uint8_t *d_out, uint64_t first_k, uint32_t n, uint32
 int rph_launch_synth_hashes(uint8_t *d_out, uint64_t first, uint64_t count, uint64_t n_total, uint64_t seed,
                             uint64_t n_clusters, hipStream_t stream);
 
+// blake3_kernels.hip: pixel hashes (BLAKE3 of to_rgba16()) of n images of one checked geometry; d_scratch: rph_pixel_hash_scratch_bytes()
+// of device memory used in stream order (nullptr when that is 0)
+size_t rph_pixel_hash_scratch_bytes(uint32_t n, uint32_t w, uint32_t h);
+int rph_launch_pixel_hash(const uint8_t *d_px, uint32_t n, uint32_t w, uint32_t h, uint32_t channels, size_t row_stride, size_t image_stride,
+                          uint8_t *d_hash32, hipStream_t stream, void *d_scratch);
+
 int rph_launch_read_stream(const void *d_buf, size_t bytes, uint32_t *d_sink, hipStream_t stream);
 
 // Runs an entry point's body; no C++ exception crosses the C ABI ("nothing aborts", include/rupphash.h)
@@ -153,6 +160,8 @@ void rph_batcher_forget(rph_ctx *ctx);
 void rph_resize_forget(rph_ctx *ctx);
 // jpeg_pipeline.cpp
 void rph_jpeg_forget(rph_ctx *ctx);
+// blake3_kernels.hip
+void rph_blake3_forget(rph_ctx *ctx);
 void rph_jpeg_forget_threads(rph_ctx *ctx);
 
 // host_grouping.cpp

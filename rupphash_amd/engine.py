@@ -155,10 +155,11 @@ class Engine:
         n = len(files)
         return (C.c_char_p * n)(*files), (C.c_size_t * n)(*[len(f) for f in files]), n
 
-    def jpeg_pdq_hash_batch(self, files, flavour=0, threads=0, want_quality=True, want_coeffs=False, want_dihedral=False):
+    def jpeg_pdq_hash_batch(self, files, flavour=0, threads=0, want_quality=True, want_coeffs=False, want_dihedral=False, want_pixel_hash=False):
         """files: list of JPEG byte strings (any mix of sizes), or the tuple jpeg_file_list() made of one.  Returns dict(hash, quality,
         coeffs, dihedral, valid, status): valid[i] = 0 with status[i] != 0 for a file that cannot be decoded, valid[i] = 0 with status 0
-        for an image below 5 px."""
+        for an image below 5 px.  want_pixel_hash adds "pixel_hash" (n x 32: BLAKE3 of to_rgba16() of each decoded image, zero bytes
+        where status != 0) through rph_jpeg_pdq_pixel_hash_batch."""
         arr, lens, n = files if isinstance(files, tuple) else self.jpeg_file_list(files)
         out = {
             "hash": np.zeros((n, 32), np.uint8),
@@ -168,10 +169,64 @@ class Engine:
             "valid": np.zeros(n, np.uint8),
             "status": np.zeros(n, np.int32),
         }
+        if want_pixel_hash:
+            out["pixel_hash"] = np.zeros((n, 32), np.uint8)
+            check(self.L.rph_jpeg_pdq_pixel_hash_batch(self.ctx, arr, lens, n, int(flavour), int(threads), _ptr(out["hash"]), _ptr(out["quality"]),
+                                                       _ptr(out["coeffs"]), _ptr(out["dihedral"]), _ptr(out["valid"]), _ptr(out["status"]),
+                                                       _ptr(out["pixel_hash"])),
+                  "rph_jpeg_pdq_pixel_hash_batch")
+            return out
         check(self.L.rph_jpeg_pdq_hash_batch(self.ctx, arr, lens, n, int(flavour), int(threads), _ptr(out["hash"]), _ptr(out["quality"]),
                                              _ptr(out["coeffs"]), _ptr(out["dihedral"]), _ptr(out["valid"]), _ptr(out["status"])),
               "rph_jpeg_pdq_hash_batch")
         return out
+
+    # ---- BLAKE3 identity hashes ----
+    @staticmethod
+    def blake3_host(data, key=None):
+        """BLAKE3 of one byte string on the host (keyed_hash with a 32-byte key): the content hash of scanner.rs:1345."""
+        data = bytes(data)
+        buf = np.frombuffer(data, np.uint8) if data else None
+        k = None if key is None else np.frombuffer(bytes(key), np.uint8)
+        if k is not None and len(k) != 32:
+            raise ValueError("blake3 key: 32 bytes")
+        out = np.zeros(32, np.uint8)
+        _lib.load().rph_blake3_host(_ptr(buf), len(data), _ptr(k), _ptr(out))
+        return out.tobytes()
+
+    def blake3_batch(self, strings, key=None):
+        """BLAKE3 (hash, or keyed_hash with a 32-byte key) of a list of byte strings on the device: (n, 32) uint8."""
+        n = len(strings)
+        k = None if key is None else np.frombuffer(bytes(key), np.uint8)
+        if k is not None and len(k) != 32:
+            raise ValueError("blake3 key: 32 bytes")
+        out = np.zeros((n, 32), np.uint8)
+        arr, lens, _ = self.jpeg_file_list([bytes(x) for x in strings])
+        check(self.L.rph_blake3_batch(self.ctx, arr, lens, n, _ptr(k), _ptr(out)), "rph_blake3_batch")
+        return out
+
+    def blake3_batch_dev(self, d_data, d_offsets, n, d_digest, key=None, stream=None):
+        k = None if key is None else np.frombuffer(bytes(key), np.uint8)
+        check(self.L.rph_blake3_batch_dev(self.ctx, d_data, d_offsets, n, _ptr(k), d_digest, stream), "rph_blake3_batch_dev")
+
+    def pixel_hash_batch(self, images):
+        """Pixel hashes (scanner.rs:1393-1404: BLAKE3 of to_rgba16()) of uint8 images (n,h,w) [Luma8] or (n,h,w,3|4): (n, 32) uint8.
+        Rows and images may be strided (a view into larger buffers) as long as each row's samples are contiguous."""
+        a = np.asarray(images, np.uint8)
+        ch = 1 if a.ndim == 3 else a.shape[3]
+        if not (a.strides[2] == ch and (a.ndim == 3 or a.strides[3] == 1)) or min(a.strides[:2]) < 0:
+            a = np.ascontiguousarray(a)
+        n, h, w = a.shape[:3]
+        out = np.zeros((n, 32), np.uint8)
+        check(self.L.rph_pixel_hash_batch(self.ctx, C.c_void_p(a.ctypes.data), n, w, h, ch, a.strides[1], a.strides[0], _ptr(out)),
+              "rph_pixel_hash_batch")
+        return out
+
+    def pixel_hash_batch_dev(self, d_px, n, w, h, channels, d_hash, row_stride=None, image_stride=None, stream=None):
+        row_stride = w * channels if row_stride is None else row_stride
+        image_stride = row_stride * h if image_stride is None else image_stride
+        check(self.L.rph_pixel_hash_batch_dev(self.ctx, d_px, n, w, h, channels, row_stride, image_stride, d_hash, stream),
+              "rph_pixel_hash_batch_dev")
 
     def pdq_batcher_config(self, max_batch=256, max_wait_us=0):
         check(self.L.rph_pdq_batcher_config(self.ctx, max_batch, max_wait_us), "rph_pdq_batcher_config")

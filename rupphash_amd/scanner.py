@@ -4,6 +4,8 @@
     group_with_pdqhash / group_files_generic       scanner.rs:1640-1832 up to the union-find
     group_max_dist                                 scanner.rs:2214-2241 (the per-group max_dist of process_raw_groups)
     load_image_fast ("jpg" | "jpeg" arm)           scanner.rs:461-508
+    pixel_hash (--pixel-hash)                      scanner.rs:1393-1404
+    identical_duplicates                           scanner.rs:1843-1864 (analyze_group steps 1-3)
 File-name logic after the union-find (merge_groups_by_stem, the sorting inside process_raw_groups) stays with the caller.
 """
 import numpy as np
@@ -25,6 +27,25 @@ def load_image_fast(path, data, engine=None, flavour=_lib.RPH_JPEG_ZUNE):
     if ext not in ("jpg", "jpeg"):
         raise ValueError(f"load_image_fast: '{ext}' files are decoded by the host's decoders, not by this library")
     return (engine or default_engine()).jpeg_decode(data, flavour)
+
+
+def pixel_hash(image, engine=None):
+    """The pixel hash of one decoded image (scanner.rs:1393-1404): blake3::hash of to_rgba16() as little-endian bytes, on the
+    device.  image: (h, w) Luma8, (h, w, 3) Rgb8 or (h, w, 4) Rgba8 uint8.  Returns 32 bytes."""
+    a = np.asarray(image, np.uint8)
+    return (engine or default_engine()).pixel_hash_batch(a[None])[0].tobytes()
+
+
+def identical_duplicates(content_hashes, pixel_hashes=None):
+    """analyze_group steps 1-3 (scanner.rs:1843-1864): True for each file whose content hash is shared by another file of the group,
+    or whose pixel hash is (a None entry, or pixel_hashes None, means no pixel hash).  Host code."""
+    from collections import Counter
+
+    ck = [bytes(c) for c in content_hashes]
+    ph = [None if p is None else bytes(p) for p in pixel_hashes] if pixel_hashes is not None else [None] * len(ck)
+    bit_counts = Counter(ck)
+    pixel_counts = Counter(p for p in ph if p is not None)
+    return [bit_counts[c] > 1 or (p is not None and pixel_counts[p] > 1) for c, p in zip(ck, ph)]
 
 
 def is_low_pdq_quality(quality):
