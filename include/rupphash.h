@@ -380,7 +380,30 @@ int rph_jpeg_pdq_hash_one(rph_ctx *ctx, const uint8_t *data, size_t len, int fla
  *                                long enough for segments), host below; progressive files on the device when the host threads
  *                                would need longer for all of them than the device for the longest (~0.6 us per byte);
  *   RPH_JPEG_ENTROPY_DEVICE_SEQUENTIAL (3)  as DEVICE, but progressive files stay with the host threads (tests, A/B timing).
- * Same results either way. */
+ * Same results either way, for damaged files too: a file the device walk flags (or does not take) is decoded again by the host
+ * decoder, and only the host decoder's verdict makes a file unreadable -- so a file's status and hash do not depend on the other
+ * files of its call.  What a damaged stream gets, in the host decoder (jpeg_host.cpp), the device walks (jpeg_kernels.hip) and the
+ * CPU oracle (oracle/jpeg_ref.c) alike:
+ *   REFUSED (status RPH_ERR_INVALID_ARG)
+ *     1. a Huffman code the table does not assign     (decode_symbol -1; jpeg_huff_kernel / BitR::symbol8 "l > 16"; huff_decode -1)
+ *     2. a DC category above 15                        (block_seq / block_dc_first "s > 15"; the kernels "s > 15"; decode_block_* "s > 15")
+ *     3. an AC value whose run passes coefficient 63, or Se in a progressive first AC scan
+ *                                                      (block_seq "kk > 64", block_ac_first "kk > sc.se"; jpeg_huff_kernel "k > 64",
+ *                                                       jpeg_prog_kernel "k > se"; decode_block_seq "kk > 63", decode_block_ac_first "kk > se")
+ *     4. a ZRL that steps past the end of the block (past Se in a first AC scan); one that ends exactly there is sixteen zeros
+ *                                                      (the same lines: "kk > 64", "kk > sc.se + 1"; "k > 64", "k > se + 1")
+ *     5. a restart boundary whose next marker is not an RSTn (any n: a renumbered RSTn is accepted; bytes before the marker are
+ *        skipped)                                      (Decoder::restart; decode_scan "RSTn"; the device takes restart intervals only
+ *                                                       when the RSTn markers are exactly the boundaries, prepare_stream, and flags a
+ *                                                       lane that reads past its interval, jpeg_huff_kernel "stream_end")
+ *     6. an AC refinement symbol with a magnitude other than 1
+ *                                                      (block_ac_refine "s != 1"; jpeg_prog_kernel "s != 1"; decode_block_ac_refine)
+ *     7. the header checks (frame, tables, scan parameters, a second frame header behind a scan).
+ *   DECODED ANYWAY, zeros fed for the missing bits
+ *     8. data that ends early, or a marker inside a scan (an 0xFF followed by anything but 0x00, fill bytes included: Bits::refill,
+ *        destuff, br_byte) -- unless a restart boundary follows (rule 5);
+ *     9. an end-of-band run longer than the blocks left in the scan; a refinement run that ends beyond Se (the block ends there).
+ * Parity with zune-jpeg on damaged streams is not pinned (nothing in the reference tree says what it does). */
 #define RPH_JPEG_ENTROPY_HOST 0
 #define RPH_JPEG_ENTROPY_DEVICE 1
 #define RPH_JPEG_ENTROPY_AUTO 2

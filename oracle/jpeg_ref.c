@@ -69,7 +69,7 @@ typedef struct {
     const uint8_t *p, *end;
     uint32_t acc;
     int nbits;
-    int hit, marker;  // hit: a marker or the end of the data was reached (zeros are fed from there on)
+    int hit;  // a marker or the end of the data was reached (zeros are fed from there on)
 } BR;
 
 static int br_byte(BR *b)
@@ -79,18 +79,16 @@ static int br_byte(BR *b)
         b->hit = 1;
         return 0;
     }
-    int c = *b->p++;
-    if (c != 0xFF) return c;
-    int d;
-    do {
-        if (b->p >= b->end) {
-            b->hit = 1;
-            return 0;
-        }
-        d = *b->p++;
-    } while (d == 0xFF);
-    if (d == 0) return 0xFF;
-    b->marker = d;
+    const int c = *b->p;
+    if (c != 0xFF) {
+        b->p++;
+        return c;
+    }
+    if (b->p + 1 < b->end && b->p[1] == 0) {
+        b->p += 2;
+        return 0xFF;
+    }
+    // any other 0xFF -- a marker, a fill byte (0xFF 0xFF), the file's last byte -- ends the segment; p stays on it (rule 8)
     b->hit = 1;
     return 0;
 }
@@ -261,10 +259,11 @@ static int decode_block_seq(Dec *d, BR *b, Comp *k, int16_t *blk)
         if (s == 0) {
             if (r != 15) break;
             kk += 16;
+            if (kk > 64) return JR_ERR_FORMAT;  // a ZRL past the end of the block (rule 4)
             continue;
         }
         kk += r;
-        if (kk > 63) return JR_ERR_FORMAT;
+        if (kk > 63) return JR_ERR_FORMAT;  // a value run past coefficient 63 (rule 3)
         blk[ZIGZAG[kk]] = (int16_t)extend(br_bits(b, s), s);
         kk++;
     }
@@ -298,6 +297,7 @@ static int decode_block_ac_first(Dec *d, BR *b, Comp *k, int16_t *blk, Scan *sc)
         if (s == 0) {
             if (r == 15) {
                 kk += 16;
+                if (kk > sc->se + 1) return JR_ERR_FORMAT;  // a ZRL past the end of the band (rule 4)
                 continue;
             }
             sc->eobrun = (1 << r) - 1;
@@ -305,7 +305,7 @@ static int decode_block_ac_first(Dec *d, BR *b, Comp *k, int16_t *blk, Scan *sc)
             break;
         }
         kk += r;
-        if (kk > 63) return JR_ERR_FORMAT;
+        if (kk > sc->se) return JR_ERR_FORMAT;  // a value run past Se (rule 3)
         blk[ZIGZAG[kk]] = (int16_t)(extend(br_bits(b, s), s) * (1 << sc->al));
         kk++;
     }
@@ -387,17 +387,13 @@ static int decode_scan(Dec *d, Scan *sc)
     for (int my = 0; my < mcus_y; my++)
         for (int mx = 0; mx < mcus_x; mx++) {
             if (d->restart_interval && until_restart == 0) {
-                // RSTn (T.81 E.2.4): byte-align, take the marker, reset the predictions and the end-of-band run
+                // RSTn (T.81 E.2.4): byte-align, skip to the next marker, which must be an RSTn (any n: rule 5), reset the predictions
+                // and the end-of-band run
                 b.nbits = 0;
-                if (!b.hit) {
-                    while (b.p + 1 < b.end && !(b.p[0] == 0xFF && b.p[1] != 0 && b.p[1] != 0xFF)) b.p++;
-                    if (b.p + 1 >= b.end) return JR_ERR_FORMAT;
-                    b.marker = b.p[1];
-                    b.p += 2;
-                }
-                if (b.marker < 0xD0 || b.marker > 0xD7) return JR_ERR_FORMAT;
+                while (b.p + 1 < b.end && !(b.p[0] == 0xFF && b.p[1] != 0 && b.p[1] != 0xFF)) b.p++;
+                if (b.p + 1 >= b.end || b.p[1] < 0xD0 || b.p[1] > 0xD7) return JR_ERR_FORMAT;
+                b.p += 2;
                 b.hit = 0;
-                b.marker = 0;
                 for (int i = 0; i < sc->ns; i++) d->comp[sc->ci[i]].pred = 0;
                 sc->eobrun = 0;
                 until_restart = d->restart_interval;
@@ -420,14 +416,11 @@ static int decode_scan(Dec *d, Scan *sc)
             }
             until_restart--;
         }
-    // position of the marker that ends the scan
-    if (b.hit && b.marker) {
-        d->pos = (size_t)(b.p - d->data) - 2;
-    } else {
-        const uint8_t *p = b.p;
-        while (p + 1 < b.end && !(p[0] == 0xFF && p[1] != 0 && p[1] != 0xFF && !(p[1] >= 0xD0 && p[1] <= 0xD7))) p++;
-        d->pos = (size_t)(p - d->data);
-    }
+    // position of the marker that ends the scan: the reader never steps over one, so it is at or after b.p (RSTn and fill bytes are
+    // passed over)
+    const uint8_t *p = b.p;
+    while (p + 1 < b.end && !(p[0] == 0xFF && p[1] != 0 && p[1] != 0xFF && !(p[1] >= 0xD0 && p[1] <= 0xD7))) p++;
+    d->pos = (size_t)(p - d->data);
     return JR_OK;
 }
 

@@ -78,10 +78,14 @@ struct PCorr {
 // restart interval is an independent stream (predictions reset, byte aligned), so a file with restart markers is walked by as many
 // lanes as it has intervals.
 constexpr uint32_t HITEM_ALL_SCANS = 0xFFFFFFFFu;
+constexpr uint32_t HITEM_NO_END = 0xFFFFFFFFu;  // HItem::stream_end of an item without a bound (a whole file, a segment)
 struct HItem {
     uint32_t image, scan, mcu_first, mcu_count, stream_off;
     uint32_t bit_skip;  // bits to drop behind stream_off before the first symbol (segments of a stream without markers begin mid-byte)
     int32_t dc[3];      // predictions at the item's first MCU, in the scan's component order (0 at a restart interval)
+    uint32_t stream_end;  // a restart interval: the byte its RSTn stood at (the host decoder reads zeros from there on; a lane that
+                          // reads past it is flagged and the file goes to the host).  0 is a real bound (an empty interval);
+                          // HITEM_NO_END: no bound (a whole file, a segment)
 };
 
 // ---- a stream WITHOUT restart markers, cut into segments of SEG_BYTES that are walked side by side (jpeg_sync_kernel) ------------------

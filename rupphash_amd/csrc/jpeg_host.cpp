@@ -222,7 +222,7 @@ struct Decoder {
             kk += r;
             blk[ZIGZAG[kk++]] = (int16_t)receive_extend(b, s);  // <= 16 + 16 bits since need32
         } while (kk < 64);
-        return kk > 64 ? RPH_ERR_INVALID_ARG : RPH_OK;
+        return kk > 64 ? RPH_ERR_INVALID_ARG : RPH_OK;  // a value run past 63 or a ZRL past the end of the block (rules 3, 4)
     }
     // ---- progressive (T.81 G.1.2)
     inline int block_dc_first(Bits &b, Comp &k, int16_t *blk, const Scan &sc)
@@ -252,6 +252,7 @@ struct Decoder {
             if (s == 0) {
                 if (r == 15) {
                     kk += 16;
+                    if (kk > sc.se + 1) return RPH_ERR_INVALID_ARG;  // a ZRL past the end of the band (rule 4)
                     continue;
                 }
                 sc.eobrun = (1u << r) - 1;
@@ -259,7 +260,7 @@ struct Decoder {
                 break;
             }
             kk += r;
-            if (kk > 63) return RPH_ERR_INVALID_ARG;
+            if (kk > sc.se) return RPH_ERR_INVALID_ARG;  // a value run past Se (rule 3)
             blk[ZIGZAG[kk++]] = (int16_t)(receive_extend(b, s) * (1 << sc.al));
         }
         return RPH_OK;
@@ -638,8 +639,10 @@ __attribute__((target("avx2"))) const uint8_t *copy_until_ff_avx2(const uint8_t 
 }
 #endif
 
-// entropy bytes of one scan, byte stuffing undone and RSTn dropped; returns the position of the marker that ends the scan
-const uint8_t *destuff(const uint8_t *p, const uint8_t *end, uint8_t *&out, uint8_t *out_end, std::vector<uint32_t> *marks)
+// entropy bytes of one scan, byte stuffing undone and RSTn dropped (counted in n_rst); returns the position of the marker that ends
+// the scan.  An 0xFF followed by anything but 0x00 or RSTn ends it, fill bytes (0xFF 0xFF) included: the host decoder's reader stops
+// there too (Bits::refill), and what follows is read as zeros.
+const uint8_t *destuff(const uint8_t *p, const uint8_t *end, uint8_t *&out, uint8_t *out_end, std::vector<uint32_t> *marks, uint32_t &n_rst)
 {
     const uint8_t *const scan_out = out;
 #if defined(__x86_64__)
@@ -672,9 +675,8 @@ const uint8_t *destuff(const uint8_t *p, const uint8_t *end, uint8_t *&out, uint
             p = q + 2;
         } else if (m >= 0xD0 && m <= 0xD7) {
             p = q + 2;  // restart marker: the decoder counts MCUs
+            n_rst++;
             if (marks) marks->push_back((uint32_t)(out - scan_out));
-        } else if (m == 0xFF) {
-            p = q + 1;  // fill byte
         } else {
             return q;  // the marker that ends the scan
         }
@@ -734,6 +736,10 @@ int prepare_stream(const uint8_t *data, size_t len, Frame &f, StreamPlan &plan, 
                     total += p[l];
                 }
                 if (total > 256 || left < 17 + total) return RPH_ERR_INVALID_ARG;
+                for (int l = 1, code = 0; l <= 16; l++, code <<= 1) {  // the host decoder refuses a table whose codes overflow (build_huff)
+                    code += t.counts[l];
+                    if (t.counts[l] && code - 1 >= (1 << l)) return RPH_ERR_INVALID_ARG;
+                }
                 memset(t.symbols, 0, sizeof t.symbols);
                 memcpy(t.symbols, p + 17, (size_t)total);
                 t.total = (uint16_t)total;
@@ -744,6 +750,11 @@ int prepare_stream(const uint8_t *data, size_t len, Frame &f, StreamPlan &plan, 
             }
             break;
         }
+        case 0xC0:
+        case 0xC1:
+        case 0xC2:
+            if (plan.n_scans) return RPH_ERR_INVALID_ARG;  // a second frame header behind a scan (as in walk)
+            break;
         case 0xC3: case 0xC5: case 0xC6: case 0xC7: case 0xC9: case 0xCA: case 0xCB: case 0xCD: case 0xCE: case 0xCF:
             return RPH_ERR_UNSUPPORTED;
         case 0xDD:
@@ -816,9 +827,15 @@ int prepare_stream(const uint8_t *data, size_t len, Frame &f, StreamPlan &plan, 
             }
             sc.restart_interval = f.restart_interval;
             sc.stream_off = (uint32_t)(o - out);
-            const bool mark = restart_marks && plan.n_scans == 0 && f.restart_interval != 0;
-            const uint8_t *stop = destuff(data + pos, data + len, o, o_end, mark ? restart_marks : nullptr);
+            // Restart intervals go to the device only as the intervals of a one-scan sequential file, one lane each, cut at the RSTn
+            // markers (run_device_entropy).  An RSTn elsewhere -- in a scan without a restart interval, or in a second scan -- leaves the
+            // file to the host decoder, whose reader stops at every marker (rules 5 and 8, rupphash.h).
+            if (f.restart_interval && plan.n_scans != 0) return RPH_ERR_UNSUPPORTED;
+            const bool mark = restart_marks && f.restart_interval != 0;
+            uint32_t n_rst = 0;
+            const uint8_t *stop = destuff(data + pos, data + len, o, o_end, mark ? restart_marks : nullptr, n_rst);
             if (!stop || (size_t)(o_end - o) < 32) return RPH_ERR_CAPACITY;
+            if (n_rst && !f.restart_interval) return RPH_ERR_UNSUPPORTED;
             sc.stream_len = (uint32_t)(o - out) - sc.stream_off;
             memset(o, 0, 32);
             o += 32;
@@ -833,12 +850,13 @@ int prepare_stream(const uint8_t *data, size_t len, Frame &f, StreamPlan &plan, 
     if (f.ncomp == 3 && f.adobe_transform == 0) return RPH_ERR_UNSUPPORTED;
     for (int c = 0; c < f.ncomp; c++)
         if (!f.qt_present[f.comp[c].tq]) return RPH_ERR_INVALID_ARG;
-    if (restart_marks && !restart_marks->empty()) {
-        // usable only if the file is one scan and the marks are exactly the interval boundaries
+    if (!f.progressive && plan.scan[0].restart_interval) {
+        // the device takes the file only if it is one scan and its markers are exactly the interval boundaries: a missing, extra or
+        // replaced RSTn is for the host decoder to judge (rule 5)
         const ScanPlan &sc = plan.scan[0];
         const uint64_t mcus = sc.ns == 1 ? (uint64_t)f.comp[sc.ci[0]].real_bw * f.comp[sc.ci[0]].real_bh : (uint64_t)f.mcus_x * f.mcus_y;
-        const uint64_t intervals = sc.restart_interval ? (mcus + sc.restart_interval - 1) / sc.restart_interval : 0;
-        if (plan.n_scans != 1 || intervals == 0 || restart_marks->size() + 1 != intervals) restart_marks->clear();
+        const uint64_t intervals = (mcus + sc.restart_interval - 1) / sc.restart_interval;
+        if (!restart_marks || plan.n_scans != 1 || restart_marks->size() + 1 != intervals) return RPH_ERR_UNSUPPORTED;
     }
     *used = (size_t)(o - out);
     return RPH_OK;

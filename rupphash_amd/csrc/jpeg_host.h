@@ -80,11 +80,13 @@ typedef uint32_t (*InternTable)(void *store, const TableSpec &t);
 // bytes of each scan to `out` with the byte stuffing undone (0xFF00 -> 0xFF) and the RSTn markers dropped (the decoder byte-aligns
 // every restart_interval MCUs instead), 32 zero bytes after each scan; at most `cap` bytes (len + 160 always suffices for a sequential
 // file, len + 160 + 32 * MAX_PROG_SCANS for a progressive one).
-// RPH_ERR_UNSUPPORTED: a sequential file of more than 4 scans, a progressive one of more than MAX_PROG_SCANS or with restart intervals
-// -- the caller uses decode_coefficients for that file.
-// `restart_marks` (nullable): for a file of ONE scan with a restart interval, the offsets (from the scan's first byte in `out`) at which
-// the restart intervals after the first begin -- every interval is an independent bit stream (predictions reset, byte aligned), so
-// the device can give each a lane of its own.  Left empty when the marks do not add up to ceil(MCUs / interval) - 1.
+// RPH_ERR_UNSUPPORTED: a sequential file of more than 4 scans, a progressive one of more than MAX_PROG_SCANS or with restart intervals,
+// a sequential file with restart intervals that is not one scan whose RSTn markers are exactly ceil(MCUs / interval) - 1, an RSTn in a
+// scan without restart interval.  Whatever the status, the caller leaves the file to decode_coefficients: only the host decoder's verdict
+// makes a file unreadable.
+// `restart_marks`: for a file of ONE scan with a restart interval, the offsets (from the scan's first byte in `out`) at which the restart
+// intervals after the first begin -- every interval is an independent bit stream (predictions reset, byte aligned), so the device can
+// give each a lane of its own, which ends at the next mark (the host decoder reads zeros behind it).
 int prepare_stream(const uint8_t *data, size_t len, Frame &f, StreamPlan &plan, uint8_t *out, size_t cap, size_t *used, InternTable intern, void *store,
                    std::vector<uint32_t> *restart_marks = nullptr);
 int build_device_lut(const TableSpec &t, DeviceLut &out);

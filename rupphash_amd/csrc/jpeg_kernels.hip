@@ -663,7 +663,8 @@ __global__ void __launch_bounds__(STAGE_WAVES > 0 ? STAGE_WAVES * 64 : 64) jpeg_
                         v = 0;
                         if (++i == ns) {
                             i = 0;
-                            if (ri && --until == 0) {  // restart interval: drop the padding bits, reset the predictions (the marker itself is gone)
+                            if (ri && --until == 0) {  // restart interval: drop the padding bits, reset the predictions (the marker itself is gone;
+                                                       // a whole-file lane meets this only behind its last MCU: prepare_stream cuts files with more intervals)
                                 const int drop = nb & 7;
                                 acc <<= drop;
                                 nb -= drop;
@@ -688,6 +689,9 @@ __global__ void __launch_bounds__(STAGE_WAVES > 0 ? STAGE_WAVES * 64 : 64) jpeg_
             }
         }
         if (!done) bad = 1;
+        // A restart interval is read up to its RSTn, zeros behind it (jpeg_host.cpp, Bits::refill).  This lane reads on into the next
+        // interval's bytes instead: if it consumed any of them, the file goes to the host decoder (rule 5, rupphash.h).
+        if (part && item.stream_end != HITEM_NO_END && 8ull * (woff - 8 - q0n / 8) - (uint64_t)nb - 8ull * lead > 8ull * (item.stream_end - skip)) bad = 1;
     }
     if (bad) status[ii] = 1;  // (the results were zeroed before the launch; several lanes may share an image)
 }
@@ -829,7 +833,7 @@ __device__ __forceinline__ void prog_publish(uint32_t *progress, uint32_t me, ui
 }
 // All lanes of the wave wait until the scans they depend on have come at least as far as they need (NONE: no such scan).  The producers
 // are in workgroups that started before this one; should one never arrive all the same, the wait ends after a few seconds and the
-// file is reported as damaged rather than hanging the device.  (The mask loads that follow are issued after the progress words have
+// file is flagged (status 2) rather than hanging the device: the host decoder then decodes it.  (The mask loads that follow are issued after the progress words have
 // come back, and they are device-scope atomic loads.)
 __device__ __forceinline__ bool prog_wait(const uint32_t *progress, uint32_t dep0, uint32_t dep1, uint32_t need)
 {
@@ -891,7 +895,7 @@ __global__ void __launch_bounds__(64) jpeg_prog_kernel(const uint8_t *__restrict
         uint32_t w = 0;
         while (__any((int)(w < P.wait_count))) {
             const uint32_t dep = w < P.wait_count ? waits[P.wait_first + w] : PSCAN_NONE;
-            if (!prog_wait(progress, dep, PSCAN_NONE, 0xFFFFFFFFu)) bad = 1;
+            if (!prog_wait(progress, dep, PSCAN_NONE, 0xFFFFFFFFu)) bad = 2;
             w++;
         }
     }
@@ -994,6 +998,10 @@ __global__ void __launch_bounds__(64) jpeg_prog_kernel(const uint8_t *__restrict
                 if (s == 0) {
                     if (r == 15) {
                         k += 16;
+                        if (k > se + 1) {  // a ZRL past the end of the band (rule 4; jpeg_host.cpp block_ac_first)
+                            bad = 1;
+                            break;
+                        }
                         if (k > se) adv = 1;
                     } else {  // end of band for this block and the next (1 << r) - 1 + bits
                         uint32_t run = (1u << r) - 1;
@@ -1002,7 +1010,7 @@ __global__ void __launch_bounds__(64) jpeg_prog_kernel(const uint8_t *__restrict
                     }
                 } else {
                     k += r;
-                    if (k > 63) {
+                    if (k > se) {  // a value run past Se (rule 3)
                         bad = 1;
                         break;
                     }
@@ -1066,7 +1074,7 @@ __global__ void __launch_bounds__(64) jpeg_prog_kernel(const uint8_t *__restrict
             };
             auto fetch_when_ready = [&]() {  // the scans this one follows must be past the blocks it is about to read the history of
                 const uint32_t need = f_bl + PROG_GROUP < total ? f_bl + PROG_GROUP : total;
-                if (!prog_wait(progress, P.chase[0], P.chase[1], f_bl < total ? need : 0u)) bad = 1;
+                if (!prog_wait(progress, P.chase[0], P.chase[1], f_bl < total ? need : 0u)) bad = 2;
                 fetch_group();
             };
             fetch_when_ready();
@@ -1169,7 +1177,9 @@ __global__ void __launch_bounds__(64) jpeg_prog_kernel(const uint8_t *__restrict
     }
 #endif
     prog_publish(progress, me, 0xFFFFFFFFu);  // (whatever became of the scan: nobody waits for it any longer)
-    if (bad) status[ii] = 1;  // (the results were zeroed before the launch; the scans of a file are different lanes)
+    // (the results were zeroed before the launch; the scans of a file are different lanes).  1: a damaged stream, 2: a wait gave up --
+    // either way the host decoder takes the file over (jpeg_pipeline.cpp, scatter_results)
+    if (bad) status[ii] = (uint8_t)bad;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -1468,6 +1478,7 @@ __global__ void __launch_bounds__(64) jpeg_seg_items_kernel(const SegFile *__res
         it.stream_off = (st.entry == SEG_NONE || behind) ? 0 : st.entry >> 3;
         it.bit_skip = (st.entry == SEG_NONE || behind) ? 0 : st.entry & 7;
         it.dc[0] = dc0, it.dc[1] = dc1, it.dc[2] = dc2;
+        it.stream_end = HITEM_NO_END;
         items[F.first_item + t] = it;
         dc0 += st.dc[0], dc1 += st.dc[1], dc2 += st.dc[2];
         prev_out = out;
@@ -1477,6 +1488,7 @@ __global__ void __launch_bounds__(64) jpeg_seg_items_kernel(const SegFile *__res
         HItem it;
         it.image = F.image, it.scan = HITEM_ALL_SCANS, it.mcu_first = 0, it.mcu_count = 0, it.stream_off = 0, it.bit_skip = 0;
         it.dc[0] = it.dc[1] = it.dc[2] = 0;
+        it.stream_end = HITEM_NO_END;
         items[F.first_item] = it;
     }
 }

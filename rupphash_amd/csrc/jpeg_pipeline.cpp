@@ -603,13 +603,19 @@ int fetch_results(Slot &S, size_t m, const Outputs &out, bool entropy_status)
 }
 
 // results of a finished chunk -> the caller's arrays (scattered through idx)
-void scatter_results(const Slot &S, Jobs &jobs, const std::vector<uint32_t> &idx, size_t first, size_t last, const Outputs &out, bool entropy_status)
+// retry (device entropy): files the device walk flagged (a damaged stream, or a progressive wait that gave up: the status byte says which)
+// are not written; they go to the host decoder, whose verdict is final (rupphash.h, rph_jpeg_set_entropy)
+void scatter_results(const Slot &S, Jobs &jobs, const std::vector<uint32_t> &idx, size_t first, size_t last, const Outputs &out,
+                     std::vector<uint32_t> *retry)
 {
     ResView R(S.res.h, S.res_images);
     for (size_t r = 0; r < last - first; r++) {
         const uint32_t g = idx[first + r];
         Job &j = jobs[g];
-        if (entropy_status && j.status == RPH_OK && R.status[r]) j.status = RPH_ERR_INVALID_ARG;  // the device walk met a corrupt stream
+        if (retry && j.status == RPH_OK && R.status[r]) {
+            retry->push_back(g);
+            continue;
+        }
         const bool ok = j.status == RPH_OK;
         if (out.hash) ok ? (void)memcpy(out.hash + (size_t)g * 32, R.hash + r * 32, 32) : (void)memset(out.hash + (size_t)g * 32, 0, 32);
         if (out.quality) ok ? (void)memcpy(out.quality + g, R.quality + r * 4, 4) : (void)memset(out.quality + g, 0, 4);
@@ -631,7 +637,7 @@ int run_host_entropy(rph_ctx *ctx, JpegPipe &P, Jobs &jobs, const std::vector<ui
         if (!pend[b].active) return RPH_OK;
         RPH_HIP_CHECK(hipStreamSynchronize(P.slot[b].stream));
         RPH_TRY(fetch_results(P.slot[b], pend[b].last - pend[b].first, out, false));
-        scatter_results(P.slot[b], jobs, idx, pend[b].first, pend[b].last, out, false);
+        scatter_results(P.slot[b], jobs, idx, pend[b].first, pend[b].last, out, nullptr);
         pend[b].active = false;
         return RPH_OK;
     };
@@ -799,7 +805,7 @@ int run_device_entropy(rph_ctx *ctx, JpegPipe &P, Jobs &jobs, std::vector<uint32
         RPH_HIP_CHECK(hipEventSynchronize(P.slot[b].done));
         RPH_JPEG_STAMP("lane %d: chunk done", b);
         RPH_TRY(fetch_results(P.slot[b], pend[b].last - pend[b].first, out, true));
-        scatter_results(P.slot[b], jobs, idx, pend[b].first, pend[b].last, out, true);
+        scatter_results(P.slot[b], jobs, idx, pend[b].first, pend[b].last, out, &leftover);
         RPH_JPEG_STAMP("lane %d: results scattered", b);
         pend[b].active = false;
         return RPH_OK;
@@ -917,8 +923,10 @@ int run_device_entropy(rph_ctx *ctx, JpegPipe &P, Jobs &jobs, std::vector<uint32
         items.reserve(m);
         for (size_t i = first; i < last; i++) {
             Job &j = jobs[idx[i]];
-            if (j.status == RPH_ERR_UNSUPPORTED || j.status == RPH_ERR_CAPACITY) leftover.push_back(idx[i]);
-            if (j.status != RPH_OK) continue;
+            if (j.status != RPH_OK) {  // whatever prepare_stream found, the host decoder judges the file
+                leftover.push_back(idx[i]);
+                continue;
+            }
             const uint32_t r = (uint32_t)(i - first);
             if (j.frame.progressive) {  // one lane per scan (jpeg_prog_kernel)
                 himgs[r].mask_first = (uint32_t)prog_blocks;
@@ -1012,7 +1020,7 @@ int run_device_entropy(rph_ctx *ctx, JpegPipe &P, Jobs &jobs, std::vector<uint32
                     seg_files.push_back(sf);
                     continue;
                 }
-                items.push_back(HItem{r, HITEM_ALL_SCANS, 0, 0, 0});
+                items.push_back(HItem{r, HITEM_ALL_SCANS, 0, 0, 0, 0, {0, 0, 0}, HITEM_NO_END});
                 item_len.push_back((uint32_t)std::min<size_t>(j.len, 0xFFFFFFFFu));
                 continue;
             }
@@ -1023,7 +1031,7 @@ int run_device_entropy(rph_ctx *ctx, JpegPipe &P, Jobs &jobs, std::vector<uint32
             for (uint32_t k = 0; k < n_int; k++) {
                 const uint32_t off = k ? j.marks[k - 1] : 0, end = k + 1 < n_int ? j.marks[k] : sp.stream_len;
                 const uint64_t m_first = (uint64_t)k * sp.restart_interval;
-                items.push_back(HItem{r, 0, (uint32_t)m_first, (uint32_t)std::min<uint64_t>(sp.restart_interval, mcus - m_first), off});
+                items.push_back(HItem{r, 0, (uint32_t)m_first, (uint32_t)std::min<uint64_t>(sp.restart_interval, mcus - m_first), off, 0, {0, 0, 0}, end});
                 item_len.push_back(end > off ? end - off : 0);
             }
         }

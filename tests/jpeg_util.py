@@ -101,10 +101,27 @@ def _fdct_blocks(plane):
     return np.einsum("ux,abxy,vy->abuv", c, b, c)
 
 
-def encode_baseline(rgb, sampling=((1, 2), (1, 1), (1, 1)), quality_scale=1.0, restart_interval=0, gray=False, sixteen_bit_tables=False, interleaved=True):
+# DC luma table with categories 12..16 as well (10..14-bit codes): what the faults "dc_cat" and "dc_cat_16" need
+DC_L_WIDE = ([0, 1, 5, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0], list(range(17)))
+
+# faults encode_baseline can write into ONE block (fault = (kind, block number in coding order[, argument])); what the decoders must
+# make of each is the rule list in include/rupphash.h (rph_jpeg_set_entropy)
+BASELINE_FAULTS = {
+    "bad_code": "refused",      # an AC code the table does not assign (sixteen 1-bits)
+    "dc_cat": "decoded",        # DC category 12..15 (argument), a legal code of a widened table
+    "dc_cat_16": "refused",     # DC category 16: a code the widened table assigns, a category no decoder takes
+    "run_past_63": "refused",   # three ZRLs, then a value with run 15: position 64
+    "zrl_past_63": "refused",   # four ZRLs from position 1: position 65
+    "zrl_to_64": "decoded",     # a value at 47, then a ZRL that ends the block exactly (no EOB)
+}
+
+
+def encode_baseline(rgb, sampling=((1, 2), (1, 1), (1, 1)), quality_scale=1.0, restart_interval=0, gray=False, sixteen_bit_tables=False, interleaved=True,
+                    fault=None):
     """A plain baseline (SOF0) encoder: rgb (h, w, 3) uint8 [or (h, w) when gray]; sampling = (H, V) per component.
     Chroma is box-averaged down.  interleaved=False writes one scan per component (each over the component's own block grid,
-    T.81 A.2.2).  Returns the JPEG byte string."""
+    T.81 A.2.2).  fault: (kind, block[, argument]) of BASELINE_FAULTS, written into that block of the first scan (luma blocks only).
+    Returns the JPEG byte string."""
     rgb = np.asarray(rgb)
     if gray:
         h, w = rgb.shape
@@ -143,18 +160,55 @@ def encode_baseline(rgb, sampling=((1, 2), (1, 1), (1, 1)), quality_scale=1.0, r
     for ci, (H, V) in enumerate(sampling):
         sof += bytes([ci + 1, (H << 4) | V, 0 if ci == 0 else 1])
     seg(0xC0, sof)
-    tables = [(0x00, DC_L), (0x10, AC_L)] + ([] if gray else [(0x01, DC_C), (0x11, AC_C)])
+    dc_l = DC_L_WIDE if fault and fault[0] in ("dc_cat", "dc_cat_16") else DC_L
+    tables = [(0x00, dc_l), (0x10, AC_L)] + ([] if gray else [(0x01, DC_C), (0x11, AC_C)])
     for tid, (counts, symbols) in tables:
         seg(0xC4, bytes([tid]) + bytes(counts) + bytes(symbols))
     if restart_interval:
         seg(0xDD, restart_interval.to_bytes(2, "big"))
-    dc_codes = [_codes(*DC_L), _codes(*DC_C)]
+    dc_codes = [_codes(*dc_l), _codes(*DC_C)]
     ac_codes = [_codes(*AC_L), _codes(*AC_C)]
     pred = [0] * len(comps)
+    luma_blocks = [0]
+
+    def put_fault(bits, kind, arg):
+        ac = ac_codes[0]
+        if kind == "dc_cat":  # the block's DC: the largest difference of the category, the prediction follows it
+            bits.put(*dc_codes[0][arg])
+            bits.put((1 << arg) - 1, arg)
+            pred[0] += (1 << arg) - 1
+            bits.put(*ac[0x00])
+        elif kind == "dc_cat_16":  # (refused at the code: no magnitude bits follow)
+            bits.put(*dc_codes[0][16])
+        elif kind == "bad_code":
+            bits.put(0xFFFF, 16)
+        elif kind == "run_past_63":
+            for _ in range(3):
+                bits.put(*ac[0xF0])
+            bits.put(*ac[0xF1])
+            bits.put(1, 1)
+        elif kind == "zrl_past_63":
+            for _ in range(4):
+                bits.put(*ac[0xF0])
+        elif kind == "zrl_to_64":
+            for _ in range(2):
+                bits.put(*ac[0xF0])
+            bits.put(*ac[0xE1])
+            bits.put(1, 1)
+            bits.put(*ac[0xF0])
+        else:
+            raise ValueError(kind)
 
     def put_block(bits, blk, ci):
         t = 0 if ci == 0 else 1
         zz = blk.reshape(64)[ZIGZAG]
+        if ci == 0:
+            luma_blocks[0] += 1
+            if fault and luma_blocks[0] - 1 == fault[1]:
+                if fault[0] not in ("dc_cat", "dc_cat_16"):
+                    bits.put(*dc_codes[0][0])  # DC difference 0
+                put_fault(bits, fault[0], fault[2] if len(fault) > 2 else 12)
+                return
         diff = int(zz[0]) - pred[ci]
         pred[ci] = int(zz[0])
         s = abs(diff).bit_length()
@@ -268,9 +322,19 @@ def _table_for(used, long_codes):
     return counts, used
 
 
-def encode_progressive(rgb, script, sampling=((2, 2), (1, 1), (1, 1)), quality_scale=1.0, gray=False, long_codes=False):
+# faults encode_progressive can put at the start of one scan (fault = (kind, scan number)); the scan must be of the kind named
+PROGRESSIVE_FAULTS = {
+    "zrl_past_se": "refused",         # AC first scan: ZRLs that step past Se
+    "run_past_se": "refused",         # AC first scan of fewer than 16 coefficients: a value with a run to Se + 1
+    "eobrun_overrun": "decoded",      # AC first scan (not refined later): an end-of-band run of 2^15 - 2 blocks, more than the scan has
+    "refine_bad_symbol": "refused",   # AC refinement scan: a symbol with a magnitude of 2
+}
+
+
+def encode_progressive(rgb, script, sampling=((2, 2), (1, 1), (1, 1)), quality_scale=1.0, gray=False, long_codes=False, fault=None):
     """script: list of (components, Ss, Se, Ah, Al), components a tuple of indices (several only for DC scans).  Every scan gets its own
-    Huffman table (written in front of it, slot 0 / 1 alternating so that slots are redefined between scans)."""
+    Huffman table (written in front of it, slot 0 / 1 alternating so that slots are redefined between scans).  fault: (kind, scan) of
+    PROGRESSIVE_FAULTS, put in front of that scan's symbols."""
     h, w, sampling, hmax, vmax, mcus_x, mcus_y, qts, blocks = _quantised_blocks(rgb, sampling, quality_scale, gray)
     ncomp = len(blocks)
     out = bytearray(b"\xff\xd8")
@@ -383,6 +447,21 @@ def encode_progressive(rgb, script, sampling=((2, 2), (1, 1), (1, 1)), quality_s
                         if eobrun == 0x7FFF or len(be) > 900:
                             flush_eobrun()
             flush_eobrun()
+            if fault and fault[1] == scan_no:
+                kind = fault[0]
+                assert ss > 0 and (ah > 0) == (kind == "refine_bad_symbol"), (kind, script[scan_no])
+                if kind == "zrl_past_se":
+                    head = [("s", ci, 0xF0)] * ((se - ss + 1) // 16 + 1)
+                elif kind == "run_past_se":
+                    assert se - ss + 1 <= 15
+                    head = [("s", ci, ((se - ss + 1) << 4) | 1), ("b", 1, 1)]
+                elif kind == "eobrun_overrun":
+                    head = [("s", ci, 14 << 4), ("b", 0x3FFF, 14)]
+                elif kind == "refine_bad_symbol":
+                    head = [("s", ci, 0x02), ("b", 3, 2)]
+                else:
+                    raise ValueError(kind)
+                toks[:0] = head
         # tables: one per component of the scan (DC first scans) or one (AC scans); none for DC refinement
         slot = scan_no & 1
         codes = {}
@@ -419,3 +498,137 @@ SCRIPT_REFINE_BEFORE_OTHER_BANDS = [((0, 1, 2), 0, 0, 0, 0), ((0,), 1, 8, 0, 1),
                                     ((1,), 1, 63, 1, 0), ((2,), 1, 30, 0, 0), ((0,), 9, 63, 1, 0), ((2,), 31, 63, 0, 1), ((2,), 31, 63, 1, 0)]
 SCRIPT_MANY_BANDS = [((0, 1, 2), 0, 0, 0, 0)] + [((c,), a, min(a + 2, 63), 0, 0) for a in range(1, 64, 3) for c in (0, 1, 2)]
 SCRIPT_GRAY = [((0,), 0, 0, 0, 1), ((0,), 1, 63, 0, 2), ((0,), 1, 63, 2, 1), ((0,), 0, 0, 1, 0), ((0,), 1, 63, 1, 0)]
+
+
+# ---- damaged streams ------------------------------------------------------------------------------------------------------------------
+# What the decoders must make of a damaged stream is written down in include/rupphash.h (rph_jpeg_set_entropy): every entropy path and the
+# CPU oracle must agree on it.  damaged_corpus() gives (name, bytes, expected) with expected "refused", "decoded" or None (random damage:
+# only agreement is asserted), deterministic for a seed.
+
+def _entropy_start(data):
+    sos = data.find(b"\xff\xda")
+    return sos + 2 + int.from_bytes(data[sos + 2:sos + 4], "big")
+
+
+def restart_fault(data, kind, which=1):
+    """a file with restart markers, RSTn number `which` (0-based) missing, renumbered, or replaced by a COM marker; or restart interval
+    number `which` emptied (its entropy bytes removed: the RSTn behind it follows the SOS header or the RSTn before it at once)"""
+    start = _entropy_start(data)
+    pos = [i for i in range(start, len(data) - 1) if data[i] == 0xFF and 0xD0 <= data[i + 1] <= 0xD7]
+    if kind == "interval_emptied":
+        first = pos[which - 1] + 2 if which else start
+        return data[:first] + data[pos[which]:]
+    i = pos[which]
+    if kind == "rst_missing":
+        return data[:i] + data[i + 2:]
+    if kind == "rst_renumbered":
+        return data[:i + 1] + bytes([0xD0 + ((data[i + 1] - 0xD0 + 3) & 7)]) + data[i + 2:]
+    if kind == "rst_replaced":
+        return data[:i + 1] + b"\xfe" + data[i + 2:]
+    raise ValueError(kind)
+
+
+RESTART_FAULTS = {"rst_missing": "refused", "rst_renumbered": "decoded", "rst_replaced": "refused", "interval_emptied": "decoded"}
+
+
+def _layouts(rng):
+    """small clean files of every layout the device has special cases for: (name, bytes)"""
+    a = np.array(make_image(45, 37, seed=int(rng.integers(1 << 30))))
+    out = []
+    for name, samp in [("444", ((1, 1), (1, 1), (1, 1))), ("422", ((2, 1), (1, 1), (1, 1))), ("420", ((2, 2), (1, 1), (1, 1))), ("440", ((1, 2), (1, 1), (1, 1)))]:
+        out.append(("base" + name, encode_baseline(a, samp)))
+        out.append(("base" + name + "_rst", encode_baseline(a, samp, restart_interval=2)))
+    out.append(("gray", encode_baseline(a[..., 0], gray=True)))
+    out.append(("gray_rst", encode_baseline(a[..., 0], gray=True, restart_interval=3)))
+    out.append(("noninterleaved", encode_baseline(a, ((2, 2), (1, 1), (1, 1)), interleaved=False)))
+    for name, script in [("libjpeg", SCRIPT_LIBJPEG), ("spectral", SCRIPT_SPECTRAL_ONLY), ("deep", SCRIPT_DEEP), ("refine_first", SCRIPT_REFINE_BEFORE_OTHER_BANDS)]:
+        out.append(("prog_" + name, encode_progressive(a, script, ((2, 1), (1, 1), (1, 1)))))
+    out.append(("prog_gray", encode_progressive(a[..., 0], SCRIPT_GRAY, gray=True)))
+    return out
+
+
+def _pillow_layouts(rng, w, h):
+    from PIL import Image
+
+    a = np.array(make_image(w, h, seed=int(rng.integers(1 << 30))))
+    out = []
+    for sub in (0, 1, 2):
+        im = Image.fromarray(a)
+        out.append((f"pil_s{sub}", pillow_jpeg(im, quality=85, subsampling=sub)))
+        out.append((f"pil_s{sub}_prog", pillow_jpeg(im, quality=85, subsampling=sub, progressive=True)))
+        out.append((f"pil_s{sub}_rst", pillow_jpeg(im, quality=85, subsampling=sub, restart_marker_blocks=2)))
+    g = Image.fromarray(a).convert("L")
+    out.append(("pil_gray", pillow_jpeg(g, quality=85)))
+    out.append(("pil_gray_prog", pillow_jpeg(g, quality=85, progressive=True)))
+    return out
+
+
+def random_damage(data, rng):
+    """bytes behind the first SOS overwritten, inserted or deleted (1..5 of them), or the file cut short"""
+    start = _entropy_start(data)
+    if len(data) - start < 8:
+        return data[:start + 1]
+    kind = int(rng.integers(0, 4))
+    if kind == 3:
+        return data[:int(rng.integers(start + 1, len(data) - 2))]
+    b = bytearray(data)
+    for _ in range(int(rng.integers(1, 6))):
+        i = int(rng.integers(start, len(b) - 2))
+        if kind == 0:
+            b[i] = int(rng.integers(0, 256))
+        elif kind == 1:
+            b.insert(i, int(rng.integers(0, 256)))
+        else:
+            del b[i]
+    return bytes(b)
+
+
+def damaged_corpus(seed=2024, n_random=120):
+    """(name, bytes, expected) -- one targeted file per rule and layout, then n_random randomly damaged ones"""
+    rng = np.random.default_rng(seed)
+    clean = _layouts(rng)
+    a = np.array(make_image(40, 33, seed=int(rng.integers(1 << 30))))
+    out = []
+    for kind, want in BASELINE_FAULTS.items():
+        for name, samp in [("444", ((1, 1), (1, 1), (1, 1))), ("420", ((2, 2), (1, 1), (1, 1))), ("440", ((1, 2), (1, 1), (1, 1)))]:
+            for blk in (0, 5):
+                f = (kind, blk, 12 + blk % 4 if blk else 15)
+                out.append((f"{kind}_{name}_b{blk}", encode_baseline(a, samp, fault=f), want))
+        out.append((f"{kind}_gray", encode_baseline(a[..., 0], gray=True, fault=(kind, 3, 13)), want))
+        out.append((f"{kind}_noninterleaved", encode_baseline(a, ((2, 1), (1, 1), (1, 1)), interleaved=False, fault=(kind, 2, 14)), want))
+        out.append((f"{kind}_rst", encode_baseline(a, ((2, 2), (1, 1), (1, 1)), restart_interval=2, fault=(kind, 9, 12)), want))
+    for kind, want in PROGRESSIVE_FAULTS.items():
+        # SCRIPT_LIBJPEG: scan 1 = luma 1..5 (first), scan 4 = luma 6..63 (first), scan 9 = luma 1..63 (refinement)
+        # (an end-of-band run that skips coefficients a later scan refines makes that scan garbage: SCRIPT_SPECTRAL_ONLY has no refinement)
+        script = SCRIPT_SPECTRAL_ONLY if kind == "eobrun_overrun" else SCRIPT_LIBJPEG
+        scans = {"refine_bad_symbol": [9], "run_past_se": [1], "eobrun_overrun": [1, 3]}.get(kind, [1, 4])
+        for sc in scans:
+            out.append((f"{kind}_s{sc}", encode_progressive(a, script, ((2, 2), (1, 1), (1, 1)), fault=(kind, sc)), want))
+        if kind != "run_past_se":  # (SCRIPT_GRAY has no band of fewer than 16 coefficients)
+            gscript = SCRIPT_GRAY[:2] if kind == "eobrun_overrun" else SCRIPT_GRAY
+            out.append((f"{kind}_gray", encode_progressive(a[..., 0], gscript, gray=True, fault=(kind, 2 if kind == "refine_bad_symbol" else 1)), want))
+    for kind, want in RESTART_FAULTS.items():
+        for name, data in clean:
+            if name.endswith("_rst"):
+                out.append((f"{kind}_{name}", restart_fault(data, kind), want))
+                if kind == "interval_emptied":  # the first interval: its bound is byte 0 of the scan
+                    out.append((f"{kind}0_{name}", restart_fault(data, kind, 0), want))
+    for name, data in clean:
+        # the first scan cut short mid-MCU, a marker inside its entropy data: decoded with zeros fed -- unless a restart boundary
+        # follows, which then has no RSTn behind it (rule 5)
+        st = _entropy_start(data)
+        end = st
+        while not (data[end] == 0xFF and data[end + 1] != 0 and not 0xD0 <= data[end + 1] <= 0xD7):
+            end += 1
+        cut = st + (end - st) // 3
+        cut += data[cut - 1] == 0xFF  # (not between the two bytes of a stuffed 0xFF)
+        rst = name.endswith("_rst")
+        out.append((f"truncated_{name}", data[:cut], "refused" if rst else "decoded"))
+        for m in (0xD9, 0xD3, 0xFE):
+            out.append((f"marker_{m:02x}_{name}", data[:cut] + bytes([0xFF, m]) + data[cut:], "refused" if rst and m != 0xD3 else (None if m == 0xFE else "decoded")))
+        out.append((f"fill_{name}", data[:cut] + b"\xff\xff" + data[cut:], None))
+    pool = clean + _pillow_layouts(rng, 61, 45)
+    for i in range(n_random):
+        name, data = pool[i % len(pool)]
+        out.append((f"random{i}_{name}", random_damage(data, rng), None))
+    return out

@@ -1,7 +1,8 @@
 """Differential fuzz of the JPEG path: the same random files through rph_jpeg_pdq_hash_batch with the Huffman streams decoded by the
 host threads and by the device walk (one file per lane) must give the same bytes (hash, quality bit pattern, 256 coefficients), in both
-arithmetic flavours; files with random damage inside their entropy segments, and truncated files, must never hang or fault either path -- nor the
-segment synchronisation (rph_jpeg_set_segments(0, 64) / (0, 1024)) -- their results are unspecified.  Files: random sizes 1..700 px, gray and colour, 4:4:4 / 4:2:2 / 4:2:0 from Pillow (baseline and progressive, optimised
+arithmetic flavours; files with random damage inside their entropy segments, and truncated files, must give the host decoder's results too
+(include/rupphash.h, rph_jpeg_set_entropy) -- with the device walk, with the segment synchronisation (rph_jpeg_set_segments(0, 64) /
+(0, 1024)), and in automatic mode.  Files: random sizes 1..700 px, gray and colour, 4:4:4 / 4:2:2 / 4:2:0 from Pillow (baseline and progressive, optimised
 tables, restart intervals), 4:4:0 / one scan per component / 16-bit tables from tests/jpeg_util.encode_baseline, progressive files with
 scan scripts of their own from tests/jpeg_util.encode_progressive, content from smooth to
 pure noise (long Huffman codes, ZRLs)."""
@@ -86,37 +87,45 @@ while time.time() < t_end:
             b[int(rng.integers(sos + 14, len(b) - 2))] = int(rng.integers(0, 256))
         bad.append(bytes(b))
     if bad:
-        res = []
-        for mode in (0, 1):
-            eng.jpeg_set_entropy(mode)
-            out = eng.jpeg_pdq_hash_batch(bad, flavour=flavour, threads=8)
-            assert out["hash"].shape == (len(bad), 32)
-            res.append(out)
-        # how far the two decoders agree on damaged streams (reported, not required: what a decoder makes of a stream that breaks
-        # T.81 is its own business, but the fewer differences the better)
-        same_status = res[0]["status"] == res[1]["status"]
-        both_ok = (res[0]["status"] == 0) & (res[1]["status"] == 0)
-        damaged_status_differs += int((~same_status).sum())
-        damaged_both_ok += int(both_ok.sum())
-        damaged_hash_differs += int((both_ok & (res[0]["hash"] != res[1]["hash"]).any(axis=1)).sum())
-        # the same damaged files, and truncated ones, with their streams cut into segments that synchronise on the device (a chain that runs
-        # past the end of a scan must neither be trusted nor read behind the stream); then the defaults again
+        # the damaged files, and truncated ones: the host decoder's results (status, hash, quality bit pattern, coefficients) whichever path
+        # walks them -- the device, its segments (a chain that runs past the end of a scan must neither be trusted nor read behind the
+        # stream), automatic mode among the good files of this round
         trunc = []
         for f in files[80:120]:
             sos = f.find(b"\xff\xda")
             if sos >= 0 and len(f) - sos > 60:
                 trunc.append(f[: sos + 14 + int(rng.integers(1, len(f) - sos - 14))])
-        for seg_bytes in (64, 1024):
-            eng.jpeg_set_segments(0, seg_bytes)
-            eng.jpeg_set_entropy(1)
-            out = eng.jpeg_pdq_hash_batch(bad + trunc, flavour=flavour, threads=8)
-            assert out["hash"].shape == (len(bad) + len(trunc), 32)
-        eng.jpeg_set_segments()
-        damaged_total += 2 * len(trunc)
+        dam = bad + trunc
+        res = []
+        for mode, seg_bytes in ((0, None), (1, None), (1, 64), (1, 1024), (2, None)):
+            if seg_bytes:
+                eng.jpeg_set_segments(0, seg_bytes)
+            eng.jpeg_set_entropy(mode)
+            # (automatic mode: the good files five times over, so that the call has the 512 lanes that take sequential files to the device)
+            out = eng.jpeg_pdq_hash_batch(dam + files * 5 if mode == 2 else dam, flavour=flavour, threads=8, want_coeffs=True)
+            eng.jpeg_set_segments()
+            res.append((mode, seg_bytes, {k: (v[: len(dam)] if v is not None else None) for k, v in out.items()}))
+            if mode == 2:
+                for key in ("hash", "valid", "status"):  # the good files of the call keep their results
+                    assert np.array_equal(out[key][len(dam):], np.concatenate([host[key]] * 5)), (seed, rounds, "auto", key)
+        ref = res[0][2]
+        both_ok = ref["status"] == 0
+        damaged_both_ok += int(both_ok.sum())
+        for mode, seg_bytes, out in res[1:]:
+            status_differs = int((out["status"] != ref["status"]).sum())
+            hash_differs = int((both_ok & (out["status"] == 0) & ((out["hash"] != ref["hash"]).any(axis=1) | (out["quality"].view(np.uint32) != ref["quality"].view(np.uint32))
+                                                                  | (out["coeffs"].view(np.uint32) != ref["coeffs"].view(np.uint32)).any(axis=1))).sum())
+            damaged_status_differs += status_differs
+            damaged_hash_differs += hash_differs
+            where = np.argwhere((out["status"] != ref["status"]) | (out["hash"] != ref["hash"]).any(axis=1))[:4].ravel().tolist()
+            assert status_differs == 0 and hash_differs == 0, (seed, rounds, mode, seg_bytes, status_differs, hash_differs, where)
+            assert np.array_equal(out["valid"], ref["valid"]), (seed, rounds, mode, seg_bytes, "valid")
+        damaged_total += len(trunc)
     files_total += len(files)
     damaged_total += len(bad)
     rounds += 1
 eng.jpeg_set_entropy(2)
 eng.close()
 print(f"fuzz_jpeg seed {seed}: {files_total} random files agree bit for bit between host and device entropy decoding (both flavours); "
-      f"{damaged_total} damaged files survived both paths ({damaged_both_ok} of them decodable by both: {damaged_hash_differs} different hashes; {damaged_status_differs} with different status)")
+      f"{damaged_total} damaged files agree too: device, segments and automatic mode against the host decoder ({damaged_both_ok} of them decodable: "
+      f"{damaged_hash_differs} different hashes; {damaged_status_differs} with different status)")
