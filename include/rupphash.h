@@ -429,6 +429,70 @@ int rph_jpeg_pdq_pixel_hash_batch(rph_ctx *ctx, const uint8_t *const *data, cons
                                   int32_t *status_out, uint8_t *pixel_hash32_out);
 
 /* =====================================================================
+ * PNG decode feeding the hasher: the "png" arm of load_image_fast (image 0.25 + png 0.18 with Transformations::EXPAND, 16-bit samples
+ * kept) followed by the pixel hash and generate_pdq_features (scanner.rs:1393-1410).  The host parses the chunks and uploads the
+ * compressed bytes; the device inflates (one wave per stream), unfilters, expands to the hasher's pixels and hashes them where they lie;
+ * only hashes come back.  Colour management chunks (gAMA, iCCP, sRGB, cHRM) are ignored, only the default image (IDAT) is decoded
+ * (APNG frames are not), Adam7 is supported.
+ * Native pixels (rph_png_decode, rph_png_decode_host): the DynamicImage the crates hand over, channels x bit_depth per sample:
+ *   gray 1/2/4/8 -> Luma8 (a sub-8-bit sample v scaled by 255 / (2^d - 1));  gray + tRNS -> LumaA8 (alpha 0 where the unscaled sample
+ *   equals the key, else 255);  RGB 8 -> Rgb8, with tRNS Rgba8 (alpha 0 where R, G and B all equal the key);  palette -> Rgb8, with tRNS
+ *   Rgba8 (entries past a short tRNS opaque, an index past the palette opaque black);  gray+alpha 8 -> LumaA8;  RGBA 8 -> Rgba8;  any of
+ *   these at 16 bit -> L16 / La16 / Rgb16 / Rgba16, samples as native uint16_t.
+ * What is hashed:
+ *   PDQ        to_luma601 (pdqhash.rs:268-284): Luma8 as it is, Rgb8 / Rgba8 through the 601 luma of R, G, B; LumaA8 as Rgba8 (l, l, l, a);
+ *              16-bit images through to_rgb8, each sample v -> round(v / 257) = (v + 128) / 257 (no ties).  That last formula is
+ *              UNPINNED against the crate (its source is not in the reference tree).
+ *   pixel hash blake3 of to_rgba16() (scanner.rs:1393-1404): 8-bit samples v -> v * 257, 16-bit samples as they are, gray replicated into
+ *              R, G, B, a missing alpha 65535.  An 8-bit PNG of a decoded JPEG therefore has the JPEG's pixel hash.
+ * ONE RULE for damaged or hostile files, the same in the host parser (png_host.cpp), the shared inflate (inflate.h: host threads and
+ * device kernel alike) and the unfilter (host and device): a file's status does not depend on the other files of its call or on where
+ * it was inflated.  Parity with the png crate on damaged input is UNPINNED.
+ *   REFUSED (RPH_ERR_INVALID_ARG)
+ *     - a bad signature; an IHDR that is not the first chunk, comes twice or has invalid fields (size 0, depth / colour type pair,
+ *       compression, filter or interlace method);
+ *     - a chunk CRC mismatch before IEND; an unknown critical chunk; a second PLTE or one whose size is not 3 .. 768 in steps of 3;
+ *       a missing PLTE for colour type 3;
+ *     - zlib: CM != 8, CINFO > 7, FCHECK, FDICT; block type 3; stored LEN / NLEN mismatch; over-subscribed or incomplete Huffman codes
+ *       (zlib's exception stands: a literal/length or distance code of a single length-1 code); HLIT > 286, HDIST > 30, a repeat with
+ *       nothing before it or past the end, no end-of-block code; literal/length symbols 286-287, distance symbols 30-31, a bit pattern
+ *       the code does not assign; a distance that reaches before the start of the output; an Adler-32 mismatch; a stream that ends
+ *       (or whose input ends) before its final block and Adler-32 -- in particular one that ends before the image's last byte;
+ *     - a filter type above 4.
+ *   ACCEPTED
+ *     - bytes after the image inside the zlib stream (decoded and checked, not stored); bytes after the Adler-32;
+ *     - chunks after IEND (not read; IEND's own CRC is not checked); a missing IEND, or a last chunk cut short by the end of the file
+ *       (the parse stops there), once the IDAT bytes before it hold a stream that has ended and verified;
+ *     - a tRNS of the wrong size for its colour type, or in colour types 4 / 6: ignored; a palette tRNS longer than the palette: cut;
+ *       a PLTE in a gray image or a truecolour image: not used.
+ *   RPH_ERR_UNSUPPORTED, before anything is allocated: an IHDR whose raw size (filter bytes included) cannot come from the file's IDAT
+ *     bytes (more than 1032 x their length: deflate expands at most 1032:1), or whose raw size exceeds 1 GiB or 2^28 pixels.
+ *   VALID BUT SMALL: an image below 5 px gets valid = 0 with status RPH_OK, and still its pixel hash.
+ * ===================================================================== */
+#define RPH_PNG_INFLATE_HOST 0   /* n_threads host threads inflate (inflate.h); the raw filtered bytes cross PCIe */
+#define RPH_PNG_INFLATE_DEVICE 1 /* one wave per stream on the device; the compressed bytes cross PCIe */
+#define RPH_PNG_INFLATE_AUTO 2   /* default: the device for chunks that inflate 32:1 or more, else the host */
+/* Header only, host code, no context: the native layout rph_png_decode will produce (channels 1-4, bit_depth 8 or 16); returns the
+ * file's status by the rule above (the zlib stream itself is not inflated). */
+int rph_png_info(const uint8_t *data, size_t len, uint32_t *w, uint32_t *h, uint32_t *channels, uint32_t *bit_depth);
+/* The whole decoder on the CPU, no context (tests, tools): native pixels, packed rows, w * h * channels samples of bit_depth bits into
+ * pixels_out (cap_bytes; RPH_ERR_CAPACITY if too small). */
+int rph_png_decode_host(const uint8_t *data, size_t len, void *pixels_out, size_t cap_bytes);
+/* load_image_fast for one PNG, decoded on the device: the same native pixels as rph_png_decode_host. */
+int rph_png_decode(rph_ctx *ctx, const uint8_t *data, size_t len, void *pixels_out, size_t cap_bytes);
+/* n PNG files -> n PDQ hashes (+ optional quality, 256 coefficients, 8 dihedral hashes, as rph_pdq_hash_batch) and optional pixel hashes
+ * (32 bytes each).  Every output after hash32_out may be NULL.  n_threads host threads parse (and inflate in HOST mode; 0 = as many as
+ * the process may use).  status_out[i] by the rule above (the call itself returns RPH_OK); a file that cannot be decoded has zero
+ * outputs and valid 0.  Files of any mix of sizes and types share a call; it is processed in chunks of bounded device memory. */
+int rph_png_pdq_hash_batch(rph_ctx *ctx, const uint8_t *const *data, const size_t *len, uint32_t n, uint32_t n_threads, uint8_t *hash32_out,
+                           float *quality_out, float *coeffs_out, uint8_t *dihedral_out, uint8_t *valid_out, int32_t *status_out,
+                           uint8_t *pixel_hash32_out);
+/* Where rph_png_pdq_hash_batch inflates (RPH_PNG_INFLATE_*); the results are identical in every mode. */
+int rph_png_set_inflate(rph_ctx *ctx, int where);
+/* The PNG path keeps its staging and device buffers in the context between calls; this returns them. */
+int rph_png_release(rph_ctx *ctx);
+
+/* =====================================================================
  * BLAKE3 identity hashes (blake3 crate 1.x, 32-byte output): the two exact hashes the reference computes next to the PDQ hash.
  *   content hash  blake3::keyed_hash(content_key, file_bytes)                     scanner.rs:1343-1347 (the cache key)
  *                 -> rph_blake3_host per file in the scan loop, or rph_blake3_batch(_dev) for a batch of files

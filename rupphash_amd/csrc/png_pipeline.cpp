@@ -1,0 +1,458 @@
+// png_pipeline.cpp -- PNG files -> PDQ hashes and pixel hashes (include/rupphash.h, PNG section).
+//
+// The host threads parse the chunks (png_host.cpp) and either gather the IDAT payloads into pinned staging (DEVICE inflate: the
+// compressed bytes cross PCIe, png_inflate_kernel decodes one stream per wave) or inflate them themselves with the same inflate.h
+// (HOST: the filtered raw bytes cross PCIe).  Everything after that runs on the device: unfilter, expand to the hasher's pixels, the
+// pixel hashes and PDQ over runs of equal geometry, as reconstruct_and_hash does for JPEG.  A call is processed in chunks whose device
+// buffers are kept in the context between calls (rph_png_release returns them).
+#include <sched.h>
+#include <string.h>
+
+#include <algorithm>
+#include <atomic>
+#include <thread>
+#include <vector>
+
+#include "png_host.h"
+#include "rph_internal.h"
+
+int rph_png_launch_inflate(const uint8_t *d_comp, const void *d_streams, uint32_t n, uint8_t *d_raw, int32_t *d_status, hipStream_t s);
+int rph_png_launch_unfilter(uint8_t *d_raw, const void *d_jobs, uint32_t n_jobs, int32_t *d_status, hipStream_t s);
+int rph_png_launch_expand(const uint8_t *d_raw, const void *d_images, const uint32_t *d_list, uint32_t n, uint64_t max_pixels, const uint8_t *d_pal,
+                          uint8_t *d_hp, uint8_t *d_x16, uint8_t *d_nat, hipStream_t s);
+
+namespace {
+
+#define RPH_TRY(expr)                  \
+    do {                               \
+        int rc_ = (expr);              \
+        if (rc_ != RPH_OK) return rc_; \
+    } while (0)
+
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+struct DevBuf {
+    uint8_t *d = nullptr;
+    size_t cap = 0;
+    void release()
+    {
+        if (d) (void)hipFree(d);
+        d = nullptr;
+        cap = 0;
+    }
+    int reserve(size_t bytes)  // the stream that used the buffer has been synchronised
+    {
+        if (cap >= bytes) return RPH_OK;
+        release();
+        bytes = align_up(bytes + bytes / 4 + 64, 4096);
+        RPH_HIP_CHECK(hipMalloc((void **)&d, bytes));
+        cap = bytes;
+        return RPH_OK;
+    }
+};
+struct HostBuf {
+    uint8_t *h = nullptr;
+    size_t cap = 0;
+    void release()
+    {
+        if (h) (void)hipHostFree(h);
+        h = nullptr;
+        cap = 0;
+    }
+    int reserve(size_t bytes)
+    {
+        if (cap >= bytes) return RPH_OK;
+        release();
+        bytes = align_up(bytes + bytes / 4 + 64, 4096);
+        RPH_HIP_CHECK(hipHostMalloc((void **)&h, bytes));
+        cap = bytes;
+        return RPH_OK;
+    }
+};
+
+struct PngPipe {
+    hipStream_t s = nullptr;
+    DevBuf comp, raw, hp, x16, nat, meta, res, b3, status, dig;
+    HostBuf h_comp, h_raw, h_meta, h_res, h_status;
+    void release()
+    {
+        for (DevBuf *b : {&comp, &raw, &hp, &x16, &nat, &meta, &res, &b3, &status, &dig}) b->release();
+        for (HostBuf *b : {&h_comp, &h_raw, &h_meta, &h_res, &h_status}) b->release();
+    }
+};
+
+// Per chunk at most this much (one image larger than a limit forms a chunk of its own)
+constexpr size_t CHUNK_FILES = 8192;
+constexpr uint64_t CHUNK_COMP = (uint64_t)256 << 20, CHUNK_RAW = (uint64_t)768 << 20, CHUNK_PIXELS = (uint64_t)192 << 20;
+// AUTO: the device inflates a chunk whose raw bytes are at least this many times its compressed bytes, the host threads inflate the rest.
+// One wave walks a stream at a rate set by its symbols, so the device pays where a symbol yields many bytes (long copies: screenshots,
+// 1920x1080 RGBA at ~400:1, 4.9 vs 3.8 GB/s of pixels for the host threads) and loses where nearly every byte is a literal (photographic
+// RGB at ~1.5:1: 1.5 vs 3.2 GB/s; palette images at ~9:1: 1.5 vs 1.7 GB/s); DESIGN.md 4.7, profiles/png_rate.txt
+constexpr uint64_t AUTO_DEVICE_MIN_RATIO = 32;
+
+struct Outputs {
+    uint8_t *hash = nullptr, *dihedral = nullptr, *valid = nullptr, *pixel = nullptr, *native = nullptr;
+    float *quality = nullptr, *coeffs = nullptr;
+    int32_t *status = nullptr;
+    bool want_pdq = true;
+};
+
+unsigned usable_threads()
+{
+    unsigned n = std::max(1u, std::thread::hardware_concurrency());
+    cpu_set_t set;
+    if (sched_getaffinity(0, sizeof set, &set) == 0) n = std::min<unsigned>(n, (unsigned)std::max(1, CPU_COUNT(&set)));
+    return std::min(n, 64u);
+}
+
+template <class F>
+void parallel_for(size_t n, unsigned threads, F &&f)
+{
+    std::atomic<size_t> next{0};
+    auto work = [&]() {
+        for (size_t i; (i = next.fetch_add(1)) < n;) f(i);
+    };
+    std::vector<std::thread> ts;
+    for (unsigned t = 1; t < threads && t < n; t++) ts.emplace_back(work);
+    work();
+    for (auto &t : ts) t.join();
+}
+
+// one chunk: files[idx[k]] for k in [0, m), all parsed RPH_OK
+int run_chunk(rph_ctx *ctx, PngPipe &P, const uint8_t *const *data, std::vector<rphp::Parsed> &parsed, const uint32_t *idx, size_t m, unsigned threads,
+              const Outputs &out)
+{
+    hipStream_t s = P.s;
+    int mode = ctx->png_inflate;
+    // raw / compressed placement
+    uint64_t raw_bytes = 0, comp_bytes = 0;
+    std::vector<uint64_t> comp_off(m);
+    for (size_t k = 0; k < m; k++) {
+        rphp::Image &im = parsed[idx[k]].im;
+        im.raw_off = raw_bytes;
+        raw_bytes += align_up(im.raw_bytes, 16);
+        comp_off[k] = comp_bytes;
+        comp_bytes += parsed[idx[k]].idat_bytes;
+    }
+    if (mode == RPH_PNG_INFLATE_AUTO) mode = raw_bytes >= AUTO_DEVICE_MIN_RATIO * comp_bytes ? RPH_PNG_INFLATE_DEVICE : RPH_PNG_INFLATE_HOST;
+    // metadata: images, palettes, streams, unfilter jobs, list
+    size_t n_jobs = 0;
+    for (size_t k = 0; k < m; k++)
+        for (int p = 0; p < 7; p++) n_jobs += parsed[idx[k]].im.pass_h[p] ? 1 : 0;
+    const size_t off_img = 0, off_pal = align_up(m * sizeof(rphp::Image), 256), off_str = off_pal + m * 1024,
+                 off_job = align_up(off_str + m * sizeof(rphp::StreamDesc), 256), off_list = align_up(off_job + n_jobs * sizeof(rphp::UnfilterJob), 256),
+                 off_b3 = align_up(off_list + m * 4, 256), meta_bytes = off_b3 + (m + 1) * 8;
+    RPH_TRY(P.meta.reserve(meta_bytes));
+    RPH_TRY(P.h_meta.reserve(meta_bytes));
+    RPH_TRY(P.raw.reserve(raw_bytes));
+    RPH_TRY(P.status.reserve(m * 4));
+    RPH_TRY(P.h_status.reserve(m * 4));
+    rphp::Image *imgs = reinterpret_cast<rphp::Image *>(P.h_meta.h + off_img);
+    rphp::StreamDesc *sd = reinterpret_cast<rphp::StreamDesc *>(P.h_meta.h + off_str);
+    rphp::UnfilterJob *jobs = reinterpret_cast<rphp::UnfilterJob *>(P.h_meta.h + off_job);
+    uint32_t *list = reinterpret_cast<uint32_t *>(P.h_meta.h + off_list);
+    int32_t *st = reinterpret_cast<int32_t *>(P.h_status.h);
+    size_t j = 0;
+    for (size_t k = 0; k < m; k++) {
+        const rphp::Parsed &pp = parsed[idx[k]];
+        imgs[k] = pp.im;
+        imgs[k].pal = (uint32_t)k;
+        memcpy(P.h_meta.h + off_pal + k * 1024, pp.palette, 1024);
+        sd[k] = rphp::StreamDesc{comp_off[k], pp.idat_bytes, pp.im.raw_off, pp.im.raw_bytes, (uint32_t)k, 0};
+        for (int p = 0; p < 7; p++)
+            if (pp.im.pass_h[p]) jobs[j++] = rphp::UnfilterJob{pp.im.raw_off + pp.im.pass_off[p], pp.im.pass_h[p], pp.im.pass_rb[p], pp.im.unit, (uint32_t)k};
+        st[k] = RPH_OK;
+    }
+    RPH_HIP_CHECK(hipMemcpyAsync(P.meta.d, P.h_meta.h, meta_bytes, hipMemcpyHostToDevice, s));
+    if (mode == RPH_PNG_INFLATE_DEVICE) {
+        RPH_TRY(P.comp.reserve(comp_bytes));
+        RPH_TRY(P.h_comp.reserve(comp_bytes));
+        parallel_for(m, threads, [&](size_t k) { rphp::gather(data[idx[k]], parsed[idx[k]], P.h_comp.h + comp_off[k]); });
+        RPH_HIP_CHECK(hipMemcpyAsync(P.comp.d, P.h_comp.h, comp_bytes, hipMemcpyHostToDevice, s));
+        RPH_HIP_CHECK(hipMemcpyAsync(P.status.d, st, m * 4, hipMemcpyHostToDevice, s));
+        RPH_TRY(rph_png_launch_inflate(P.comp.d, P.meta.d + off_str, (uint32_t)m, P.raw.d, (int32_t *)P.status.d, s));
+    } else {
+        RPH_TRY(P.h_raw.reserve(raw_bytes));
+        parallel_for(m, threads, [&](size_t k) {
+            const rphp::Parsed &pp = parsed[idx[k]];
+            std::vector<uint8_t> z(pp.idat_bytes);
+            rphp::gather(data[idx[k]], pp, z.data());
+            if (rphz::inflate_host(z.data(), z.size(), P.h_raw.h + pp.im.raw_off, pp.im.raw_bytes) != rphz::Z_OK) st[k] = RPH_ERR_INVALID_ARG;
+        });
+        RPH_HIP_CHECK(hipMemcpyAsync(P.raw.d, P.h_raw.h, raw_bytes, hipMemcpyHostToDevice, s));
+        RPH_HIP_CHECK(hipMemcpyAsync(P.status.d, st, m * 4, hipMemcpyHostToDevice, s));
+    }
+    RPH_TRY(rph_png_launch_unfilter(P.raw.d, P.meta.d + off_job, (uint32_t)n_jobs, (int32_t *)P.status.d, s));
+    RPH_HIP_CHECK(hipMemcpyAsync(st, P.status.d, m * 4, hipMemcpyDeviceToHost, s));
+    RPH_HIP_CHECK(hipStreamSynchronize(s));
+    // the decodable images in runs of equal geometry: (w, h, hasher channels, bit depth: 16-bit images take another pixel hash)
+    std::vector<uint32_t> good;
+    for (size_t k = 0; k < m; k++) {
+        out.status[idx[k]] = st[k];
+        if (st[k] == RPH_OK) good.push_back((uint32_t)k);
+    }
+    if (good.empty()) return RPH_OK;
+    std::stable_sort(good.begin(), good.end(), [&](uint32_t a, uint32_t b) {
+        const rphp::Image &x = imgs[a], &y = imgs[b];
+        return x.w != y.w ? x.w < y.w : x.h != y.h ? x.h < y.h : x.hc != y.hc ? x.hc < y.hc : x.out_depth < y.out_depth;
+    });
+    const size_t g = good.size();
+    const bool want_hp = out.want_pdq || out.pixel, want_x16 = out.pixel != nullptr;
+    uint64_t hp_bytes = 0, x16_bytes = 0, nat_bytes = 0, max_px = 0;
+    uint64_t *b3off = reinterpret_cast<uint64_t *>(P.h_meta.h + off_b3);
+    size_t n16 = 0;
+    for (size_t q = 0; q < g; q++) {
+        rphp::Image &im = imgs[good[q]];
+        list[q] = good[q];
+        max_px = std::max<uint64_t>(max_px, (uint64_t)im.w * im.h);
+        if (want_hp) {
+            im.hstride = (uint32_t)(im.hc * align_up(im.w, 8));
+            im.hp_off = hp_bytes;
+            hp_bytes += align_up((uint64_t)im.hstride * im.h, 64);
+        }
+        if (want_x16 && im.out_depth == 16) {
+            im.x16_off = x16_bytes;
+            b3off[n16++] = x16_bytes;
+            x16_bytes += (uint64_t)im.w * im.h * 8;
+        }
+        if (out.native) {
+            im.nat_off = nat_bytes;
+            nat_bytes += align_up((uint64_t)im.w * im.h * im.out_ch * (im.out_depth / 8), 64);
+        }
+    }
+    b3off[n16] = x16_bytes;
+    // buffers of this stage (the stream is idle: reserve may reallocate)
+    const size_t res_bytes = g * (32 + 4 + 1024 + 256 + 1 + 32) + 4 * 256;
+    RPH_TRY(P.hp.reserve(hp_bytes));
+    if (x16_bytes) RPH_TRY(P.x16.reserve(x16_bytes));
+    if (nat_bytes) RPH_TRY(P.nat.reserve(nat_bytes));
+    RPH_TRY(P.res.reserve(res_bytes));
+    RPH_TRY(P.h_res.reserve(res_bytes));
+    size_t b3_scratch = 0;
+    for (size_t q = 0; q < g;) {  // runs of equal geometry
+        const rphp::Image &a = imgs[good[q]];
+        size_t e = q + 1;
+        while (e < g && imgs[good[e]].w == a.w && imgs[good[e]].h == a.h && imgs[good[e]].hc == a.hc && imgs[good[e]].out_depth == a.out_depth) e++;
+        if (out.pixel && a.out_depth != 16) b3_scratch = std::max(b3_scratch, rph_pixel_hash_scratch_bytes((uint32_t)(e - q), a.w, a.h));
+        q = e;
+    }
+    if (b3_scratch) RPH_TRY(P.b3.reserve(b3_scratch));
+    if (n16) RPH_TRY(P.dig.reserve(n16 * 32));
+    RPH_HIP_CHECK(hipMemcpyAsync(P.meta.d, P.h_meta.h, meta_bytes, hipMemcpyHostToDevice, s));
+    RPH_TRY(rph_png_launch_expand(P.raw.d, P.meta.d + off_img, (const uint32_t *)(P.meta.d + off_list), (uint32_t)g, max_px, P.meta.d + off_pal,
+                                  want_hp ? P.hp.d : nullptr, x16_bytes ? P.x16.d : nullptr, nat_bytes ? P.nat.d : nullptr, s));
+    // result sections, each 256-byte aligned
+    const size_t o_q = align_up(g * 32, 256), o_c = o_q + align_up(g * 4, 256), o_d = o_c + g * 1024, o_v = o_d + g * 256, o_px = o_v + align_up(g, 256);
+    uint8_t *R = P.res.d;
+    uint8_t *r_hash = R, *r_q = R + o_q, *r_c = R + o_c, *r_d = R + o_d, *r_v = R + o_v, *r_px = R + o_px;
+    size_t k16 = 0;
+    for (size_t q = 0; q < g;) {
+        const rphp::Image &a = imgs[good[q]];
+        size_t e = q + 1;
+        while (e < g && imgs[good[e]].w == a.w && imgs[good[e]].h == a.h && imgs[good[e]].hc == a.hc && imgs[good[e]].out_depth == a.out_depth) e++;
+        const uint32_t cnt = (uint32_t)(e - q);
+        const size_t istride = align_up((uint64_t)a.hstride * a.h, 64);
+        // pixel hashes first: the reference hashes to_rgba16() before generate_pdq_features (scanner.rs:1393-1410)
+        if (out.pixel) {
+            if (a.out_depth == 16) {
+                // a run of 16-bit images is consecutive in the RGBA16 buffer: hashed below, all 16-bit images of the chunk at once
+                k16 += cnt;
+            } else {
+                RPH_TRY(rph_launch_pixel_hash(P.hp.d + a.hp_off, cnt, a.w, a.h, a.hc, a.hstride, istride, r_px + q * 32, s, b3_scratch ? P.b3.d : nullptr));
+            }
+        }
+        if (out.want_pdq)
+            RPH_TRY(rph_pdq_hash_batch_dev(ctx, P.hp.d + a.hp_off, cnt, a.w, a.h, a.hc, a.hstride, istride, r_hash + q * 32, out.quality ? r_q + q * 4 : nullptr,
+                                           out.coeffs ? r_c + q * 1024 : nullptr, out.dihedral ? r_d + q * 256 : nullptr, r_v + q, s));
+        q = e;
+    }
+    // 16-bit pixel hashes: BLAKE3 of the RGBA16 strings, digests into the result slots of those images (in the same order)
+    std::vector<uint8_t> dig16(n16 * 32);
+    if (n16) RPH_TRY(rph_blake3_batch_dev(ctx, P.x16.d, P.meta.d + off_b3, (uint32_t)n16, nullptr, P.dig.d, s));
+    if (n16) RPH_HIP_CHECK(hipMemcpyAsync(dig16.data(), P.dig.d, n16 * 32, hipMemcpyDeviceToHost, s));
+    (void)k16;
+    RPH_HIP_CHECK(hipMemcpyAsync(P.h_res.h, R, res_bytes, hipMemcpyDeviceToHost, s));
+    if (out.native) RPH_HIP_CHECK(hipMemcpyAsync(out.native, P.nat.d, nat_bytes, hipMemcpyDeviceToHost, s));
+    RPH_HIP_CHECK(hipStreamSynchronize(s));
+    const uint8_t *H = P.h_res.h;
+    const uint8_t *h_hash = H, *h_q = H + o_q, *h_c = H + o_c, *h_d = H + o_d, *h_v = H + o_v, *h_px = H + o_px;
+    size_t i16 = 0;
+    for (size_t q = 0; q < g; q++) {
+        const uint32_t f = idx[good[q]];
+        if (out.want_pdq) {
+            memcpy(out.hash + (size_t)f * 32, h_hash + q * 32, 32);
+            if (out.quality) memcpy(out.quality + f, h_q + q * 4, 4);
+            if (out.coeffs) memcpy(out.coeffs + (size_t)f * 256, h_c + q * 1024, 1024);
+            if (out.dihedral) memcpy(out.dihedral + (size_t)f * 256, h_d + q * 256, 256);
+            if (out.valid) out.valid[f] = h_v[q];
+        }
+        if (out.pixel) {
+            if (imgs[good[q]].out_depth == 16)
+                memcpy(out.pixel + (size_t)f * 32, dig16.data() + 32 * i16++, 32);
+            else
+                memcpy(out.pixel + (size_t)f * 32, h_px + q * 32, 32);
+        }
+    }
+    return RPH_OK;
+}
+
+int run(rph_ctx *ctx, const uint8_t *const *data, const size_t *len, uint32_t n, unsigned threads, const Outputs &out)
+{
+    std::lock_guard<std::mutex> lock(ctx->png_mu);
+    RPH_HIP_CHECK(hipSetDevice(ctx->device));
+    PngPipe *P = static_cast<PngPipe *>(ctx->png);
+    if (!P) {
+        P = new PngPipe();
+        hipError_t e = hipStreamCreateWithFlags(&P->s, hipStreamNonBlocking);
+        if (e != hipSuccess) {
+            delete P;
+            rph_set_error("hipStreamCreate failed: %s", hipGetErrorString(e));
+            return RPH_ERR_HIP;
+        }
+        ctx->png = P;
+    }
+    if (!threads) threads = usable_threads();
+    std::vector<rphp::Parsed> parsed(n);
+    parallel_for(n, threads, [&](size_t i) { out.status[i] = (data[i] && len[i]) ? rphp::parse(data[i], len[i], parsed[i]) : RPH_ERR_INVALID_ARG; });
+    std::vector<uint32_t> ok;
+    for (uint32_t i = 0; i < n; i++)
+        if (out.status[i] == RPH_OK) ok.push_back(i);
+    for (size_t a = 0; a < ok.size();) {
+        size_t b = a;
+        uint64_t comp = 0, raw = 0, px = 0;
+        while (b < ok.size() && b - a < CHUNK_FILES) {
+            const rphp::Parsed &p = parsed[ok[b]];
+            const uint64_t pix = (uint64_t)p.im.w * p.im.h;
+            if (b > a && (comp + p.idat_bytes > CHUNK_COMP || raw + p.im.raw_bytes > CHUNK_RAW || px + pix > CHUNK_PIXELS)) break;
+            comp += p.idat_bytes;
+            raw += p.im.raw_bytes;
+            px += pix;
+            b++;
+        }
+        RPH_TRY(run_chunk(ctx, *P, data, parsed, ok.data() + a, b - a, threads, out));
+        a = b;
+    }
+    return RPH_OK;
+}
+
+}  // namespace
+
+void rph_png_forget(rph_ctx *ctx)
+{
+    PngPipe *P = static_cast<PngPipe *>(ctx->png);
+    if (!P) return;
+    (void)hipStreamSynchronize(P->s);
+    P->release();
+    (void)hipStreamDestroy(P->s);
+    delete P;
+    ctx->png = nullptr;
+}
+
+extern "C" {
+
+int rph_png_info(const uint8_t *data, size_t len, uint32_t *w, uint32_t *h, uint32_t *channels, uint32_t *bit_depth)
+{
+    return rph_guarded("rph_png_info", [&]() -> int {
+        if (!data) return RPH_ERR_INVALID_ARG;
+        rphp::Parsed p;
+        const int rc = rphp::parse(data, len, p);
+        if (rc) return rc;
+        if (w) *w = p.im.w;
+        if (h) *h = p.im.h;
+        if (channels) *channels = p.im.out_ch;
+        if (bit_depth) *bit_depth = p.im.out_depth;
+        return RPH_OK;
+    });
+}
+
+int rph_png_decode_host(const uint8_t *data, size_t len, void *pixels_out, size_t cap_bytes)
+{
+    return rph_guarded("rph_png_decode_host", [&]() -> int {
+        if (!data || !pixels_out) return RPH_ERR_INVALID_ARG;
+        rphp::Parsed p;
+        std::vector<uint8_t> px;
+        const int rc = rphp::decode_host(data, len, p, px);
+        if (rc) return rc;
+        if (px.size() > cap_bytes) {
+            rph_set_error("rph_png_decode_host: %zu bytes needed", px.size());
+            return RPH_ERR_CAPACITY;
+        }
+        memcpy(pixels_out, px.data(), px.size());
+        return RPH_OK;
+    });
+}
+
+int rph_png_decode(rph_ctx *ctx, const uint8_t *data, size_t len, void *pixels_out, size_t cap_bytes)
+{
+    return rph_guarded("rph_png_decode", [&]() -> int {
+        if (!ctx || !data || !pixels_out) return RPH_ERR_INVALID_ARG;
+        rphp::Parsed p;
+        int rc = rphp::parse(data, len, p);
+        if (rc) return rc;
+        const size_t need = (size_t)p.im.w * p.im.h * p.im.out_ch * (p.im.out_depth / 8);
+        if (need > cap_bytes) {
+            rph_set_error("rph_png_decode: %zu bytes needed", need);
+            return RPH_ERR_CAPACITY;
+        }
+        int32_t status = RPH_OK;
+        Outputs o;
+        o.want_pdq = false;
+        o.status = &status;
+        // (the pinned result copy is skipped: the native pixels land in a device buffer and are copied to the caller's memory)
+        std::vector<uint8_t> staging(align_up(need, 64) + 64);
+        o.native = staging.data();
+        RPH_TRY(run(ctx, &data, &len, 1, 1, o));
+        if (status != RPH_OK) return status;
+        memcpy(pixels_out, staging.data(), need);
+        return RPH_OK;
+    });
+}
+
+int rph_png_pdq_hash_batch(rph_ctx *ctx, const uint8_t *const *data, const size_t *len, uint32_t n, uint32_t n_threads, uint8_t *hash32_out,
+                           float *quality_out, float *coeffs_out, uint8_t *dihedral_out, uint8_t *valid_out, int32_t *status_out,
+                           uint8_t *pixel_hash32_out)
+{
+    return rph_guarded("rph_png_pdq_hash_batch", [&]() -> int {
+        if (!ctx || (n && (!data || !len || !hash32_out))) {
+            rph_set_error("rph_png_pdq_hash_batch: null argument");
+            return RPH_ERR_INVALID_ARG;
+        }
+        if (n == 0) return RPH_OK;
+        std::vector<int32_t> st_local(status_out ? 0 : n);
+        std::vector<uint8_t> v_local(valid_out ? 0 : n);
+        Outputs o;
+        o.hash = hash32_out;
+        o.quality = quality_out;
+        o.coeffs = coeffs_out;
+        o.dihedral = dihedral_out;
+        o.valid = valid_out ? valid_out : v_local.data();
+        o.status = status_out ? status_out : st_local.data();
+        o.pixel = pixel_hash32_out;
+        memset(hash32_out, 0, (size_t)n * 32);
+        if (quality_out) memset(quality_out, 0, (size_t)n * 4);
+        if (coeffs_out) memset(coeffs_out, 0, (size_t)n * 1024);
+        if (dihedral_out) memset(dihedral_out, 0, (size_t)n * 256);
+        memset(o.valid, 0, n);
+        if (pixel_hash32_out) memset(pixel_hash32_out, 0, (size_t)n * 32);
+        return run(ctx, data, len, n, n_threads, o);
+    });
+}
+
+int rph_png_set_inflate(rph_ctx *ctx, int where)
+{
+    if (!ctx || where < RPH_PNG_INFLATE_HOST || where > RPH_PNG_INFLATE_AUTO) return RPH_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lock(ctx->png_mu);
+    ctx->png_inflate = where;
+    return RPH_OK;
+}
+
+int rph_png_release(rph_ctx *ctx)
+{
+    if (!ctx) return RPH_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lock(ctx->png_mu);
+    (void)hipSetDevice(ctx->device);
+    rph_png_forget(ctx);
+    return RPH_OK;
+}
+
+}  // extern "C"

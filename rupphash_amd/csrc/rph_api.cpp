@@ -274,6 +274,7 @@ int rph_shutdown(rph_ctx *ctx)
     rph_pipe_forget(ctx);
     rph_resize_forget(ctx);
     rph_jpeg_forget(ctx);
+    rph_png_forget(ctx);
     rph_blake3_forget(ctx);
     rph_jpeg_forget_threads(ctx);
     if (ctx->scratch) (void)hipFree(ctx->scratch);

@@ -70,6 +70,11 @@ struct rph_ctx {
     bool jpeg_leader = false;
     std::vector<void *> jpeg_thread_buffers;  // the callers' pinned coefficient buffers (one per calling thread), freed with the context
     uint64_t serial = 0;                      // distinguishes this context from an earlier one at the same address
+    // PNG path (png_pipeline.cpp): staging and device buffers kept across calls, one batch call at a time; where the zlib streams are
+    // inflated (RPH_PNG_INFLATE_*)
+    std::mutex png_mu;
+    void *png = nullptr;
+    int png_inflate = RPH_PNG_INFLATE_AUTO;
     void *b3 = nullptr;                       // BLAKE3 scratch (blake3_kernels.hip): plan and group values, ordered between streams by an event
 };
 
@@ -160,6 +165,8 @@ void rph_batcher_forget(rph_ctx *ctx);
 void rph_resize_forget(rph_ctx *ctx);
 // jpeg_pipeline.cpp
 void rph_jpeg_forget(rph_ctx *ctx);
+// png_pipeline.cpp
+void rph_png_forget(rph_ctx *ctx);
 // blake3_kernels.hip
 void rph_blake3_forget(rph_ctx *ctx);
 void rph_jpeg_forget_threads(rph_ctx *ctx);

@@ -4,6 +4,7 @@
     group_with_pdqhash / group_files_generic       scanner.rs:1640-1832 up to the union-find
     group_max_dist                                 scanner.rs:2214-2241 (the per-group max_dist of process_raw_groups)
     load_image_fast ("jpg" | "jpeg" arm)           scanner.rs:461-508
+    load_png (the "png" arm, image + png crates)    scanner.rs:461-736 (load_image_fast's generic path for .png)
     pixel_hash (--pixel-hash)                      scanner.rs:1393-1404
     identical_duplicates                           scanner.rs:1843-1864 (analyze_group steps 1-3)
 File-name logic after the union-find (merge_groups_by_stem, the sorting inside process_raw_groups) stays with the caller.
@@ -27,6 +28,19 @@ def load_image_fast(path, data, engine=None, flavour=_lib.RPH_JPEG_ZUNE):
     if ext not in ("jpg", "jpeg"):
         raise ValueError(f"load_image_fast: '{ext}' files are decoded by the host's decoders, not by this library")
     return (engine or default_engine()).jpeg_decode(data, flavour)
+
+
+def load_png(path, data, engine=None):
+    """The png arm of load_image_fast: decoded on the device and returned as the DynamicImage the image crate builds with
+    Transformations::EXPAND -- (h, w) Luma8 / L16, (h, w, 2) LumaA, (h, w, 3) Rgb, (h, w, 4) Rgba; uint8, or uint16 for 16-bit files.
+    A file the damaged-file rule refuses raises RphError (include/rupphash.h, PNG section); other extensions raise ValueError.
+    load_image_fast itself stays JPEG-only: a scan loop routes .png files here."""
+    import os
+
+    ext = os.path.splitext(str(path))[1].lstrip(".").lower()
+    if ext != "png":
+        raise ValueError(f"load_png: '{ext}' is not a PNG file name")
+    return (engine or default_engine()).png_decode(data)
 
 
 def pixel_hash(image, engine=None):
