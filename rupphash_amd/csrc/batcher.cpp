@@ -44,36 +44,20 @@ constexpr size_t kRecordBytes = 32 + 4 + 1 + 1024 + 16;  // hash, quality, valid
 double g_ev[4];  // trace: summed stage times on the GPU timeline (ms; updated by batch leaders, read at teardown)
 
 struct Slot {
-    hipStream_t stream = nullptr;
-    uint8_t *h_px = nullptr, *h_out = nullptr;  // pinned: pixels in, result records out
-    void *d_px = nullptr, *d_out = nullptr;
-    size_t px_cap = 0;
+    hipStream_t stream = nullptr;  // (release: synchronised before the buffers are freed)
+    PinnedBuf h_px, h_out;         // pixels in, result records out
+    DevBuf d_px, d_out;
     bool busy = false;  // owned by a batch (filling, in flight, or results still being read)
 
-    bool ensure(size_t px_bytes)
+    bool ensure(size_t px_bytes)  // only ever called on an idle slot
     {
         if (!stream && hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) return false;
-        if (!h_out) {
-            if (hipHostMalloc((void **)&h_out, (size_t)kSlotImages * kRecordBytes) != hipSuccess || hipMalloc(&d_out, (size_t)kSlotImages * kRecordBytes) != hipSuccess)
-                return false;
-        }
-        if (px_cap < px_bytes) {  // only ever called on an idle slot
-            if (h_px) (void)hipHostFree(h_px);
-            if (d_px) (void)hipFree(d_px);
-            h_px = nullptr;
-            d_px = nullptr;
-            px_cap = 0;
-            if (hipHostMalloc((void **)&h_px, px_bytes) != hipSuccess || hipMalloc(&d_px, px_bytes) != hipSuccess) return false;
-            px_cap = px_bytes;
-        }
-        return true;
+        const size_t out_bytes = (size_t)kSlotImages * kRecordBytes;
+        return h_out.reserve(out_bytes, stream) == RPH_OK && d_out.reserve(out_bytes, stream) == RPH_OK && h_px.reserve(px_bytes, stream) == RPH_OK &&
+               d_px.reserve(px_bytes, stream) == RPH_OK;
     }
     void release()
     {
-        for (void *p : {(void *)h_px, (void *)h_out})
-            if (p) (void)hipHostFree(p);
-        for (void *p : {d_px, d_out})
-            if (p) (void)hipFree(p);
         if (stream) {
             (void)hipStreamSynchronize(stream);
             (void)hipStreamDestroy(stream);
@@ -156,8 +140,8 @@ int run_batch(rph_ctx *ctx, Batch &b)
     b.o_q = (size_t)n * 32;
     b.o_v = b.o_q + (size_t)n * 4;
     b.o_c = align16(b.o_v + n);
-    uint8_t *d_out = (uint8_t *)s.d_out;
-    RPH_HIP_CHECK(hipMemcpyAsync(s.d_px, s.h_px, b.bytes, hipMemcpyHostToDevice, s.stream));
+    uint8_t *d_out = s.d_out.data();
+    RPH_HIP_CHECK(hipMemcpyAsync(s.d_px.data(), s.h_px.data(), b.bytes, hipMemcpyHostToDevice, s.stream));
     if (kTrace) (void)hipEventRecord(ev[1], s.stream);
     for (uint32_t first = 0; first < n;) {  // one launch sequence per run of equal geometry (packed back to back at a uniform stride)
         const Item &a = b.items[first];
@@ -166,7 +150,7 @@ int run_batch(rph_ctx *ctx, Batch &b)
         while (first + m < n && b.items[first + m].w == a.w && b.items[first + m].h == a.h && b.items[first + m].channels == a.channels &&
                b.items[first + m].off == a.off + (size_t)m * stride)
             m++;
-        const int rc = rph_pdq_hash_batch_dev(ctx, (const uint8_t *)s.d_px + a.off, m, a.w, a.h, a.channels, (size_t)a.w * a.channels, stride,
+        const int rc = rph_pdq_hash_batch_dev(ctx, s.d_px.data() + a.off, m, a.w, a.h, a.channels, (size_t)a.w * a.channels, stride,
                                               d_out + (size_t)first * 32, d_out + b.o_q + (size_t)first * 4,
                                               b.want_coeffs ? d_out + b.o_c + (size_t)first * 1024 : nullptr, nullptr, d_out + b.o_v + first, s.stream);
         if (rc != RPH_OK) {
@@ -176,7 +160,7 @@ int run_batch(rph_ctx *ctx, Batch &b)
         first += m;
     }
     if (kTrace) (void)hipEventRecord(ev[2], s.stream);
-    RPH_HIP_CHECK(hipMemcpyAsync(s.h_out, s.d_out, b.want_coeffs ? b.o_c + (size_t)n * 1024 : b.o_v + n, hipMemcpyDeviceToHost, s.stream));
+    RPH_HIP_CHECK(hipMemcpyAsync(s.h_out.data(), s.d_out.data(), b.want_coeffs ? b.o_c + (size_t)n * 1024 : b.o_v + n, hipMemcpyDeviceToHost, s.stream));
     if (kTrace) (void)hipEventRecord(ev[3], s.stream);
     RPH_HIP_CHECK(hipStreamSynchronize(s.stream));
     if (kTrace) {
@@ -256,7 +240,7 @@ extern "C" int rph_pdq_hash_one(rph_ctx *ctx, const uint8_t *px, uint32_t w, uin
         } inside_guard(B);
         // ---- join the open batch, or open one on a free slot
         for (;;) {
-            if (B.open && !B.open->closed && B.open->items.size() < B.open->cap && B.open->bytes + need <= B.open->slot->px_cap) {
+            if (B.open && !B.open->closed && B.open->items.size() < B.open->cap && B.open->bytes + need <= B.open->slot->h_px.capacity()) {
                 b = B.open;
                 break;
             }
@@ -297,7 +281,7 @@ extern "C" int rph_pdq_hash_one(rph_ctx *ctx, const uint8_t *px, uint32_t w, uin
         lock.unlock();
         // ---- copy this caller's pixels into its place (outside the lock: copies of different callers run in parallel)
         {
-            uint8_t *dst = b->slot->h_px + off;
+            uint8_t *dst = b->slot->h_px.data() + off;
             if (row_stride == line)
                 std::memcpy(dst, px, image_bytes);
             else
@@ -350,7 +334,7 @@ extern "C" int rph_pdq_hash_one(rph_ctx *ctx, const uint8_t *px, uint32_t w, uin
         const int rc = b->status;
         lock.unlock();
         if (rc == RPH_OK) {
-            const uint8_t *out = b->slot->h_out;
+            const uint8_t *out = b->slot->h_out.data();
             std::memcpy(hash32_out, out + (size_t)slot_index * 32, 32);
             if (quality_out) std::memcpy(quality_out, out + b->o_q + (size_t)slot_index * 4, 4);
             if (coeffs_out) std::memcpy(coeffs_out, out + b->o_c + (size_t)slot_index * 1024, 1024);

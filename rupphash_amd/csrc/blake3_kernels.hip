@@ -303,65 +303,6 @@ Key key_of(const uint8_t *key32)
     return k;
 }
 
-// The context's BLAKE3 scratch (plan + group values), shared by every caller stream: a call holds ctx->mu while it enqueues, waits on
-// the stream of the previous user's event, and records its own
-struct B3Scratch {
-    void *p = nullptr;
-    size_t bytes = 0;
-    hipEvent_t done = nullptr;
-    hipStream_t last = nullptr;
-    bool used = false;
-};
-
-int scratch_acquire(rph_ctx *ctx, size_t bytes, hipStream_t s, void **out)
-{
-    if (!ctx->b3) ctx->b3 = new B3Scratch();
-    B3Scratch &B = *static_cast<B3Scratch *>(ctx->b3);
-    if (!B.done) RPH_HIP_CHECK(hipEventCreateWithFlags(&B.done, hipEventDisableTiming));
-    if (B.bytes < bytes) {
-        if (B.used) RPH_HIP_CHECK(hipEventSynchronize(B.done));
-        if (B.p) (void)hipFree(B.p);
-        B.p = nullptr;
-        B.bytes = 0;
-        bytes += bytes / 4;
-        RPH_HIP_CHECK(hipMalloc(&B.p, bytes));
-        B.bytes = bytes;
-    } else if (B.used && B.last != s) {
-        RPH_HIP_CHECK(hipStreamWaitEvent(s, B.done, 0));
-    }
-    *out = B.p;
-    return RPH_OK;
-}
-
-int scratch_release(rph_ctx *ctx, hipStream_t s)
-{
-    B3Scratch &B = *static_cast<B3Scratch *>(ctx->b3);
-    RPH_HIP_CHECK(hipEventRecord(B.done, s));
-    B.last = s;
-    B.used = true;
-    return RPH_OK;
-}
-
-// a device buffer owned by one call, freed when it returns
-struct DevMem {
-    void *p = nullptr;
-    ~DevMem()
-    {
-        if (p) (void)hipFree(p);
-    }
-    int alloc(size_t bytes)
-    {
-        RPH_HIP_CHECK(hipMalloc(&p, bytes ? bytes : 4));
-        return RPH_OK;
-    }
-};
-
-#define RPH_B3_TRY(expr)               \
-    do {                               \
-        int rc_ = (expr);              \
-        if (rc_ != RPH_OK) return rc_; \
-    } while (0)
-
 bool pixel_geometry_ok(uint32_t n, uint32_t w, uint32_t h, uint32_t channels, size_t row_stride, size_t image_stride)
 {
     if (channels != 1 && channels != 3 && channels != 4) return false;
@@ -406,7 +347,6 @@ int rph_launch_pixel_hash(const uint8_t *d_px, uint32_t n, uint32_t w, uint32_t 
 }
 
 namespace {
-size_t align_up_b3(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // the API's pixel hash: group values in the context's scratch
 int pixel_hash_on(rph_ctx *ctx, const uint8_t *d_px, uint32_t n, uint32_t w, uint32_t h, uint32_t channels, size_t row_stride, size_t image_stride,
@@ -415,22 +355,11 @@ int pixel_hash_on(rph_ctx *ctx, const uint8_t *d_px, uint32_t n, uint32_t w, uin
     const size_t need = rph_pixel_hash_scratch_bytes(n, w, h);
     if (!need) return rph_launch_pixel_hash(d_px, n, w, h, channels, row_stride, image_stride, d_hash32, s, nullptr);
     std::lock_guard<std::mutex> lock(ctx->mu);
-    void *scratch = nullptr;
-    RPH_B3_TRY(scratch_acquire(ctx, need, s, &scratch));
-    RPH_B3_TRY(rph_launch_pixel_hash(d_px, n, w, h, channels, row_stride, image_stride, d_hash32, s, scratch));
-    return scratch_release(ctx, s);
+    RPH_TRY(ctx->b3_scratch.acquire(s, need, need + need / 4));
+    RPH_TRY(rph_launch_pixel_hash(d_px, n, w, h, channels, row_stride, image_stride, d_hash32, s, ctx->b3_scratch.data()));
+    return ctx->b3_scratch.publish(s);
 }
 }  // namespace
-
-void rph_blake3_forget(rph_ctx *ctx)
-{
-    if (!ctx->b3) return;
-    B3Scratch *B = static_cast<B3Scratch *>(ctx->b3);
-    if (B->p) (void)hipFree(B->p);
-    if (B->done) (void)hipEventDestroy(B->done);
-    delete B;
-    ctx->b3 = nullptr;
-}
 
 extern "C" {
 
@@ -497,11 +426,11 @@ int rph_blake3_batch_dev(rph_ctx *ctx, const void *d_data, const void *d_offsets
             return RPH_ERR_UNSUPPORTED;
         }
         const uint32_t cap = (uint32_t)cap64;
-        const size_t first_bytes = align_up_b3(((size_t)n + 1) * 4);
+        const size_t first_bytes = align_up(((size_t)n + 1) * 4, 256);
         std::lock_guard<std::mutex> lock(ctx->mu);
-        void *scratch = nullptr;
-        RPH_B3_TRY(scratch_acquire(ctx, first_bytes + (size_t)cap * 32, s, &scratch));
-        uint32_t *d_first = (uint32_t *)scratch, *d_cvs = (uint32_t *)((uint8_t *)scratch + first_bytes);
+        const size_t need = first_bytes + (size_t)cap * 32;
+        RPH_TRY(ctx->b3_scratch.acquire(s, need, need + need / 4));
+        uint32_t *d_first = ctx->b3_scratch.as<uint32_t>(), *d_cvs = (uint32_t *)(ctx->b3_scratch.data() + first_bytes);
         const Key key = key_of(key32);
         const uint32_t flags = key32 ? B3_KEYED_HASH : 0u;
         hipLaunchKernelGGL(b3_plan_kernel, dim3(1), dim3(1024), 0, s, off, n, d_first);
@@ -513,7 +442,7 @@ int rph_blake3_batch_dev(rph_ctx *ctx, const void *d_data, const void *d_offsets
         hipLaunchKernelGGL(b3_fold_kernel, dim3(n), dim3(64), 0, s, d_first, 0u, cap, key, flags, d_cvs,
                            (uint8_t *)d_digest32);
         RPH_HIP_CHECK(hipGetLastError());
-        return scratch_release(ctx, s);
+        return ctx->b3_scratch.publish(s);
     });
 }
 
@@ -537,15 +466,15 @@ int rph_blake3_batch(rph_ctx *ctx, const uint8_t *const *data, const size_t *len
         std::vector<uint8_t> packed(off[n]);
         for (uint32_t i = 0; i < n; i++)
             if (len[i]) memcpy(packed.data() + off[i], data[i], len[i]);
-        DevMem d_data, d_off, d_dig;
-        RPH_B3_TRY(d_data.alloc(off[n]));
-        RPH_B3_TRY(d_off.alloc(off.size() * 8));
-        RPH_B3_TRY(d_dig.alloc((size_t)n * 32));
+        DevBuf d_data, d_off, d_dig;
+        RPH_TRY(d_data.alloc(off[n] ? off[n] : 4));
+        RPH_TRY(d_off.alloc(off.size() * 8));
+        RPH_TRY(d_dig.alloc((size_t)n * 32));
         hipStream_t s = ctx->stream;
-        if (off[n]) RPH_HIP_CHECK(hipMemcpyAsync(d_data.p, packed.data(), off[n], hipMemcpyHostToDevice, s));
-        RPH_HIP_CHECK(hipMemcpyAsync(d_off.p, off.data(), off.size() * 8, hipMemcpyHostToDevice, s));
-        RPH_B3_TRY(rph_blake3_batch_dev(ctx, d_data.p, d_off.p, n, key32, d_dig.p, s));
-        RPH_HIP_CHECK(hipMemcpyAsync(digest32_out, d_dig.p, (size_t)n * 32, hipMemcpyDeviceToHost, s));
+        if (off[n]) RPH_HIP_CHECK(hipMemcpyAsync(d_data.data(), packed.data(), off[n], hipMemcpyHostToDevice, s));
+        RPH_HIP_CHECK(hipMemcpyAsync(d_off.data(), off.data(), off.size() * 8, hipMemcpyHostToDevice, s));
+        RPH_TRY(rph_blake3_batch_dev(ctx, d_data.data(), d_off.data(), n, key32, d_dig.data(), s));
+        RPH_HIP_CHECK(hipMemcpyAsync(digest32_out, d_dig.data(), (size_t)n * 32, hipMemcpyDeviceToHost, s));
         RPH_HIP_CHECK(hipStreamSynchronize(s));
         return RPH_OK;
     });
@@ -579,13 +508,13 @@ int rph_pixel_hash_batch(rph_ctx *ctx, const uint8_t *px, uint32_t n, uint32_t w
         RPH_HIP_CHECK(hipSetDevice(ctx->device));
         const size_t one = h ? row_stride * (h - 1) + (size_t)w * channels : 0;
         const size_t bytes = w && h ? (size_t)(n - 1) * image_stride + one : 0;
-        DevMem d_px, d_h;
-        RPH_B3_TRY(d_px.alloc(bytes));
-        RPH_B3_TRY(d_h.alloc((size_t)n * 32));
+        DevBuf d_px, d_h;
+        RPH_TRY(d_px.alloc(bytes ? bytes : 4));
+        RPH_TRY(d_h.alloc((size_t)n * 32));
         hipStream_t s = ctx->stream;
-        if (bytes) RPH_HIP_CHECK(hipMemcpyAsync(d_px.p, px, bytes, hipMemcpyHostToDevice, s));
-        RPH_B3_TRY(pixel_hash_on(ctx, (const uint8_t *)d_px.p, n, w, h, channels, row_stride, image_stride, (uint8_t *)d_h.p, s));
-        RPH_HIP_CHECK(hipMemcpyAsync(hash32_out, d_h.p, (size_t)n * 32, hipMemcpyDeviceToHost, s));
+        if (bytes) RPH_HIP_CHECK(hipMemcpyAsync(d_px.data(), px, bytes, hipMemcpyHostToDevice, s));
+        RPH_TRY(pixel_hash_on(ctx, d_px.data(), n, w, h, channels, row_stride, image_stride, d_h.data(), s));
+        RPH_HIP_CHECK(hipMemcpyAsync(hash32_out, d_h.data(), (size_t)n * 32, hipMemcpyDeviceToHost, s));
         RPH_HIP_CHECK(hipStreamSynchronize(s));
         return RPH_OK;
     });

@@ -816,17 +816,8 @@ static int prepare_sorted(rph_ctx *ctx, const uint8_t *d_hashes, uint64_t n, int
                                                      (uint32_t *)nullptr, (int)n, 0, 9, stream));
     const size_t o_sorted = 0, o_kin = o_sorted + align256(n * 32), o_kout = o_kin + align256(n * 2), o_iin = o_kout + align256(n * 2),
                  o_iout = o_iin + align256(n * 4), o_temp = o_iout + align256(n * 4), need = o_temp + align256(temp_bytes);
-    if (ctx->sweep_scratch_bytes < need) {
-        RPH_HIP_CHECK(hipDeviceSynchronize());  // kernels of any stream may still be using the old scratch
-        if (ctx->sweep_scratch) RPH_HIP_CHECK(hipFree(ctx->sweep_scratch));
-        ctx->sweep_scratch = nullptr;
-        ctx->sweep_scratch_bytes = 0;
-        RPH_HIP_CHECK(hipMalloc(&ctx->sweep_scratch, need + need / 4));
-        ctx->sweep_scratch_bytes = need + need / 4;
-    }
-    if (!ctx->sweep_done) RPH_HIP_CHECK(hipEventCreateWithFlags(&ctx->sweep_done, hipEventDisableTiming));
-    if (ctx->sweep_used && ctx->sweep_stream != stream) RPH_HIP_CHECK(hipStreamWaitEvent(stream, ctx->sweep_done, 0));
-    uint8_t *base = (uint8_t *)ctx->sweep_scratch;
+    RPH_TRY(ctx->sweep_scratch.acquire(stream, need, need + need / 4));
+    uint8_t *base = ctx->sweep_scratch.data();
     uint16_t *kin = (uint16_t *)(base + o_kin), *kout = (uint16_t *)(base + o_kout);
     uint32_t *iin = (uint32_t *)(base + o_iin), *iout = (uint32_t *)(base + o_iout);
     const unsigned grid = (unsigned)std::min<unsigned long long>((n + 255) / 256, 65536);
@@ -931,11 +922,7 @@ int rph_launch_hamming_sweep(rph_ctx *ctx, const uint8_t *d_rows, uint32_t n_var
         }
         RPH_HIP_CHECK(hipGetLastError());
     }
-    if (zero_one) {  // later users of the sorted scratch on another stream wait for this sweep
-        RPH_HIP_CHECK(hipEventRecord(ctx->sweep_done, stream));
-        ctx->sweep_stream = stream;
-        ctx->sweep_used = true;
-    }
+    if (zero_one) RPH_TRY(ctx->sweep_scratch.publish(stream));
     return RPH_OK;
 }
 

@@ -1,8 +1,6 @@
 // jpeg_pipeline.cpp -- host side of the JPEG path (row N3 of SURVEY 8f) and its C ABI: chunking, the two lanes of staging / device
 // buffers, host entropy decoding or stream preparation for the device walk, reconstruction + hashing sub-batches, the one-file queue.
 // The kernels are in jpeg_kernels.hip, the entropy decoder and the stream preparation in jpeg_host.cpp.
-#include <sched.h>
-
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -19,34 +17,17 @@
 
 namespace {
 
-#define RPH_TRY(expr)                  \
-    do {                               \
-        int rc_ = (expr);              \
-        if (rc_ != RPH_OK) return rc_; \
-    } while (0)
+// growth of the pinned buffers: a quarter more, to whole 4 KiB pages
+inline size_t pinned_slack(size_t bytes) { return align_up(bytes + bytes / 4, 4096); }
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-// A pinned host buffer with its device twin, grown on demand (the caller has synchronised the stream that used it)
+// A pinned host buffer with its device twin, grown together; `user` is the stream whose work uses them
 struct Twin {
-    uint8_t *h = nullptr, *d = nullptr;
-    size_t cap = 0;
-    void release()
+    PinnedBuf h;
+    DevBuf d;
+    int reserve(size_t bytes, hipStream_t user)
     {
-        if (h) (void)hipHostFree(h);
-        if (d) (void)hipFree(d);
-        h = d = nullptr;
-        cap = 0;
-    }
-    int reserve(size_t bytes, bool host = true, bool dev = true)
-    {
-        if (cap >= bytes) return RPH_OK;
-        release();
-        bytes = align_up(bytes + bytes / 4, 4096);
-        if (host) RPH_HIP_CHECK(hipHostMalloc((void **)&h, bytes));
-        if (dev) RPH_HIP_CHECK(hipMalloc((void **)&d, bytes));
-        cap = bytes;
-        return RPH_OK;
+        RPH_TRY(h.reserve(bytes, pinned_slack(bytes), user));
+        return d.reserve(bytes, pinned_slack(bytes), user);
     }
 };
 
@@ -72,34 +53,21 @@ struct ResView {  // the per-image result arrays inside one buffer laid out for 
 //                   prepares streams; reconstruction + hashing then runs over the chunk in sub-batches through small buffers
 // ---------------------------------------------------------------------------------------------------------------------------
 struct Slot {
-    hipStream_t stream = nullptr;
+    hipStream_t stream = nullptr;  // (release: synchronised before the buffers are freed)
     hipEvent_t done = nullptr;  // device entropy: the slot's chunk (work on another slot's stream) has delivered its results
     Twin coef;              // host entropy: pinned staging + device; device entropy: unused
     Twin stream_bytes;      // device entropy: de-stuffed entropy bytes
     Twin meta;              // descriptors (planes | images | tables | HImage | order | DeviceLut)
-    Twin res;               // results
+    PinnedBuf res;          // results
     size_t res_images = 0;
     bool res_pixel = false;  // the results buffer has room for the pixel hashes (ResView::pixel)
-    uint8_t *d_segwork = nullptr;  // device entropy, segmented streams: states | records of round 0 | out positions | segment -> file map
-    size_t segwork_cap = 0;
-    unsigned long long *d_pmask = nullptr;  // device entropy, progressive files: which coefficients are nonzero, one word per block
-    size_t pmask_cap = 0;
-    PCorr *d_pcorr = nullptr;               // and the records of their AC refinement scans (jpeg_device.h)
-    size_t pcorr_cap = 0;
-    uint8_t *d_pdc = nullptr;               // and the bits of their DC refinement scans, one byte per block
-    size_t pdc_cap = 0;
+    DevBuf segwork;  // device entropy, segmented streams: states | records of round 0 | out positions | segment -> file map
+    DevBuf pmask;    // device entropy, progressive files: which coefficients are nonzero, one word per block
+    DevBuf pcorr;    // and the records of their AC refinement scans (PCorr, jpeg_device.h)
+    DevBuf pdc;      // and the bits of their DC refinement scans, one byte per block
     void release()
     {
         if (stream) (void)hipStreamSynchronize(stream);
-        if (res.d == res.h) res.d = nullptr;  // (one allocation: see reserve_res)
-        coef.release();
-        stream_bytes.release();
-        meta.release();
-        res.release();
-        if (d_segwork) (void)hipFree(d_segwork);
-        if (d_pmask) (void)hipFree(d_pmask);
-        if (d_pcorr) (void)hipFree(d_pcorr);
-        if (d_pdc) (void)hipFree(d_pdc);
         if (stream) (void)hipStreamDestroy(stream);
         if (done) (void)hipEventDestroy(done);
         *this = Slot();
@@ -110,16 +78,14 @@ struct Slot {
         if (!done) RPH_HIP_CHECK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
         return RPH_OK;
     }
-    int reserve_res(size_t images, bool pixel)  // the caller has made sure nothing in flight still uses the slot's buffers
+    int reserve_res(size_t images, bool pixel)
     {
         if (res_images >= images && (res_pixel || !pixel)) return RPH_OK;
-        RPH_HIP_CHECK(hipStreamSynchronize(stream));
         images += images / 4;
         // pinned host memory the kernels write into directly (32 B .. 1.3 KB per image cross PCIe as they are produced): a copy back at the
         // end of a chunk queued behind the other lanes' kernels and held the lane up for tens of milliseconds
-        if (res.d == res.h) res.d = nullptr;
-        RPH_TRY(res.reserve(images * (RES_BYTES + (pixel ? 32 : 0)), true, false));
-        res.d = res.h;
+        const size_t bytes = images * (RES_BYTES + (pixel ? 32 : 0));
+        RPH_TRY(res.reserve(bytes, pinned_slack(bytes), stream));
         res_images = images;
         res_pixel = pixel;
         return RPH_OK;
@@ -127,63 +93,32 @@ struct Slot {
 };
 constexpr int JPEG_LANES = 4;  // chunks in flight in the device-entropy pipeline (the host-entropy pipeline uses the first two)
 struct JpegPipe {
-    Slot slot[JPEG_LANES];
+    // (~JpegPipe synchronises the slots' streams, which use every buffer here, before the members are freed)
+    DevBuf coef;  // device entropy: the chunk's coefficient buffer (one: chunks run back to back on one stream)
     // reconstruction buffers (sample planes, packed pixels) shared by the slots' sub-batches: used in stream order, one sub-batch at a
     // time per stream; each slot owns one pair
-    uint8_t *d_planes[JPEG_LANES] = {}, *d_out[JPEG_LANES] = {};
+    DevBuf planes[JPEG_LANES], pixels[JPEG_LANES];
     size_t recon_coef_bytes[JPEG_LANES] = {};
     // pixel hashes: the group values of the images above 8192 px (allocated by the first call that asks for pixel hashes)
-    void *d_b3[JPEG_LANES] = {};
-    size_t b3_bytes[JPEG_LANES] = {};
-    // device entropy: the chunk's coefficient buffer (one: chunks run back to back on one stream)
-    int16_t *d_coef = nullptr;
-    size_t d_coef_bytes = 0;
+    DevBuf b3[JPEG_LANES];
+    Slot slot[JPEG_LANES];
     // the per-file records of the last call (std::vector<Job>, defined below), kept: a call of 100 000 files spent 15 ms constructing and
     // first-touching 120 MB of them before the first byte moved
     void *jobs_cache = nullptr;
     void (*jobs_cache_free)(void *) = nullptr;
-    void release()
+    ~JpegPipe()
     {
         if (jobs_cache) jobs_cache_free(jobs_cache);
-        jobs_cache = nullptr;
-        for (int b = 0; b < JPEG_LANES; b++) {
-            slot[b].release();
-            if (d_planes[b]) (void)hipFree(d_planes[b]);
-            if (d_out[b]) (void)hipFree(d_out[b]);
-            if (d_b3[b]) (void)hipFree(d_b3[b]);
-            d_planes[b] = d_out[b] = nullptr;
-            d_b3[b] = nullptr;
-            recon_coef_bytes[b] = b3_bytes[b] = 0;
-        }
-        if (d_coef) (void)hipFree(d_coef);
-        d_coef = nullptr;
-        d_coef_bytes = 0;
+        for (Slot &S : slot) S.release();
     }
     // sample planes and packed pixels for sub-batches of up to `coef_need` bytes of coefficients
     int reserve_recon(int b, size_t coef_need, hipStream_t s)
     {
         if (recon_coef_bytes[b] >= coef_need) return RPH_OK;
-        RPH_HIP_CHECK(hipStreamSynchronize(s));
-        if (d_planes[b]) (void)hipFree(d_planes[b]);
-        if (d_out[b]) (void)hipFree(d_out[b]);
-        d_planes[b] = d_out[b] = nullptr;
-        recon_coef_bytes[b] = 0;
-        RPH_HIP_CHECK(hipMalloc((void **)&d_planes[b], coef_need / 2 + 256));  // 64 bytes of samples per 128 bytes of coefficients
+        RPH_TRY(planes[b].reserve(coef_need / 2 + 256, s));  // 64 bytes of samples per 128 bytes of coefficients
         // packed pixels never exceed the coefficient bytes (4:2:0: both 3 w h; Luma8: w h against 2 w h), plus row / image padding
-        RPH_HIP_CHECK(hipMalloc((void **)&d_out[b], coef_need + coef_need / 8 + 65536));
+        RPH_TRY(pixels[b].reserve(coef_need + coef_need / 8 + 65536, s));
         recon_coef_bytes[b] = coef_need;
-        return RPH_OK;
-    }
-    int reserve_b3(int b, size_t bytes, hipStream_t s)
-    {
-        if (b3_bytes[b] >= bytes) return RPH_OK;
-        RPH_HIP_CHECK(hipStreamSynchronize(s));
-        if (d_b3[b]) (void)hipFree(d_b3[b]);
-        d_b3[b] = nullptr;
-        b3_bytes[b] = 0;
-        bytes += bytes / 4;
-        RPH_HIP_CHECK(hipMalloc(&d_b3[b], bytes));
-        b3_bytes[b] = bytes;
         return RPH_OK;
     }
 };
@@ -357,52 +292,6 @@ inline bool trace_on() { return trace_level() == 1; }
     } while (0)
 static double g_trace_t0 = 0;
 
-// Host threads when the caller does not say: what this process may actually use (its affinity mask, and the cgroup CPU quota a
-// container runs under -- hardware_concurrency() reports the machine's 256 threads inside a 16-CPU container)
-unsigned default_threads()
-{
-    unsigned n = std::max(1u, std::thread::hardware_concurrency());
-    cpu_set_t set;
-    if (sched_getaffinity(0, sizeof set, &set) == 0) n = std::min<unsigned>(n, (unsigned)std::max(1, CPU_COUNT(&set)));
-    long long quota = -1, period = 100000;
-    if (FILE *f = fopen("/sys/fs/cgroup/cpu.max", "r")) {  // cgroup v2: "max 100000" or "1600000 100000"
-        char q[32] = "";
-        if (fscanf(f, "%31s %lld", q, &period) == 2 && strcmp(q, "max") != 0) quota = atoll(q);
-        fclose(f);
-    } else if (FILE *g = fopen("/sys/fs/cgroup/cpu/cpu.cfs_quota_us", "r")) {  // cgroup v1
-        if (fscanf(g, "%lld", &quota) != 1) quota = -1;
-        fclose(g);
-        if (FILE *h = fopen("/sys/fs/cgroup/cpu/cpu.cfs_period_us", "r")) {
-            if (fscanf(h, "%lld", &period) != 1) period = 100000;
-            fclose(h);
-        }
-    }
-    if (quota > 0 && period > 0) n = std::min<unsigned>(n, (unsigned)std::max<long long>(1, (quota + period - 1) / period));
-    return n;
-}
-
-template <class F>
-void parallel_for(size_t first, size_t last, unsigned threads, F &&body)
-{
-    std::atomic<size_t> next{first};
-    auto work = [&]() {
-        for (;;) {
-            const size_t i = next.fetch_add(1);
-            if (i >= last) return;
-            body(i);
-        }
-    };
-    const unsigned nt = (unsigned)std::min<size_t>(std::max(1u, threads), last > first ? last - first : 1);
-    if (nt <= 1) {
-        work();
-        return;
-    }
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t + 1 < nt; t++) th.emplace_back(work);
-    work();
-    for (auto &t : th) t.join();
-}
-
 struct Outputs {
     uint8_t *hash = nullptr;
     float *quality = nullptr;
@@ -528,10 +417,10 @@ int reconstruct_and_hash(rph_ctx *ctx, JpegPipe &P, int b, Slot &S, Jobs &jobs, 
         max_groups = std::max<uint32_t>(max_groups, (uint32_t)(((f.w + 7) / 8) * (size_t)f.h));
     }
     if (i0 == UINT32_MAX) return RPH_OK;
-    const JPlane *dp = reinterpret_cast<const JPlane *>(S.meta.d + D.off_planes) + p0;
-    const JImage *di = reinterpret_cast<const JImage *>(S.meta.d + D.off_images) + i0;
-    const uint16_t *dq = reinterpret_cast<const uint16_t *>(S.meta.d + D.off_tables);
-    const JImage *hi_all = reinterpret_cast<const JImage *>(S.meta.h + D.off_images);
+    const JPlane *dp = reinterpret_cast<const JPlane *>(S.meta.d.data() + D.off_planes) + p0;
+    const JImage *di = reinterpret_cast<const JImage *>(S.meta.d.data() + D.off_images) + i0;
+    const uint16_t *dq = reinterpret_cast<const uint16_t *>(S.meta.d.data() + D.off_tables);
+    const JImage *hi_all = reinterpret_cast<const JImage *>(S.meta.h.data() + D.off_images);
     uint32_t n_fused = 0, max_tiles = 0;
     for (uint32_t q = i0; q < i1; q++)
         if (hi_all[q].fused) {
@@ -539,12 +428,12 @@ int reconstruct_and_hash(rph_ctx *ctx, JpegPipe &P, int b, Slot &S, Jobs &jobs, 
             max_tiles = std::max(max_tiles, hi_all[q].tiles_x * hi_all[q].tiles_y);
         }
     if (n_fused < i1 - i0) {  // (the plane kernels skip the images the fused kernel takes)
-        RPH_TRY(rph_jpeg_launch_idct(flavour, max_blocks, p1 - p0, s, d_coef, dq, dp, P.d_planes[b], D.d_refs, D.d_corr, D.d_dcbits));
-        RPH_TRY(rph_jpeg_launch_color(flavour, max_groups, i1 - i0, s, P.d_planes[b], di, P.d_out[b]));
+        RPH_TRY(rph_jpeg_launch_idct(flavour, max_blocks, p1 - p0, s, d_coef, dq, dp, P.planes[b].data(), D.d_refs, D.d_corr, D.d_dcbits));
+        RPH_TRY(rph_jpeg_launch_color(flavour, max_groups, i1 - i0, s, P.planes[b].data(), di, P.pixels[b].data()));
     }
-    if (n_fused) RPH_TRY(rph_jpeg_launch_fused(flavour, max_tiles, i1 - i0, s, d_coef, dq, dp, di, P.d_out[b], D.d_refs, D.d_corr, D.d_dcbits));
-    ResView R(S.res.d, S.res_images);
-    const JImage *hi = reinterpret_cast<const JImage *>(S.meta.h + D.off_images);
+    if (n_fused) RPH_TRY(rph_jpeg_launch_fused(flavour, max_tiles, i1 - i0, s, d_coef, dq, dp, di, P.pixels[b].data(), D.d_refs, D.d_corr, D.d_dcbits));
+    ResView R(S.res.data(), S.res_images);
+    const JImage *hi = reinterpret_cast<const JImage *>(S.meta.h.data() + D.off_images);
     // pixel hashes (scanner.rs:1393-1404, before generate_pdq_features: images below 5 px have one too), runs of equal geometry
     for (size_t r = r0; out.pixel_hash && r < r1;) {
         if (D.image_of[r] == UINT32_MAX) {
@@ -556,9 +445,9 @@ int reconstruct_and_hash(rph_ctx *ctx, JpegPipe &P, int b, Slot &S, Jobs &jobs, 
         size_t e = r + 1;
         while (e < r1 && D.image_of[e] != UINT32_MAX && jobs[idx[first + e]].frame.w == f.w && jobs[idx[first + e]].frame.h == f.h && jobs[idx[first + e]].frame.ncomp == f.ncomp) e++;
         const size_t scratch = rph_pixel_hash_scratch_bytes((uint32_t)(e - r), f.w, f.h);
-        if (scratch) RPH_TRY(P.reserve_b3(b, scratch, s));  // (runs of one stream follow each other: one buffer serves them all)
-        RPH_TRY(rph_launch_pixel_hash(P.d_out[b] + hi[D.image_of[r]].out_off, (uint32_t)(e - r), f.w, f.h, och, (size_t)och * align_up(f.w, 8), out_bytes_of(f, och),
-                                      R.pixel + r * 32, s, P.d_b3[b]));
+        if (scratch) RPH_TRY(P.b3[b].reserve(scratch, scratch + scratch / 4, s));  // (runs of one stream follow each other: one buffer serves them all)
+        RPH_TRY(rph_launch_pixel_hash(P.pixels[b].data() + hi[D.image_of[r]].out_off, (uint32_t)(e - r), f.w, f.h, och, (size_t)och * align_up(f.w, 8), out_bytes_of(f, och),
+                                      R.pixel + r * 32, s, P.b3[b].data()));
         r = e;
     }
     if (!out.want_hash) return RPH_OK;
@@ -572,7 +461,7 @@ int reconstruct_and_hash(rph_ctx *ctx, JpegPipe &P, int b, Slot &S, Jobs &jobs, 
         const uint32_t och = out_channels(f, out.rgb_wanted());
         size_t e = r + 1;
         while (e < r1 && D.image_of[e] != UINT32_MAX && jobs[idx[first + e]].frame.w == f.w && jobs[idx[first + e]].frame.h == f.h && jobs[idx[first + e]].frame.ncomp == f.ncomp) e++;
-        RPH_TRY(rph_pdq_hash_batch_dev(ctx, P.d_out[b] + hi[D.image_of[r]].out_off, (uint32_t)(e - r), f.w, f.h, och, (size_t)och * align_up(f.w, 8), out_bytes_of(f, och),
+        RPH_TRY(rph_pdq_hash_batch_dev(ctx, P.pixels[b].data() + hi[D.image_of[r]].out_off, (uint32_t)(e - r), f.w, f.h, och, (size_t)och * align_up(f.w, 8), out_bytes_of(f, och),
                                        R.hash + r * 32, out.quality ? R.quality + r * 4 : nullptr, out.coeffs ? R.coeffs + r * 1024 : nullptr,
                                        out.dihedral ? R.dihedral + r * 256 : nullptr, R.valid + r, s));
         r = e;
@@ -586,7 +475,7 @@ int reconstruct_and_hash(rph_ctx *ctx, JpegPipe &P, int b, Slot &S, Jobs &jobs, 
 // the first m entries of the slot's result arrays cleared by the host (the lane is idle: its previous chunk has delivered)
 void zero_results(Slot &S, size_t m, const Outputs &out)
 {
-    ResView H(S.res.h, S.res_images);
+    ResView H(S.res.data(), S.res_images);
     memset(H.hash, 0, m * 32);
     memset(H.quality, 0, m * 4);
     if (out.coeffs) memset(H.coeffs, 0, m * 1024);
@@ -608,7 +497,7 @@ int fetch_results(Slot &S, size_t m, const Outputs &out, bool entropy_status)
 void scatter_results(const Slot &S, Jobs &jobs, const std::vector<uint32_t> &idx, size_t first, size_t last, const Outputs &out,
                      std::vector<uint32_t> *retry)
 {
-    ResView R(S.res.h, S.res_images);
+    ResView R(S.res.data(), S.res_images);
     for (size_t r = 0; r < last - first; r++) {
         const uint32_t g = idx[first + r];
         Job &j = jobs[g];
@@ -659,17 +548,11 @@ int run_host_entropy(rph_ctx *ctx, JpegPipe &P, Jobs &jobs, const std::vector<ui
         RPH_TRY(S.ready());
         const size_t m = last - first;
         const size_t coef_need = std::max(CHUNK_COEF_BYTES, blocks * 128);
-        if (S.coef.cap < coef_need) {
-            RPH_HIP_CHECK(hipStreamSynchronize(S.stream));
-            RPH_TRY(S.coef.reserve(coef_need));
-        }
+        RPH_TRY(S.coef.reserve(coef_need, S.stream));
         RPH_TRY(P.reserve_recon(b, coef_need, S.stream));
         RPH_TRY(S.reserve_res(std::max<size_t>(m, std::min<size_t>(n, CHUNK_MAX_IMAGES)), out.pixel_hash != nullptr));
         const size_t meta_need = std::max<size_t>(m, std::min<size_t>(n, CHUNK_MAX_IMAGES)) * (3 * sizeof(JPlane) + sizeof(JImage) + 3 * 128);
-        if (S.meta.cap < meta_need) {
-            RPH_HIP_CHECK(hipStreamSynchronize(S.stream));
-            RPH_TRY(S.meta.reserve(meta_need));
-        }
+        RPH_TRY(S.meta.reserve(meta_need, S.stream));
         {
             uint64_t fb = 0;
             for (size_t i = first; i < last; i++) {
@@ -678,7 +561,7 @@ int run_host_entropy(rph_ctx *ctx, JpegPipe &P, Jobs &jobs, const std::vector<ui
                 if (j.status == RPH_OK) fb += j.frame.total_blocks;
             }
         }
-        int16_t *h_coef = reinterpret_cast<int16_t *>(S.coef.h);
+        int16_t *h_coef = reinterpret_cast<int16_t *>(S.coef.h.data());
         bool predecoded = false;
         for (size_t i = first; i < last; i++) predecoded |= jobs[idx[i]].pre != nullptr;
         if (!predecoded)
@@ -689,7 +572,7 @@ int run_host_entropy(rph_ctx *ctx, JpegPipe &P, Jobs &jobs, const std::vector<ui
         RPH_JPEG_STAMP("lane %d: chunk %d buffers sized", b, k);
         ChunkDesc D;
         std::vector<size_t> subs;
-        RPH_TRY(build_descriptors(jobs, idx, first, last, flavour, out.rgb_wanted(), SIZE_MAX / 256, S.meta.h, 0, D, subs));
+        RPH_TRY(build_descriptors(jobs, idx, first, last, flavour, out.rgb_wanted(), SIZE_MAX / 256, S.meta.h.data(), 0, D, subs));
         hipStream_t s = S.stream;
         zero_results(S, m, out);
         if (D.n_images) {
@@ -697,18 +580,18 @@ int run_host_entropy(rph_ctx *ctx, JpegPipe &P, Jobs &jobs, const std::vector<ui
                 for (size_t i = first; i < last; i++) {
                     const Job &j = jobs[idx[i]];
                     if (j.status == RPH_OK)
-                        RPH_HIP_CHECK(hipMemcpyAsync(S.coef.d + j.first_block * 128, j.pre, (size_t)j.frame.total_blocks * 128, hipMemcpyHostToDevice, s));
+                        RPH_HIP_CHECK(hipMemcpyAsync(S.coef.d.data() + j.first_block * 128, j.pre, (size_t)j.frame.total_blocks * 128, hipMemcpyHostToDevice, s));
                 }
             } else {
-                RPH_HIP_CHECK(hipMemcpyAsync(S.coef.d, S.coef.h, blocks * 128, hipMemcpyHostToDevice, s));
+                RPH_HIP_CHECK(hipMemcpyAsync(S.coef.d.data(), S.coef.h.data(), blocks * 128, hipMemcpyHostToDevice, s));
             }
-            RPH_HIP_CHECK(hipMemcpyAsync(S.meta.d, S.meta.h, D.off_end, hipMemcpyHostToDevice, s));
-            RPH_TRY(reconstruct_and_hash(ctx, P, b, S, jobs, idx, first, D, 0, m, reinterpret_cast<const int16_t *>(S.coef.d), flavour, out, s));
+            RPH_HIP_CHECK(hipMemcpyAsync(S.meta.d.data(), S.meta.h.data(), D.off_end, hipMemcpyHostToDevice, s));
+            RPH_TRY(reconstruct_and_hash(ctx, P, b, S, jobs, idx, first, D, 0, m, reinterpret_cast<const int16_t *>(S.coef.d.data()), flavour, out, s));
         }
         if (out.pixels && m == 1 && jobs[idx[first]].status == RPH_OK) {  // single-image decode: rows without their padding
             const rphj::Frame &f = jobs[idx[first]].frame;
             const size_t row = (size_t)f.ncomp * f.w, stride = (size_t)f.ncomp * align_up(f.w, 8);
-            RPH_HIP_CHECK(hipMemcpy2DAsync(out.pixels, row, P.d_out[b], stride, row, f.h, hipMemcpyDeviceToHost, s));
+            RPH_HIP_CHECK(hipMemcpy2DAsync(out.pixels, row, P.pixels[b].data(), stride, row, f.h, hipMemcpyDeviceToHost, s));
         }
         pend[b].active = true;
         pend[b].first = first;
@@ -746,7 +629,7 @@ int run_device_entropy(rph_ctx *ctx, JpegPipe &P, Jobs &jobs, std::vector<uint32
     for (uint32_t g : idx) need += (size_t)jobs[g].frame.total_blocks * 128;
     size_t free_b = 0, total_b = 0;
     RPH_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-    const size_t budget = std::max<size_t>((size_t)1 << 30, std::min<size_t>((free_b + P.d_coef_bytes) / 2, (size_t)96 << 30));
+    const size_t budget = std::max<size_t>((size_t)1 << 30, std::min<size_t>((free_b + P.coef.capacity()) / 2, (size_t)96 << 30));
     // Up to JPEG_LANES lanes of resources (stream, staging, a share of the coefficient buffer, reconstruction buffers), chunks take them in
     // turn: the host prepares chunk k + 1 and its bytes cross PCIe while chunk k is on the device, and the latency-bound walk of one
     // chunk runs beside the bandwidth-bound reconstruction of the other.  A call is cut into about four chunks when it is large
@@ -785,15 +668,9 @@ int run_device_entropy(rph_ctx *ctx, JpegPipe &P, Jobs &jobs, std::vector<uint32
     const bool single = need <= chunk_target && need <= budget;
     const int lanes = single ? 1 : (int)std::min<size_t>(JPEG_LANES, (need + chunk_target - 1) / chunk_target);  // chunks in flight
     const size_t want = single ? need : std::min(budget, (size_t)lanes * chunk_target);
-    if (P.d_coef_bytes < want) {
-        RPH_HIP_CHECK(hipDeviceSynchronize());
-        if (P.d_coef) (void)hipFree(P.d_coef);
-        P.d_coef = nullptr;
-        P.d_coef_bytes = 0;
-        RPH_HIP_CHECK(hipMalloc((void **)&P.d_coef, want));
-        P.d_coef_bytes = want;
-    }
-    const size_t region = (P.d_coef_bytes / (size_t)lanes) / 128 * 128;
+    if (P.coef.capacity() < want) RPH_HIP_CHECK(hipDeviceSynchronize());  // every lane's stream may still use it
+    RPH_TRY(P.coef.reserve(want, synced));
+    const size_t region = (P.coef.capacity() / (size_t)lanes) / 128 * 128;
     const size_t chunk_bytes = std::min(region, chunk_target);
     struct Pending {
         bool active = false;
@@ -840,10 +717,10 @@ int run_device_entropy(rph_ctx *ctx, JpegPipe &P, Jobs &jobs, std::vector<uint32
         RPH_TRY(finish(b));  // the lane is free again once its previous chunk (`lanes` chunks back) has delivered its results
         Slot &S = P.slot[b];
         hipStream_t s = S.stream;
-        int16_t *d_coef = P.d_coef + (size_t)b * (region / 2);  // (int16 elements: region bytes per lane)
+        int16_t *d_coef = P.coef.as<int16_t>() + (size_t)b * (region / 2);  // (int16 elements: region bytes per lane)
         const size_t m = last - first;
         RPH_TRY(S.reserve_res(m, out.pixel_hash != nullptr));
-        RPH_TRY(S.stream_bytes.reserve(file_bytes + 64));
+        RPH_TRY(S.stream_bytes.reserve(file_bytes + 64, s));
         // ---- streams and scan plans (host threads: memchr + memcpy)
         const double t0 = now_ms();
         {
@@ -864,7 +741,7 @@ int run_device_entropy(rph_ctx *ctx, JpegPipe &P, Jobs &jobs, std::vector<uint32
             Job &j = jobs[idx[i]];
             HImage &hi = himgs[i - first];
             memset(&hi, 0, sizeof hi);
-            j.status = rphj::prepare_stream(j.data, j.len, j.frame, j.plan, S.stream_bytes.h + j.stream_off, stream_cap(j), &j.stream_used, &TableStore::intern, &store, &j.marks);
+            j.status = rphj::prepare_stream(j.data, j.len, j.frame, j.plan, S.stream_bytes.h.data() + j.stream_off, stream_cap(j), &j.stream_used, &TableStore::intern, &store, &j.marks);
             if (j.status != RPH_OK) return;
             const rphj::Frame &f = j.frame;
             hi.first_block = j.first_block;
@@ -1113,60 +990,40 @@ int run_device_entropy(rph_ctx *ctx, JpegPipe &P, Jobs &jobs, std::vector<uint32
                      off_prefs = align_up(off_pitems + pitems.size() * 4, 16), off_pwaits = align_up(off_prefs + prefs.size() * sizeof(PRef), 16),
                      off_items = align_up(off_pwaits + pwaits.size() * 4, 16),
                      upload_bytes = off_items + items.size() * sizeof(HItem), meta_bytes = off_items + (size_t)n_items * sizeof(HItem);
-        RPH_TRY(S.meta.reserve(meta_bytes));
+        RPH_TRY(S.meta.reserve(meta_bytes, s));
         const size_t segwork = align_up((size_t)n_segs * sizeof(SegState), 16) + rph_jpeg_segment_work_bytes(n_segs);
-        if (n_segs && S.segwork_cap < segwork) {
-            if (S.d_segwork) (void)hipFree(S.d_segwork);
-            S.d_segwork = nullptr, S.segwork_cap = 0;
-            RPH_HIP_CHECK(hipMalloc((void **)&S.d_segwork, segwork + segwork / 4));
-            S.segwork_cap = segwork + segwork / 4;
-        }
+        if (n_segs) RPH_TRY(S.segwork.reserve(segwork, segwork + segwork / 4, s));
         if (prog_blocks >= ((uint64_t)1 << 32)) return RPH_ERR_CAPACITY;  // (a chunk's coefficients are capped far below: 2^32 blocks are 512 GB)
         if (prog_corr >= ((uint64_t)1 << 32) || prog_dcb >= ((uint64_t)1 << 32)) return RPH_ERR_CAPACITY;
-        if (prog_dcb && S.pdc_cap < prog_dcb) {
-            if (S.d_pdc) (void)hipFree(S.d_pdc);
-            S.d_pdc = nullptr, S.pdc_cap = 0;
-            RPH_HIP_CHECK(hipMalloc((void **)&S.d_pdc, prog_dcb + prog_dcb / 4 + 64));
-            S.pdc_cap = prog_dcb + prog_dcb / 4 + 64;
-        }
-        if (prog_corr && S.pcorr_cap < prog_corr * sizeof(PCorr)) {
-            if (S.d_pcorr) (void)hipFree(S.d_pcorr);
-            S.d_pcorr = nullptr, S.pcorr_cap = 0;
-            RPH_HIP_CHECK(hipMalloc((void **)&S.d_pcorr, prog_corr * sizeof(PCorr) + prog_corr * 4));
-            S.pcorr_cap = prog_corr * sizeof(PCorr) + prog_corr * 4;
-        }
+        if (prog_dcb) RPH_TRY(S.pdc.reserve(prog_dcb, prog_dcb + prog_dcb / 4 + 64, s));
+        if (prog_corr) RPH_TRY(S.pcorr.reserve(prog_corr * sizeof(PCorr), prog_corr * sizeof(PCorr) + prog_corr * 4, s));
         // (one mask word per block, and behind them one progress word per scan)
         const size_t pmask_need = prog_blocks * 8 + align_up(pscans.size() * 4, 16);
-        if (prog_blocks && S.pmask_cap < pmask_need) {
-            if (S.d_pmask) (void)hipFree(S.d_pmask);
-            S.d_pmask = nullptr, S.pmask_cap = 0;
-            RPH_HIP_CHECK(hipMalloc((void **)&S.d_pmask, pmask_need + pmask_need / 4));
-            S.pmask_cap = pmask_need + pmask_need / 4;
-        }
+        if (prog_blocks) RPH_TRY(S.pmask.reserve(pmask_need, pmask_need + pmask_need / 4, s));
         ChunkDesc D;
         std::vector<size_t> subs;
-        RPH_TRY(build_descriptors(jobs, idx, first, last, flavour, out.rgb_wanted(), P.recon_coef_bytes[b], S.meta.h, 0, D, subs));
-        memcpy(S.meta.h + off_himg, himgs.data(), m * sizeof(HImage));
-        memcpy(S.meta.h + off_items, items.data(), items.size() * sizeof(HItem));
-        memcpy(S.meta.h + off_order, order.data(), order.size() * 4);
-        if (!luts.empty()) store.copy_luts(reinterpret_cast<rphj::DeviceLut *>(S.meta.h + off_luts));
-        if (n_segs) memcpy(S.meta.h + off_segf, seg_files.data(), seg_files.size() * sizeof(SegFile));
+        RPH_TRY(build_descriptors(jobs, idx, first, last, flavour, out.rgb_wanted(), P.recon_coef_bytes[b], S.meta.h.data(), 0, D, subs));
+        memcpy(S.meta.h.data() + off_himg, himgs.data(), m * sizeof(HImage));
+        memcpy(S.meta.h.data() + off_items, items.data(), items.size() * sizeof(HItem));
+        memcpy(S.meta.h.data() + off_order, order.data(), order.size() * 4);
+        if (!luts.empty()) store.copy_luts(reinterpret_cast<rphj::DeviceLut *>(S.meta.h.data() + off_luts));
+        if (n_segs) memcpy(S.meta.h.data() + off_segf, seg_files.data(), seg_files.size() * sizeof(SegFile));
         if (!prog_order.empty()) {
-            memcpy(S.meta.h + off_pscan, pscans.data(), pscans.size() * sizeof(PScan));
-            memcpy(S.meta.h + off_porder, prog_order.data(), prog_order.size() * 4);
-            memcpy(S.meta.h + off_pitems, pitems.data(), pitems.size() * 4);
-            if (!pwaits.empty()) memcpy(S.meta.h + off_pwaits, pwaits.data(), pwaits.size() * 4);
+            memcpy(S.meta.h.data() + off_pscan, pscans.data(), pscans.size() * sizeof(PScan));
+            memcpy(S.meta.h.data() + off_porder, prog_order.data(), prog_order.size() * 4);
+            memcpy(S.meta.h.data() + off_pitems, pitems.data(), pitems.size() * 4);
+            if (!pwaits.empty()) memcpy(S.meta.h.data() + off_pwaits, pwaits.data(), pwaits.size() * 4);
             if (!prefs.empty()) {
-                memcpy(S.meta.h + off_prefs, prefs.data(), prefs.size() * sizeof(PRef));
-                JPlane *hp = reinterpret_cast<JPlane *>(S.meta.h + D.off_planes);
+                memcpy(S.meta.h.data() + off_prefs, prefs.data(), prefs.size() * sizeof(PRef));
+                JPlane *hp = reinterpret_cast<JPlane *>(S.meta.h.data() + D.off_planes);
                 for (const PlaneRefs &pr : plane_refs) {
                     if (D.plane_of[pr.r] == UINT32_MAX) continue;
                     const int nc = jobs[idx[first + pr.r]].frame.ncomp;
                     for (int c = 0; c < nc && c < 3; c++) hp[D.plane_of[pr.r] + c].ref_first = pr.first[c], hp[D.plane_of[pr.r] + c].ref_count = pr.count[c];
                 }
-                D.d_refs = reinterpret_cast<const PRef *>(S.meta.d + off_prefs);
-                D.d_corr = S.d_pcorr;
-                D.d_dcbits = S.d_pdc;
+                D.d_refs = reinterpret_cast<const PRef *>(S.meta.d.data() + off_prefs);
+                D.d_corr = S.pcorr.as<PCorr>();
+                D.d_dcbits = S.pdc.data();
             }
         }
         RPH_JPEG_STAMP("lane %d: chunk %d descriptors written", b, k);
@@ -1180,18 +1037,18 @@ int run_device_entropy(rph_ctx *ctx, JpegPipe &P, Jobs &jobs, std::vector<uint32
                 t = now_ms();
             }
         };
-        ResView R(S.res.d, S.res_images);
+        ResView R(S.res.data(), S.res_images);
         zero_results(S, m, out);
         if (n_items || !prog_order.empty()) {
-            RPH_HIP_CHECK(hipMemcpyAsync(S.stream_bytes.d, S.stream_bytes.h, file_bytes + 64, hipMemcpyHostToDevice, s));
-            RPH_HIP_CHECK(hipMemcpyAsync(S.meta.d, S.meta.h, upload_bytes, hipMemcpyHostToDevice, s));
+            RPH_HIP_CHECK(hipMemcpyAsync(S.stream_bytes.d.data(), S.stream_bytes.h.data(), file_bytes + 64, hipMemcpyHostToDevice, s));
+            RPH_HIP_CHECK(hipMemcpyAsync(S.meta.d.data(), S.meta.h.data(), upload_bytes, hipMemcpyHostToDevice, s));
             lap(t_up);
             if (n_segs) {  // streams without markers: their segments find their entries and become walk items
-                SegState *d_segs = reinterpret_cast<SegState *>(S.d_segwork);
-                void *d_segtab = S.d_segwork + align_up((size_t)n_segs * sizeof(SegState), 16);
-                RPH_TRY(rph_jpeg_launch_segments(s, S.stream_bytes.d, reinterpret_cast<const HImage *>(S.meta.d + off_himg), reinterpret_cast<const SegFile *>(S.meta.d + off_segf),
+                SegState *d_segs = reinterpret_cast<SegState *>(S.segwork.data());
+                void *d_segtab = S.segwork.data() + align_up((size_t)n_segs * sizeof(SegState), 16);
+                RPH_TRY(rph_jpeg_launch_segments(s, S.stream_bytes.d.data(), reinterpret_cast<const HImage *>(S.meta.d.data() + off_himg), reinterpret_cast<const SegFile *>(S.meta.d.data() + off_segf),
                                                  (uint32_t)seg_files.size(), d_segs, n_segs, ctx->jpeg_seg_bytes, d_segtab, 8,
-                                                 reinterpret_cast<const rphj::DeviceLut *>(S.meta.d + off_luts), (uint32_t)luts.size(), reinterpret_cast<HItem *>(S.meta.d + off_items)));
+                                                 reinterpret_cast<const rphj::DeviceLut *>(S.meta.d.data() + off_luts), (uint32_t)luts.size(), reinterpret_cast<HItem *>(S.meta.d.data() + off_items)));
             }
             lap(t_seg);
             // The coefficients start from zero -- unless the walk writes whole blocks and covers every block of the chunk: sequential files of
@@ -1200,21 +1057,21 @@ int run_device_entropy(rph_ctx *ctx, JpegPipe &P, Jobs &jobs, std::vector<uint32
             if (!(rph_jpeg_walk_writes_whole_blocks(n_items) && all_one_scan && prog_order.empty())) RPH_HIP_CHECK(hipMemsetAsync(d_coef, 0, blocks * 128, s));
             lap(t_zero);
             if (n_items)
-                RPH_TRY(rph_jpeg_launch_walk(s, S.stream_bytes.d, reinterpret_cast<const HImage *>(S.meta.d + off_himg), reinterpret_cast<const HItem *>(S.meta.d + off_items),
-                                             reinterpret_cast<const uint32_t *>(S.meta.d + off_order), n_ordered, n_items,
-                                             reinterpret_cast<const rphj::DeviceLut *>(S.meta.d + off_luts), (uint32_t)luts.size(), d_coef, R.status));
-            if (prog_blocks) RPH_HIP_CHECK(hipMemsetAsync(S.d_pmask, 0, prog_blocks * 8 + align_up(pscans.size() * 4, 16), s));
-            RPH_TRY(rph_jpeg_launch_prog(s, S.stream_bytes.d, reinterpret_cast<const HImage *>(S.meta.d + off_himg), reinterpret_cast<const PScan *>(S.meta.d + off_pscan),
-                                         (uint32_t)pscans.size(), reinterpret_cast<const uint32_t *>(S.meta.d + off_pitems), (uint32_t)pitems.size(),
-                                         reinterpret_cast<const uint32_t *>(S.meta.d + off_pwaits), reinterpret_cast<const rphj::DeviceLut *>(S.meta.d + off_luts),
-                                         (uint32_t)luts.size(), d_coef, S.d_pmask, reinterpret_cast<uint32_t *>(S.d_pmask + prog_blocks), S.d_pcorr, (size_t)prog_corr, S.d_pdc, (size_t)prog_dcb, R.status));
+                RPH_TRY(rph_jpeg_launch_walk(s, S.stream_bytes.d.data(), reinterpret_cast<const HImage *>(S.meta.d.data() + off_himg), reinterpret_cast<const HItem *>(S.meta.d.data() + off_items),
+                                             reinterpret_cast<const uint32_t *>(S.meta.d.data() + off_order), n_ordered, n_items,
+                                             reinterpret_cast<const rphj::DeviceLut *>(S.meta.d.data() + off_luts), (uint32_t)luts.size(), d_coef, R.status));
+            if (prog_blocks) RPH_HIP_CHECK(hipMemsetAsync(S.pmask.data(), 0, prog_blocks * 8 + align_up(pscans.size() * 4, 16), s));
+            RPH_TRY(rph_jpeg_launch_prog(s, S.stream_bytes.d.data(), reinterpret_cast<const HImage *>(S.meta.d.data() + off_himg), reinterpret_cast<const PScan *>(S.meta.d.data() + off_pscan),
+                                         (uint32_t)pscans.size(), reinterpret_cast<const uint32_t *>(S.meta.d.data() + off_pitems), (uint32_t)pitems.size(),
+                                         reinterpret_cast<const uint32_t *>(S.meta.d.data() + off_pwaits), reinterpret_cast<const rphj::DeviceLut *>(S.meta.d.data() + off_luts),
+                                         (uint32_t)luts.size(), d_coef, S.pmask.as<unsigned long long>(), reinterpret_cast<uint32_t *>(S.pmask.as<unsigned long long>() + prog_blocks), S.pcorr.as<PCorr>(), (size_t)prog_corr, S.pdc.data(), (size_t)prog_dcb, R.status));
             lap(t_walk);
             for (size_t q = 0; q < subs.size(); q++) {
                 const size_t r0 = subs[q], r1 = q + 1 < subs.size() ? subs[q + 1] : m;
                 RPH_TRY(reconstruct_and_hash(ctx, P, b, S, jobs, idx, first, D, r0, r1, d_coef, flavour, out, s));
             }
             lap(t_rec);
-            if (tr && n_segs) rph_jpeg_debug_segment_stats(s, S.d_segwork + align_up((size_t)n_segs * sizeof(SegState), 16), n_segs);  // (behind the timed phases)
+            if (tr && n_segs) rph_jpeg_debug_segment_stats(s, S.segwork.data() + align_up((size_t)n_segs * sizeof(SegState), 16), n_segs);  // (behind the timed phases)
             if (tr)
                 fprintf(stderr, "[rph_jpeg] chunk of %zu files in %zu lanes (%.1f MB of entropy bytes, %.2f GB of coefficients, %zu tables, %zu sub-batches): prepare %.1f ms, "
                                 "descriptors %.1f ms, upload %.1f ms, %u segments %.1f ms, zero %.1f ms, walk %.1f ms, reconstruct + hash %.1f ms\n",
@@ -1243,7 +1100,7 @@ int run_batch(rph_ctx *ctx, const uint8_t *const *data, const size_t *len, uint3
     RPH_HIP_CHECK(hipSetDevice(ctx->device));
     if (!ctx->jpeg) ctx->jpeg = new JpegPipe();
     JpegPipe &P = *static_cast<JpegPipe *>(ctx->jpeg);
-    unsigned threads = n_threads ? n_threads : default_threads();
+    unsigned threads = n_threads ? n_threads : rph_host_threads();
     threads = std::min(threads, 256u);
 
     g_trace_t0 = now_ms();
@@ -1326,12 +1183,8 @@ void rph_jpeg_forget_threads(rph_ctx *ctx)  // rph_shutdown: no caller is inside
 
 void rph_jpeg_forget(rph_ctx *ctx)
 {
-    if (ctx->jpeg) {
-        JpegPipe *P = static_cast<JpegPipe *>(ctx->jpeg);
-        P->release();
-        delete P;
-        ctx->jpeg = nullptr;
-    }
+    delete static_cast<JpegPipe *>(ctx->jpeg);
+    ctx->jpeg = nullptr;
 }
 
 extern "C" {

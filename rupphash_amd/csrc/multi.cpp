@@ -67,12 +67,6 @@ int load_rccl(Rccl &r)
         }                                                                                                         \
     } while (0)
 
-#define RPH_TRY(expr)                  \
-    do {                               \
-        int rc_ = (expr);              \
-        if (rc_ != RPH_OK) return rc_; \
-    } while (0)
-
 struct DevMem {  // device buffer bound to a device (freed there)
     void *p = nullptr;
     int device = 0;

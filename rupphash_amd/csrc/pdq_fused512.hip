@@ -965,24 +965,14 @@ int rph_launch_pdq_fused512_ll(rph_ctx *ctx, const uint8_t *d_px, uint32_t n, si
     const size_t need = (size_t)chunk * LL_SAMPLE_FLOATS * sizeof(float);
     if (ctx->ll_scratch.size() > 256 && ctx->ll_scratch.find(stream) == ctx->ll_scratch.end()) {  // streams come and go: start over
         RPH_HIP_CHECK(hipDeviceSynchronize());
-        for (auto &kv : ctx->ll_scratch) (void)hipFree(kv.second.p);
         ctx->ll_scratch.clear();
     }
-    rph_ctx::LLScratch &sc = ctx->ll_scratch[stream];
-    if (sc.bytes < need) {
-        if (sc.p) {
-            RPH_HIP_CHECK(hipStreamSynchronize(stream));  // only this stream's kernels use it
-            RPH_HIP_CHECK(hipFree(sc.p));
-        }
-        sc.p = nullptr;
-        sc.bytes = 0;
-        RPH_HIP_CHECK(hipMalloc((void **)&sc.p, need));
-        sc.bytes = need;
-    }
+    DevBuf &sc = ctx->ll_scratch[stream];
+    RPH_TRY(sc.reserve(need, stream));  // only this stream's kernels use it
     for (uint32_t first = 0; first < n; first += chunk) {
         const uint32_t m = (n - first) < chunk ? (n - first) : chunk;
         hipLaunchKernelGGL((pdq_fused512_ll_kernel<Geo<64, 3, false>>), dim3(m), dim3(512), 0, stream, d_px + (size_t)first * image_stride, m, row_stride, image_stride,
-                           sc.p, d_hash + (size_t)first * 32, d_quality ? d_quality + first : nullptr, d_coeffs ? d_coeffs + (size_t)first * 256 : nullptr,
+                           sc.as<float>(), d_hash + (size_t)first * 32, d_quality ? d_quality + first : nullptr, d_coeffs ? d_coeffs + (size_t)first * 256 : nullptr,
                            d_dihedral ? d_dihedral + (size_t)first * 256 : nullptr, d_valid ? d_valid + first : nullptr);
         RPH_HIP_CHECK(hipGetLastError());
     }

@@ -429,20 +429,8 @@ int rph_launch_pdq_generic(rph_ctx *ctx, const uint8_t *d_px, uint32_t n, uint32
     if (chunk < 1) chunk = 1;
     if (chunk > n) chunk = n;
     const size_t need = 2 * plane_bytes * chunk;
-    if (ctx->scratch_bytes < need) {
-        // kernels of any stream may still be using the old scratch
-        RPH_HIP_CHECK(hipDeviceSynchronize());
-        if (ctx->scratch) RPH_HIP_CHECK(hipFree(ctx->scratch));
-        ctx->scratch = nullptr;
-        ctx->scratch_bytes = 0;
-        RPH_HIP_CHECK(hipMalloc((void **)&ctx->scratch, need));
-        ctx->scratch_bytes = need;
-    }
-    // one scratch for all caller streams (the caller holds ctx->mu while enqueueing): order this launch behind the previous
-    // user's kernels if they went to another stream
-    if (!ctx->scratch_done) RPH_HIP_CHECK(hipEventCreateWithFlags(&ctx->scratch_done, hipEventDisableTiming));
-    if (ctx->scratch_used && ctx->scratch_stream != stream) RPH_HIP_CHECK(hipStreamWaitEvent(stream, ctx->scratch_done, 0));
-    float *a = ctx->scratch, *b = ctx->scratch + (size_t)chunk * (plane_bytes / sizeof(float));
+    RPH_TRY(ctx->scratch.acquire(stream, need));
+    float *a = ctx->scratch.as<float>(), *b = a + (size_t)chunk * (plane_bytes / sizeof(float));
     const uint32_t win_rows = (w + 63) / 64;  // window along rows = ceil(cols / 64)   pdqhash.rs:246
     const uint32_t win_cols = (h + 63) / 64;  // window along cols = ceil(rows / 64)   pdqhash.rs:247
     for (uint32_t first = 0; first < n; first += chunk) {
@@ -480,8 +468,5 @@ int rph_launch_pdq_generic(rph_ctx *ctx, const uint8_t *d_px, uint32_t n, uint32
                            d_dihedral ? d_dihedral + (size_t)first * 256 : nullptr);
         RPH_HIP_CHECK(hipGetLastError());
     }
-    RPH_HIP_CHECK(hipEventRecord(ctx->scratch_done, stream));
-    ctx->scratch_stream = stream;
-    ctx->scratch_used = true;
-    return RPH_OK;
+    return ctx->scratch.publish(stream);
 }

@@ -480,17 +480,8 @@ int rph_launch_pdq_stream_color(rph_ctx *ctx, const uint8_t *d_px, uint32_t n, u
     uint32_t chunk = (uint32_t)(((size_t)1 << 30) / plane);
     chunk = chunk > n ? n : (chunk > 65535u ? 65535u : chunk);
     const size_t need = plane * chunk;
-    if (ctx->scratch_bytes < need) {
-        RPH_HIP_CHECK(hipDeviceSynchronize());  // kernels of any stream may still be using the old scratch
-        if (ctx->scratch) RPH_HIP_CHECK(hipFree(ctx->scratch));
-        ctx->scratch = nullptr;
-        ctx->scratch_bytes = 0;
-        RPH_HIP_CHECK(hipMalloc((void **)&ctx->scratch, need));
-        ctx->scratch_bytes = need;
-    }
-    if (!ctx->scratch_done) RPH_HIP_CHECK(hipEventCreateWithFlags(&ctx->scratch_done, hipEventDisableTiming));
-    if (ctx->scratch_used && ctx->scratch_stream != stream) RPH_HIP_CHECK(hipStreamWaitEvent(stream, ctx->scratch_done, 0));
-    uint8_t *luma = reinterpret_cast<uint8_t *>(ctx->scratch);
+    RPH_TRY(ctx->scratch.acquire(stream, need));
+    uint8_t *luma = ctx->scratch.data();
     const uint32_t quads = (w + 3) / 4;
     for (uint32_t first = 0; first < n; first += chunk) {
         const uint32_t m = (n - first) < chunk ? (n - first) : chunk;
@@ -507,10 +498,7 @@ int rph_launch_pdq_stream_color(rph_ctx *ctx, const uint8_t *d_px, uint32_t n, u
                            d_dihedral ? d_dihedral + (size_t)first * 256 : nullptr, d_valid ? d_valid + first : nullptr);
         RPH_HIP_CHECK(hipGetLastError());
     }
-    RPH_HIP_CHECK(hipEventRecord(ctx->scratch_done, stream));
-    ctx->scratch_stream = stream;
-    ctx->scratch_used = true;
-    return RPH_OK;
+    return ctx->scratch.publish(stream);
 }
 
 int rph_launch_pdq_stream(rph_ctx *ctx, const uint8_t *d_px, uint32_t n, uint32_t w, uint32_t h, size_t row_stride, size_t image_stride, uint8_t *d_hash,

@@ -5,12 +5,9 @@
 // (HOST: the filtered raw bytes cross PCIe).  Everything after that runs on the device: unfilter, expand to the hasher's pixels, the
 // pixel hashes and PDQ over runs of equal geometry, as reconstruct_and_hash does for JPEG.  A call is processed in chunks whose device
 // buffers are kept in the context between calls (rph_png_release returns them).
-#include <sched.h>
 #include <string.h>
 
 #include <algorithm>
-#include <atomic>
-#include <thread>
 #include <vector>
 
 #include "png_host.h"
@@ -23,62 +20,10 @@ int rph_png_launch_expand(const uint8_t *d_raw, const void *d_images, const uint
 
 namespace {
 
-#define RPH_TRY(expr)                  \
-    do {                               \
-        int rc_ = (expr);              \
-        if (rc_ != RPH_OK) return rc_; \
-    } while (0)
-
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-struct DevBuf {
-    uint8_t *d = nullptr;
-    size_t cap = 0;
-    void release()
-    {
-        if (d) (void)hipFree(d);
-        d = nullptr;
-        cap = 0;
-    }
-    int reserve(size_t bytes)  // the stream that used the buffer has been synchronised
-    {
-        if (cap >= bytes) return RPH_OK;
-        release();
-        bytes = align_up(bytes + bytes / 4 + 64, 4096);
-        RPH_HIP_CHECK(hipMalloc((void **)&d, bytes));
-        cap = bytes;
-        return RPH_OK;
-    }
-};
-struct HostBuf {
-    uint8_t *h = nullptr;
-    size_t cap = 0;
-    void release()
-    {
-        if (h) (void)hipHostFree(h);
-        h = nullptr;
-        cap = 0;
-    }
-    int reserve(size_t bytes)
-    {
-        if (cap >= bytes) return RPH_OK;
-        release();
-        bytes = align_up(bytes + bytes / 4 + 64, 4096);
-        RPH_HIP_CHECK(hipHostMalloc((void **)&h, bytes));
-        cap = bytes;
-        return RPH_OK;
-    }
-};
-
 struct PngPipe {
-    hipStream_t s = nullptr;
+    hipStream_t s = nullptr;  // (rph_png_forget: synchronised before the buffers are freed)
     DevBuf comp, raw, hp, x16, nat, meta, res, b3, status, dig;
-    HostBuf h_comp, h_raw, h_meta, h_res, h_status;
-    void release()
-    {
-        for (DevBuf *b : {&comp, &raw, &hp, &x16, &nat, &meta, &res, &b3, &status, &dig}) b->release();
-        for (HostBuf *b : {&h_comp, &h_raw, &h_meta, &h_res, &h_status}) b->release();
-    }
+    PinnedBuf h_comp, h_raw, h_meta, h_res, h_status;
 };
 
 // Per chunk at most this much (one image larger than a limit forms a chunk of its own)
@@ -97,32 +42,12 @@ struct Outputs {
     bool want_pdq = true;
 };
 
-unsigned usable_threads()
-{
-    unsigned n = std::max(1u, std::thread::hardware_concurrency());
-    cpu_set_t set;
-    if (sched_getaffinity(0, sizeof set, &set) == 0) n = std::min<unsigned>(n, (unsigned)std::max(1, CPU_COUNT(&set)));
-    return std::min(n, 64u);
-}
-
-template <class F>
-void parallel_for(size_t n, unsigned threads, F &&f)
-{
-    std::atomic<size_t> next{0};
-    auto work = [&]() {
-        for (size_t i; (i = next.fetch_add(1)) < n;) f(i);
-    };
-    std::vector<std::thread> ts;
-    for (unsigned t = 1; t < threads && t < n; t++) ts.emplace_back(work);
-    work();
-    for (auto &t : ts) t.join();
-}
-
 // one chunk: files[idx[k]] for k in [0, m), all parsed RPH_OK
 int run_chunk(rph_ctx *ctx, PngPipe &P, const uint8_t *const *data, std::vector<rphp::Parsed> &parsed, const uint32_t *idx, size_t m, unsigned threads,
               const Outputs &out)
 {
     hipStream_t s = P.s;
+    auto reserve = [s](auto &buf, size_t bytes) { return buf.reserve(bytes, align_up(bytes + bytes / 4 + 64, 4096), s); };  // +25 % + 64, whole pages
     int mode = ctx->png_inflate;
     // raw / compressed placement
     uint64_t raw_bytes = 0, comp_bytes = 0;
@@ -142,48 +67,48 @@ int run_chunk(rph_ctx *ctx, PngPipe &P, const uint8_t *const *data, std::vector<
     const size_t off_img = 0, off_pal = align_up(m * sizeof(rphp::Image), 256), off_str = off_pal + m * 1024,
                  off_job = align_up(off_str + m * sizeof(rphp::StreamDesc), 256), off_list = align_up(off_job + n_jobs * sizeof(rphp::UnfilterJob), 256),
                  off_b3 = align_up(off_list + m * 4, 256), meta_bytes = off_b3 + (m + 1) * 8;
-    RPH_TRY(P.meta.reserve(meta_bytes));
-    RPH_TRY(P.h_meta.reserve(meta_bytes));
-    RPH_TRY(P.raw.reserve(raw_bytes));
-    RPH_TRY(P.status.reserve(m * 4));
-    RPH_TRY(P.h_status.reserve(m * 4));
-    rphp::Image *imgs = reinterpret_cast<rphp::Image *>(P.h_meta.h + off_img);
-    rphp::StreamDesc *sd = reinterpret_cast<rphp::StreamDesc *>(P.h_meta.h + off_str);
-    rphp::UnfilterJob *jobs = reinterpret_cast<rphp::UnfilterJob *>(P.h_meta.h + off_job);
-    uint32_t *list = reinterpret_cast<uint32_t *>(P.h_meta.h + off_list);
-    int32_t *st = reinterpret_cast<int32_t *>(P.h_status.h);
+    RPH_TRY(reserve(P.meta, meta_bytes));
+    RPH_TRY(reserve(P.h_meta, meta_bytes));
+    RPH_TRY(reserve(P.raw, raw_bytes));
+    RPH_TRY(reserve(P.status, m * 4));
+    RPH_TRY(reserve(P.h_status, m * 4));
+    rphp::Image *imgs = reinterpret_cast<rphp::Image *>(P.h_meta.data() + off_img);
+    rphp::StreamDesc *sd = reinterpret_cast<rphp::StreamDesc *>(P.h_meta.data() + off_str);
+    rphp::UnfilterJob *jobs = reinterpret_cast<rphp::UnfilterJob *>(P.h_meta.data() + off_job);
+    uint32_t *list = reinterpret_cast<uint32_t *>(P.h_meta.data() + off_list);
+    int32_t *st = reinterpret_cast<int32_t *>(P.h_status.data());
     size_t j = 0;
     for (size_t k = 0; k < m; k++) {
         const rphp::Parsed &pp = parsed[idx[k]];
         imgs[k] = pp.im;
         imgs[k].pal = (uint32_t)k;
-        memcpy(P.h_meta.h + off_pal + k * 1024, pp.palette, 1024);
+        memcpy(P.h_meta.data() + off_pal + k * 1024, pp.palette, 1024);
         sd[k] = rphp::StreamDesc{comp_off[k], pp.idat_bytes, pp.im.raw_off, pp.im.raw_bytes, (uint32_t)k, 0};
         for (int p = 0; p < 7; p++)
             if (pp.im.pass_h[p]) jobs[j++] = rphp::UnfilterJob{pp.im.raw_off + pp.im.pass_off[p], pp.im.pass_h[p], pp.im.pass_rb[p], pp.im.unit, (uint32_t)k};
         st[k] = RPH_OK;
     }
-    RPH_HIP_CHECK(hipMemcpyAsync(P.meta.d, P.h_meta.h, meta_bytes, hipMemcpyHostToDevice, s));
+    RPH_HIP_CHECK(hipMemcpyAsync(P.meta.data(), P.h_meta.data(), meta_bytes, hipMemcpyHostToDevice, s));
     if (mode == RPH_PNG_INFLATE_DEVICE) {
-        RPH_TRY(P.comp.reserve(comp_bytes));
-        RPH_TRY(P.h_comp.reserve(comp_bytes));
-        parallel_for(m, threads, [&](size_t k) { rphp::gather(data[idx[k]], parsed[idx[k]], P.h_comp.h + comp_off[k]); });
-        RPH_HIP_CHECK(hipMemcpyAsync(P.comp.d, P.h_comp.h, comp_bytes, hipMemcpyHostToDevice, s));
-        RPH_HIP_CHECK(hipMemcpyAsync(P.status.d, st, m * 4, hipMemcpyHostToDevice, s));
-        RPH_TRY(rph_png_launch_inflate(P.comp.d, P.meta.d + off_str, (uint32_t)m, P.raw.d, (int32_t *)P.status.d, s));
+        RPH_TRY(reserve(P.comp, comp_bytes));
+        RPH_TRY(reserve(P.h_comp, comp_bytes));
+        parallel_for(0, m, threads, [&](size_t k) { rphp::gather(data[idx[k]], parsed[idx[k]], P.h_comp.data() + comp_off[k]); });
+        RPH_HIP_CHECK(hipMemcpyAsync(P.comp.data(), P.h_comp.data(), comp_bytes, hipMemcpyHostToDevice, s));
+        RPH_HIP_CHECK(hipMemcpyAsync(P.status.data(), st, m * 4, hipMemcpyHostToDevice, s));
+        RPH_TRY(rph_png_launch_inflate(P.comp.data(), P.meta.data() + off_str, (uint32_t)m, P.raw.data(), (int32_t *)P.status.data(), s));
     } else {
-        RPH_TRY(P.h_raw.reserve(raw_bytes));
-        parallel_for(m, threads, [&](size_t k) {
+        RPH_TRY(reserve(P.h_raw, raw_bytes));
+        parallel_for(0, m, threads, [&](size_t k) {
             const rphp::Parsed &pp = parsed[idx[k]];
             std::vector<uint8_t> z(pp.idat_bytes);
             rphp::gather(data[idx[k]], pp, z.data());
-            if (rphz::inflate_host(z.data(), z.size(), P.h_raw.h + pp.im.raw_off, pp.im.raw_bytes) != rphz::Z_OK) st[k] = RPH_ERR_INVALID_ARG;
+            if (rphz::inflate_host(z.data(), z.size(), P.h_raw.data() + pp.im.raw_off, pp.im.raw_bytes) != rphz::Z_OK) st[k] = RPH_ERR_INVALID_ARG;
         });
-        RPH_HIP_CHECK(hipMemcpyAsync(P.raw.d, P.h_raw.h, raw_bytes, hipMemcpyHostToDevice, s));
-        RPH_HIP_CHECK(hipMemcpyAsync(P.status.d, st, m * 4, hipMemcpyHostToDevice, s));
+        RPH_HIP_CHECK(hipMemcpyAsync(P.raw.data(), P.h_raw.data(), raw_bytes, hipMemcpyHostToDevice, s));
+        RPH_HIP_CHECK(hipMemcpyAsync(P.status.data(), st, m * 4, hipMemcpyHostToDevice, s));
     }
-    RPH_TRY(rph_png_launch_unfilter(P.raw.d, P.meta.d + off_job, (uint32_t)n_jobs, (int32_t *)P.status.d, s));
-    RPH_HIP_CHECK(hipMemcpyAsync(st, P.status.d, m * 4, hipMemcpyDeviceToHost, s));
+    RPH_TRY(rph_png_launch_unfilter(P.raw.data(), P.meta.data() + off_job, (uint32_t)n_jobs, (int32_t *)P.status.data(), s));
+    RPH_HIP_CHECK(hipMemcpyAsync(st, P.status.data(), m * 4, hipMemcpyDeviceToHost, s));
     RPH_HIP_CHECK(hipStreamSynchronize(s));
     // the decodable images in runs of equal geometry: (w, h, hasher channels, bit depth: 16-bit images take another pixel hash)
     std::vector<uint32_t> good;
@@ -199,7 +124,7 @@ int run_chunk(rph_ctx *ctx, PngPipe &P, const uint8_t *const *data, std::vector<
     const size_t g = good.size();
     const bool want_hp = out.want_pdq || out.pixel, want_x16 = out.pixel != nullptr;
     uint64_t hp_bytes = 0, x16_bytes = 0, nat_bytes = 0, max_px = 0;
-    uint64_t *b3off = reinterpret_cast<uint64_t *>(P.h_meta.h + off_b3);
+    uint64_t *b3off = reinterpret_cast<uint64_t *>(P.h_meta.data() + off_b3);
     size_t n16 = 0;
     for (size_t q = 0; q < g; q++) {
         rphp::Image &im = imgs[good[q]];
@@ -221,13 +146,13 @@ int run_chunk(rph_ctx *ctx, PngPipe &P, const uint8_t *const *data, std::vector<
         }
     }
     b3off[n16] = x16_bytes;
-    // buffers of this stage (the stream is idle: reserve may reallocate)
+    // buffers of this stage
     const size_t res_bytes = g * (32 + 4 + 1024 + 256 + 1 + 32) + 4 * 256;
-    RPH_TRY(P.hp.reserve(hp_bytes));
-    if (x16_bytes) RPH_TRY(P.x16.reserve(x16_bytes));
-    if (nat_bytes) RPH_TRY(P.nat.reserve(nat_bytes));
-    RPH_TRY(P.res.reserve(res_bytes));
-    RPH_TRY(P.h_res.reserve(res_bytes));
+    RPH_TRY(reserve(P.hp, hp_bytes));
+    if (x16_bytes) RPH_TRY(reserve(P.x16, x16_bytes));
+    if (nat_bytes) RPH_TRY(reserve(P.nat, nat_bytes));
+    RPH_TRY(reserve(P.res, res_bytes));
+    RPH_TRY(reserve(P.h_res, res_bytes));
     size_t b3_scratch = 0;
     for (size_t q = 0; q < g;) {  // runs of equal geometry
         const rphp::Image &a = imgs[good[q]];
@@ -236,14 +161,14 @@ int run_chunk(rph_ctx *ctx, PngPipe &P, const uint8_t *const *data, std::vector<
         if (out.pixel && a.out_depth != 16) b3_scratch = std::max(b3_scratch, rph_pixel_hash_scratch_bytes((uint32_t)(e - q), a.w, a.h));
         q = e;
     }
-    if (b3_scratch) RPH_TRY(P.b3.reserve(b3_scratch));
-    if (n16) RPH_TRY(P.dig.reserve(n16 * 32));
-    RPH_HIP_CHECK(hipMemcpyAsync(P.meta.d, P.h_meta.h, meta_bytes, hipMemcpyHostToDevice, s));
-    RPH_TRY(rph_png_launch_expand(P.raw.d, P.meta.d + off_img, (const uint32_t *)(P.meta.d + off_list), (uint32_t)g, max_px, P.meta.d + off_pal,
-                                  want_hp ? P.hp.d : nullptr, x16_bytes ? P.x16.d : nullptr, nat_bytes ? P.nat.d : nullptr, s));
+    if (b3_scratch) RPH_TRY(reserve(P.b3, b3_scratch));
+    if (n16) RPH_TRY(reserve(P.dig, n16 * 32));
+    RPH_HIP_CHECK(hipMemcpyAsync(P.meta.data(), P.h_meta.data(), meta_bytes, hipMemcpyHostToDevice, s));
+    RPH_TRY(rph_png_launch_expand(P.raw.data(), P.meta.data() + off_img, (const uint32_t *)(P.meta.data() + off_list), (uint32_t)g, max_px, P.meta.data() + off_pal,
+                                  want_hp ? P.hp.data() : nullptr, x16_bytes ? P.x16.data() : nullptr, nat_bytes ? P.nat.data() : nullptr, s));
     // result sections, each 256-byte aligned
     const size_t o_q = align_up(g * 32, 256), o_c = o_q + align_up(g * 4, 256), o_d = o_c + g * 1024, o_v = o_d + g * 256, o_px = o_v + align_up(g, 256);
-    uint8_t *R = P.res.d;
+    uint8_t *R = P.res.data();
     uint8_t *r_hash = R, *r_q = R + o_q, *r_c = R + o_c, *r_d = R + o_d, *r_v = R + o_v, *r_px = R + o_px;
     size_t k16 = 0;
     for (size_t q = 0; q < g;) {
@@ -258,23 +183,23 @@ int run_chunk(rph_ctx *ctx, PngPipe &P, const uint8_t *const *data, std::vector<
                 // a run of 16-bit images is consecutive in the RGBA16 buffer: hashed below, all 16-bit images of the chunk at once
                 k16 += cnt;
             } else {
-                RPH_TRY(rph_launch_pixel_hash(P.hp.d + a.hp_off, cnt, a.w, a.h, a.hc, a.hstride, istride, r_px + q * 32, s, b3_scratch ? P.b3.d : nullptr));
+                RPH_TRY(rph_launch_pixel_hash(P.hp.data() + a.hp_off, cnt, a.w, a.h, a.hc, a.hstride, istride, r_px + q * 32, s, b3_scratch ? P.b3.data() : nullptr));
             }
         }
         if (out.want_pdq)
-            RPH_TRY(rph_pdq_hash_batch_dev(ctx, P.hp.d + a.hp_off, cnt, a.w, a.h, a.hc, a.hstride, istride, r_hash + q * 32, out.quality ? r_q + q * 4 : nullptr,
+            RPH_TRY(rph_pdq_hash_batch_dev(ctx, P.hp.data() + a.hp_off, cnt, a.w, a.h, a.hc, a.hstride, istride, r_hash + q * 32, out.quality ? r_q + q * 4 : nullptr,
                                            out.coeffs ? r_c + q * 1024 : nullptr, out.dihedral ? r_d + q * 256 : nullptr, r_v + q, s));
         q = e;
     }
     // 16-bit pixel hashes: BLAKE3 of the RGBA16 strings, digests into the result slots of those images (in the same order)
     std::vector<uint8_t> dig16(n16 * 32);
-    if (n16) RPH_TRY(rph_blake3_batch_dev(ctx, P.x16.d, P.meta.d + off_b3, (uint32_t)n16, nullptr, P.dig.d, s));
-    if (n16) RPH_HIP_CHECK(hipMemcpyAsync(dig16.data(), P.dig.d, n16 * 32, hipMemcpyDeviceToHost, s));
+    if (n16) RPH_TRY(rph_blake3_batch_dev(ctx, P.x16.data(), P.meta.data() + off_b3, (uint32_t)n16, nullptr, P.dig.data(), s));
+    if (n16) RPH_HIP_CHECK(hipMemcpyAsync(dig16.data(), P.dig.data(), n16 * 32, hipMemcpyDeviceToHost, s));
     (void)k16;
-    RPH_HIP_CHECK(hipMemcpyAsync(P.h_res.h, R, res_bytes, hipMemcpyDeviceToHost, s));
-    if (out.native) RPH_HIP_CHECK(hipMemcpyAsync(out.native, P.nat.d, nat_bytes, hipMemcpyDeviceToHost, s));
+    RPH_HIP_CHECK(hipMemcpyAsync(P.h_res.data(), R, res_bytes, hipMemcpyDeviceToHost, s));
+    if (out.native) RPH_HIP_CHECK(hipMemcpyAsync(out.native, P.nat.data(), nat_bytes, hipMemcpyDeviceToHost, s));
     RPH_HIP_CHECK(hipStreamSynchronize(s));
-    const uint8_t *H = P.h_res.h;
+    const uint8_t *H = P.h_res.data();
     const uint8_t *h_hash = H, *h_q = H + o_q, *h_c = H + o_c, *h_d = H + o_d, *h_v = H + o_v, *h_px = H + o_px;
     size_t i16 = 0;
     for (size_t q = 0; q < g; q++) {
@@ -311,9 +236,9 @@ int run(rph_ctx *ctx, const uint8_t *const *data, const size_t *len, uint32_t n,
         }
         ctx->png = P;
     }
-    if (!threads) threads = usable_threads();
+    if (!threads) threads = rph_host_threads();
     std::vector<rphp::Parsed> parsed(n);
-    parallel_for(n, threads, [&](size_t i) { out.status[i] = (data[i] && len[i]) ? rphp::parse(data[i], len[i], parsed[i]) : RPH_ERR_INVALID_ARG; });
+    parallel_for(0, n, threads, [&](size_t i) { out.status[i] = (data[i] && len[i]) ? rphp::parse(data[i], len[i], parsed[i]) : RPH_ERR_INVALID_ARG; });
     std::vector<uint32_t> ok;
     for (uint32_t i = 0; i < n; i++)
         if (out.status[i] == RPH_OK) ok.push_back(i);
@@ -342,7 +267,6 @@ void rph_png_forget(rph_ctx *ctx)
     PngPipe *P = static_cast<PngPipe *>(ctx->png);
     if (!P) return;
     (void)hipStreamSynchronize(P->s);
-    P->release();
     (void)hipStreamDestroy(P->s);
     delete P;
     ctx->png = nullptr;

@@ -523,9 +523,6 @@ void rph_resize_forget(rph_ctx *ctx)
         delete c;
         ctx->axis_cache = nullptr;
     }
-    if (ctx->rz_scratch) (void)hipFree(ctx->rz_scratch);
-    ctx->rz_scratch = nullptr;
-    ctx->rz_bytes = 0;
 }
 
 // Called with ctx->mu held (rph_pdq_hash_batch_dev).  Asynchronous on `stream`: nothing is allocated per call once the
@@ -575,18 +572,8 @@ int rph_launch_pdq_resized(rph_ctx *ctx, const uint8_t *d_px, uint32_t n, uint32
     uint32_t chunk = (uint32_t)std::max<size_t>(1, (fused ? (size_t)1 << 30 : (size_t)256 << 20) / (stream_hasher ? small : (fused ? small * 4 : full)));
     chunk = std::min(std::min(chunk, n), 65535u);
     const size_t need = (full + tmp + small) * chunk;
-    if (ctx->rz_bytes < need) {
-        RPH_HIP_CHECK(hipDeviceSynchronize());  // kernels of any stream may still be using the old planes
-        if (ctx->rz_scratch) RPH_HIP_CHECK(hipFree(ctx->rz_scratch));
-        ctx->rz_scratch = nullptr;
-        ctx->rz_bytes = 0;
-        RPH_HIP_CHECK(hipMalloc((void **)&ctx->rz_scratch, need));
-        ctx->rz_bytes = need;
-    }
-    // the planes are shared by every caller stream, like the generic kernel's f32 planes, and are ordered by the same event
-    if (!ctx->scratch_done) RPH_HIP_CHECK(hipEventCreateWithFlags(&ctx->scratch_done, hipEventDisableTiming));
-    if (ctx->scratch_used && ctx->scratch_stream != stream) RPH_HIP_CHECK(hipStreamWaitEvent(stream, ctx->scratch_done, 0));
-    uint8_t *p_luma = ctx->rz_scratch, *p_tmp = p_luma + full * chunk, *p_small = p_tmp + tmp * chunk;
+    RPH_TRY(ctx->rz_scratch.acquire(stream, need));
+    uint8_t *p_luma = ctx->rz_scratch.data(), *p_tmp = p_luma + full * chunk, *p_small = p_tmp + tmp * chunk;
     for (uint32_t first = 0; first < n; first += chunk) {
         const uint32_t m = std::min(chunk, n - first);
         if (fused) {
@@ -609,31 +596,25 @@ int rph_launch_pdq_resized(rph_ctx *ctx, const uint8_t *d_px, uint32_t n, uint32
         hipLaunchKernelGGL(resize_v_kernel, dim3(grid_for((uint64_t)m * nh * nw)), dim3(256), 0, stream, (const uint8_t *)p_tmp, p_small, m, h, nw, nh, dy);
         }
         RPH_HIP_CHECK(hipGetLastError());
-        // generate_pdq_from_luma on the thumbnail (no second size check in the reference: a 4000x5 input is hashed from 512x1).
-        // It records scratch_done on `stream` when it is through, which also covers the planes above.
-        if (stream_hasher) {  // one streaming kernel per thumbnail
+        // generate_pdq_from_luma on the thumbnail (no second size check in the reference: a 4000x5 input is hashed from 512x1)
+        if (stream_hasher)  // one streaming kernel per thumbnail
             rc = rph_launch_pdq_stream(ctx, (const uint8_t *)p_small, m, nw, nh, np, small, d_hash + (size_t)first * 32, d_quality ? d_quality + first : nullptr,
                                        d_coeffs ? d_coeffs + (size_t)first * 256 : nullptr, d_dihedral ? d_dihedral + (size_t)first * 256 : nullptr,
                                        d_valid ? d_valid + first : nullptr, stream);
-            if (rc != RPH_OK) return rc;
-            RPH_HIP_CHECK(hipEventRecord(ctx->scratch_done, stream));  // (the multi-pass hasher records it itself)
-            ctx->scratch_stream = stream;
-            ctx->scratch_used = true;
-            continue;
-        }
-        rc = rph_launch_pdq_generic(ctx, (const uint8_t *)p_small, m, nw, nh, 1, np, small, d_hash + (size_t)first * 32,
-                                    d_quality ? d_quality + first : nullptr, d_coeffs ? d_coeffs + (size_t)first * 256 : nullptr,
-                                    d_dihedral ? d_dihedral + (size_t)first * 256 : nullptr, d_valid ? d_valid + first : nullptr, stream);
+        else
+            rc = rph_launch_pdq_generic(ctx, (const uint8_t *)p_small, m, nw, nh, 1, np, small, d_hash + (size_t)first * 32,
+                                        d_quality ? d_quality + first : nullptr, d_coeffs ? d_coeffs + (size_t)first * 256 : nullptr,
+                                        d_dihedral ? d_dihedral + (size_t)first * 256 : nullptr, d_valid ? d_valid + first : nullptr, stream);
         if (rc != RPH_OK) return rc;
     }
-    return RPH_OK;
+    return ctx->rz_scratch.publish(stream);
 }
 
 // debug / tests: the thumbnails the last pre-downsample call of this context left in its scratch (first `bytes` bytes, rows of align16(new_w))
 extern "C" int rph_debug_copy_thumbnails(rph_ctx *ctx, void *host_dst, size_t bytes)
 {
-    if (!ctx || !host_dst || bytes > ctx->rz_bytes) return RPH_ERR_INVALID_ARG;
+    if (!ctx || !host_dst || bytes > ctx->rz_scratch.capacity()) return RPH_ERR_INVALID_ARG;
     RPH_HIP_CHECK(hipDeviceSynchronize());
-    RPH_HIP_CHECK(hipMemcpy(host_dst, ctx->rz_scratch, bytes, hipMemcpyDeviceToHost));
+    RPH_HIP_CHECK(hipMemcpy(host_dst, ctx->rz_scratch.data(), bytes, hipMemcpyDeviceToHost));
     return RPH_OK;
 }

@@ -1,10 +1,13 @@
 // rph_api.cpp -- extern "C" surface of librupphash_hip.so (see include/rupphash.h).
 // Host-pointer entry points stage through device memory and call the *_dev twins; there is no
 // CPU implementation of any kernel behind this API.
+#include <sched.h>
+
 #include <algorithm>
 #include <atomic>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <thread>
 #include <vector>
@@ -22,30 +25,6 @@ void rph_set_error(const char *fmt, ...)
 }
 
 namespace {
-// RAII device buffer for the host-pointer wrappers
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf()
-    {
-        if (p) (void)hipFree(p);
-    }
-    int alloc(size_t bytes)
-    {
-        RPH_HIP_CHECK(hipMalloc(&p, bytes ? bytes : 1));
-        return RPH_OK;
-    }
-    template <class T>
-    T *as() const
-    {
-        return reinterpret_cast<T *>(p);
-    }
-};
-#define RPH_TRY(expr)            \
-    do {                         \
-        int rc_ = (expr);        \
-        if (rc_ != RPH_OK) return rc_; \
-    } while (0)
-
 hipStream_t pick(rph_ctx *ctx, void *stream) { return stream ? (hipStream_t)stream : ctx->stream; }
 }  // namespace
 
@@ -62,35 +41,35 @@ static int sweep_host(rph_ctx *ctx, const uint8_t *variants, uint32_t n_variants
     RPH_HIP_CHECK(hipSetDevice(ctx->device));
     DevBuf d_h, d_v, d_lc, d_hf, d_e, d_cnt;
     RPH_TRY(d_h.alloc(n * 32));
-    RPH_HIP_CHECK(hipMemcpyAsync(d_h.p, hashes32, n * 32, hipMemcpyHostToDevice, ctx->stream));
-    const uint8_t *rows = (const uint8_t *)d_h.p;
+    RPH_HIP_CHECK(hipMemcpyAsync(d_h.data(), hashes32, n * 32, hipMemcpyHostToDevice, ctx->stream));
+    const uint8_t *rows = (const uint8_t *)d_h.data();
     if (variants) {
         RPH_TRY(d_v.alloc(n * 32 * n_variants));
-        RPH_HIP_CHECK(hipMemcpyAsync(d_v.p, variants, n * 32 * n_variants, hipMemcpyHostToDevice, ctx->stream));
-        rows = (const uint8_t *)d_v.p;
+        RPH_HIP_CHECK(hipMemcpyAsync(d_v.data(), variants, n * 32 * n_variants, hipMemcpyHostToDevice, ctx->stream));
+        rows = (const uint8_t *)d_v.data();
     } else {
         n_variants = 1;
     }
     if (low_conf) {
         RPH_TRY(d_lc.alloc(n));
-        RPH_HIP_CHECK(hipMemcpyAsync(d_lc.p, low_conf, n, hipMemcpyHostToDevice, ctx->stream));
+        RPH_HIP_CHECK(hipMemcpyAsync(d_lc.data(), low_conf, n, hipMemcpyHostToDevice, ctx->stream));
     }
     if (has_features) {
         RPH_TRY(d_hf.alloc(n));
-        RPH_HIP_CHECK(hipMemcpyAsync(d_hf.p, has_features, n, hipMemcpyHostToDevice, ctx->stream));
+        RPH_HIP_CHECK(hipMemcpyAsync(d_hf.data(), has_features, n, hipMemcpyHostToDevice, ctx->stream));
     }
     RPH_TRY(d_e.alloc(cap * sizeof(rph_edge)));
     RPH_TRY(d_cnt.alloc(8));
-    RPH_HIP_CHECK(hipMemsetAsync(d_cnt.p, 0, 8, ctx->stream));
-    RPH_TRY(rph_launch_hamming_sweep(ctx, rows, n_variants, (const uint8_t *)d_h.p, (const uint8_t *)d_lc.p,
-                                     (const uint8_t *)d_hf.p, n, thr, part, nparts, (rph_edge *)d_e.p, cap,
-                                     (unsigned long long *)d_cnt.p, ctx->stream, ctx->hamming_kernel));
+    RPH_HIP_CHECK(hipMemsetAsync(d_cnt.data(), 0, 8, ctx->stream));
+    RPH_TRY(rph_launch_hamming_sweep(ctx, rows, n_variants, (const uint8_t *)d_h.data(), (const uint8_t *)d_lc.data(),
+                                     (const uint8_t *)d_hf.data(), n, thr, part, nparts, (rph_edge *)d_e.data(), cap,
+                                     (unsigned long long *)d_cnt.data(), ctx->stream, ctx->hamming_kernel));
     unsigned long long cnt = 0;
-    RPH_HIP_CHECK(hipMemcpyAsync(&cnt, d_cnt.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+    RPH_HIP_CHECK(hipMemcpyAsync(&cnt, d_cnt.data(), 8, hipMemcpyDeviceToHost, ctx->stream));
     RPH_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     *n_edges_out = cnt;
     const uint64_t take = std::min<uint64_t>(cnt, cap);
-    if (take) RPH_HIP_CHECK(hipMemcpy(edges, d_e.p, take * sizeof(rph_edge), hipMemcpyDeviceToHost));
+    if (take) RPH_HIP_CHECK(hipMemcpy(edges, d_e.data(), take * sizeof(rph_edge), hipMemcpyDeviceToHost));
     if (cnt > cap) {
         rph_set_error("hamming sweep: %llu edges found, capacity %llu", cnt, (unsigned long long)cap);
         return RPH_ERR_CAPACITY;
@@ -128,25 +107,20 @@ static bool pdq_geometry_ok(uint32_t n, uint32_t w, uint32_t h, uint32_t channel
 // ---- staging pipe of rph_pdq_hash_batch ----
 namespace {
 constexpr size_t kPipeChunkBytes = (size_t)64 << 20;
+struct PipeSet {  // one staging set: pinned host + device buffers of one chunk and the stream they are used on
+    hipStream_t stream = nullptr;
+    PinnedBuf h_px, h_hash, h_q, h_c, h_d, h_v;
+    DevBuf d_px, d_hash, d_q, d_c, d_d, d_v;
+};
 struct HostPipe {
-    hipStream_t stream[2] = {nullptr, nullptr};
-    uint8_t *h_px[2] = {nullptr, nullptr}, *h_hash[2] = {nullptr, nullptr}, *h_d[2] = {nullptr, nullptr}, *h_v[2] = {nullptr, nullptr};
-    float *h_q[2] = {nullptr, nullptr}, *h_c[2] = {nullptr, nullptr};
-    void *d_px[2] = {nullptr, nullptr}, *d_hash[2] = {nullptr, nullptr}, *d_q[2] = {nullptr, nullptr}, *d_c[2] = {nullptr, nullptr}, *d_d[2] = {nullptr, nullptr},
-         *d_v[2] = {nullptr, nullptr};
-    size_t px_bytes = 0;
-    uint32_t images = 0;
-    void release()
+    PipeSet set[2];
+    ~HostPipe()  // the streams first: their work may still use the buffers
     {
-        for (int b = 0; b < 2; b++) {
-            if (stream[b]) (void)hipStreamSynchronize(stream[b]);
-            for (void *p : {(void *)h_px[b], (void *)h_hash[b], (void *)h_d[b], (void *)h_v[b], (void *)h_q[b], (void *)h_c[b]})
-                if (p) (void)hipHostFree(p);
-            for (void *p : {d_px[b], d_hash[b], d_q[b], d_c[b], d_d[b], d_v[b]})
-                if (p) (void)hipFree(p);
-            if (stream[b]) (void)hipStreamDestroy(stream[b]);
-        }
-        *this = HostPipe();
+        for (PipeSet &S : set)
+            if (S.stream) {
+                (void)hipStreamSynchronize(S.stream);
+                (void)hipStreamDestroy(S.stream);
+            }
     }
 };
 
@@ -154,27 +128,18 @@ int pipe_of(rph_ctx *ctx, size_t px_bytes, uint32_t images, HostPipe **out)
 {
     if (!ctx->pipe) ctx->pipe = new HostPipe();
     HostPipe &P = *static_cast<HostPipe *>(ctx->pipe);
-    if (P.px_bytes < px_bytes || P.images < images) {
-        const size_t nb = std::max(px_bytes, P.px_bytes);
-        const uint32_t ni = std::max(images, P.images);
-        P.release();
-        for (int b = 0; b < 2; b++) {
-            RPH_HIP_CHECK(hipStreamCreateWithFlags(&P.stream[b], hipStreamNonBlocking));
-            RPH_HIP_CHECK(hipHostMalloc((void **)&P.h_px[b], nb));
-            RPH_HIP_CHECK(hipMalloc(&P.d_px[b], nb));
-            RPH_HIP_CHECK(hipHostMalloc((void **)&P.h_hash[b], (size_t)ni * 32));
-            RPH_HIP_CHECK(hipHostMalloc((void **)&P.h_q[b], (size_t)ni * 4));
-            RPH_HIP_CHECK(hipHostMalloc((void **)&P.h_c[b], (size_t)ni * 1024));
-            RPH_HIP_CHECK(hipHostMalloc((void **)&P.h_d[b], (size_t)ni * 256));
-            RPH_HIP_CHECK(hipHostMalloc((void **)&P.h_v[b], ni));
-            RPH_HIP_CHECK(hipMalloc(&P.d_hash[b], (size_t)ni * 32));
-            RPH_HIP_CHECK(hipMalloc(&P.d_q[b], (size_t)ni * 4));
-            RPH_HIP_CHECK(hipMalloc(&P.d_c[b], (size_t)ni * 1024));
-            RPH_HIP_CHECK(hipMalloc(&P.d_d[b], (size_t)ni * 256));
-            RPH_HIP_CHECK(hipMalloc(&P.d_v[b], ni));
-        }
-        P.px_bytes = nb;
-        P.images = ni;
+    for (PipeSet &S : P.set) {
+        if (!S.stream) RPH_HIP_CHECK(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking));
+        auto twin = [&](PinnedBuf &h, DevBuf &d, size_t bytes) -> int {
+            RPH_TRY(h.reserve(bytes, S.stream));
+            return d.reserve(bytes, S.stream);
+        };
+        RPH_TRY(twin(S.h_px, S.d_px, px_bytes));
+        RPH_TRY(twin(S.h_hash, S.d_hash, (size_t)images * 32));
+        RPH_TRY(twin(S.h_q, S.d_q, (size_t)images * 4));
+        RPH_TRY(twin(S.h_c, S.d_c, (size_t)images * 1024));
+        RPH_TRY(twin(S.h_d, S.d_d, (size_t)images * 256));
+        RPH_TRY(twin(S.h_v, S.d_v, images));
     }
     *out = &P;
     return RPH_OK;
@@ -183,31 +148,42 @@ int pipe_of(rph_ctx *ctx, size_t px_bytes, uint32_t images, HostPipe **out)
 // pageable -> pinned with a few threads (one core moves ~10 GB/s, PCIe takes ~55)
 void parallel_copy(uint8_t *dst, const uint8_t *src, size_t bytes)
 {
-    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-    const unsigned nt = (unsigned)std::min<size_t>(std::min(8u, hw), bytes / ((size_t)4 << 20) + 1);
-    if (nt <= 1) {
-        std::memcpy(dst, src, bytes);
-        return;
-    }
-    std::vector<std::thread> th;
-    const size_t part = ((bytes / nt) + 4095) & ~(size_t)4095;
-    for (unsigned t = 1; t < nt; t++) {
+    const size_t parts = bytes / ((size_t)4 << 20) + 1;
+    const unsigned nt = parts > 1 ? (unsigned)std::min<size_t>(std::min(8u, rph_host_threads()), parts) : 1;
+    const size_t part = align_up(bytes / nt, 4096);
+    parallel_for(0, nt, nt, [&](size_t t) {
         const size_t lo = std::min(bytes, part * t), hi = std::min(bytes, part * (t + 1));
-        if (hi > lo) th.emplace_back([=] { std::memcpy(dst + lo, src + lo, hi - lo); });
-    }
-    std::memcpy(dst, src, std::min(bytes, part));
-    for (auto &x : th) x.join();
+        if (hi > lo) std::memcpy(dst + lo, src + lo, hi - lo);
+    });
 }
 }  // namespace
 
+unsigned rph_host_threads()
+{
+    unsigned n = std::max(1u, std::thread::hardware_concurrency());
+    cpu_set_t set;
+    if (sched_getaffinity(0, sizeof set, &set) == 0) n = std::min<unsigned>(n, (unsigned)std::max(1, CPU_COUNT(&set)));
+    long long quota = -1, period = 100000;
+    if (FILE *f = fopen("/sys/fs/cgroup/cpu.max", "r")) {  // cgroup v2: "max 100000" or "1600000 100000"
+        char q[32] = "";
+        if (fscanf(f, "%31s %lld", q, &period) == 2 && strcmp(q, "max") != 0) quota = atoll(q);
+        fclose(f);
+    } else if (FILE *g = fopen("/sys/fs/cgroup/cpu/cpu.cfs_quota_us", "r")) {  // cgroup v1
+        if (fscanf(g, "%lld", &quota) != 1) quota = -1;
+        fclose(g);
+        if (FILE *h = fopen("/sys/fs/cgroup/cpu/cpu.cfs_period_us", "r")) {
+            if (fscanf(h, "%lld", &period) != 1) period = 100000;
+            fclose(h);
+        }
+    }
+    if (quota > 0 && period > 0) n = std::min<unsigned>(n, (unsigned)std::max<long long>(1, (quota + period - 1) / period));
+    return n;
+}
+
 void rph_pipe_forget(rph_ctx *ctx)
 {
-    if (ctx->pipe) {
-        HostPipe *P = static_cast<HostPipe *>(ctx->pipe);
-        P->release();
-        delete P;
-        ctx->pipe = nullptr;
-    }
+    delete static_cast<HostPipe *>(ctx->pipe);
+    ctx->pipe = nullptr;
 }
 
 extern "C" {
@@ -275,16 +251,10 @@ int rph_shutdown(rph_ctx *ctx)
     rph_resize_forget(ctx);
     rph_jpeg_forget(ctx);
     rph_png_forget(ctx);
-    rph_blake3_forget(ctx);
     rph_jpeg_forget_threads(ctx);
-    if (ctx->scratch) (void)hipFree(ctx->scratch);
-    for (auto &kv : ctx->ll_scratch) (void)hipFree(kv.second.p);
     if (ctx->sink) (void)hipFree(ctx->sink);
-    if (ctx->scratch_done) (void)hipEventDestroy(ctx->scratch_done);
-    if (ctx->sweep_scratch) (void)hipFree(ctx->sweep_scratch);
-    if (ctx->sweep_done) (void)hipEventDestroy(ctx->sweep_done);
     (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    delete ctx;  // the shared and per-stream scratch free themselves
     return RPH_OK;
 }
 
@@ -413,13 +383,14 @@ int rph_pdq_hash_batch_keep(rph_ctx *ctx, const uint8_t *px, uint32_t n, uint32_
         } pend[2];
         auto finish = [&](int b) -> int {  // results of the chunk that used set b -> the caller's arrays
             if (!pend[b].active) return RPH_OK;
-            RPH_HIP_CHECK(hipStreamSynchronize(P->stream[b]));
+            const PipeSet &S = P->set[b];
+            RPH_HIP_CHECK(hipStreamSynchronize(S.stream));
             const uint32_t first = pend[b].first, m = pend[b].m;
-            std::memcpy(hash32_out + (size_t)first * 32, P->h_hash[b], (size_t)m * 32);
-            if (quality_out) std::memcpy(quality_out + first, P->h_q[b], (size_t)m * 4);
-            if (coeffs_out) std::memcpy(coeffs_out + (size_t)first * 256, P->h_c[b], (size_t)m * 1024);
-            if (dihedral_out) std::memcpy(dihedral_out + (size_t)first * 256, P->h_d[b], (size_t)m * 256);
-            if (valid_out) std::memcpy(valid_out + first, P->h_v[b], m);
+            std::memcpy(hash32_out + (size_t)first * 32, S.h_hash.data(), (size_t)m * 32);
+            if (quality_out) std::memcpy(quality_out + first, S.h_q.data(), (size_t)m * 4);
+            if (coeffs_out) std::memcpy(coeffs_out + (size_t)first * 256, S.h_c.data(), (size_t)m * 1024);
+            if (dihedral_out) std::memcpy(dihedral_out + (size_t)first * 256, S.h_d.data(), (size_t)m * 256);
+            if (valid_out) std::memcpy(valid_out + first, S.h_v.data(), m);
             pend[b].active = false;
             return RPH_OK;
         };
@@ -427,23 +398,24 @@ int rph_pdq_hash_batch_keep(rph_ctx *ctx, const uint8_t *px, uint32_t n, uint32_
         for (uint32_t first = 0; first < n; first += chunk, k++) {
             const int b = k & 1;
             RPH_TRY(finish(b));
+            PipeSet &S = P->set[b];
             const uint32_t m = std::min(chunk, n - first);
             const size_t bytes = (size_t)(m - 1) * per + one_image;  // the last image may be shorter than image_stride in the caller's buffer
-            parallel_copy(P->h_px[b], px + (size_t)first * per, bytes);
-            hipStream_t s = P->stream[b];
-            RPH_HIP_CHECK(hipMemcpyAsync(P->d_px[b], P->h_px[b], bytes, hipMemcpyHostToDevice, s));
+            parallel_copy(S.h_px.data(), px + (size_t)first * per, bytes);
+            hipStream_t s = S.stream;
+            RPH_HIP_CHECK(hipMemcpyAsync(S.d_px.data(), S.h_px.data(), bytes, hipMemcpyHostToDevice, s));
             const bool want_q = quality_out || d_quality_keep, want_d = dihedral_out || d_dihedral_keep;
-            RPH_TRY(rph_pdq_hash_batch_dev(ctx, P->d_px[b], m, w, h, channels, row_stride, per, P->d_hash[b], want_q ? P->d_q[b] : nullptr,
-                                           coeffs_out ? P->d_c[b] : nullptr, want_d ? P->d_d[b] : nullptr, valid_out ? P->d_v[b] : nullptr, s));
-            if (d_hash_keep) RPH_HIP_CHECK(hipMemcpyAsync((uint8_t *)d_hash_keep + (size_t)first * 32, P->d_hash[b], (size_t)m * 32, hipMemcpyDeviceToDevice, s));
-            if (d_quality_keep) RPH_HIP_CHECK(hipMemcpyAsync((float *)d_quality_keep + first, P->d_q[b], (size_t)m * 4, hipMemcpyDeviceToDevice, s));
+            RPH_TRY(rph_pdq_hash_batch_dev(ctx, S.d_px.data(), m, w, h, channels, row_stride, per, S.d_hash.data(), want_q ? S.d_q.data() : nullptr,
+                                           coeffs_out ? S.d_c.data() : nullptr, want_d ? S.d_d.data() : nullptr, valid_out ? S.d_v.data() : nullptr, s));
+            if (d_hash_keep) RPH_HIP_CHECK(hipMemcpyAsync((uint8_t *)d_hash_keep + (size_t)first * 32, S.d_hash.data(), (size_t)m * 32, hipMemcpyDeviceToDevice, s));
+            if (d_quality_keep) RPH_HIP_CHECK(hipMemcpyAsync((float *)d_quality_keep + first, S.d_q.data(), (size_t)m * 4, hipMemcpyDeviceToDevice, s));
             if (d_dihedral_keep)
-                RPH_HIP_CHECK(hipMemcpyAsync((uint8_t *)d_dihedral_keep + (size_t)first * 256, P->d_d[b], (size_t)m * 256, hipMemcpyDeviceToDevice, s));
-            RPH_HIP_CHECK(hipMemcpyAsync(P->h_hash[b], P->d_hash[b], (size_t)m * 32, hipMemcpyDeviceToHost, s));
-            if (quality_out) RPH_HIP_CHECK(hipMemcpyAsync(P->h_q[b], P->d_q[b], (size_t)m * 4, hipMemcpyDeviceToHost, s));
-            if (coeffs_out) RPH_HIP_CHECK(hipMemcpyAsync(P->h_c[b], P->d_c[b], (size_t)m * 1024, hipMemcpyDeviceToHost, s));
-            if (dihedral_out) RPH_HIP_CHECK(hipMemcpyAsync(P->h_d[b], P->d_d[b], (size_t)m * 256, hipMemcpyDeviceToHost, s));
-            if (valid_out) RPH_HIP_CHECK(hipMemcpyAsync(P->h_v[b], P->d_v[b], m, hipMemcpyDeviceToHost, s));
+                RPH_HIP_CHECK(hipMemcpyAsync((uint8_t *)d_dihedral_keep + (size_t)first * 256, S.d_d.data(), (size_t)m * 256, hipMemcpyDeviceToDevice, s));
+            RPH_HIP_CHECK(hipMemcpyAsync(S.h_hash.data(), S.d_hash.data(), (size_t)m * 32, hipMemcpyDeviceToHost, s));
+            if (quality_out) RPH_HIP_CHECK(hipMemcpyAsync(S.h_q.data(), S.d_q.data(), (size_t)m * 4, hipMemcpyDeviceToHost, s));
+            if (coeffs_out) RPH_HIP_CHECK(hipMemcpyAsync(S.h_c.data(), S.d_c.data(), (size_t)m * 1024, hipMemcpyDeviceToHost, s));
+            if (dihedral_out) RPH_HIP_CHECK(hipMemcpyAsync(S.h_d.data(), S.d_d.data(), (size_t)m * 256, hipMemcpyDeviceToHost, s));
+            if (valid_out) RPH_HIP_CHECK(hipMemcpyAsync(S.h_v.data(), S.d_v.data(), m, hipMemcpyDeviceToHost, s));
             pend[b].first = first;
             pend[b].m = m;
             pend[b].active = true;
@@ -480,10 +452,10 @@ int rph_pdq_hashes_from_coeffs(rph_ctx *ctx, const float *coeffs, uint32_t n, ui
         RPH_TRY(d_c.alloc((size_t)n * 1024));
         if (hash32_out) RPH_TRY(d_h.alloc((size_t)n * 32));
         if (dihedral_out) RPH_TRY(d_d.alloc((size_t)n * 256));
-        RPH_HIP_CHECK(hipMemcpyAsync(d_c.p, coeffs, (size_t)n * 1024, hipMemcpyHostToDevice, ctx->stream));
-        RPH_TRY(rph_pdq_hashes_from_coeffs_dev(ctx, d_c.p, n, d_h.p, d_d.p, ctx->stream));
-        if (hash32_out) RPH_HIP_CHECK(hipMemcpyAsync(hash32_out, d_h.p, (size_t)n * 32, hipMemcpyDeviceToHost, ctx->stream));
-        if (dihedral_out) RPH_HIP_CHECK(hipMemcpyAsync(dihedral_out, d_d.p, (size_t)n * 256, hipMemcpyDeviceToHost, ctx->stream));
+        RPH_HIP_CHECK(hipMemcpyAsync(d_c.data(), coeffs, (size_t)n * 1024, hipMemcpyHostToDevice, ctx->stream));
+        RPH_TRY(rph_pdq_hashes_from_coeffs_dev(ctx, d_c.data(), n, d_h.data(), d_d.data(), ctx->stream));
+        if (hash32_out) RPH_HIP_CHECK(hipMemcpyAsync(hash32_out, d_h.data(), (size_t)n * 32, hipMemcpyDeviceToHost, ctx->stream));
+        if (dihedral_out) RPH_HIP_CHECK(hipMemcpyAsync(dihedral_out, d_d.data(), (size_t)n * 256, hipMemcpyDeviceToHost, ctx->stream));
         RPH_HIP_CHECK(hipStreamSynchronize(ctx->stream));
         return RPH_OK;
     });
@@ -568,16 +540,16 @@ int rph_hamming_all_pairs64(rph_ctx *ctx, const uint64_t *hashes64, uint64_t n, 
         RPH_TRY(d_h.alloc(n * 8));
         RPH_TRY(d_e.alloc(cap * sizeof(rph_edge)));
         RPH_TRY(d_cnt.alloc(8));
-        RPH_HIP_CHECK(hipMemcpyAsync(d_h.p, hashes64, n * 8, hipMemcpyHostToDevice, ctx->stream));
-        RPH_HIP_CHECK(hipMemsetAsync(d_cnt.p, 0, 8, ctx->stream));
-        RPH_TRY(rph_launch_hamming64_sweep((const uint64_t *)d_h.p, n, threshold, part, nparts, (rph_edge *)d_e.p, cap,
-                                           (unsigned long long *)d_cnt.p, ctx->stream, ctx->hamming_kernel));
+        RPH_HIP_CHECK(hipMemcpyAsync(d_h.data(), hashes64, n * 8, hipMemcpyHostToDevice, ctx->stream));
+        RPH_HIP_CHECK(hipMemsetAsync(d_cnt.data(), 0, 8, ctx->stream));
+        RPH_TRY(rph_launch_hamming64_sweep((const uint64_t *)d_h.data(), n, threshold, part, nparts, (rph_edge *)d_e.data(), cap,
+                                           (unsigned long long *)d_cnt.data(), ctx->stream, ctx->hamming_kernel));
         unsigned long long cnt = 0;
-        RPH_HIP_CHECK(hipMemcpyAsync(&cnt, d_cnt.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+        RPH_HIP_CHECK(hipMemcpyAsync(&cnt, d_cnt.data(), 8, hipMemcpyDeviceToHost, ctx->stream));
         RPH_HIP_CHECK(hipStreamSynchronize(ctx->stream));
         *n_edges_out = cnt;
         const uint64_t take = std::min<uint64_t>(cnt, cap);
-        if (take) RPH_HIP_CHECK(hipMemcpy(edges, d_e.p, take * sizeof(rph_edge), hipMemcpyDeviceToHost));
+        if (take) RPH_HIP_CHECK(hipMemcpy(edges, d_e.data(), take * sizeof(rph_edge), hipMemcpyDeviceToHost));
         if (cnt > cap) {
             rph_set_error("hamming64 sweep: %llu edges found, capacity %llu", cnt, (unsigned long long)cap);
             return RPH_ERR_CAPACITY;
@@ -674,15 +646,15 @@ int rph_group_files_pdq(rph_ctx *ctx, const uint8_t *hashes32, const float *coef
         hipStream_t s = ctx->stream;
         DevBuf d_h, d_var, d_lc, d_hf, d_stage, d_e, d_cnt;
         RPH_TRY(d_h.alloc(n * 32));
-        RPH_HIP_CHECK(hipMemcpyAsync(d_h.p, hashes32, n * 32, hipMemcpyHostToDevice, s));
+        RPH_HIP_CHECK(hipMemcpyAsync(d_h.data(), hashes32, n * 32, hipMemcpyHostToDevice, s));
         if (quality) {
             RPH_TRY(d_lc.alloc(n));
-            RPH_HIP_CHECK(hipMemcpyAsync(d_lc.p, low_conf.data(), n, hipMemcpyHostToDevice, s));
+            RPH_HIP_CHECK(hipMemcpyAsync(d_lc.data(), low_conf.data(), n, hipMemcpyHostToDevice, s));
         }
         const bool use_hf = coeffs && has_features;
         if (use_hf) {
             RPH_TRY(d_hf.alloc(n));
-            RPH_HIP_CHECK(hipMemcpyAsync(d_hf.p, has_features, n, hipMemcpyHostToDevice, s));
+            RPH_HIP_CHECK(hipMemcpyAsync(d_hf.data(), has_features, n, hipMemcpyHostToDevice, s));
         }
         if (coeffs) {
             RPH_TRY(d_var.alloc(n * 256));
@@ -690,8 +662,8 @@ int rph_group_files_pdq(rph_ctx *ctx, const uint8_t *hashes32, const float *coef
             RPH_TRY(d_stage.alloc(std::min<uint64_t>(step, n) * 1024));
             for (uint64_t first = 0; first < n; first += step) {
                 const uint32_t m = (uint32_t)std::min<uint64_t>(step, n - first);
-                RPH_HIP_CHECK(hipMemcpyAsync(d_stage.p, coeffs + first * 256, (size_t)m * 1024, hipMemcpyHostToDevice, s));
-                RPH_TRY(rph_launch_pdq_from_coeffs((const float *)d_stage.p, m, nullptr, d_var.as<uint8_t>() + first * 256, s));
+                RPH_HIP_CHECK(hipMemcpyAsync(d_stage.data(), coeffs + first * 256, (size_t)m * 1024, hipMemcpyHostToDevice, s));
+                RPH_TRY(rph_launch_pdq_from_coeffs((const float *)d_stage.data(), m, nullptr, d_var.as<uint8_t>() + first * 256, s));
             }
             if (use_hf) RPH_TRY(rph_launch_featureless_variants(d_h.as<uint8_t>(), d_hf.as<uint8_t>(), n, d_var.as<uint8_t>(), s));
         }
@@ -702,24 +674,22 @@ int rph_group_files_pdq(rph_ctx *ctx, const uint8_t *hashes32, const float *coef
         RPH_TRY(d_cnt.alloc(8));
         for (int attempt = 0;; attempt++) {
             RPH_TRY(d_e.alloc(cap * sizeof(rph_edge)));
-            RPH_HIP_CHECK(hipMemsetAsync(d_cnt.p, 0, 8, s));
+            RPH_HIP_CHECK(hipMemsetAsync(d_cnt.data(), 0, 8, s));
             RPH_TRY(rph_launch_hamming_sweep(ctx, coeffs ? d_var.as<uint8_t>() : d_h.as<uint8_t>(), coeffs ? 8 : 1, d_h.as<uint8_t>(), d_lc.as<uint8_t>(),
                                              use_hf ? d_hf.as<uint8_t>() : nullptr, n, similarity, 0, 1, d_e.as<rph_edge>(), cap,
                                              d_cnt.as<unsigned long long>(), s, ctx->hamming_kernel));
             unsigned long long found = 0;
-            RPH_HIP_CHECK(hipMemcpyAsync(&found, d_cnt.p, 8, hipMemcpyDeviceToHost, s));
+            RPH_HIP_CHECK(hipMemcpyAsync(&found, d_cnt.data(), 8, hipMemcpyDeviceToHost, s));
             RPH_HIP_CHECK(hipStreamSynchronize(s));
             if (found <= cap) {
                 edges.resize(found);
-                if (found) RPH_HIP_CHECK(hipMemcpy(edges.data(), d_e.p, found * sizeof(rph_edge), hipMemcpyDeviceToHost));
+                if (found) RPH_HIP_CHECK(hipMemcpy(edges.data(), d_e.data(), found * sizeof(rph_edge), hipMemcpyDeviceToHost));
                 break;
             }
             if (attempt >= 2) {
                 rph_set_error("rph_group_files_pdq: edge list kept growing (%llu)", found);
                 return RPH_ERR_CAPACITY;
             }
-            (void)hipFree(d_e.p);
-            d_e.p = nullptr;
             cap = found + found / 16 + 1024;
         }
         if (comparison_count_out) *comparison_count_out = edges.size();
@@ -740,13 +710,13 @@ int rph_mih_build256(rph_ctx *ctx, const uint8_t *hashes32, uint64_t n, uint32_t
         RPH_TRY(d_h.alloc(n * 32));
         RPH_TRY(d_o.alloc(n_off * 4));
         RPH_TRY(d_v.alloc(n * 16 * 4));
-        RPH_HIP_CHECK(hipMemcpyAsync(d_h.p, hashes32, n * 32, hipMemcpyHostToDevice, ctx->stream));
+        RPH_HIP_CHECK(hipMemcpyAsync(d_h.data(), hashes32, n * 32, hipMemcpyHostToDevice, ctx->stream));
         {
             std::lock_guard<std::mutex> lock(ctx->mu);
-            RPH_TRY(rph_launch_mih_build256(ctx, (const uint8_t *)d_h.p, n, (uint32_t *)d_o.p, (uint32_t *)d_v.p, ctx->stream));
+            RPH_TRY(rph_launch_mih_build256(ctx, (const uint8_t *)d_h.data(), n, (uint32_t *)d_o.data(), (uint32_t *)d_v.data(), ctx->stream));
         }
-        RPH_HIP_CHECK(hipMemcpyAsync(offsets, d_o.p, n_off * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (n) RPH_HIP_CHECK(hipMemcpyAsync(values, d_v.p, n * 16 * 4, hipMemcpyDeviceToHost, ctx->stream));
+        RPH_HIP_CHECK(hipMemcpyAsync(offsets, d_o.data(), n_off * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (n) RPH_HIP_CHECK(hipMemcpyAsync(values, d_v.data(), n * 16 * 4, hipMemcpyDeviceToHost, ctx->stream));
         RPH_HIP_CHECK(hipStreamSynchronize(ctx->stream));
         return RPH_OK;
     });
@@ -766,10 +736,10 @@ int rph_mih_build64(rph_ctx *ctx, const uint64_t *hashes64, uint64_t n, uint32_t
         RPH_TRY(d_o.alloc(n_off * 4));
         RPH_TRY(d_v.alloc(n * 8 * 4));
         std::lock_guard<std::mutex> lock(ctx->mu);
-        RPH_HIP_CHECK(hipMemcpyAsync(d_h.p, hashes64, n * 8, hipMemcpyHostToDevice, ctx->stream));
-        RPH_TRY(rph_launch_mih_build64(ctx, (const uint64_t *)d_h.p, n, (uint32_t *)d_o.p, (uint32_t *)d_v.p, ctx->stream));
-        RPH_HIP_CHECK(hipMemcpyAsync(offsets, d_o.p, n_off * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (n) RPH_HIP_CHECK(hipMemcpyAsync(values, d_v.p, n * 8 * 4, hipMemcpyDeviceToHost, ctx->stream));
+        RPH_HIP_CHECK(hipMemcpyAsync(d_h.data(), hashes64, n * 8, hipMemcpyHostToDevice, ctx->stream));
+        RPH_TRY(rph_launch_mih_build64(ctx, (const uint64_t *)d_h.data(), n, (uint32_t *)d_o.data(), (uint32_t *)d_v.data(), ctx->stream));
+        RPH_HIP_CHECK(hipMemcpyAsync(offsets, d_o.data(), n_off * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (n) RPH_HIP_CHECK(hipMemcpyAsync(values, d_v.data(), n * 8 * 4, hipMemcpyDeviceToHost, ctx->stream));
         RPH_HIP_CHECK(hipStreamSynchronize(ctx->stream));
         return RPH_OK;
     });
@@ -865,13 +835,8 @@ int rph_stream_destroy(rph_ctx *ctx, void *stream)
     RPH_HIP_CHECK(hipSetDevice(ctx->device));
     std::lock_guard<std::mutex> lock(ctx->mu);
     RPH_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
-    if (ctx->scratch_stream == (hipStream_t)stream) ctx->scratch_used = false;  // its work is complete: nothing left to order behind
-    if (ctx->sweep_stream == (hipStream_t)stream) ctx->sweep_used = false;
-    auto ll = ctx->ll_scratch.find((hipStream_t)stream);
-    if (ll != ctx->ll_scratch.end()) {
-        (void)hipFree(ll->second.p);
-        ctx->ll_scratch.erase(ll);
-    }
+    for (SharedScratch *sc : {&ctx->scratch, &ctx->rz_scratch, &ctx->sweep_scratch, &ctx->b3_scratch}) sc->forget_stream((hipStream_t)stream);
+    ctx->ll_scratch.erase((hipStream_t)stream);
     RPH_HIP_CHECK(hipStreamDestroy((hipStream_t)stream));
     return RPH_OK;
 }

@@ -10,43 +10,26 @@
 #include <vector>
 
 #include "../../include/rupphash.h"
+#include "rph_buffers.h"
 
 struct rph_ctx {
     int device = 0;
     int compute_units = 0;
     hipStream_t stream = nullptr;
     std::mutex mu;
-    // scratch for the generic (multi-pass) PDQ kernel: two f32 planes per in-flight image
-    float *scratch = nullptr;
-    size_t scratch_bytes = 0;
     uint32_t *sink = nullptr;  // 4-byte result slot of the read-stream probe
-    // the scratch planes are shared by every caller stream: a launch on another stream first waits for the last user's event
-    hipEvent_t scratch_done = nullptr;
-    hipStream_t scratch_stream = nullptr;
-    bool scratch_used = false;
+    // device scratch shared by every caller stream (rph_buffers.h): the generic (multi-pass) PDQ kernel's two f32 planes per in-flight
+    // image; the pre-downsample's u8 planes for > 512 px inputs (full-resolution luma, horizontal pass, thumbnail); the popcount-sorted
+    // sweep's sorted hashes, permutation, popcounts and radix-sort workspace; BLAKE3's plan and group values
+    SharedScratch scratch, rz_scratch, sweep_scratch, b3_scratch;
     // sample scratch of the low-latency PDQ kernel, one per caller stream (133 KB per image of a launch chunk): launches on different
     // streams -- the one-image queue's pipeline slots -- share nothing and need no ordering between them
-    struct LLScratch {
-        float *p = nullptr;
-        size_t bytes = 0;
-    };
-    std::map<hipStream_t, LLScratch> ll_scratch;
+    std::map<hipStream_t, DevBuf> ll_scratch;
     // rph_pdq_hash_batch (host pointers): two pinned staging sets + device twins, alternated over two streams so that the host
     // copy / H2D of one chunk overlaps the transfer and kernels of the other (rph_api.cpp); one host-batch call at a time
     std::mutex pipe_mu;
     void *pipe = nullptr;
-    // pre-downsample (> 512 px inputs): u8 planes (full-resolution luma, horizontal pass, thumbnail) and the per-geometry
-    // coefficient tables, kept across calls; ordered between streams together with `scratch` (the generic kernel follows on the
-    // same stream and records scratch_done)
-    uint8_t *rz_scratch = nullptr;
-    size_t rz_bytes = 0;
-    void *axis_cache = nullptr;  // resize_kernels.hip
-    // scratch of the popcount-sorted sweep (sorted hashes, permutation, popcounts, radix-sort workspace); same stream ordering rule
-    void *sweep_scratch = nullptr;
-    size_t sweep_scratch_bytes = 0;
-    hipEvent_t sweep_done = nullptr;
-    hipStream_t sweep_stream = nullptr;
-    bool sweep_used = false;
+    void *axis_cache = nullptr;  // per-geometry coefficient tables of the pre-downsample, kept across calls (resize_kernels.hip)
     // 2 = fp4 MFMA formulation of the sweep's fast path, popcount-sorted {0,1} operands for plain all-pairs sweeps (default),
     // 3 = fp4 MFMA with +-1 operands everywhere, 4 = sorted {0,1} at every size, 1 = int8 MFMA, 0 = VALU xor + popcount
     int hamming_kernel = 2;
@@ -75,19 +58,7 @@ struct rph_ctx {
     std::mutex png_mu;
     void *png = nullptr;
     int png_inflate = RPH_PNG_INFLATE_AUTO;
-    void *b3 = nullptr;                       // BLAKE3 scratch (blake3_kernels.hip): plan and group values, ordered between streams by an event
 };
-
-void rph_set_error(const char *fmt, ...);
-
-#define RPH_HIP_CHECK(expr)                                                                  \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            rph_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return e_ == hipErrorOutOfMemory ? RPH_ERR_OOM : RPH_ERR_HIP;                    \
-        }                                                                                    \
-    } while (0)
 
 // ---- launchers implemented in the .hip files (all asynchronous on `stream`) ----
 // pdq_kernels.hip
@@ -167,8 +138,6 @@ void rph_resize_forget(rph_ctx *ctx);
 void rph_jpeg_forget(rph_ctx *ctx);
 // png_pipeline.cpp
 void rph_png_forget(rph_ctx *ctx);
-// blake3_kernels.hip
-void rph_blake3_forget(rph_ctx *ctx);
 void rph_jpeg_forget_threads(rph_ctx *ctx);
 
 // host_grouping.cpp

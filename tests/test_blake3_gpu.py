@@ -109,6 +109,40 @@ def test_pixel_hash_dev_form(eng):
         assert bytes(got[k]) == b3.pixel_hash(im)
 
 
+def test_pixel_hash_dev_on_two_caller_streams():
+    """Images above 8192 px keep their group values in one scratch per context, shared by every caller stream.  On a fresh context
+    the second geometry needs more of it, so it grows while the other stream may still be using it."""
+    from rupphash_amd import Engine
+
+    eng = Engine(0)
+    rng = np.random.default_rng(35)
+    sets = [rng.integers(0, 256, (4, 100, 120, 3), dtype=np.uint8), rng.integers(0, 256, (6, 130, 160, 4), dtype=np.uint8)]
+    streams = [eng.stream_create(), eng.stream_create()]
+    d_px = [eng.dev_alloc(s.nbytes) for s in sets]
+    d_h = [eng.dev_alloc(len(s) * 32) for s in sets]
+    try:
+        for k in range(2):
+            eng.dev_upload(d_px[k], sets[k])
+        eng.synchronize()
+        for rep in range(20):  # no host synchronisation between the launches
+            for k in range(2):
+                n, h, w, ch = sets[k].shape
+                eng.pixel_hash_batch_dev(d_px[k], n, w, h, ch, d_h[k], stream=streams[k])
+        for st in streams:
+            eng.stream_synchronize(st)
+        for k in range(2):
+            got = np.zeros((len(sets[k]), 32), np.uint8)
+            eng.dev_download(got, d_h[k])
+            for i in range(len(sets[k])):
+                assert bytes(got[i]) == b3.pixel_hash(sets[k][i]), (k, i)
+    finally:
+        for p in d_px + d_h:
+            eng.dev_free(p)
+        for st in streams:
+            eng.stream_destroy(st)
+        eng.close()
+
+
 def test_scanner_pixel_hash(eng):
     from rupphash_amd import scanner
 

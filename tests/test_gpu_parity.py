@@ -15,6 +15,16 @@ def eng():
     e.close()
 
 
+@pytest.fixture
+def fresh_eng():
+    """a context of its own: its shared scratches start empty, so a test sees them grow"""
+    from rupphash_amd import Engine
+
+    e = Engine(0)
+    yield e
+    e.close()
+
+
 def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
@@ -904,3 +914,124 @@ def test_generic_path_on_two_caller_streams(eng, oracle):
             eng.dev_free(p)
         for st in streams:
             eng.stream_destroy(st)
+
+
+def test_resize_path_on_two_caller_streams(fresh_eng, oracle):
+    """Inputs above 512 px are downsampled in planes every caller stream shares, then hashed from the PDQ planes: both scratches are
+    ordered between the streams.  On a fresh context the second set (thumbnails as large, twice the images) grows both while the
+    first set's work is still queued on the other stream."""
+    eng = fresh_eng
+    rng = np.random.default_rng(32)
+    sets = [rng.integers(0, 256, (4, 600, 560, 3), dtype=np.uint8), rng.integers(0, 256, (8, 640, 600, 3), dtype=np.uint8)]
+    streams = [eng.stream_create(), eng.stream_create()]
+    d_px = [eng.dev_alloc(s.nbytes) for s in sets]
+    d_h = [eng.dev_alloc(len(s) * 32) for s in sets]
+    try:
+        for k in range(2):
+            eng.dev_upload(d_px[k], sets[k])
+        eng.synchronize()
+        for rep in range(10):  # no host synchronisation between the launches
+            for k in range(2):
+                n, h, w, ch = sets[k].shape
+                eng.pdq_hash_batch_dev(d_px[k], n, w, h, ch, d_h[k], stream=streams[k])
+        for st in streams:
+            eng.stream_synchronize(st)
+        for k in range(2):
+            got = np.zeros((len(sets[k]), 32), np.uint8)
+            eng.dev_download(got, d_h[k])
+            for i in range(len(sets[k])):
+                rc, c, _ = oracle.pdq_features(sets[k][i])
+                assert np.array_equal(got[i], oracle.to_hash(c)), (k, i)
+    finally:
+        for p in d_px + d_h:
+            eng.dev_free(p)
+        for st in streams:
+            eng.stream_destroy(st)
+
+
+def test_sorted_sweep_on_two_caller_streams(fresh_eng, oracle):
+    """Kernel 4 takes the popcount-sorted sweep at every size; its sorted copy lives in one scratch per context.  Two hash sets of
+    different sizes on two streams of a fresh context: the larger one grows the scratch while the other stream may still be using it."""
+    from rupphash_amd import EDGE_DTYPE
+
+    eng = fresh_eng
+    rng = np.random.default_rng(33)
+    hsets = [clustered_hashes(rng, 3000, 40, 24), clustered_hashes(rng, 7000, 60, 24)]
+    streams = [eng.stream_create(), eng.stream_create()]
+    cap = 1 << 16
+    d_h = [eng.dev_alloc(hs.nbytes) for hs in hsets]
+    d_e = [eng.dev_alloc(cap * 12) for _ in hsets]
+    d_c = [eng.dev_alloc(8) for _ in hsets]
+    try:
+        for k in range(2):
+            eng.dev_upload(d_h[k], hsets[k])
+        eng.synchronize()
+        eng.set_hamming_kernel(4)
+        for rep in range(10):
+            for k in range(2):
+                eng.dev_memset(d_c[k], 0, 8, stream=streams[k])
+                eng.hamming_all_pairs_dev(d_h[k], len(hsets[k]), 32, d_e[k], cap, d_c[k], stream=streams[k])
+        for st in streams:
+            eng.stream_synchronize(st)
+        for k in range(2):
+            cnt = np.zeros(1, np.uint64)
+            eng.dev_download(cnt, d_c[k])
+            assert 0 < int(cnt[0]) <= cap
+            edges = np.zeros(int(cnt[0]), EDGE_DTYPE)
+            eng.dev_download(edges, d_e[k])
+            assert edge_set(edges) == sorted(map(tuple, oracle.all_pairs256(hsets[k], 32).tolist())), k
+    finally:
+        eng.set_hamming_kernel(2)
+        for p in d_h + d_e + d_c:
+            eng.dev_free(p)
+        for st in streams:
+            eng.stream_destroy(st)
+
+
+def test_shared_scratch_after_stream_destroy(eng, oracle):
+    """A stream that used all four shared scratches (PDQ planes, resize planes, sorted sweep, BLAKE3 group values) is destroyed (its
+    handle may come back for the next stream); a new stream then uses them again and gets the same results."""
+    import blake3_util as b3
+
+    rng = np.random.default_rng(34)
+    imgs = rng.integers(0, 256, (4, 640, 600, 3), dtype=np.uint8)  # above 512 px: resized; 384 000 px each: BLAKE3 group values
+    hs = clustered_hashes(rng, 2000, 30, 24)
+    want_h = [oracle.to_hash(oracle.pdq_features(im)[1]) for im in imgs]
+    want_p = [b3.pixel_hash(im) for im in imgs]
+    want_e = sorted(map(tuple, oracle.all_pairs256(hs, 32).tolist()))
+    from rupphash_amd import EDGE_DTYPE
+
+    cap = 1 << 16
+    d_px, d_h, d_p = eng.dev_alloc(imgs.nbytes), eng.dev_alloc(4 * 32), eng.dev_alloc(4 * 32)
+    d_hs, d_e, d_c = eng.dev_alloc(hs.nbytes), eng.dev_alloc(cap * 12), eng.dev_alloc(8)
+    try:
+        eng.dev_upload(d_px, imgs)
+        eng.dev_upload(d_hs, hs)
+        eng.set_hamming_kernel(4)
+        for rnd in range(3):
+            st = eng.stream_create()
+            try:
+                eng.dev_memset(d_h, 0, 4 * 32, stream=st)
+                eng.dev_memset(d_p, 0, 4 * 32, stream=st)
+                eng.dev_memset(d_c, 0, 8, stream=st)
+                eng.pdq_hash_batch_dev(d_px, 4, 600, 640, 3, d_h, stream=st)
+                eng.pixel_hash_batch_dev(d_px, 4, 600, 640, 3, d_p, stream=st)
+                eng.hamming_all_pairs_dev(d_hs, len(hs), 32, d_e, cap, d_c, stream=st)
+                eng.stream_synchronize(st)
+            finally:
+                eng.stream_destroy(st)
+            got, got_p = np.zeros((4, 32), np.uint8), np.zeros((4, 32), np.uint8)
+            eng.dev_download(got, d_h)
+            eng.dev_download(got_p, d_p)
+            for i in range(4):
+                assert np.array_equal(got[i], want_h[i]), (rnd, i)
+                assert bytes(got_p[i]) == want_p[i], (rnd, i)
+            cnt = np.zeros(1, np.uint64)
+            eng.dev_download(cnt, d_c)
+            edges = np.zeros(int(cnt[0]), EDGE_DTYPE)
+            eng.dev_download(edges, d_e)
+            assert edge_set(edges) == want_e, rnd
+    finally:
+        eng.set_hamming_kernel(2)
+        for p in (d_px, d_h, d_p, d_hs, d_e, d_c):
+            eng.dev_free(p)
