@@ -57,7 +57,7 @@ struct Slot {
     hipEvent_t done = nullptr;  // device entropy: the slot's chunk (work on another slot's stream) has delivered its results
     Twin coef;              // host entropy: pinned staging + device; device entropy: unused
     Twin stream_bytes;      // device entropy: de-stuffed entropy bytes
-    Twin meta;              // descriptors (planes | images | tables | HImage | order | DeviceLut)
+    Twin meta;              // descriptors (write_meta)
     PinnedBuf res;          // results
     size_t res_images = 0;
     bool res_pixel = false;  // the results buffer has room for the pixel hashes (ResView::pixel)
@@ -91,6 +91,22 @@ struct Slot {
         return RPH_OK;
     }
 };
+
+struct Job {
+    Job() {}  // user-provided on purpose: std::vector<Job>(n) then runs the member initialisers only instead of zeroing ~1 KB per job first
+    const uint8_t *data = nullptr;
+    size_t len = 0;
+    rphj::Frame frame;
+    int status = RPH_OK;
+    uint64_t first_block = 0;  // within the chunk's coefficient buffer
+    rphj::StreamPlan plan;     // device entropy
+    const int16_t *pre = nullptr;  // coefficients already decoded by the caller into pinned memory (rph_jpeg_pdq_hash_one)
+    std::vector<uint32_t> marks;   // device entropy: where the restart intervals of a one-scan file begin (empty: walk the file with one lane)
+    size_t stream_off = 0, stream_used = 0;
+};
+
+using Jobs = std::vector<Job>;
+
 constexpr int JPEG_LANES = 4;  // chunks in flight in the device-entropy pipeline (the host-entropy pipeline uses the first two)
 struct JpegPipe {
     // (~JpegPipe synchronises the slots' streams, which use every buffer here, before the members are freed)
@@ -102,13 +118,11 @@ struct JpegPipe {
     // pixel hashes: the group values of the images above 8192 px (allocated by the first call that asks for pixel hashes)
     DevBuf b3[JPEG_LANES];
     Slot slot[JPEG_LANES];
-    // the per-file records of the last call (std::vector<Job>, defined below), kept: a call of 100 000 files spent 15 ms constructing and
-    // first-touching 120 MB of them before the first byte moved
-    void *jobs_cache = nullptr;
-    void (*jobs_cache_free)(void *) = nullptr;
+    // the per-file records of the last call, kept: a call of 100 000 files spent 15 ms constructing and first-touching 120 MB of them
+    // before the first byte moved
+    Jobs jobs_cache;
     ~JpegPipe()
     {
-        if (jobs_cache) jobs_cache_free(jobs_cache);
         for (Slot &S : slot) S.release();
     }
     // sample planes and packed pixels for sub-batches of up to `coef_need` bytes of coefficients
@@ -147,7 +161,7 @@ struct TableStore {
     std::mutex grow_mu;
     std::atomic<rphj::DeviceLut *> lut_block[MAX_BLOCKS];
     std::atomic<rphj::TableSpec *> spec_block[MAX_BLOCKS];
-    std::atomic<uint32_t> count{0};
+    std::atomic<uint32_t> count{0};  // slots taken: never more than BLOCK * MAX_BLOCKS
     uint64_t serial = next_serial();  // tells a thread's cache of ids that it belongs to another store
     TableStore()
     {
@@ -186,10 +200,12 @@ struct TableStore {
             if (same(spec(it->second), t)) return it->second;
         return UINT32_MAX;
     }
-    uint32_t new_slot()  // UINT32_MAX: full (the file then goes to the host decoder)
+    uint32_t new_slot()  // UINT32_MAX: full (the file then goes to the host decoder); a full store does not count the refused slot
     {
-        const uint32_t id = count.fetch_add(1, std::memory_order_acq_rel);
-        if (id >= BLOCK * MAX_BLOCKS) return UINT32_MAX;
+        uint32_t id = count.load(std::memory_order_acquire);
+        do {
+            if (id >= BLOCK * MAX_BLOCKS) return UINT32_MAX;
+        } while (!count.compare_exchange_weak(id, id + 1, std::memory_order_acq_rel, std::memory_order_acquire));
         const uint32_t b = id / BLOCK;
         if (!lut_block[b].load(std::memory_order_acquire) || !spec_block[b].load(std::memory_order_acquire)) {
             std::lock_guard<std::mutex> lock(grow_mu);
@@ -246,21 +262,6 @@ struct TableStore {
     }
 };
 
-struct Job {
-    Job() {}  // user-provided on purpose: std::vector<Job>(n) then runs the member initialisers only instead of zeroing ~1 KB per job first
-    const uint8_t *data = nullptr;
-    size_t len = 0;
-    rphj::Frame frame;
-    int status = RPH_OK;
-    uint64_t first_block = 0;  // within the chunk's coefficient buffer
-    rphj::StreamPlan plan;     // device entropy
-    const int16_t *pre = nullptr;  // coefficients already decoded by the caller into pinned memory (rph_jpeg_pdq_hash_one)
-    std::vector<uint32_t> marks;   // device entropy: where the restart intervals of a one-scan file begin (empty: walk the file with one lane)
-    size_t stream_off = 0, stream_used = 0;
-};
-
-using Jobs = std::vector<Job>;
-
 // bytes of the chunk's stream buffer a file may need (prepare_stream: 32 zero bytes behind every scan)
 inline size_t stream_cap(const Job &j) { return align_up(j.len + 160 + (j.frame.progressive ? 32 * (size_t)rphj::MAX_PROG_SCANS : 0), 16); }
 
@@ -293,11 +294,8 @@ inline bool trace_on() { return trace_level() == 1; }
 static double g_trace_t0 = 0;
 
 struct Outputs {
-    uint8_t *hash = nullptr;
-    float *quality = nullptr;
-    float *coeffs = nullptr;
-    uint8_t *dihedral = nullptr;
-    uint8_t *valid = nullptr;
+    uint8_t *hash = nullptr, *dihedral = nullptr, *valid = nullptr;
+    float *quality = nullptr, *coeffs = nullptr;
     int32_t *status = nullptr;
     uint8_t *pixels = nullptr;  // single-image decode: packed w * h * channels
     uint8_t *pixel_hash = nullptr;  // n x 32: BLAKE3 of to_rgba16() of every decoded image (rph_jpeg_pdq_pixel_hash_batch)
@@ -305,35 +303,41 @@ struct Outputs {
     bool rgb_wanted() const { return pixels || pixel_hash; }  // colour files reconstructed as Rgb8 (no luma-only fused kernel)
 };
 
-// Descriptors of the chunk idx[first..last) and where they live in the slot's meta buffer (host and device at the same offsets)
+// Reconstruction descriptors of the chunk idx[first..last): planes | images | quantisation tables at the start of the slot's meta buffer
+// (host and device at the same offsets)
 struct ChunkDesc {
-    size_t m = 0;
-    size_t off_planes = 0, off_images = 0, off_tables = 0, off_end = 0;
+    size_t bytes = 0;                  // of the three sections
+    JPlane *planes = nullptr;          // host side
+    JImage *images = nullptr;
+    const JPlane *d_planes = nullptr;  // device side
+    const JImage *d_images = nullptr;
+    const uint16_t *d_tables = nullptr;
     std::vector<uint32_t> image_of, plane_of;  // per chunk position: index of its JImage / first JPlane (UINT32_MAX: not decodable)
     uint32_t n_planes = 0, n_images = 0;
     const PRef *d_refs = nullptr;   // device entropy, progressive files: the AC refinement scans of their planes and the records of
     const PCorr *d_corr = nullptr;  // their corrections (the IDCT kernel applies them)
     const uint8_t *d_dcbits = nullptr;
+    std::vector<size_t> sub_starts;  // first chunk position of every sub-batch (build_descriptors)
 };
 
-// Sub-batch boundaries are where the offsets of planes and pixels restart from 0: `sub_of[r]` = first chunk position of r's sub-batch.
-int build_descriptors(Jobs &jobs, const std::vector<uint32_t> &idx, size_t first, size_t last, int flavour, bool rgb_wanted, size_t sub_coef_bytes, uint8_t *h_meta,
-                      size_t meta_base, ChunkDesc &D, std::vector<size_t> &sub_starts)
+// Sub-batch boundaries are where the offsets of planes and pixels restart from 0 (D.sub_starts).
+int build_descriptors(Jobs &jobs, const std::vector<uint32_t> &idx, size_t first, size_t last, int flavour, bool rgb_wanted, size_t sub_coef_bytes, const Twin &meta,
+                      ChunkDesc &D)
 {
     const size_t m = last - first;
-    D.m = m;
-    D.off_planes = meta_base;
-    D.off_images = D.off_planes + m * 3 * sizeof(JPlane);
-    D.off_tables = D.off_images + m * sizeof(JImage);
-    D.off_end = D.off_tables + m * 3 * 128;
-    JPlane *hp = reinterpret_cast<JPlane *>(h_meta + D.off_planes);
-    JImage *hi = reinterpret_cast<JImage *>(h_meta + D.off_images);
-    uint16_t *hq = reinterpret_cast<uint16_t *>(h_meta + D.off_tables);
+    Layout L;
+    const size_t off_planes = L.add(m * 3 * sizeof(JPlane)), off_images = L.add(m * sizeof(JImage)), off_tables = L.add(m * 3 * 128);
+    D.bytes = L.end();
+    D.planes = reinterpret_cast<JPlane *>(meta.h.data() + off_planes);
+    D.images = reinterpret_cast<JImage *>(meta.h.data() + off_images);
+    uint16_t *hq = reinterpret_cast<uint16_t *>(meta.h.data() + off_tables);
+    D.d_planes = reinterpret_cast<const JPlane *>(meta.d.data() + off_planes);
+    D.d_images = reinterpret_cast<const JImage *>(meta.d.data() + off_images);
+    D.d_tables = reinterpret_cast<const uint16_t *>(meta.d.data() + off_tables);
     D.image_of.assign(m, UINT32_MAX);
     D.plane_of.assign(m, UINT32_MAX);
     D.n_planes = D.n_images = 0;
-    sub_starts.clear();
-    sub_starts.push_back(0);
+    D.sub_starts.assign(1, 0);
     size_t plane_bytes = 0, out_bytes = 0, sub_blocks = 0, sub_images = 0;
     uint32_t sub_first_plane = 0;
     static const bool fuse = !getenv("RPH_JPEG_NO_FUSED");  // (A/B: the two-kernel reconstruction for every image)
@@ -344,7 +348,7 @@ int build_descriptors(Jobs &jobs, const std::vector<uint32_t> &idx, size_t first
         // a sub-batch is full when its coefficients would not fit the reconstruction buffers, or at 16 384 images (the kernels take
         // the plane / image index from blockIdx.y, which ends at 65 535): offsets restart
         if (sub_blocks && ((sub_blocks + f.total_blocks) * 128 > sub_coef_bytes || sub_images == SUB_MAX_IMAGES)) {
-            sub_starts.push_back(r);
+            D.sub_starts.push_back(r);
             plane_bytes = out_bytes = sub_blocks = 0;
             sub_images = 0;
             sub_first_plane = D.n_planes;
@@ -357,45 +361,30 @@ int build_descriptors(Jobs &jobs, const std::vector<uint32_t> &idx, size_t first
         // three components (luma sampled once or twice the chroma) and only the hasher reads the pixels: IDCT + upsampling + colour in one kernel
         const bool fused = fuse && f.ncomp == 3 && out_channels(f, rgb_wanted) == 1 && f.comp[0].H <= 2 && f.comp[0].V <= 2 && f.comp[1].H == 1 && f.comp[1].V == 1 &&
                            f.comp[2].H == 1 && f.comp[2].V == 1;
-        im.fused = fused;
-        im.first_plane = D.n_planes - sub_first_plane;
+        im.fused = fused, im.first_plane = D.n_planes - sub_first_plane;
         im.tiles_x = (f.comp[0].blocks_w + 15) / 16, im.tiles_y = (f.comp[0].blocks_h + 7) / 8;
         for (int c = 0; c < f.ncomp; c++) {
             const rphj::Comp &kc = f.comp[c];
-            JPlane pl;
-            pl.first_block = j.first_block + kc.first_block;
-            pl.out_off = plane_bytes;
-            pl.blocks_w = kc.blocks_w;
-            pl.blocks_h = kc.blocks_h;
-            pl.qt = D.n_planes;
-            pl.pitch = kc.blocks_w * 8;
-            pl.real_bw = kc.real_bw;
-            pl.real_bh = kc.real_bh;
-            pl.ref_first = pl.ref_count = 0;
-            pl.fused = fused, pl.pad_ = 0;
+            const JPlane pl{j.first_block + kc.first_block, plane_bytes, kc.blocks_w, kc.blocks_h, D.n_planes, kc.blocks_w * 8, kc.real_bw, kc.real_bh, 0, 0, fused, 0};
             memcpy(hq + (size_t)D.n_planes * 64, f.qt[kc.tq], 128);
             im.plane_off[c] = plane_bytes;
             im.pitch[c] = pl.pitch;
             plane_bytes += (size_t)pl.pitch * kc.blocks_h * 8;
-            hp[D.n_planes++] = pl;
+            D.planes[D.n_planes++] = pl;
         }
-        im.w = f.w;
-        im.h = f.h;
-        im.ncomp = (uint32_t)f.ncomp;
+        im.w = f.w, im.h = f.h, im.ncomp = (uint32_t)f.ncomp;
         im.hs = im.vs = 1;
         if (f.ncomp == 3) {
-            im.hs = f.comp[0].H / f.comp[1].H;
-            im.vs = f.comp[0].V / f.comp[1].V;
+            im.hs = f.comp[0].H / f.comp[1].H, im.vs = f.comp[0].V / f.comp[1].V;
             im.cw = flavour == RPH_JPEG_LIBJPEG ? f.comp[1].samp_w : f.comp[1].blocks_w * 8;
             im.ch = flavour == RPH_JPEG_LIBJPEG ? f.comp[1].samp_h : f.comp[1].blocks_h * 8;
         }
         const uint32_t och = out_channels(f, rgb_wanted);
         im.luma_out = f.ncomp == 3 && och == 1;
-        im.out_stride = (uint32_t)((size_t)och * align_up(f.w, 8));
-        im.out_off = out_bytes;
+        im.out_stride = (uint32_t)((size_t)och * align_up(f.w, 8)), im.out_off = out_bytes;
         out_bytes += out_bytes_of(f, och);
         D.image_of[r] = D.n_images;
-        hi[D.n_images++] = im;
+        D.images[D.n_images++] = im;
     }
     return RPH_OK;
 }
@@ -417,23 +406,20 @@ int reconstruct_and_hash(rph_ctx *ctx, JpegPipe &P, int b, Slot &S, Jobs &jobs, 
         max_groups = std::max<uint32_t>(max_groups, (uint32_t)(((f.w + 7) / 8) * (size_t)f.h));
     }
     if (i0 == UINT32_MAX) return RPH_OK;
-    const JPlane *dp = reinterpret_cast<const JPlane *>(S.meta.d.data() + D.off_planes) + p0;
-    const JImage *di = reinterpret_cast<const JImage *>(S.meta.d.data() + D.off_images) + i0;
-    const uint16_t *dq = reinterpret_cast<const uint16_t *>(S.meta.d.data() + D.off_tables);
-    const JImage *hi_all = reinterpret_cast<const JImage *>(S.meta.h.data() + D.off_images);
+    const JPlane *dp = D.d_planes + p0;
+    const JImage *di = D.d_images + i0;
     uint32_t n_fused = 0, max_tiles = 0;
     for (uint32_t q = i0; q < i1; q++)
-        if (hi_all[q].fused) {
+        if (D.images[q].fused) {
             n_fused++;
-            max_tiles = std::max(max_tiles, hi_all[q].tiles_x * hi_all[q].tiles_y);
+            max_tiles = std::max(max_tiles, D.images[q].tiles_x * D.images[q].tiles_y);
         }
     if (n_fused < i1 - i0) {  // (the plane kernels skip the images the fused kernel takes)
-        RPH_TRY(rph_jpeg_launch_idct(flavour, max_blocks, p1 - p0, s, d_coef, dq, dp, P.planes[b].data(), D.d_refs, D.d_corr, D.d_dcbits));
+        RPH_TRY(rph_jpeg_launch_idct(flavour, max_blocks, p1 - p0, s, d_coef, D.d_tables, dp, P.planes[b].data(), D.d_refs, D.d_corr, D.d_dcbits));
         RPH_TRY(rph_jpeg_launch_color(flavour, max_groups, i1 - i0, s, P.planes[b].data(), di, P.pixels[b].data()));
     }
-    if (n_fused) RPH_TRY(rph_jpeg_launch_fused(flavour, max_tiles, i1 - i0, s, d_coef, dq, dp, di, P.pixels[b].data(), D.d_refs, D.d_corr, D.d_dcbits));
+    if (n_fused) RPH_TRY(rph_jpeg_launch_fused(flavour, max_tiles, i1 - i0, s, d_coef, D.d_tables, dp, di, P.pixels[b].data(), D.d_refs, D.d_corr, D.d_dcbits));
     ResView R(S.res.data(), S.res_images);
-    const JImage *hi = reinterpret_cast<const JImage *>(S.meta.h.data() + D.off_images);
     // pixel hashes (scanner.rs:1393-1404, before generate_pdq_features: images below 5 px have one too), runs of equal geometry
     for (size_t r = r0; out.pixel_hash && r < r1;) {
         if (D.image_of[r] == UINT32_MAX) {
@@ -446,7 +432,7 @@ int reconstruct_and_hash(rph_ctx *ctx, JpegPipe &P, int b, Slot &S, Jobs &jobs, 
         while (e < r1 && D.image_of[e] != UINT32_MAX && jobs[idx[first + e]].frame.w == f.w && jobs[idx[first + e]].frame.h == f.h && jobs[idx[first + e]].frame.ncomp == f.ncomp) e++;
         const size_t scratch = rph_pixel_hash_scratch_bytes((uint32_t)(e - r), f.w, f.h);
         if (scratch) RPH_TRY(P.b3[b].reserve(scratch, scratch + scratch / 4, s));  // (runs of one stream follow each other: one buffer serves them all)
-        RPH_TRY(rph_launch_pixel_hash(P.pixels[b].data() + hi[D.image_of[r]].out_off, (uint32_t)(e - r), f.w, f.h, och, (size_t)och * align_up(f.w, 8), out_bytes_of(f, och),
+        RPH_TRY(rph_launch_pixel_hash(P.pixels[b].data() + D.images[D.image_of[r]].out_off, (uint32_t)(e - r), f.w, f.h, och, (size_t)och * align_up(f.w, 8), out_bytes_of(f, och),
                                       R.pixel + r * 32, s, P.b3[b].data()));
         r = e;
     }
@@ -461,7 +447,7 @@ int reconstruct_and_hash(rph_ctx *ctx, JpegPipe &P, int b, Slot &S, Jobs &jobs, 
         const uint32_t och = out_channels(f, out.rgb_wanted());
         size_t e = r + 1;
         while (e < r1 && D.image_of[e] != UINT32_MAX && jobs[idx[first + e]].frame.w == f.w && jobs[idx[first + e]].frame.h == f.h && jobs[idx[first + e]].frame.ncomp == f.ncomp) e++;
-        RPH_TRY(rph_pdq_hash_batch_dev(ctx, P.pixels[b].data() + hi[D.image_of[r]].out_off, (uint32_t)(e - r), f.w, f.h, och, (size_t)och * align_up(f.w, 8), out_bytes_of(f, och),
+        RPH_TRY(rph_pdq_hash_batch_dev(ctx, P.pixels[b].data() + D.images[D.image_of[r]].out_off, (uint32_t)(e - r), f.w, f.h, och, (size_t)och * align_up(f.w, 8), out_bytes_of(f, och),
                                        R.hash + r * 32, out.quality ? R.quality + r * 4 : nullptr, out.coeffs ? R.coeffs + r * 1024 : nullptr,
                                        out.dihedral ? R.dihedral + r * 256 : nullptr, R.valid + r, s));
         r = e;
@@ -469,9 +455,6 @@ int reconstruct_and_hash(rph_ctx *ctx, JpegPipe &P, int b, Slot &S, Jobs &jobs, 
     return RPH_OK;
 }
 
-// The results of a chunk are fetched only when the chunk is known to be finished.  Enqueued behind the chunk's kernels instead, the
-// transfer would sit in the copy engine's queue waiting for them, and the next chunk's upload -- same engine, another stream --
-// would wait behind it (measured: uploads did not overlap the other lane's kernels at all).
 // the first m entries of the slot's result arrays cleared by the host (the lane is idle: its previous chunk has delivered)
 void zero_results(Slot &S, size_t m, const Outputs &out)
 {
@@ -485,13 +468,7 @@ void zero_results(Slot &S, size_t m, const Outputs &out)
     if (out.pixel_hash) memset(H.pixel, 0, m * 32);
 }
 
-int fetch_results(Slot &S, size_t m, const Outputs &out, bool entropy_status)
-{
-    (void)S, (void)m, (void)out, (void)entropy_status;  // the kernels wrote into the slot's pinned results buffer; the caller has waited for them
-    return RPH_OK;
-}
-
-// results of a finished chunk -> the caller's arrays (scattered through idx)
+// results of a finished chunk -> the caller's arrays (scattered through idx); the kernels wrote them into the slot's pinned results buffer
 // retry (device entropy): files the device walk flagged (a damaged stream, or a progressive wait that gave up: the status byte says which)
 // are not written; they go to the host decoder, whose verdict is final (rupphash.h, rph_jpeg_set_entropy)
 void scatter_results(const Slot &S, Jobs &jobs, const std::vector<uint32_t> &idx, size_t first, size_t last, const Outputs &out,
@@ -515,21 +492,29 @@ void scatter_results(const Slot &S, Jobs &jobs, const std::vector<uint32_t> &idx
     }
 }
 
+// The chunk lane b has in flight: positions idx[first, last) of the call's file list
+struct InFlight {
+    bool active = false;
+    size_t first = 0, last = 0;
+    // frees the lane: waits for the chunk, if any -- for the slot's event `done` (device entropy) or its stream (host entropy) -- and
+    // scatters its results (retry: as scatter_results)
+    int finish(int b, const Slot &S, bool on_event, Jobs &jobs, const std::vector<uint32_t> &idx, const Outputs &out, std::vector<uint32_t> *retry)
+    {
+        if (!active) return RPH_OK;
+        RPH_JPEG_STAMP("lane %d: waiting for its chunk", b);
+        RPH_HIP_CHECK(on_event ? hipEventSynchronize(S.done) : hipStreamSynchronize(S.stream));
+        RPH_JPEG_STAMP("lane %d: chunk done", b);
+        scatter_results(S, jobs, idx, first, last, out, retry);
+        RPH_JPEG_STAMP("lane %d: results scattered", b);
+        active = false;
+        return RPH_OK;
+    }
+};
+
 // ---- host entropy decoding: the files idx[...] in chunks over the two slots
 int run_host_entropy(rph_ctx *ctx, JpegPipe &P, Jobs &jobs, const std::vector<uint32_t> &idx, int flavour, unsigned threads, const Outputs &out)
 {
-    struct Pending {
-        bool active = false;
-        size_t first = 0, last = 0;
-    } pend[2];
-    auto finish = [&](int b) -> int {
-        if (!pend[b].active) return RPH_OK;
-        RPH_HIP_CHECK(hipStreamSynchronize(P.slot[b].stream));
-        RPH_TRY(fetch_results(P.slot[b], pend[b].last - pend[b].first, out, false));
-        scatter_results(P.slot[b], jobs, idx, pend[b].first, pend[b].last, out, nullptr);
-        pend[b].active = false;
-        return RPH_OK;
-    };
+    InFlight lane[2];
     const size_t n = idx.size();
     int k = 0;
     RPH_JPEG_STAMP("buffers ready");
@@ -543,7 +528,7 @@ int run_host_entropy(rph_ctx *ctx, JpegPipe &P, Jobs &jobs, const std::vector<ui
             last++;
         }
         const int b = k & 1;
-        RPH_TRY(finish(b));
+        RPH_TRY(lane[b].finish(b, P.slot[b], false, jobs, idx, out, nullptr));
         Slot &S = P.slot[b];
         RPH_TRY(S.ready());
         const size_t m = last - first;
@@ -553,13 +538,11 @@ int run_host_entropy(rph_ctx *ctx, JpegPipe &P, Jobs &jobs, const std::vector<ui
         RPH_TRY(S.reserve_res(std::max<size_t>(m, std::min<size_t>(n, CHUNK_MAX_IMAGES)), out.pixel_hash != nullptr));
         const size_t meta_need = std::max<size_t>(m, std::min<size_t>(n, CHUNK_MAX_IMAGES)) * (3 * sizeof(JPlane) + sizeof(JImage) + 3 * 128);
         RPH_TRY(S.meta.reserve(meta_need, S.stream));
-        {
-            uint64_t fb = 0;
-            for (size_t i = first; i < last; i++) {
-                Job &j = jobs[idx[i]];
-                j.first_block = fb;
-                if (j.status == RPH_OK) fb += j.frame.total_blocks;
-            }
+        uint64_t fb = 0;
+        for (size_t i = first; i < last; i++) {
+            Job &j = jobs[idx[i]];
+            j.first_block = fb;
+            if (j.status == RPH_OK) fb += j.frame.total_blocks;
         }
         int16_t *h_coef = reinterpret_cast<int16_t *>(S.coef.h.data());
         bool predecoded = false;
@@ -571,8 +554,7 @@ int run_host_entropy(rph_ctx *ctx, JpegPipe &P, Jobs &jobs, const std::vector<ui
             });
         RPH_JPEG_STAMP("lane %d: chunk %d buffers sized", b, k);
         ChunkDesc D;
-        std::vector<size_t> subs;
-        RPH_TRY(build_descriptors(jobs, idx, first, last, flavour, out.rgb_wanted(), SIZE_MAX / 256, S.meta.h.data(), 0, D, subs));
+        RPH_TRY(build_descriptors(jobs, idx, first, last, flavour, out.rgb_wanted(), SIZE_MAX / 256, S.meta, D));
         hipStream_t s = S.stream;
         zero_results(S, m, out);
         if (D.n_images) {
@@ -585,7 +567,7 @@ int run_host_entropy(rph_ctx *ctx, JpegPipe &P, Jobs &jobs, const std::vector<ui
             } else {
                 RPH_HIP_CHECK(hipMemcpyAsync(S.coef.d.data(), S.coef.h.data(), blocks * 128, hipMemcpyHostToDevice, s));
             }
-            RPH_HIP_CHECK(hipMemcpyAsync(S.meta.d.data(), S.meta.h.data(), D.off_end, hipMemcpyHostToDevice, s));
+            RPH_HIP_CHECK(hipMemcpyAsync(S.meta.d.data(), S.meta.h.data(), D.bytes, hipMemcpyHostToDevice, s));
             RPH_TRY(reconstruct_and_hash(ctx, P, b, S, jobs, idx, first, D, 0, m, reinterpret_cast<const int16_t *>(S.coef.d.data()), flavour, out, s));
         }
         if (out.pixels && m == 1 && jobs[idx[first]].status == RPH_OK) {  // single-image decode: rows without their padding
@@ -593,26 +575,39 @@ int run_host_entropy(rph_ctx *ctx, JpegPipe &P, Jobs &jobs, const std::vector<ui
             const size_t row = (size_t)f.ncomp * f.w, stride = (size_t)f.ncomp * align_up(f.w, 8);
             RPH_HIP_CHECK(hipMemcpy2DAsync(out.pixels, row, P.pixels[b].data(), stride, row, f.h, hipMemcpyDeviceToHost, s));
         }
-        pend[b].active = true;
-        pend[b].first = first;
-        pend[b].last = last;
+        lane[b] = InFlight{true, first, last};
         first = last;
     }
-    RPH_TRY(finish(k & 1));
-    RPH_TRY(finish((k + 1) & 1));
+    RPH_TRY(lane[k & 1].finish(k & 1, P.slot[k & 1], false, jobs, idx, out, nullptr));
+    RPH_TRY(lane[(k + 1) & 1].finish((k + 1) & 1, P.slot[(k + 1) & 1], false, jobs, idx, out, nullptr));
     return RPH_OK;
 }
 
-// ---- device entropy decoding: the sequential files idx[...]; files the device walk does not take come back in `leftover` for the host
+// ---- device entropy decoding: the files idx[...]; files the device walk does not take come back in `leftover` for the host
+// The walk of one lane takes ~0.65 us per entropy byte however few lanes there are (21 ms for 29 KB files, 236 ms for 366 KB photos)
+constexpr double WALK_SECONDS_PER_BYTE = 0.65e-6;
 // entropy bytes per second the segment passes (synchronisation + walk) move when the device is theirs: 2 GB in 14 + 18 ms
 inline double seg_rate()
 {
     static const double r = getenv("RPH_JPEG_SEG_RATE") ? atof(getenv("RPH_JPEG_SEG_RATE")) * 1e9 : 60e9;
     return r;
 }
+// Segments (three decoding passes over every byte, but a lane per KB) or one lane per file (one pass, as long as the longest file)?
+// The walk of whole files takes ~0.65 us per byte of the longest one while there are fewer lanes than the device has (65 536); the
+// segment passes move ~31 GB/s of entropy bytes (5 275 photos of 366 KB: 67 ms against 236; 25 000 files of 158 KB: 129 ms against
+// 103).  Whole-file walks also leave most of the device to the other lane's chunk, so segments must win clearly.
+// `files` files of `bytes` entropy bytes in all, the longest of them `longest` bytes.
+inline bool segments_pay(size_t longest, double files, double bytes)
+{
+    const double t_whole = WALK_SECONDS_PER_BYTE * (double)longest * std::max(1.0, files / 65536.0), t_seg = bytes / seg_rate();
+    return t_seg < 0.7 * t_whole;
+}
 
-int run_device_entropy(rph_ctx *ctx, JpegPipe &P, Jobs &jobs, std::vector<uint32_t> idx, int flavour, unsigned threads, const Outputs &out,
-                       std::vector<uint32_t> &leftover)
+// How a call's device-entropy files are cut into chunks: `lanes` chunks in flight, `region` bytes of the coefficient buffer per lane,
+// chunks of at most `chunk_bytes` of coefficients (one larger image makes a chunk of its own)
+struct DevicePlan { int lanes = 1; size_t region = 0, chunk_bytes = 0; };
+// ---- call plan: sorts idx, sizes the coefficient buffer, readies the lanes' slots and reconstruction buffers
+int plan_device_call(rph_ctx *ctx, JpegPipe &P, const Jobs &jobs, std::vector<uint32_t> &idx, DevicePlan &plan)
 {
     // images of similar stream length share a wave: sort the whole list by file length first (chunks then are slices of it)
     {  // (keys side by side: sorting through the job records themselves took 22 ms per 100 000 files)
@@ -634,10 +629,9 @@ int run_device_entropy(rph_ctx *ctx, JpegPipe &P, Jobs &jobs, std::vector<uint32
     // turn: the host prepares chunk k + 1 and its bytes cross PCIe while chunk k is on the device, and the latency-bound walk of one
     // chunk runs beside the bandwidth-bound reconstruction of the other.  A call is cut into about four chunks when it is large
     // enough for each to still fill the device's lanes (16 GB of coefficients = 20 000 images of 512x512); a smaller call is one chunk.
-    // The walk of a chunk takes as long as its longest file (~0.65 us per entropy byte: 21 ms for 29 KB files, 236 ms for 366 KB photos)
-    // however few files it has, and walks of different chunks only overlap pairwise (two lanes): small files are cut into four chunks
-    // for the pipelining, files whose lanes have long streams (photos without markers, segments switched off) into two so that the walks are
-    // not paid four times.
+    // The walk of a chunk takes as long as its longest file (WALK_SECONDS_PER_BYTE) however few files it has, and walks of different
+    // chunks only overlap pairwise (two lanes): small files are cut into four chunks for the pipelining, files whose lanes have long
+    // streams (photos without markers, segments switched off) into two so that the walks are not paid four times.
     size_t max_len = 0;  // longest stream one lane will walk: a file, or one restart interval of it (as the frame header announces them)
     size_t longest_plain = 0, plain_bytes = 0, plain_files = 0;  // files without restart intervals that are long enough for segments
     for (uint32_t g : idx) {
@@ -651,440 +645,462 @@ int run_device_entropy(rph_ctx *ctx, JpegPipe &P, Jobs &jobs, std::vector<uint32
         max_len = std::max(max_len, lane_len);
     }
     bool by_segments = false;
-    if (plain_files) {  // will a quarter of them be walked as segments (the chunk loop decides the same way, per chunk)?
-        const double t_whole = 0.65e-6 * (double)longest_plain * std::max(1.0, (double)plain_files / 4 / 65536.0), t_seg = (double)plain_bytes / 4 / seg_rate();
-        by_segments = t_seg < 0.7 * t_whole;
+    if (plain_files) {  // will a quarter of them be walked as segments (list_sequential decides the same way, per chunk)?
+        by_segments = segments_pay(longest_plain, (double)plain_files / 4, (double)plain_bytes / 4);
         max_len = std::max(max_len, by_segments ? (size_t)ctx->jpeg_seg_bytes : longest_plain);
     }
-    size_t min_chunk = (size_t)16 << 30, parts = 0.65e-6 * (double)max_len > 0.08 ? 2 : 4;
+    const bool long_lanes = WALK_SECONDS_PER_BYTE * (double)max_len > 0.08;
+    size_t min_chunk = (size_t)16 << 30, parts = long_lanes ? 2 : 4;
     // A call whose long streams are cut into segments has no long lane: its walk scales with the bytes, and the call is bound by PCIe
     // (the entropy bytes of 20 000 photos cross it in 143 ms of the call's 240).  Many small chunks then keep the copy engine busy from
     // the first prepared chunk to the last and leave little device work behind the last upload (20 000 photos: 4 chunks 75 k files/s,
     // 8 chunks 81 k, 16 chunks 86 k, 32 chunks 71 k).
-    if (by_segments && 0.65e-6 * (double)max_len <= 0.08) min_chunk = (size_t)4 << 30, parts = 16;
+    if (by_segments && !long_lanes) min_chunk = (size_t)4 << 30, parts = 16;
     if (const char *e = getenv("RPH_JPEG_CHUNK_GB")) min_chunk = (size_t)atoi(e) << 30;  // experiments
     if (const char *e = getenv("RPH_JPEG_PARTS")) parts = (size_t)std::max(1, atoi(e));
     const size_t chunk_target = std::min(need, std::max(need / parts + 128, min_chunk));
     const bool single = need <= chunk_target && need <= budget;
-    const int lanes = single ? 1 : (int)std::min<size_t>(JPEG_LANES, (need + chunk_target - 1) / chunk_target);  // chunks in flight
-    const size_t want = single ? need : std::min(budget, (size_t)lanes * chunk_target);
+    plan.lanes = single ? 1 : (int)std::min<size_t>(JPEG_LANES, (need + chunk_target - 1) / chunk_target);
+    const size_t want = single ? need : std::min(budget, (size_t)plan.lanes * chunk_target);
     if (P.coef.capacity() < want) RPH_HIP_CHECK(hipDeviceSynchronize());  // every lane's stream may still use it
     RPH_TRY(P.coef.reserve(want, synced));
-    const size_t region = (P.coef.capacity() / (size_t)lanes) / 128 * 128;
-    const size_t chunk_bytes = std::min(region, chunk_target);
-    struct Pending {
-        bool active = false;
-        size_t first = 0, last = 0;
-    } pend[JPEG_LANES];
-    auto finish = [&](int b) -> int {
-        if (!pend[b].active) return RPH_OK;
-        RPH_JPEG_STAMP("lane %d: waiting for its chunk", b);
-        RPH_HIP_CHECK(hipEventSynchronize(P.slot[b].done));
-        RPH_JPEG_STAMP("lane %d: chunk done", b);
-        RPH_TRY(fetch_results(P.slot[b], pend[b].last - pend[b].first, out, true));
-        scatter_results(P.slot[b], jobs, idx, pend[b].first, pend[b].last, out, &leftover);
-        RPH_JPEG_STAMP("lane %d: results scattered", b);
-        pend[b].active = false;
-        return RPH_OK;
-    };
-    for (int b = 0; b < lanes; b++) RPH_TRY(P.slot[b].ready());
-    {
-        size_t max_img = 0;  // a sub-batch holds at least one image
-        for (uint32_t g : idx) max_img = std::max(max_img, (size_t)jobs[g].frame.total_blocks * 128);
-        const size_t recon = std::max(std::min(SUB_COEF_BYTES, std::max(std::min(want, chunk_bytes), (size_t)64 << 20)), max_img);
-        for (int b = 0; b < lanes; b++) RPH_TRY(P.reserve_recon(b, recon, P.slot[b].stream));
+    plan.region = (P.coef.capacity() / (size_t)plan.lanes) / 128 * 128;
+    plan.chunk_bytes = std::min(plan.region, chunk_target);
+    for (int b = 0; b < plan.lanes; b++) RPH_TRY(P.slot[b].ready());
+    size_t max_img = 0;  // a sub-batch holds at least one image
+    for (uint32_t g : idx) max_img = std::max(max_img, (size_t)jobs[g].frame.total_blocks * 128);
+    const size_t recon = std::max(std::min(SUB_COEF_BYTES, std::max(std::min(want, plan.chunk_bytes), (size_t)64 << 20)), max_img);
+    for (int b = 0; b < plan.lanes; b++) RPH_TRY(P.reserve_recon(b, recon, P.slot[b].stream));
+    return RPH_OK;
+}
+
+// One chunk: positions idx[first, last) of the call's sorted list, with `blocks` coefficient blocks and `file_bytes` of the slot's stream
+// buffer (stream_cap); the call's k-th chunk, on lane b
+struct Chunk {
+    size_t first = 0, last = 0, blocks = 0, file_bytes = 0;
+    int b = 0, k = 0;
+    size_t m() const { return last - first; }
+};
+
+// the walk's record of a file that prepare_stream has accepted (`hi` zeroed before)
+void fill_himage(const Job &j, HImage &hi)
+{
+    const rphj::Frame &f = j.frame;
+    hi.first_block = j.first_block, hi.stream_base = j.stream_off;
+    hi.mcus_x = f.mcus_x, hi.mcus_y = f.mcus_y;
+    hi.n_scans = f.progressive ? 0u : (uint32_t)j.plan.n_scans, hi.ncomp = (uint32_t)f.ncomp;
+    for (int c = 0; c < f.ncomp; c++) {
+        const rphj::Comp &kc = f.comp[c];
+        hi.comp[c] = HComp{kc.blocks_w, kc.real_bw, kc.real_bh, (uint32_t)kc.first_block, kc.H, kc.V};
     }
+    for (int q = 0; q < (f.progressive ? 0 : j.plan.n_scans); q++) {
+        const rphj::ScanPlan &sp = j.plan.scan[q];
+        HScan &hs = hi.scan[q];
+        hs.off = sp.stream_off, hs.len = sp.stream_len, hs.restart_interval = sp.restart_interval, hs.ns = sp.ns;
+        for (int c = 0; c < sp.ns; c++) hs.ci[c] = sp.ci[c], hs.dc[c] = sp.dc[c], hs.ac[c] = sp.ac[c];
+    }
+}
+
+// ---- chunk preparation (host threads: memchr + memcpy): the files' places in the stream and coefficient buffers, their de-stuffed
+// streams in the slot's staging, their walk records (zero where prepare_stream refused the file) and the chunk's Huffman tables
+void prepare_chunk(Jobs &jobs, const std::vector<uint32_t> &idx, const Chunk &C, unsigned threads, Slot &S, TableStore &store, std::vector<HImage> &himgs)
+{
+    size_t off = 0;
+    uint64_t fb = 0;
+    for (size_t i = C.first; i < C.last; i++) {
+        Job &j = jobs[idx[i]];
+        j.stream_off = off;
+        off += stream_cap(j);
+        j.first_block = fb;
+        fb += j.frame.total_blocks;
+    }
+    himgs.resize(C.m());
+    RPH_JPEG_STAMP("lane %d: chunk %d laid out", C.b, C.k);
+    parallel_for(C.first, C.last, threads, [&](size_t i) {
+        Job &j = jobs[idx[i]];
+        HImage &hi = himgs[i - C.first];
+        memset(&hi, 0, sizeof hi);
+        j.status = rphj::prepare_stream(j.data, j.len, j.frame, j.plan, S.stream_bytes.h.data() + j.stream_off, stream_cap(j), &j.stream_used, &TableStore::intern, &store, &j.marks);
+        if (j.status == RPH_OK) fill_himage(j, hi);
+    });
+}
+
+// The walk items of a chunk's sequential files
+struct SeqWork {
+    std::vector<HItem> items;        // the host's: one per restart interval where a file has them, else one per file
+    std::vector<uint32_t> order;     // the host's items, longest first (the lanes take them in this order)
+    std::vector<SegFile> seg_files;  // long streams without markers, cut into segments
+    uint32_t n_segs = 0, n_items = 0;  // n_items: the host's items, then one per segment (the device writes those)
+    bool all_one_scan = true;        // every sequential file of the chunk has one scan: its MCUs cover all blocks of its components
+};
+// ---- sequential work.  Files that prepare_stream refused (more than four scans, damage it saw) go to `leftover` for the host decoder;
+// they keep their place in the chunk as holes.  Progressive files are ProgPlan's.
+SeqWork list_sequential(const rph_ctx *ctx, const Jobs &jobs, const std::vector<uint32_t> &idx, const Chunk &C, std::vector<uint32_t> &leftover)
+{
+    SeqWork W;
+    bool use_segments = ctx->jpeg_seg_bytes != 0;
+    if (use_segments && ctx->jpeg_seg_min_bytes > 0) use_segments = segments_pay(jobs[idx[C.first]].len, (double)C.m(), (double)C.file_bytes);
+    std::vector<uint32_t> item_len;
+    W.items.reserve(C.m());
+    for (size_t i = C.first; i < C.last; i++) {
+        const Job &j = jobs[idx[i]];
+        if (j.status != RPH_OK) {  // whatever prepare_stream found, the host decoder judges the file
+            leftover.push_back(idx[i]);
+            continue;
+        }
+        if (j.frame.progressive) continue;
+        const uint32_t r = (uint32_t)(i - C.first);
+        const rphj::Frame &f = j.frame;
+        const rphj::ScanPlan &sp = j.plan.scan[0];
+        if (j.plan.n_scans != 1 || sp.ns != f.ncomp) W.all_one_scan = false;
+        if (f.ncomp == 1 && (f.comp[0].blocks_w != f.comp[0].real_bw || f.comp[0].blocks_h != f.comp[0].real_bh))
+            W.all_one_scan = false;  // (a one-component scan walks the real blocks only: a padded grid keeps its zeroing)
+        if (j.marks.empty()) {
+            if (use_segments && j.plan.n_scans == 1 && sp.restart_interval == 0 && sp.stream_len >= ctx->jpeg_seg_min_bytes && sp.stream_len < ((uint32_t)1 << 28)) {
+                // a long stream without restart markers: cut into segments that synchronise on the device (jpeg_device.h); its items go
+                // behind the host's (first_item, set below)
+                const uint32_t n_segs = (sp.stream_len + ctx->jpeg_seg_bytes - 1) / ctx->jpeg_seg_bytes;
+                const uint32_t total_mcus = sp.ns == 1 ? f.comp[sp.ci[0]].real_bw * f.comp[sp.ci[0]].real_bh : f.mcus_x * f.mcus_y;
+                W.seg_files.push_back(SegFile{r, W.n_segs, n_segs, 0, total_mcus, sp.stream_len * 8});
+                W.n_segs += n_segs;
+                continue;
+            }
+            W.items.push_back(HItem{r, HITEM_ALL_SCANS, 0, 0, 0, 0, {0, 0, 0}, HITEM_NO_END});
+            item_len.push_back((uint32_t)std::min<size_t>(j.len, 0xFFFFFFFFu));
+            continue;
+        }
+        const uint64_t mcus = sp.ns == 1 ? (uint64_t)f.comp[sp.ci[0]].real_bw * f.comp[sp.ci[0]].real_bh : (uint64_t)f.mcus_x * f.mcus_y;
+        const uint32_t n_int = (uint32_t)j.marks.size() + 1;
+        for (uint32_t q = 0; q < n_int; q++) {
+            const uint32_t off = q ? j.marks[q - 1] : 0, end = q + 1 < n_int ? j.marks[q] : sp.stream_len;
+            const uint64_t m_first = (uint64_t)q * sp.restart_interval;
+            W.items.push_back(HItem{r, 0, (uint32_t)m_first, (uint32_t)std::min<uint64_t>(sp.restart_interval, mcus - m_first), off, 0, {0, 0, 0}, end});
+            item_len.push_back(end > off ? end - off : 0);
+        }
+    }
+    W.order.resize(W.items.size());
+    for (uint32_t t = 0; t < W.order.size(); t++) W.order[t] = t;
+    std::stable_sort(W.order.begin(), W.order.end(), [&](uint32_t x, uint32_t y) { return item_len[x] > item_len[y]; });
+    // the segments' items follow the host's: the device writes them, and the lanes take them as they lie (they are short, so they go last)
+    W.n_items = (uint32_t)W.items.size();
+    for (SegFile &sf : W.seg_files) sf.first_item = W.n_items, W.n_items += sf.n_segs;
+    return W;
+}
+
+// ---- progressive plan: the scans of a chunk's progressive files (one lane per scan: jpeg_prog_kernel) and what they wait for
+struct ProgPlan {
+    std::vector<PScan> pscans;
+    std::vector<uint32_t> pwaits;  // scans (indices into pscans) that must have ended before a scan begins (PScan::wait_first / wait_count)
+    std::vector<PRef> prefs;       // their refinement scans, grouped by plane (file order within a plane)
+    struct PlaneRefs { uint32_t r, first[3], count[3]; };  // a file's chunk position, and per component its range of prefs
+    std::vector<PlaneRefs> plane_refs;
+    std::vector<uint32_t> files;  // the progressive files (chunk positions)
+    // their blocks (one mask word each), the records of their AC refinement scans, the bytes of their DC refinement scans
+    uint64_t blocks = 0, corr = 0, dc_bytes = 0;
+    size_t mask_bytes() const { return blocks * 8 + align_up(pscans.size() * 4, 16); }  // one mask word per block, then one progress word per scan
+
+    // the scans of the file at chunk position r, the dependencies among them and their refinement records; hi: the file's walk record
+    void add(uint32_t r, const Job &j, HImage &hi)
+    {
+        hi.mask_first = (uint32_t)blocks;
+        blocks += j.frame.total_blocks;
+        hi.pscan_first = (uint32_t)pscans.size();
+        hi.pscan_count = (uint32_t)j.plan.prog.size();
+        const size_t p0 = pscans.size();
+        for (const rphj::ScanPlan &sp : j.plan.prog) {
+            PScan ps;
+            ps.off = sp.stream_off, ps.len = sp.stream_len, ps.ns = sp.ns, ps.ss = sp.ss, ps.se = sp.se, ps.ah = sp.ah, ps.al = sp.al;
+            for (int c = 0; c < 3; c++) ps.ci[c] = sp.ci[c], ps.dc[c] = sp.dc[c], ps.dcb[c] = 0;
+            ps.ac = sp.ac[0], ps.image = r, ps.corr_first = 0;
+            for (int c = 0; sp.ss == 0 && sp.ah > 0 && c < sp.ns && c < 3; c++) {
+                const rphj::Comp &kc = j.frame.comp[sp.ci[c]];
+                ps.dcb[c] = (uint32_t)dc_bytes;
+                dc_bytes += (uint64_t)kc.blocks_w * kc.blocks_h;
+            }
+            if (sp.ss > 0 && sp.ah > 0) {
+                const rphj::Comp &kc = j.frame.comp[sp.ci[0]];
+                ps.corr_first = (uint32_t)corr;
+                corr += (uint64_t)kc.real_bw * kc.real_bh;
+            }
+            // The scans this one must come after: the earlier scans of the file that share a component and a coefficient with it.
+            // An AC scan follows up to two of them (the longest) block by block (PScan::chase); the others must have ended.
+            ps.chase[0] = ps.chase[1] = PSCAN_NONE, ps.wait_first = (uint32_t)pwaits.size();
+            uint32_t my_comps = 0;
+            for (uint32_t c = 0; c < ps.ns && c < 3; c++) my_comps |= 1u << ps.ci[c];
+            uint32_t deps[rphj::MAX_PROG_SCANS], n_deps = 0;
+            for (size_t q = p0; q < pscans.size(); q++) {
+                const PScan &e = pscans[q];
+                uint32_t its = 0;
+                for (uint32_t c = 0; c < e.ns && c < 3; c++) its |= 1u << e.ci[c];
+                if ((its & my_comps) && e.ss <= ps.se && ps.ss <= e.se) deps[n_deps++] = (uint32_t)q;
+            }
+            if (ps.ss > 0) {  // (AC scans of one component walk the same raster of blocks): the two longest are followed
+                for (int t = 0; t < 2; t++) {
+                    uint32_t best = PSCAN_NONE;
+                    for (uint32_t d = 0; d < n_deps; d++)
+                        if (deps[d] != PSCAN_NONE && (best == PSCAN_NONE || pscans[deps[d]].len > pscans[deps[best]].len)) best = d;
+                    if (best == PSCAN_NONE) break;
+                    ps.chase[t] = deps[best];
+                    deps[best] = PSCAN_NONE;
+                }
+                for (uint32_t d = 0; d < n_deps; d++)
+                    if (deps[d] != PSCAN_NONE) pwaits.push_back(deps[d]);
+            } else if (ps.ah == 0) {
+                pwaits.insert(pwaits.end(), deps, deps + n_deps);
+            }  // (a DC refinement scan writes its bits beside the coefficients and reads nothing: it waits for nobody)
+            ps.wait_count = (uint32_t)pwaits.size() - ps.wait_first;
+            pscans.push_back(ps);
+        }
+        PlaneRefs pr{r, {}, {}};
+        for (uint32_t c = 0; c < 3; c++) {
+            pr.first[c] = (uint32_t)prefs.size();
+            for (size_t q = p0; q < pscans.size(); q++) {
+                const PScan &x = pscans[q];
+                if (x.ss > 0 && x.ah > 0 && x.ci[0] == c) prefs.push_back(PRef{x.corr_first, x.al});
+                if (x.ss == 0 && x.ah > 0)
+                    for (uint32_t u = 0; u < x.ns && u < 3; u++)
+                        if (x.ci[u] == c) prefs.push_back(PRef{x.dcb[u], x.al | PREF_DC});
+            }
+            pr.count[c] = (uint32_t)prefs.size() - pr.first[c];
+        }
+        plane_refs.push_back(pr);
+        files.push_back(r);
+    }
+};
+
+// ---- wave order: the lanes of the progressive launch, one scan (index into G.pscans) or PSCAN_NONE each.  64 files of one scan script
+// make a batch, and wave k of a batch walks the k-th scan of each of them -- one kind of scan per wave, and a scan's producers in earlier
+// workgroups of the same launch, which start first (jpeg_kernels.hip).
+std::vector<uint32_t> order_waves(const ProgPlan &G, const std::vector<HImage> &himgs)
+{
+    auto signature = [&](uint32_t r) {
+        uint64_t h = 1469598103934665603ull;
+        for (uint32_t q = 0; q < himgs[r].pscan_count; q++) {
+            const PScan &x = G.pscans[himgs[r].pscan_first + q];
+            const uint32_t f[6] = {x.ns, x.ss, x.se, x.ah, x.al, x.ci[0] | (x.ci[1] << 8) | (x.ci[2] << 16)};
+            for (uint32_t v : f) h = (h ^ v) * 1099511628211ull;
+        }
+        return h;
+    };
+    std::vector<std::pair<uint64_t, uint32_t>> sig(G.files.size());  // (script, file), files of a script in the chunk's order: longest first
+    for (size_t t = 0; t < G.files.size(); t++) sig[t] = {signature(G.files[t]), G.files[t]};
+    std::stable_sort(sig.begin(), sig.end(), [](const std::pair<uint64_t, uint32_t> &a, const std::pair<uint64_t, uint32_t> &b) { return a.first < b.first; });
+    // A wave = (batch, k-th scan).  Waves go into the grid by how much work still hangs on them -- their own (bytes x the rate of their
+    // kind of scan) plus the longest chain of scans behind them -- so the scans on a file's critical path (libjpeg's script: luma 6-63,
+    // then its two refinements) start at once for every batch and the short scans fill the slots that are left; a producer always
+    // ranks above its consumers, i.e. comes first in the grid.
+    struct Wave {
+        double rank;
+        uint32_t batch, first, count, k;  // files sig[first .. first + count), their k-th scans
+    };
+    std::vector<Wave> waves;
+    uint32_t n_batches = 0;
+    for (size_t t0 = 0; t0 < sig.size();) {
+        size_t t1 = t0;
+        while (t1 < sig.size() && t1 - t0 < 64 && sig[t1].first == sig[t0].first) t1++;
+        const HImage &h0 = himgs[sig[t0].second];  // (the batch's longest file stands for all of them)
+        const uint32_t n_scans = h0.pscan_count;
+        std::vector<double> rank(n_scans, 0.0);
+        for (uint32_t q = n_scans; q-- > 0;) {
+            const PScan &x = G.pscans[h0.pscan_first + q];
+            double behind = 0.0;
+            for (uint32_t c = q + 1; c < n_scans; c++) {  // scans that wait for q or follow it
+                const PScan &y = G.pscans[h0.pscan_first + c];
+                bool dep = y.chase[0] == h0.pscan_first + q || y.chase[1] == h0.pscan_first + q;
+                for (uint32_t w = 0; w < y.wait_count && !dep; w++) dep = G.pwaits[y.wait_first + w] == h0.pscan_first + q;
+                if (dep) behind = std::max(behind, rank[c]);
+            }
+            rank[q] = (double)x.len * (x.ss && x.ah ? 1.05 : 0.55) + 1.0 + behind;
+        }
+        for (uint32_t q = 0; q < n_scans; q++) waves.push_back(Wave{rank[q], n_batches, (uint32_t)t0, (uint32_t)(t1 - t0), q});
+        n_batches++;
+        t0 = t1;
+    }
+    std::stable_sort(waves.begin(), waves.end(), [](const Wave &a, const Wave &b) { return a.rank > b.rank; });
+    std::vector<uint32_t> pitems;
+    pitems.reserve(waves.size() * 64);
+    for (const Wave &w : waves)
+        for (uint32_t l = 0; l < 64; l++) pitems.push_back(l < w.count ? himgs[sig[w.first + l].second].pscan_first + w.k : PSCAN_NONE);
+    return pitems;
+}
+
+// bytes of the segments' states at the start of the slot's segment work buffer (the kernels' work area follows)
+inline size_t seg_states_bytes(uint32_t n_segs) { return align_up((size_t)n_segs * sizeof(SegState), 16); }
+
+// A chunk's meta buffer as its launches read it (device side), behind the reconstruction descriptors
+struct ChunkMeta {
+    ChunkDesc D;
+    size_t upload_bytes = 0;  // what the host fills: everything but the segments' items
+    uint32_t n_luts = 0;
+    const HImage *himgs = nullptr;
+    const uint32_t *order = nullptr, *pitems = nullptr, *pwaits = nullptr;
+    const rphj::DeviceLut *luts = nullptr;
+    const SegFile *seg_files = nullptr;
+    const PScan *pscans = nullptr;
+    HItem *items = nullptr;
+};
+// ---- meta: lays out the slot's meta buffer for a chunk, sizes the walks' work buffers and fills the meta buffer's host side:
+//   reconstruction descriptors | HImage | item order | tables | SegFile | PScan | progressive files | wave lanes | PRef | waits | items
+// (host and device at the same offsets; the segments' items exist on the device only: room is left for them, the upload stops before)
+int write_meta(JpegPipe &P, Jobs &jobs, const std::vector<uint32_t> &idx, const Chunk &C, int flavour, bool rgb_wanted, const TableStore &store,
+               const std::vector<HImage> &himgs, const SeqWork &W, const ProgPlan &G, const std::vector<uint32_t> &pitems, ChunkMeta &M)
+{
+    Slot &S = P.slot[C.b];
+    hipStream_t s = S.stream;
+    const size_t m = C.m();
+    M.n_luts = store.size();  // (the tables lie in the store's blocks)
+    Layout L;
+    L.add(m * (3 * sizeof(JPlane) + sizeof(JImage) + 3 * 128));  // (build_descriptors)
+    const size_t off_himg = L.add(m * sizeof(HImage), 16), off_order = L.add(W.order.size() * 4), off_luts = L.add(M.n_luts * sizeof(rphj::DeviceLut), 16),
+                 off_segf = L.add(W.seg_files.size() * sizeof(SegFile), 16), off_pscan = L.add(G.pscans.size() * sizeof(PScan), 16),
+                 off_porder = L.add(G.files.size() * 4), off_pitems = L.add(pitems.size() * 4), off_prefs = L.add(G.prefs.size() * sizeof(PRef), 16),
+                 off_pwaits = L.add(G.pwaits.size() * 4, 16), off_items = L.add(W.items.size() * sizeof(HItem), 16);
+    M.upload_bytes = L.end();
+    RPH_TRY(S.meta.reserve(off_items + (size_t)W.n_items * sizeof(HItem), s));
+    // the walks' work buffers: segment states and work, the progressive files' masks, correction records and DC bits
+    const size_t segwork = seg_states_bytes(W.n_segs) + rph_jpeg_segment_work_bytes(W.n_segs);
+    if (W.n_segs) RPH_TRY(S.segwork.reserve(segwork, segwork + segwork / 4, s));
+    if (G.blocks >= ((uint64_t)1 << 32)) return RPH_ERR_CAPACITY;  // (a chunk's coefficients are capped far below: 2^32 blocks are 512 GB)
+    if (G.corr >= ((uint64_t)1 << 32) || G.dc_bytes >= ((uint64_t)1 << 32)) return RPH_ERR_CAPACITY;
+    if (G.dc_bytes) RPH_TRY(S.pdc.reserve(G.dc_bytes, G.dc_bytes + G.dc_bytes / 4 + 64, s));
+    if (G.corr) RPH_TRY(S.pcorr.reserve(G.corr * sizeof(PCorr), G.corr * sizeof(PCorr) + G.corr * 4, s));
+    if (G.blocks) RPH_TRY(S.pmask.reserve(G.mask_bytes(), G.mask_bytes() + G.mask_bytes() / 4, s));
+    RPH_TRY(build_descriptors(jobs, idx, C.first, C.last, flavour, rgb_wanted, P.recon_coef_bytes[C.b], S.meta, M.D));
+    uint8_t *h = S.meta.h.data();
+    const uint8_t *d = S.meta.d.data();
+    memcpy(h + off_himg, himgs.data(), m * sizeof(HImage));
+    memcpy(h + off_items, W.items.data(), W.items.size() * sizeof(HItem));
+    memcpy(h + off_order, W.order.data(), W.order.size() * 4);
+    if (M.n_luts) store.copy_luts(reinterpret_cast<rphj::DeviceLut *>(h + off_luts));
+    if (W.n_segs) memcpy(h + off_segf, W.seg_files.data(), W.seg_files.size() * sizeof(SegFile));
+    if (!G.files.empty()) {
+        memcpy(h + off_pscan, G.pscans.data(), G.pscans.size() * sizeof(PScan));
+        memcpy(h + off_porder, G.files.data(), G.files.size() * 4);
+        memcpy(h + off_pitems, pitems.data(), pitems.size() * 4);
+        if (!G.pwaits.empty()) memcpy(h + off_pwaits, G.pwaits.data(), G.pwaits.size() * 4);
+        if (!G.prefs.empty()) {
+            memcpy(h + off_prefs, G.prefs.data(), G.prefs.size() * sizeof(PRef));
+            for (const ProgPlan::PlaneRefs &pr : G.plane_refs) {
+                if (M.D.plane_of[pr.r] == UINT32_MAX) continue;
+                JPlane *pl = M.D.planes + M.D.plane_of[pr.r];
+                const int nc = jobs[idx[C.first + pr.r]].frame.ncomp;
+                for (int c = 0; c < nc && c < 3; c++) pl[c].ref_first = pr.first[c], pl[c].ref_count = pr.count[c];
+            }
+            M.D.d_refs = reinterpret_cast<const PRef *>(d + off_prefs);
+            M.D.d_corr = S.pcorr.as<PCorr>();
+            M.D.d_dcbits = S.pdc.data();
+        }
+    }
+    M.himgs = reinterpret_cast<const HImage *>(d + off_himg), M.luts = reinterpret_cast<const rphj::DeviceLut *>(d + off_luts);
+    M.order = reinterpret_cast<const uint32_t *>(d + off_order), M.seg_files = reinterpret_cast<const SegFile *>(d + off_segf);
+    M.pscans = reinterpret_cast<const PScan *>(d + off_pscan), M.pitems = reinterpret_cast<const uint32_t *>(d + off_pitems);
+    M.pwaits = reinterpret_cast<const uint32_t *>(d + off_pwaits), M.items = reinterpret_cast<HItem *>(S.meta.d.data() + off_items);
+    return RPH_OK;
+}
+
+// ---- launch: streams and descriptors up, segments, zeroed coefficients, the walks, then reconstruction + hashing sub-batch by sub-batch.
+// RPH_JPEG_TRACE=1: synchronise after every phase and print where the time goes (stderr); t_host: start, prepared, descriptors written.
+int launch_chunk(rph_ctx *ctx, JpegPipe &P, const Chunk &C, int16_t *d_coef, Jobs &jobs, const std::vector<uint32_t> &idx, int flavour, const Outputs &out,
+                 const SeqWork &W, const ProgPlan &G, const std::vector<uint32_t> &pitems, const ChunkMeta &M, const double (&t_host)[3])
+{
+    Slot &S = P.slot[C.b];
+    hipStream_t s = S.stream;
+    const size_t m = C.m();
+    const bool tr = trace_on();
+    double t_up = 0, t_seg = 0, t_zero = 0, t_walk = 0, t_rec = 0;
+    auto lap = [&](double &t) { if (tr) (void)hipStreamSynchronize(s), t = now_ms(); };
+    ResView R(S.res.data(), S.res_images);
+    zero_results(S, m, out);
+    if (!W.n_items && G.files.empty()) return RPH_OK;
+    RPH_HIP_CHECK(hipMemcpyAsync(S.stream_bytes.d.data(), S.stream_bytes.h.data(), C.file_bytes + 64, hipMemcpyHostToDevice, s));
+    RPH_HIP_CHECK(hipMemcpyAsync(S.meta.d.data(), S.meta.h.data(), M.upload_bytes, hipMemcpyHostToDevice, s));
+    lap(t_up);
+    if (W.n_segs)  // streams without markers: their segments find their entries and become walk items
+        RPH_TRY(rph_jpeg_launch_segments(s, S.stream_bytes.d.data(), M.himgs, M.seg_files, (uint32_t)W.seg_files.size(), S.segwork.as<SegState>(), W.n_segs,
+                                         ctx->jpeg_seg_bytes, S.segwork.data() + seg_states_bytes(W.n_segs), 8, M.luts, M.n_luts, M.items));
+    lap(t_seg);
+    // The coefficients start from zero -- unless the walk writes whole blocks and covers every block of the chunk: sequential files of
+    // one scan (interleaved, or one component), no progressive file.  (A file whose walk breaks off is reported as damaged; what its
+    // remaining blocks hold is not looked at.)
+    if (!(rph_jpeg_walk_writes_whole_blocks(W.n_items) && W.all_one_scan && G.files.empty())) RPH_HIP_CHECK(hipMemsetAsync(d_coef, 0, C.blocks * 128, s));
+    lap(t_zero);
+    if (W.n_items)
+        RPH_TRY(rph_jpeg_launch_walk(s, S.stream_bytes.d.data(), M.himgs, M.items, M.order, (uint32_t)W.items.size(), W.n_items, M.luts, M.n_luts, d_coef, R.status));
+    if (G.blocks) RPH_HIP_CHECK(hipMemsetAsync(S.pmask.data(), 0, G.mask_bytes(), s));
+    RPH_TRY(rph_jpeg_launch_prog(s, S.stream_bytes.d.data(), M.himgs, M.pscans, (uint32_t)G.pscans.size(), M.pitems, (uint32_t)pitems.size(), M.pwaits, M.luts, M.n_luts,
+                                 d_coef, S.pmask.as<unsigned long long>(), reinterpret_cast<uint32_t *>(S.pmask.as<unsigned long long>() + G.blocks), S.pcorr.as<PCorr>(),
+                                 (size_t)G.corr, S.pdc.data(), (size_t)G.dc_bytes, R.status));
+    lap(t_walk);
+    const std::vector<size_t> &subs = M.D.sub_starts;
+    for (size_t q = 0; q < subs.size(); q++)
+        RPH_TRY(reconstruct_and_hash(ctx, P, C.b, S, jobs, idx, C.first, M.D, subs[q], q + 1 < subs.size() ? subs[q + 1] : m, d_coef, flavour, out, s));
+    lap(t_rec);
+    if (tr && W.n_segs) rph_jpeg_debug_segment_stats(s, S.segwork.data() + seg_states_bytes(W.n_segs), W.n_segs);  // (behind the timed phases)
+    if (tr)
+        fprintf(stderr, "[rph_jpeg] chunk of %zu files in %zu lanes (%.1f MB of entropy bytes, %.2f GB of coefficients, %zu tables, %zu sub-batches): prepare %.1f ms, "
+                        "descriptors %.1f ms, upload %.1f ms, %u segments %.1f ms, zero %.1f ms, walk %.1f ms, reconstruct + hash %.1f ms\n",
+                m, (size_t)W.n_items, C.file_bytes / 1e6, C.blocks * 128 / 1e9, (size_t)M.n_luts, subs.size(), t_host[1] - t_host[0], t_host[2] - t_host[1],
+                t_up - t_host[2], W.n_segs, t_seg - t_up, t_zero - t_seg, t_walk - t_zero, t_rec - t_walk);
+    return RPH_OK;
+}
+
+// The sequential and progressive files idx[...] with their Huffman streams walked on the device: the call plan, then chunk by chunk
+// over the lanes.  Files the walk does not take, or flags, come back in `leftover` for the host decoder.
+int run_device_entropy(rph_ctx *ctx, JpegPipe &P, Jobs &jobs, std::vector<uint32_t> idx, int flavour, unsigned threads, const Outputs &out,
+                       std::vector<uint32_t> &leftover)
+{
+    DevicePlan plan;
+    RPH_TRY(plan_device_call(ctx, P, jobs, idx, plan));
+    InFlight lane[JPEG_LANES];
     const size_t n = idx.size();
     int k = 0;
     RPH_JPEG_STAMP("buffers ready");
     for (size_t first = 0; first < n; k++) {
-        size_t last = first, blocks = 0, file_bytes = 0;
-        while (last < n) {
-            const Job &j = jobs[idx[last]];
-            const size_t nb = (size_t)j.frame.total_blocks;
-            if (last > first && (blocks + nb) * 128 > chunk_bytes) break;
-            blocks += nb;
-            file_bytes += stream_cap(j);
-            last++;
+        Chunk C;  // ---- pick the chunk: files while their coefficients fit plan.chunk_bytes, at least one
+        for (C.first = C.last = first; C.last < n; C.last++) {
+            const Job &j = jobs[idx[C.last]];
+            if (C.last > first && (C.blocks + j.frame.total_blocks) * 128 > plan.chunk_bytes) break;
+            C.blocks += j.frame.total_blocks, C.file_bytes += stream_cap(j);
         }
-        if (blocks * 128 > region) {  // one image larger than a whole region: the host path takes it
-            leftover.push_back(idx[first]);
-            first = last;
+        first = C.last;
+        if (C.blocks * 128 > plan.region) {  // one image larger than a whole region: the host path takes it
+            leftover.push_back(idx[C.first]);
             k--;
             continue;
         }
-        const int b = k % lanes;
-        RPH_TRY(finish(b));  // the lane is free again once its previous chunk (`lanes` chunks back) has delivered its results
-        Slot &S = P.slot[b];
-        hipStream_t s = S.stream;
-        int16_t *d_coef = P.coef.as<int16_t>() + (size_t)b * (region / 2);  // (int16 elements: region bytes per lane)
-        const size_t m = last - first;
-        RPH_TRY(S.reserve_res(m, out.pixel_hash != nullptr));
-        RPH_TRY(S.stream_bytes.reserve(file_bytes + 64, s));
-        // ---- streams and scan plans (host threads: memchr + memcpy)
-        const double t0 = now_ms();
-        {
-            size_t off = 0;
-            uint64_t fb = 0;
-            for (size_t i = first; i < last; i++) {
-                Job &j = jobs[idx[i]];
-                j.stream_off = off;
-                off += stream_cap(j);
-                j.first_block = fb;
-                fb += j.frame.total_blocks;
-            }
-        }
+        C.b = k % plan.lanes, C.k = k;
+        // the lane is free again once its previous chunk (`lanes` chunks back) has delivered its results
+        RPH_TRY(lane[C.b].finish(C.b, P.slot[C.b], true, jobs, idx, out, &leftover));
+        Slot &S = P.slot[C.b];
+        RPH_TRY(S.reserve_res(C.m(), out.pixel_hash != nullptr));
+        RPH_TRY(S.stream_bytes.reserve(C.file_bytes + 64, S.stream));
+        double t_host[3] = {now_ms(), 0, 0};
         TableStore store;
-        std::vector<HImage> himgs(m);
-        RPH_JPEG_STAMP("lane %d: chunk %d laid out", b, k);
-        parallel_for(first, last, threads, [&](size_t i) {
-            Job &j = jobs[idx[i]];
-            HImage &hi = himgs[i - first];
-            memset(&hi, 0, sizeof hi);
-            j.status = rphj::prepare_stream(j.data, j.len, j.frame, j.plan, S.stream_bytes.h.data() + j.stream_off, stream_cap(j), &j.stream_used, &TableStore::intern, &store, &j.marks);
-            if (j.status != RPH_OK) return;
-            const rphj::Frame &f = j.frame;
-            hi.first_block = j.first_block;
-            hi.stream_base = j.stream_off;
-            hi.mcus_x = f.mcus_x;
-            hi.mcus_y = f.mcus_y;
-            hi.n_scans = f.progressive ? 0u : (uint32_t)j.plan.n_scans;
-            hi.ncomp = (uint32_t)f.ncomp;
-            for (int c = 0; c < f.ncomp; c++) {
-                const rphj::Comp &kc = f.comp[c];
-                hi.comp[c] = HComp{kc.blocks_w, kc.real_bw, kc.real_bh, (uint32_t)kc.first_block, kc.H, kc.V};
-            }
-            for (int q = 0; q < (f.progressive ? 0 : j.plan.n_scans); q++) {
-                const rphj::ScanPlan &sp = j.plan.scan[q];
-                HScan &hs = hi.scan[q];
-                hs.off = sp.stream_off;
-                hs.len = sp.stream_len;
-                hs.restart_interval = sp.restart_interval;
-                hs.ns = sp.ns;
-                for (int c = 0; c < sp.ns; c++) {
-                    hs.ci[c] = sp.ci[c];
-                    hs.dc[c] = sp.dc[c];
-                    hs.ac[c] = sp.ac[c];
-                }
-            }
-        });
-        const double t_prep = now_ms();
-        RPH_JPEG_STAMP("lane %d: chunk %d prepared (%zu files)", b, k, m);
-        // files the walk does not take (more than four scans) go back to the host decoder; they keep their place in the chunk as holes.
-        // Work items: one per restart interval where a file has them, else one per file; lanes take them longest first.
-        // Segments (three decoding passes over every byte, but a lane per KB) or one lane per file (one pass, as long as the longest file)?
-        // The walk of whole files takes ~0.65 us per byte of the longest one while the chunk has fewer lanes than the device (65 536); the
-        // segment passes move ~31 GB/s of entropy bytes (5 275 photos of 366 KB: 67 ms against 236; 25 000 files of 158 KB: 129 ms against
-        // 103).  Whole-file walks also leave most of the device to the other lane's chunk, so segments must win clearly.
-        bool use_segments = ctx->jpeg_seg_bytes != 0;
-        if (use_segments && ctx->jpeg_seg_min_bytes > 0) {
-            const double t_whole = 0.65e-6 * (double)jobs[idx[first]].len * std::max(1.0, (double)m / 65536.0), t_seg = (double)file_bytes / seg_rate();
-            use_segments = t_seg < 0.7 * t_whole;
-        }
-        std::vector<HItem> items;
-        std::vector<uint32_t> item_len;
-        std::vector<SegFile> seg_files;
-        std::vector<PScan> pscans;            // the scans of the chunk's progressive files
-        std::vector<uint32_t> prog_order;     // the progressive files (indices into the chunk)
-        std::vector<uint32_t> pwaits;         // scans (indices into pscans) that must have ended before a scan begins (PScan::wait_first / wait_count)
-        std::vector<PRef> prefs;              // their AC refinement scans, grouped by plane (file order within a plane)
-        struct PlaneRefs {
-            uint32_t r, first[3], count[3];
-        };
-        std::vector<PlaneRefs> plane_refs;
-        uint64_t prog_blocks = 0;             // their blocks: one mask word each
-        uint64_t prog_corr = 0;               // records of their AC refinement scans
-        uint64_t prog_dcb = 0;                // bytes of their DC refinement scans
-        uint32_t n_segs = 0;
-        bool all_one_scan = true;  // every sequential file of the chunk has one scan: its MCUs cover all blocks of its components
-        items.reserve(m);
-        for (size_t i = first; i < last; i++) {
-            Job &j = jobs[idx[i]];
-            if (j.status != RPH_OK) {  // whatever prepare_stream found, the host decoder judges the file
-                leftover.push_back(idx[i]);
-                continue;
-            }
-            const uint32_t r = (uint32_t)(i - first);
-            if (j.frame.progressive) {  // one lane per scan (jpeg_prog_kernel)
-                himgs[r].mask_first = (uint32_t)prog_blocks;
-                prog_blocks += j.frame.total_blocks;
-                himgs[r].pscan_first = (uint32_t)pscans.size();
-                himgs[r].pscan_count = (uint32_t)j.plan.prog.size();
-                const size_t p0 = pscans.size();
-                for (const rphj::ScanPlan &sp : j.plan.prog) {
-                    PScan ps;
-                    ps.off = sp.stream_off, ps.len = sp.stream_len, ps.ns = sp.ns, ps.ss = sp.ss, ps.se = sp.se, ps.ah = sp.ah, ps.al = sp.al;
-                    for (int c = 0; c < 3; c++) ps.ci[c] = sp.ci[c], ps.dc[c] = sp.dc[c];
-                    ps.ac = sp.ac[0];
-                    ps.image = r;
-                    ps.corr_first = 0;
-                    ps.dcb[0] = ps.dcb[1] = ps.dcb[2] = 0;
-                    if (sp.ss == 0 && sp.ah > 0) {
-                        for (int c = 0; c < sp.ns && c < 3; c++) {
-                            const rphj::Comp &kc = j.frame.comp[sp.ci[c]];
-                            ps.dcb[c] = (uint32_t)prog_dcb;
-                            prog_dcb += (uint64_t)kc.blocks_w * kc.blocks_h;
-                        }
-                    }
-                    if (sp.ss > 0 && sp.ah > 0) {
-                        const rphj::Comp &kc = j.frame.comp[sp.ci[0]];
-                        ps.corr_first = (uint32_t)prog_corr;
-                        prog_corr += (uint64_t)kc.real_bw * kc.real_bh;
-                    }
-                    // The scans this one must come after: the earlier scans of the file that share a component and a coefficient with it.
-                    // An AC scan follows up to two of them (the longest) block by block (PScan::chase); the others must have ended.
-                    ps.chase[0] = ps.chase[1] = PSCAN_NONE;
-                    ps.wait_first = (uint32_t)pwaits.size();
-                    uint32_t my_comps = 0;
-                    for (uint32_t c = 0; c < ps.ns && c < 3; c++) my_comps |= 1u << ps.ci[c];
-                    uint32_t deps[rphj::MAX_PROG_SCANS], n_deps = 0;
-                    for (size_t q = p0; q < pscans.size(); q++) {
-                        const PScan &e = pscans[q];
-                        uint32_t its = 0;
-                        for (uint32_t c = 0; c < e.ns && c < 3; c++) its |= 1u << e.ci[c];
-                        if ((its & my_comps) && e.ss <= ps.se && ps.ss <= e.se) deps[n_deps++] = (uint32_t)q;
-                    }
-                    if (ps.ss > 0) {  // (AC scans of one component walk the same raster of blocks): the two longest are followed
-                        for (int k = 0; k < 2; k++) {
-                            uint32_t best = PSCAN_NONE;
-                            for (uint32_t d = 0; d < n_deps; d++)
-                                if (deps[d] != PSCAN_NONE && (best == PSCAN_NONE || pscans[deps[d]].len > pscans[deps[best]].len)) best = d;
-                            if (best == PSCAN_NONE) break;
-                            ps.chase[k] = deps[best];
-                            deps[best] = PSCAN_NONE;
-                        }
-                        for (uint32_t d = 0; d < n_deps; d++)
-                            if (deps[d] != PSCAN_NONE) pwaits.push_back(deps[d]);
-                    } else if (ps.ah == 0) {
-                        pwaits.insert(pwaits.end(), deps, deps + n_deps);
-                    }  // (a DC refinement scan writes its bits beside the coefficients and reads nothing: it waits for nobody)
-                    ps.wait_count = (uint32_t)pwaits.size() - ps.wait_first;
-                    pscans.push_back(ps);
-                }
-                PlaneRefs pr;
-                pr.r = r;
-                for (uint32_t c = 0; c < 3; c++) {
-                    pr.first[c] = (uint32_t)prefs.size();
-                    for (size_t q = p0; q < pscans.size(); q++) {
-                        const PScan &x = pscans[q];
-                        if (x.ss > 0 && x.ah > 0 && x.ci[0] == c) prefs.push_back(PRef{x.corr_first, x.al});
-                        if (x.ss == 0 && x.ah > 0)
-                            for (uint32_t k = 0; k < x.ns && k < 3; k++)
-                                if (x.ci[k] == c) prefs.push_back(PRef{x.dcb[k], x.al | PREF_DC});
-                    }
-                    pr.count[c] = (uint32_t)prefs.size() - pr.first[c];
-                }
-                plane_refs.push_back(pr);
-                prog_order.push_back(r);
-                continue;
-            }
-            if (j.plan.n_scans != 1 || j.plan.scan[0].ns != j.frame.ncomp) all_one_scan = false;
-            if (j.frame.ncomp == 1 && (j.frame.comp[0].blocks_w != j.frame.comp[0].real_bw || j.frame.comp[0].blocks_h != j.frame.comp[0].real_bh))
-                all_one_scan = false;  // (a one-component scan walks the real blocks only: a padded grid keeps its zeroing)
-            if (j.marks.empty()) {
-                const rphj::ScanPlan &sp0 = j.plan.scan[0];
-                if (use_segments && j.plan.n_scans == 1 && sp0.restart_interval == 0 && sp0.stream_len >= ctx->jpeg_seg_min_bytes && sp0.stream_len < ((uint32_t)1 << 28)) {
-                    // a long stream without restart markers: cut into segments that synchronise on the device (jpeg_device.h)
-                    const rphj::Frame &f = j.frame;
-                    SegFile sf;
-                    sf.image = r;
-                    sf.first_seg = n_segs;
-                    sf.n_segs = (sp0.stream_len + ctx->jpeg_seg_bytes - 1) / ctx->jpeg_seg_bytes;
-                    sf.first_item = 0;  // set below, behind the host's items
-                    sf.total_mcus = sp0.ns == 1 ? f.comp[sp0.ci[0]].real_bw * f.comp[sp0.ci[0]].real_bh : f.mcus_x * f.mcus_y;
-                    sf.scan_bits = sp0.stream_len * 8;
-                    n_segs += sf.n_segs;
-                    seg_files.push_back(sf);
-                    continue;
-                }
-                items.push_back(HItem{r, HITEM_ALL_SCANS, 0, 0, 0, 0, {0, 0, 0}, HITEM_NO_END});
-                item_len.push_back((uint32_t)std::min<size_t>(j.len, 0xFFFFFFFFu));
-                continue;
-            }
-            const rphj::ScanPlan &sp = j.plan.scan[0];
-            const rphj::Frame &f = j.frame;
-            const uint64_t mcus = sp.ns == 1 ? (uint64_t)f.comp[sp.ci[0]].real_bw * f.comp[sp.ci[0]].real_bh : (uint64_t)f.mcus_x * f.mcus_y;
-            const uint32_t n_int = (uint32_t)j.marks.size() + 1;
-            for (uint32_t k = 0; k < n_int; k++) {
-                const uint32_t off = k ? j.marks[k - 1] : 0, end = k + 1 < n_int ? j.marks[k] : sp.stream_len;
-                const uint64_t m_first = (uint64_t)k * sp.restart_interval;
-                items.push_back(HItem{r, 0, (uint32_t)m_first, (uint32_t)std::min<uint64_t>(sp.restart_interval, mcus - m_first), off, 0, {0, 0, 0}, end});
-                item_len.push_back(end > off ? end - off : 0);
-            }
-        }
-        RPH_JPEG_STAMP("lane %d: chunk %d items listed", b, k);
-        // The lanes of the launch: 64 files of one scan script make a batch, and wave k of a batch walks the k-th scan of each of them -- one
-        // kind of scan per wave, and a scan's producers in earlier workgroups of the same launch, which start first (jpeg_kernels.hip).
-        std::vector<uint32_t> pitems;
-        {
-            auto signature = [&](uint32_t r) {
-                uint64_t h = 1469598103934665603ull;
-                for (uint32_t q = 0; q < himgs[r].pscan_count; q++) {
-                    const PScan &x = pscans[himgs[r].pscan_first + q];
-                    const uint32_t f[6] = {x.ns, x.ss, x.se, x.ah, x.al, x.ci[0] | (x.ci[1] << 8) | (x.ci[2] << 16)};
-                    for (uint32_t v : f) h = (h ^ v) * 1099511628211ull;
-                }
-                return h;
-            };
-            std::vector<std::pair<uint64_t, uint32_t>> sig(prog_order.size());  // (script, file), files of a script in the chunk's order: longest first
-            for (size_t t = 0; t < prog_order.size(); t++) sig[t] = {signature(prog_order[t]), prog_order[t]};
-            std::stable_sort(sig.begin(), sig.end(), [](const std::pair<uint64_t, uint32_t> &a, const std::pair<uint64_t, uint32_t> &b) { return a.first < b.first; });
-            // A wave = (batch, k-th scan).  Waves go into the grid by how much work still hangs on them -- their own (bytes x the rate of their
-            // kind of scan) plus the longest chain of scans behind them -- so the scans on a file's critical path (libjpeg's script: luma 6-63,
-            // then its two refinements) start at once for every batch and the short scans fill the slots that are left; a producer always
-            // ranks above its consumers, i.e. comes first in the grid.
-            struct Wave {
-                double rank;
-                uint32_t batch, first, count, k;  // files sig[first .. first + count), their k-th scans
-            };
-            std::vector<Wave> waves;
-            uint32_t n_batches = 0;
-            for (size_t t0 = 0; t0 < sig.size();) {
-                size_t t1 = t0;
-                while (t1 < sig.size() && t1 - t0 < 64 && sig[t1].first == sig[t0].first) t1++;
-                const HImage &h0 = himgs[sig[t0].second];  // (the batch's longest file stands for all of them)
-                const uint32_t n_scans = h0.pscan_count;
-                std::vector<double> rank(n_scans, 0.0);
-                for (uint32_t q = n_scans; q-- > 0;) {
-                    const PScan &x = pscans[h0.pscan_first + q];
-                    double behind = 0.0;
-                    for (uint32_t c = q + 1; c < n_scans; c++) {  // scans that wait for q or follow it
-                        const PScan &y = pscans[h0.pscan_first + c];
-                        bool dep = y.chase[0] == h0.pscan_first + q || y.chase[1] == h0.pscan_first + q;
-                        for (uint32_t w = 0; w < y.wait_count && !dep; w++) dep = pwaits[y.wait_first + w] == h0.pscan_first + q;
-                        if (dep) behind = std::max(behind, rank[c]);
-                    }
-                    rank[q] = (double)x.len * (x.ss && x.ah ? 1.05 : 0.55) + 1.0 + behind;
-                }
-                for (uint32_t q = 0; q < n_scans; q++) waves.push_back(Wave{rank[q], n_batches, (uint32_t)t0, (uint32_t)(t1 - t0), q});
-                n_batches++;
-                t0 = t1;
-            }
-            std::stable_sort(waves.begin(), waves.end(), [](const Wave &a, const Wave &b) { return a.rank > b.rank; });
-            pitems.reserve(waves.size() * 64);
-            for (const Wave &w : waves)
-                for (uint32_t l = 0; l < 64; l++) pitems.push_back(l < w.count ? himgs[sig[w.first + l].second].pscan_first + w.k : PSCAN_NONE);
-        }
-        RPH_JPEG_STAMP("lane %d: chunk %d waves ordered", b, k);
-        std::vector<uint32_t> order(items.size());
-        for (uint32_t t = 0; t < order.size(); t++) order[t] = t;
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return item_len[a] > item_len[b]; });
-        // the segments' items follow the host's: the device writes them, and the lanes take them as they lie (they are short, so they go last)
-        const uint32_t n_ordered = (uint32_t)items.size();
-        uint32_t n_items = n_ordered;
-        for (SegFile &sf : seg_files) {
-            sf.first_item = n_items;
-            n_items += sf.n_segs;
-        }
-        struct {
-            uint32_t n;
-            size_t size() const { return n; }
-            bool empty() const { return n == 0; }
-        } luts{store.size()};  // (the tables' count: they lie in the store's blocks)
-        // ---- meta buffer: reconstruction descriptors | HImage | order | tables
-        const size_t recon_bytes = m * (3 * sizeof(JPlane) + sizeof(JImage) + 3 * 128);
-        // (the items of the segments exist on the device only: d_meta has room for them, the upload stops before them)
-        const size_t off_himg = align_up(recon_bytes, 16), off_order = off_himg + m * sizeof(HImage), off_luts = align_up(off_order + order.size() * 4, 16),
-                     off_segf = align_up(off_luts + luts.size() * sizeof(rphj::DeviceLut), 16), off_pscan = align_up(off_segf + seg_files.size() * sizeof(SegFile), 16),
-                     off_porder = off_pscan + pscans.size() * sizeof(PScan), off_pitems = off_porder + prog_order.size() * 4,
-                     off_prefs = align_up(off_pitems + pitems.size() * 4, 16), off_pwaits = align_up(off_prefs + prefs.size() * sizeof(PRef), 16),
-                     off_items = align_up(off_pwaits + pwaits.size() * 4, 16),
-                     upload_bytes = off_items + items.size() * sizeof(HItem), meta_bytes = off_items + (size_t)n_items * sizeof(HItem);
-        RPH_TRY(S.meta.reserve(meta_bytes, s));
-        const size_t segwork = align_up((size_t)n_segs * sizeof(SegState), 16) + rph_jpeg_segment_work_bytes(n_segs);
-        if (n_segs) RPH_TRY(S.segwork.reserve(segwork, segwork + segwork / 4, s));
-        if (prog_blocks >= ((uint64_t)1 << 32)) return RPH_ERR_CAPACITY;  // (a chunk's coefficients are capped far below: 2^32 blocks are 512 GB)
-        if (prog_corr >= ((uint64_t)1 << 32) || prog_dcb >= ((uint64_t)1 << 32)) return RPH_ERR_CAPACITY;
-        if (prog_dcb) RPH_TRY(S.pdc.reserve(prog_dcb, prog_dcb + prog_dcb / 4 + 64, s));
-        if (prog_corr) RPH_TRY(S.pcorr.reserve(prog_corr * sizeof(PCorr), prog_corr * sizeof(PCorr) + prog_corr * 4, s));
-        // (one mask word per block, and behind them one progress word per scan)
-        const size_t pmask_need = prog_blocks * 8 + align_up(pscans.size() * 4, 16);
-        if (prog_blocks) RPH_TRY(S.pmask.reserve(pmask_need, pmask_need + pmask_need / 4, s));
-        ChunkDesc D;
-        std::vector<size_t> subs;
-        RPH_TRY(build_descriptors(jobs, idx, first, last, flavour, out.rgb_wanted(), P.recon_coef_bytes[b], S.meta.h.data(), 0, D, subs));
-        memcpy(S.meta.h.data() + off_himg, himgs.data(), m * sizeof(HImage));
-        memcpy(S.meta.h.data() + off_items, items.data(), items.size() * sizeof(HItem));
-        memcpy(S.meta.h.data() + off_order, order.data(), order.size() * 4);
-        if (!luts.empty()) store.copy_luts(reinterpret_cast<rphj::DeviceLut *>(S.meta.h.data() + off_luts));
-        if (n_segs) memcpy(S.meta.h.data() + off_segf, seg_files.data(), seg_files.size() * sizeof(SegFile));
-        if (!prog_order.empty()) {
-            memcpy(S.meta.h.data() + off_pscan, pscans.data(), pscans.size() * sizeof(PScan));
-            memcpy(S.meta.h.data() + off_porder, prog_order.data(), prog_order.size() * 4);
-            memcpy(S.meta.h.data() + off_pitems, pitems.data(), pitems.size() * 4);
-            if (!pwaits.empty()) memcpy(S.meta.h.data() + off_pwaits, pwaits.data(), pwaits.size() * 4);
-            if (!prefs.empty()) {
-                memcpy(S.meta.h.data() + off_prefs, prefs.data(), prefs.size() * sizeof(PRef));
-                JPlane *hp = reinterpret_cast<JPlane *>(S.meta.h.data() + D.off_planes);
-                for (const PlaneRefs &pr : plane_refs) {
-                    if (D.plane_of[pr.r] == UINT32_MAX) continue;
-                    const int nc = jobs[idx[first + pr.r]].frame.ncomp;
-                    for (int c = 0; c < nc && c < 3; c++) hp[D.plane_of[pr.r] + c].ref_first = pr.first[c], hp[D.plane_of[pr.r] + c].ref_count = pr.count[c];
-                }
-                D.d_refs = reinterpret_cast<const PRef *>(S.meta.d.data() + off_prefs);
-                D.d_corr = S.pcorr.as<PCorr>();
-                D.d_dcbits = S.pdc.data();
-            }
-        }
-        RPH_JPEG_STAMP("lane %d: chunk %d descriptors written", b, k);
-        // ---- device: streams up, zeroed coefficients, the walk, then reconstruction + hashing sub-batch by sub-batch
-        const double t_desc = now_ms();
-        const bool tr = trace_on();  // RPH_JPEG_TRACE: synchronise after every phase and print where the time goes (stderr)
-        double t_up = 0, t_seg = 0, t_zero = 0, t_walk = 0, t_rec = 0;
-        auto lap = [&](double &t) {
-            if (tr) {
-                (void)hipStreamSynchronize(s);
-                t = now_ms();
-            }
-        };
-        ResView R(S.res.data(), S.res_images);
-        zero_results(S, m, out);
-        if (n_items || !prog_order.empty()) {
-            RPH_HIP_CHECK(hipMemcpyAsync(S.stream_bytes.d.data(), S.stream_bytes.h.data(), file_bytes + 64, hipMemcpyHostToDevice, s));
-            RPH_HIP_CHECK(hipMemcpyAsync(S.meta.d.data(), S.meta.h.data(), upload_bytes, hipMemcpyHostToDevice, s));
-            lap(t_up);
-            if (n_segs) {  // streams without markers: their segments find their entries and become walk items
-                SegState *d_segs = reinterpret_cast<SegState *>(S.segwork.data());
-                void *d_segtab = S.segwork.data() + align_up((size_t)n_segs * sizeof(SegState), 16);
-                RPH_TRY(rph_jpeg_launch_segments(s, S.stream_bytes.d.data(), reinterpret_cast<const HImage *>(S.meta.d.data() + off_himg), reinterpret_cast<const SegFile *>(S.meta.d.data() + off_segf),
-                                                 (uint32_t)seg_files.size(), d_segs, n_segs, ctx->jpeg_seg_bytes, d_segtab, 8,
-                                                 reinterpret_cast<const rphj::DeviceLut *>(S.meta.d.data() + off_luts), (uint32_t)luts.size(), reinterpret_cast<HItem *>(S.meta.d.data() + off_items)));
-            }
-            lap(t_seg);
-            // The coefficients start from zero -- unless the walk writes whole blocks and covers every block of the chunk: sequential files of
-            // one scan (interleaved, or one component), no progressive file.  (A file whose walk breaks off is reported as damaged; what its
-            // remaining blocks hold is not looked at.)
-            if (!(rph_jpeg_walk_writes_whole_blocks(n_items) && all_one_scan && prog_order.empty())) RPH_HIP_CHECK(hipMemsetAsync(d_coef, 0, blocks * 128, s));
-            lap(t_zero);
-            if (n_items)
-                RPH_TRY(rph_jpeg_launch_walk(s, S.stream_bytes.d.data(), reinterpret_cast<const HImage *>(S.meta.d.data() + off_himg), reinterpret_cast<const HItem *>(S.meta.d.data() + off_items),
-                                             reinterpret_cast<const uint32_t *>(S.meta.d.data() + off_order), n_ordered, n_items,
-                                             reinterpret_cast<const rphj::DeviceLut *>(S.meta.d.data() + off_luts), (uint32_t)luts.size(), d_coef, R.status));
-            if (prog_blocks) RPH_HIP_CHECK(hipMemsetAsync(S.pmask.data(), 0, prog_blocks * 8 + align_up(pscans.size() * 4, 16), s));
-            RPH_TRY(rph_jpeg_launch_prog(s, S.stream_bytes.d.data(), reinterpret_cast<const HImage *>(S.meta.d.data() + off_himg), reinterpret_cast<const PScan *>(S.meta.d.data() + off_pscan),
-                                         (uint32_t)pscans.size(), reinterpret_cast<const uint32_t *>(S.meta.d.data() + off_pitems), (uint32_t)pitems.size(),
-                                         reinterpret_cast<const uint32_t *>(S.meta.d.data() + off_pwaits), reinterpret_cast<const rphj::DeviceLut *>(S.meta.d.data() + off_luts),
-                                         (uint32_t)luts.size(), d_coef, S.pmask.as<unsigned long long>(), reinterpret_cast<uint32_t *>(S.pmask.as<unsigned long long>() + prog_blocks), S.pcorr.as<PCorr>(), (size_t)prog_corr, S.pdc.data(), (size_t)prog_dcb, R.status));
-            lap(t_walk);
-            for (size_t q = 0; q < subs.size(); q++) {
-                const size_t r0 = subs[q], r1 = q + 1 < subs.size() ? subs[q + 1] : m;
-                RPH_TRY(reconstruct_and_hash(ctx, P, b, S, jobs, idx, first, D, r0, r1, d_coef, flavour, out, s));
-            }
-            lap(t_rec);
-            if (tr && n_segs) rph_jpeg_debug_segment_stats(s, S.segwork.data() + align_up((size_t)n_segs * sizeof(SegState), 16), n_segs);  // (behind the timed phases)
-            if (tr)
-                fprintf(stderr, "[rph_jpeg] chunk of %zu files in %zu lanes (%.1f MB of entropy bytes, %.2f GB of coefficients, %zu tables, %zu sub-batches): prepare %.1f ms, "
-                                "descriptors %.1f ms, upload %.1f ms, %u segments %.1f ms, zero %.1f ms, walk %.1f ms, reconstruct + hash %.1f ms\n",
-                        m, (size_t)n_items, file_bytes / 1e6, blocks * 128 / 1e9, luts.size(), subs.size(), t_prep - t0, t_desc - t_prep, t_up - t_desc, n_segs, t_seg - t_up, t_zero - t_seg, t_walk - t_zero, t_rec - t_walk);
-        }
-        RPH_HIP_CHECK(hipEventRecord(S.done, s));
-        RPH_JPEG_STAMP("lane %d: chunk %d enqueued", b, k);
-        pend[b].active = true;
-        pend[b].first = first;
-        pend[b].last = last;
-        first = last;
+        std::vector<HImage> himgs;
+        prepare_chunk(jobs, idx, C, threads, S, store, himgs);
+        t_host[1] = now_ms();
+        RPH_JPEG_STAMP("lane %d: chunk %d prepared (%zu files)", C.b, C.k, C.m());
+        const SeqWork W = list_sequential(ctx, jobs, idx, C, leftover);
+        ProgPlan G;
+        for (size_t i = C.first; i < C.last; i++)
+            if (jobs[idx[i]].status == RPH_OK && jobs[idx[i]].frame.progressive) G.add((uint32_t)(i - C.first), jobs[idx[i]], himgs[i - C.first]);
+        RPH_JPEG_STAMP("lane %d: chunk %d items listed", C.b, C.k);
+        const std::vector<uint32_t> pitems = order_waves(G, himgs);
+        RPH_JPEG_STAMP("lane %d: chunk %d waves ordered", C.b, C.k);
+        ChunkMeta M;
+        RPH_TRY(write_meta(P, jobs, idx, C, flavour, out.rgb_wanted(), store, himgs, W, G, pitems, M));
+        RPH_JPEG_STAMP("lane %d: chunk %d descriptors written", C.b, C.k);
+        t_host[2] = now_ms();
+        int16_t *d_coef = P.coef.as<int16_t>() + (size_t)C.b * (plan.region / 2);  // (int16 elements: region bytes per lane)
+        RPH_TRY(launch_chunk(ctx, P, C, d_coef, jobs, idx, flavour, out, W, G, pitems, M, t_host));
+        RPH_HIP_CHECK(hipEventRecord(S.done, S.stream));
+        RPH_JPEG_STAMP("lane %d: chunk %d enqueued", C.b, C.k);
+        lane[C.b] = InFlight{true, C.first, C.last};
     }
-    for (int t = 0; t < lanes; t++) RPH_TRY(finish((k + t) % lanes));  // oldest first
+    for (int t = 0; t < plan.lanes; t++) {  // oldest first
+        const int b = (k + t) % plan.lanes;
+        RPH_TRY(lane[b].finish(b, P.slot[b], true, jobs, idx, out, &leftover));
+    }
     // files handed to the host decoder start over there
     for (uint32_t g : leftover) jobs[g].status = RPH_OK;
     return RPH_OK;
@@ -1105,11 +1121,7 @@ int run_batch(rph_ctx *ctx, const uint8_t *const *data, const size_t *len, uint3
 
     g_trace_t0 = now_ms();
     RPH_JPEG_STAMP("call: %u files", n);
-    if (!prepared && !P.jobs_cache) {
-        P.jobs_cache = new Jobs();
-        P.jobs_cache_free = [](void *p) { delete static_cast<Jobs *>(p); };
-    }
-    Jobs &jobs = prepared ? *prepared : *static_cast<Jobs *>(P.jobs_cache);
+    Jobs &jobs = prepared ? *prepared : P.jobs_cache;
     if (!prepared && jobs.size() < n) jobs.resize(n);  // (grown by this thread: first-touching the storage from the parsing threads is 5x slower, page faults under contention)
     if (!prepared)
         parallel_for(0, n, n >= 1024 ? threads : 1, [&](size_t i) {
@@ -1239,12 +1251,7 @@ int rph_jpeg_coefficients(const uint8_t *data, size_t len, uint32_t *geometry, u
             uint32_t *g = geometry + 8 * c;
             g[0] = k.blocks_w, g[1] = k.blocks_h, g[2] = k.H, g[3] = k.V, g[4] = k.tq, g[5] = k.samp_w, g[6] = k.samp_h, g[7] = (uint32_t)k.first_block;
         }
-        for (int t = 0; t < 4; t++) {
-            if (f.qt_present[t])
-                memcpy(qt + 64 * t, f.qt[t], 128);
-            else
-                memset(qt + 64 * t, 0, 128);
-        }
+        for (int t = 0; t < 4; t++) f.qt_present[t] ? (void)memcpy(qt + 64 * t, f.qt[t], 128) : (void)memset(qt + 64 * t, 0, 128);
         return RPH_OK;
     });
 }

@@ -60,13 +60,13 @@ int run_chunk(rph_ctx *ctx, PngPipe &P, const uint8_t *const *data, std::vector<
         comp_bytes += parsed[idx[k]].idat_bytes;
     }
     if (mode == RPH_PNG_INFLATE_AUTO) mode = raw_bytes >= AUTO_DEVICE_MIN_RATIO * comp_bytes ? RPH_PNG_INFLATE_DEVICE : RPH_PNG_INFLATE_HOST;
-    // metadata: images, palettes, streams, unfilter jobs, list
+    // metadata: images, palettes, streams, unfilter jobs, list, BLAKE3 offsets (each section 256-byte aligned)
     size_t n_jobs = 0;
     for (size_t k = 0; k < m; k++)
         for (int p = 0; p < 7; p++) n_jobs += parsed[idx[k]].im.pass_h[p] ? 1 : 0;
-    const size_t off_img = 0, off_pal = align_up(m * sizeof(rphp::Image), 256), off_str = off_pal + m * 1024,
-                 off_job = align_up(off_str + m * sizeof(rphp::StreamDesc), 256), off_list = align_up(off_job + n_jobs * sizeof(rphp::UnfilterJob), 256),
-                 off_b3 = align_up(off_list + m * 4, 256), meta_bytes = off_b3 + (m + 1) * 8;
+    Layout L;
+    const size_t off_img = L.add(m * sizeof(rphp::Image)), off_pal = L.add(m * 1024, 256), off_str = L.add(m * sizeof(rphp::StreamDesc), 256),
+                 off_job = L.add(n_jobs * sizeof(rphp::UnfilterJob), 256), off_list = L.add(m * 4, 256), off_b3 = L.add((m + 1) * 8, 256), meta_bytes = L.end();
     RPH_TRY(reserve(P.meta, meta_bytes));
     RPH_TRY(reserve(P.h_meta, meta_bytes));
     RPH_TRY(reserve(P.raw, raw_bytes));
@@ -167,25 +167,19 @@ int run_chunk(rph_ctx *ctx, PngPipe &P, const uint8_t *const *data, std::vector<
     RPH_TRY(rph_png_launch_expand(P.raw.data(), P.meta.data() + off_img, (const uint32_t *)(P.meta.data() + off_list), (uint32_t)g, max_px, P.meta.data() + off_pal,
                                   want_hp ? P.hp.data() : nullptr, x16_bytes ? P.x16.data() : nullptr, nat_bytes ? P.nat.data() : nullptr, s));
     // result sections, each 256-byte aligned
-    const size_t o_q = align_up(g * 32, 256), o_c = o_q + align_up(g * 4, 256), o_d = o_c + g * 1024, o_v = o_d + g * 256, o_px = o_v + align_up(g, 256);
-    uint8_t *R = P.res.data();
-    uint8_t *r_hash = R, *r_q = R + o_q, *r_c = R + o_c, *r_d = R + o_d, *r_v = R + o_v, *r_px = R + o_px;
-    size_t k16 = 0;
+    Layout RL;
+    const size_t o_hash = RL.add(g * 32), o_q = RL.add(g * 4, 256), o_c = RL.add(g * 1024, 256), o_d = RL.add(g * 256, 256), o_v = RL.add(g, 256), o_px = RL.add(g * 32, 256);
+    uint8_t *R = P.res.data(), *r_hash = R + o_hash, *r_q = R + o_q, *r_c = R + o_c, *r_d = R + o_d, *r_v = R + o_v, *r_px = R + o_px;
     for (size_t q = 0; q < g;) {
         const rphp::Image &a = imgs[good[q]];
         size_t e = q + 1;
         while (e < g && imgs[good[e]].w == a.w && imgs[good[e]].h == a.h && imgs[good[e]].hc == a.hc && imgs[good[e]].out_depth == a.out_depth) e++;
         const uint32_t cnt = (uint32_t)(e - q);
         const size_t istride = align_up((uint64_t)a.hstride * a.h, 64);
-        // pixel hashes first: the reference hashes to_rgba16() before generate_pdq_features (scanner.rs:1393-1410)
-        if (out.pixel) {
-            if (a.out_depth == 16) {
-                // a run of 16-bit images is consecutive in the RGBA16 buffer: hashed below, all 16-bit images of the chunk at once
-                k16 += cnt;
-            } else {
-                RPH_TRY(rph_launch_pixel_hash(P.hp.data() + a.hp_off, cnt, a.w, a.h, a.hc, a.hstride, istride, r_px + q * 32, s, b3_scratch ? P.b3.data() : nullptr));
-            }
-        }
+        // pixel hashes first: the reference hashes to_rgba16() before generate_pdq_features (scanner.rs:1393-1410).  (A run of 16-bit
+        // images is consecutive in the RGBA16 buffer: hashed below, all 16-bit images of the chunk at once.)
+        if (out.pixel && a.out_depth != 16)
+            RPH_TRY(rph_launch_pixel_hash(P.hp.data() + a.hp_off, cnt, a.w, a.h, a.hc, a.hstride, istride, r_px + q * 32, s, b3_scratch ? P.b3.data() : nullptr));
         if (out.want_pdq)
             RPH_TRY(rph_pdq_hash_batch_dev(ctx, P.hp.data() + a.hp_off, cnt, a.w, a.h, a.hc, a.hstride, istride, r_hash + q * 32, out.quality ? r_q + q * 4 : nullptr,
                                            out.coeffs ? r_c + q * 1024 : nullptr, out.dihedral ? r_d + q * 256 : nullptr, r_v + q, s));
@@ -195,12 +189,10 @@ int run_chunk(rph_ctx *ctx, PngPipe &P, const uint8_t *const *data, std::vector<
     std::vector<uint8_t> dig16(n16 * 32);
     if (n16) RPH_TRY(rph_blake3_batch_dev(ctx, P.x16.data(), P.meta.data() + off_b3, (uint32_t)n16, nullptr, P.dig.data(), s));
     if (n16) RPH_HIP_CHECK(hipMemcpyAsync(dig16.data(), P.dig.data(), n16 * 32, hipMemcpyDeviceToHost, s));
-    (void)k16;
     RPH_HIP_CHECK(hipMemcpyAsync(P.h_res.data(), R, res_bytes, hipMemcpyDeviceToHost, s));
     if (out.native) RPH_HIP_CHECK(hipMemcpyAsync(out.native, P.nat.data(), nat_bytes, hipMemcpyDeviceToHost, s));
     RPH_HIP_CHECK(hipStreamSynchronize(s));
-    const uint8_t *H = P.h_res.data();
-    const uint8_t *h_hash = H, *h_q = H + o_q, *h_c = H + o_c, *h_d = H + o_d, *h_v = H + o_v, *h_px = H + o_px;
+    const uint8_t *H = P.h_res.data(), *h_hash = H + o_hash, *h_q = H + o_q, *h_c = H + o_c, *h_d = H + o_d, *h_v = H + o_v, *h_px = H + o_px;
     size_t i16 = 0;
     for (size_t q = 0; q < g; q++) {
         const uint32_t f = idx[good[q]];

@@ -30,6 +30,22 @@ void rph_set_error(const char *fmt, ...);
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// Sections of one buffer, one behind the other: add(bytes, align) places the next section at the first multiple of `align` behind the
+// last one and returns its offset; end() is where the last section ends
+class Layout {
+  public:
+    size_t add(size_t bytes, size_t align = 1)
+    {
+        const size_t off = align_up(end_, align);
+        end_ = off + bytes;
+        return off;
+    }
+    size_t end() const { return end_; }
+
+  private:
+    size_t end_ = 0;
+};
+
 // reserve() argument: the caller has already synchronised every stream whose work uses the buffer
 struct Synced {};
 constexpr Synced synced{};
