@@ -493,6 +493,82 @@ int rph_png_set_inflate(rph_ctx *ctx, int where);
 int rph_png_release(rph_ctx *ctx);
 
 /* =====================================================================
+ * TIFF decode feeding the hasher: the "tiff" arm of load_image_fast (scanner.rs:628-708: image 0.25's TiffDecoder over tiff 0.11 + weezl)
+ * followed by the pixel hash and generate_pdq_features.  The host parses the first IFD into a table of segments (strips or tiles), which
+ * are compressed independently: the device decompresses one segment per wave, then one expand kernel undoes the predictor, the byte
+ * order and the tiling and writes the hasher's pixels, which are hashed where they lie; only hashes come back.
+ * What is decoded (first IFD only; Orientation is ignored: the reference reads it apart from hashing, scanner.rs:130):
+ *   container    classic TIFF, II and MM; further IFDs and unknown tags ignored.  BigTIFF (version 43): RPH_ERR_UNSUPPORTED.
+ *   layout       strips (RowsPerStrip absent or above the height = one strip; a short last strip) and tiles (edge tiles decoded whole,
+ *                cropped).  PlanarConfiguration 2 (with more than one sample) and FillOrder 2: RPH_ERR_UNSUPPORTED.
+ *   Compression  1 none, 5 LZW (codes most significant bit first, "early change", Clear 256, EOI 257), 8 and 32946 zlib / Deflate,
+ *                32773 PackBits.  Every other (JPEG 6 / 7, CCITT 2-4, old-style LSB-first LZW, ...): RPH_ERR_UNSUPPORTED.
+ *   Photometric  0 WhiteIsZero (every sample inverted, an alpha sample included: UNPINNED), 1 BlackIsZero, 2 RGB; absent = 1 for one or
+ *                two samples, 2 for more.  3 palette, 5 CMYK, 6 YCbCr, others: RPH_ERR_UNSUPPORTED.
+ *   samples      gray at 1 / 2 / 4 / 8 / 16 bit; gray + alpha, RGB, RGBA at 8 / 16 bit; SampleFormat 1; the 4th (2nd for gray) sample is
+ *                alpha whatever ExtraSamples says.  Unequal BitsPerSample, more samples, other SampleFormat: RPH_ERR_UNSUPPORTED.
+ *   Predictor    1; 2 (horizontal differencing per sample, modulo 2^8 or 2^16, 16-bit words byte-swapped before accumulating) with
+ *                Compression 5 / 8 / 32946.  3 (floating point), 2 on sub-8-bit samples, 2 with Compression 1 or 32773 (decoders
+ *                disagree whether the tag applies there: libtiff implements the predictor only inside its LZW / Deflate codecs):
+ *                RPH_ERR_UNSUPPORTED.
+ * A file answered with RPH_ERR_UNSUPPORTED goes to the caller's own decoders, as a CMYK JPEG does (JPEG-in-TIFF, the reference's second
+ * tier at scanner.rs:658-702, among them).
+ * Native pixels (rph_tiff_decode, rph_tiff_decode_host) and what is hashed follow the PNG section word for word: Luma8 / LumaA8 / Rgb8 /
+ * Rgba8 / L16 / La16 / Rgb16 / Rgba16, sub-8-bit gray scaled by 255 / (2^d - 1); PDQ through to_luma601 (LumaA8 as (l, l, l, a), 16-bit
+ * through round(v / 257)); pixel hash = blake3 of to_rgba16() little-endian.  An 8-bit TIFF of the pixels of a PNG or of a decoded JPEG
+ * therefore has that file's PDQ hash and pixel hash.  The reference's Rgb8 fast path (scanner.rs:639-647) and its from_decoder path
+ * yield the same pixels: one path here.  Parity with the tiff / image crates is UNPINNED (their sources are not in the reference tree);
+ * for a lossless format the pixels are fixed by the TIFF 6.0 text and pinned in the tests against libtiff (Pillow).
+ * ONE RULE for damaged or hostile files, the same in the host parser and decompressors (tiff_host.cpp), the shared decoders (tiff_lzw.h,
+ * inflate.h: host threads and device kernels alike): a file's status does not depend on the other files of its call or on where it was
+ * decompressed.
+ *   REFUSED (RPH_ERR_INVALID_ARG)
+ *     - a bad byte-order mark or version; an IFD offset, entry count, or the value array of a tag that is read, reaching outside the
+ *       file; a strip or tile whose offset + byte count reaches outside the file;
+ *     - a required tag missing (ImageWidth, ImageLength, Strip / TileOffsets, TileWidth and TileLength for tiles; the byte counts
+ *       unless Compression is 1, where they are computed); a tag that is read with a type other than SHORT / LONG or a wrong count
+ *       (BitsPerSample count != SamplesPerPixel, a scalar with count != 1); zero width, height, RowsPerStrip, tile size or
+ *       SamplesPerPixel; a strip or tile count that does not match the geometry;
+ *     - LZW: the first code of a segment or after a Clear is 256 or above (a Clear as the very first code is the usual start); a code
+ *       above the next free entry; a stream that runs out of bits, or sends EOI, before the segment's bytes are produced; a table that
+ *       would grow past 4096 entries (a conforming writer sends Clear at 4094; libtiff refuses such a stream too, weezl is believed
+ *       to go on: UNPINNED);
+ *     - PackBits: a run or literal cut off by the end of the input before the segment's bytes are produced;
+ *     - Deflate: everything the PNG section lists for zlib, and a stream that ends before the segment's last byte.
+ *   ACCEPTED
+ *     - LZW and PackBits stop when the segment is full: trailing bits, a missing EOI, further runs are not examined;
+ *     - Deflate output past the segment's bytes is decoded and checked, not stored (the PNG rule); bytes after the Adler-32;
+ *     - a tag that comes twice (the last one counts); tags out of order.
+ *   RPH_ERR_UNSUPPORTED, before any pixel memory is allocated: the layouts named above; more than 2^28 pixels or 1 GiB of decoded bytes
+ *     (the PNG bounds); a strip or tile whose decoded bytes exceed the most its compressed bytes can expand to: 1032:1 Deflate, 128:2
+ *     PackBits, 1:1 uncompressed (a short uncompressed strip therefore lands here), 3839 bytes per 9 bits LZW (tiff_lzw.h).
+ *   Where both apply, the order is: header, IFD and tag checks; width / height present and non-zero, SamplesPerPixel, BitsPerSample
+ *   count; the UNSUPPORTED layouts; tile / strip tags; the size limits; segment counts; offsets inside the file; the expansion bounds.
+ *   VALID BUT SMALL: an image below 5 px gets valid = 0 with status RPH_OK, and still its pixel hash.
+ * ===================================================================== */
+#define RPH_TIFF_DECOMPRESS_HOST 0   /* n_threads host threads decompress (tiff_lzw.h, inflate.h); the decoded bytes cross PCIe */
+#define RPH_TIFF_DECOMPRESS_DEVICE 1 /* one wave per strip or tile on the device; the compressed bytes cross PCIe */
+#define RPH_TIFF_DECOMPRESS_AUTO 2   /* default: the device for chunks that expand 16:1 or more, else the host */
+/* Header only, host code, no context: the native layout rph_tiff_decode will produce (channels 1-4, bit_depth 8 or 16); returns the
+ * file's status by the rule above (the strips and tiles themselves are not decompressed). */
+int rph_tiff_info(const uint8_t *data, size_t len, uint32_t *w, uint32_t *h, uint32_t *channels, uint32_t *bit_depth);
+/* The whole decoder on the CPU, no context (tests, tools): native pixels, packed rows, w * h * channels samples of bit_depth bits into
+ * pixels_out (cap_bytes; RPH_ERR_CAPACITY if too small). */
+int rph_tiff_decode_host(const uint8_t *data, size_t len, void *pixels_out, size_t cap_bytes);
+/* load_image_fast for one TIFF, decoded on the device: the same native pixels as rph_tiff_decode_host. */
+int rph_tiff_decode(rph_ctx *ctx, const uint8_t *data, size_t len, void *pixels_out, size_t cap_bytes);
+/* n TIFF files -> n PDQ hashes (+ optional quality, 256 coefficients, 8 dihedral hashes, as rph_pdq_hash_batch) and optional pixel
+ * hashes (32 bytes each); the arguments mean what they mean in rph_png_pdq_hash_batch.  status_out[i] by the rule above (the call itself
+ * returns RPH_OK); a file that cannot be decoded has zero outputs and valid 0. */
+int rph_tiff_pdq_hash_batch(rph_ctx *ctx, const uint8_t *const *data, const size_t *len, uint32_t n, uint32_t n_threads, uint8_t *hash32_out,
+                            float *quality_out, float *coeffs_out, uint8_t *dihedral_out, uint8_t *valid_out, int32_t *status_out,
+                            uint8_t *pixel_hash32_out);
+/* Where rph_tiff_pdq_hash_batch decompresses (RPH_TIFF_DECOMPRESS_*); the results are identical in every mode. */
+int rph_tiff_set_decompress(rph_ctx *ctx, int where);
+/* The TIFF path keeps its staging and device buffers in the context between calls; this returns them. */
+int rph_tiff_release(rph_ctx *ctx);
+
+/* =====================================================================
  * BLAKE3 identity hashes (blake3 crate 1.x, 32-byte output): the two exact hashes the reference computes next to the PDQ hash.
  *   content hash  blake3::keyed_hash(content_key, file_bytes)                     scanner.rs:1343-1347 (the cache key)
  *                 -> rph_blake3_host per file in the scan loop, or rph_blake3_batch(_dev) for a batch of files

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "inflate.h"
+#include "pixel_rules.h"
 
 namespace rphp {
 
@@ -149,38 +150,9 @@ RPHZ_HD void pixel(const Image &im, const uint8_t *raw, const uint8_t *pal, uint
     v[3] = c3;
 }
 
-// The 8-bit pixels the hasher takes (hc channels): Luma8 as it is; LumaA8 as Rgba8 (l, l, l, a); Rgb8 / Rgba8 as they are; 16-bit
-// images as to_rgb8 gives them, each sample v -> round(v / 257) = (v + 128) / 257 (no ties: 257 is odd) -- UNPINNED against the crate
-RPHZ_HD void hasher_pixel(const Image &im, const uint32_t v[4], uint8_t o[4])
-{
-    if (im.out_depth == 16) {
-        const uint32_t g = (v[0] + 128) / 257;
-        if (im.out_ch <= 2) {
-            o[0] = o[1] = o[2] = (uint8_t)g;
-        } else {
-            o[0] = (uint8_t)g;
-            o[1] = (uint8_t)((v[1] + 128) / 257);
-            o[2] = (uint8_t)((v[2] + 128) / 257);
-        }
-        return;
-    }
-    switch (im.out_ch) {
-    case 1: o[0] = (uint8_t)v[0]; break;
-    case 2: o[0] = o[1] = o[2] = (uint8_t)v[0]; o[3] = (uint8_t)v[1]; break;
-    default: o[0] = (uint8_t)v[0]; o[1] = (uint8_t)v[1]; o[2] = (uint8_t)v[2]; o[3] = (uint8_t)v[3]; break;
-    }
-}
-
-// to_rgba16 of a 16-bit pixel (gray replicated, missing alpha 65535)
-RPHZ_HD void rgba16_pixel(const Image &im, const uint32_t v[4], uint16_t o[4])
-{
-    switch (im.out_ch) {
-    case 1: o[0] = o[1] = o[2] = (uint16_t)v[0]; o[3] = 65535; break;
-    case 2: o[0] = o[1] = o[2] = (uint16_t)v[0]; o[3] = (uint16_t)v[1]; break;
-    case 3: o[0] = (uint16_t)v[0]; o[1] = (uint16_t)v[1]; o[2] = (uint16_t)v[2]; o[3] = 65535; break;
-    default: o[0] = (uint16_t)v[0]; o[1] = (uint16_t)v[1]; o[2] = (uint16_t)v[2]; o[3] = (uint16_t)v[3]; break;
-    }
-}
+// The 8-bit pixels the hasher takes (hc channels) and to_rgba16 of a 16-bit pixel: pixel_rules.h, shared with the TIFF path
+RPHZ_HD void hasher_pixel(const Image &im, const uint32_t v[4], uint8_t o[4]) { rphx::hasher_pixel(im.out_ch, im.out_depth, v, o); }
+RPHZ_HD void rgba16_pixel(const Image &im, const uint32_t v[4], uint16_t o[4]) { rphx::rgba16_pixel(im.out_ch, v, o); }
 
 RPHZ_HD uint8_t paeth(int a, int b, int c)
 {

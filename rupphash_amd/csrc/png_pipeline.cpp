@@ -10,10 +10,10 @@
 #include <algorithm>
 #include <vector>
 
+#include "decoded_hash.h"
 #include "png_host.h"
 #include "rph_internal.h"
 
-int rph_png_launch_inflate(const uint8_t *d_comp, const void *d_streams, uint32_t n, uint8_t *d_raw, int32_t *d_status, hipStream_t s);
 int rph_png_launch_unfilter(uint8_t *d_raw, const void *d_jobs, uint32_t n_jobs, int32_t *d_status, hipStream_t s);
 int rph_png_launch_expand(const uint8_t *d_raw, const void *d_images, const uint32_t *d_list, uint32_t n, uint64_t max_pixels, const uint8_t *d_pal,
                           uint8_t *d_hp, uint8_t *d_x16, uint8_t *d_nat, hipStream_t s);
@@ -22,32 +22,25 @@ namespace {
 
 struct PngPipe {
     hipStream_t s = nullptr;  // (rph_png_forget: synchronised before the buffers are freed)
-    DevBuf comp, raw, hp, x16, nat, meta, res, b3, status, dig;
-    PinnedBuf h_comp, h_raw, h_meta, h_res, h_status;
+    DevBuf comp, raw, meta, status;
+    PinnedBuf h_comp, h_raw, h_meta, h_status;
+    HashStageBufs hash;
 };
 
-// Per chunk at most this much (one image larger than a limit forms a chunk of its own)
-constexpr size_t CHUNK_FILES = 8192;
-constexpr uint64_t CHUNK_COMP = (uint64_t)256 << 20, CHUNK_RAW = (uint64_t)768 << 20, CHUNK_PIXELS = (uint64_t)192 << 20;
 // AUTO: the device inflates a chunk whose raw bytes are at least this many times its compressed bytes, the host threads inflate the rest.
 // One wave walks a stream at a rate set by its symbols, so the device pays where a symbol yields many bytes (long copies: screenshots,
 // 1920x1080 RGBA at ~400:1, 4.9 vs 3.8 GB/s of pixels for the host threads) and loses where nearly every byte is a literal (photographic
 // RGB at ~1.5:1: 1.5 vs 3.2 GB/s; palette images at ~9:1: 1.5 vs 1.7 GB/s); DESIGN.md 4.7, profiles/png_rate.txt
 constexpr uint64_t AUTO_DEVICE_MIN_RATIO = 32;
 
-struct Outputs {
-    uint8_t *hash = nullptr, *dihedral = nullptr, *valid = nullptr, *pixel = nullptr, *native = nullptr;
-    float *quality = nullptr, *coeffs = nullptr;
-    int32_t *status = nullptr;
-    bool want_pdq = true;
-};
+using Outputs = FileOutputs;
 
 // one chunk: files[idx[k]] for k in [0, m), all parsed RPH_OK
 int run_chunk(rph_ctx *ctx, PngPipe &P, const uint8_t *const *data, std::vector<rphp::Parsed> &parsed, const uint32_t *idx, size_t m, unsigned threads,
               const Outputs &out)
 {
     hipStream_t s = P.s;
-    auto reserve = [s](auto &buf, size_t bytes) { return buf.reserve(bytes, align_up(bytes + bytes / 4 + 64, 4096), s); };  // +25 % + 64, whole pages
+    auto reserve = [s](auto &buf, size_t bytes) { return reserve_slack(buf, bytes, s); };
     int mode = ctx->png_inflate;
     // raw / compressed placement
     uint64_t raw_bytes = 0, comp_bytes = 0;
@@ -110,107 +103,13 @@ int run_chunk(rph_ctx *ctx, PngPipe &P, const uint8_t *const *data, std::vector<
     RPH_TRY(rph_png_launch_unfilter(P.raw.data(), P.meta.data() + off_job, (uint32_t)n_jobs, (int32_t *)P.status.data(), s));
     RPH_HIP_CHECK(hipMemcpyAsync(st, P.status.data(), m * 4, hipMemcpyDeviceToHost, s));
     RPH_HIP_CHECK(hipStreamSynchronize(s));
-    // the decodable images in runs of equal geometry: (w, h, hasher channels, bit depth: 16-bit images take another pixel hash)
-    std::vector<uint32_t> good;
-    for (size_t k = 0; k < m; k++) {
-        out.status[idx[k]] = st[k];
-        if (st[k] == RPH_OK) good.push_back((uint32_t)k);
-    }
-    if (good.empty()) return RPH_OK;
-    std::stable_sort(good.begin(), good.end(), [&](uint32_t a, uint32_t b) {
-        const rphp::Image &x = imgs[a], &y = imgs[b];
-        return x.w != y.w ? x.w < y.w : x.h != y.h ? x.h < y.h : x.hc != y.hc ? x.hc < y.hc : x.out_depth < y.out_depth;
-    });
-    const size_t g = good.size();
-    const bool want_hp = out.want_pdq || out.pixel, want_x16 = out.pixel != nullptr;
-    uint64_t hp_bytes = 0, x16_bytes = 0, nat_bytes = 0, max_px = 0;
-    uint64_t *b3off = reinterpret_cast<uint64_t *>(P.h_meta.data() + off_b3);
-    size_t n16 = 0;
-    for (size_t q = 0; q < g; q++) {
-        rphp::Image &im = imgs[good[q]];
-        list[q] = good[q];
-        max_px = std::max<uint64_t>(max_px, (uint64_t)im.w * im.h);
-        if (want_hp) {
-            im.hstride = (uint32_t)(im.hc * align_up(im.w, 8));
-            im.hp_off = hp_bytes;
-            hp_bytes += align_up((uint64_t)im.hstride * im.h, 64);
-        }
-        if (want_x16 && im.out_depth == 16) {
-            im.x16_off = x16_bytes;
-            b3off[n16++] = x16_bytes;
-            x16_bytes += (uint64_t)im.w * im.h * 8;
-        }
-        if (out.native) {
-            im.nat_off = nat_bytes;
-            nat_bytes += align_up((uint64_t)im.w * im.h * im.out_ch * (im.out_depth / 8), 64);
-        }
-    }
-    b3off[n16] = x16_bytes;
-    // buffers of this stage
-    const size_t res_bytes = g * (32 + 4 + 1024 + 256 + 1 + 32) + 4 * 256;
-    RPH_TRY(reserve(P.hp, hp_bytes));
-    if (x16_bytes) RPH_TRY(reserve(P.x16, x16_bytes));
-    if (nat_bytes) RPH_TRY(reserve(P.nat, nat_bytes));
-    RPH_TRY(reserve(P.res, res_bytes));
-    RPH_TRY(reserve(P.h_res, res_bytes));
-    size_t b3_scratch = 0;
-    for (size_t q = 0; q < g;) {  // runs of equal geometry
-        const rphp::Image &a = imgs[good[q]];
-        size_t e = q + 1;
-        while (e < g && imgs[good[e]].w == a.w && imgs[good[e]].h == a.h && imgs[good[e]].hc == a.hc && imgs[good[e]].out_depth == a.out_depth) e++;
-        if (out.pixel && a.out_depth != 16) b3_scratch = std::max(b3_scratch, rph_pixel_hash_scratch_bytes((uint32_t)(e - q), a.w, a.h));
-        q = e;
-    }
-    if (b3_scratch) RPH_TRY(reserve(P.b3, b3_scratch));
-    if (n16) RPH_TRY(reserve(P.dig, n16 * 32));
-    RPH_HIP_CHECK(hipMemcpyAsync(P.meta.data(), P.h_meta.data(), meta_bytes, hipMemcpyHostToDevice, s));
-    RPH_TRY(rph_png_launch_expand(P.raw.data(), P.meta.data() + off_img, (const uint32_t *)(P.meta.data() + off_list), (uint32_t)g, max_px, P.meta.data() + off_pal,
-                                  want_hp ? P.hp.data() : nullptr, x16_bytes ? P.x16.data() : nullptr, nat_bytes ? P.nat.data() : nullptr, s));
-    // result sections, each 256-byte aligned
-    Layout RL;
-    const size_t o_hash = RL.add(g * 32), o_q = RL.add(g * 4, 256), o_c = RL.add(g * 1024, 256), o_d = RL.add(g * 256, 256), o_v = RL.add(g, 256), o_px = RL.add(g * 32, 256);
-    uint8_t *R = P.res.data(), *r_hash = R + o_hash, *r_q = R + o_q, *r_c = R + o_c, *r_d = R + o_d, *r_v = R + o_v, *r_px = R + o_px;
-    for (size_t q = 0; q < g;) {
-        const rphp::Image &a = imgs[good[q]];
-        size_t e = q + 1;
-        while (e < g && imgs[good[e]].w == a.w && imgs[good[e]].h == a.h && imgs[good[e]].hc == a.hc && imgs[good[e]].out_depth == a.out_depth) e++;
-        const uint32_t cnt = (uint32_t)(e - q);
-        const size_t istride = align_up((uint64_t)a.hstride * a.h, 64);
-        // pixel hashes first: the reference hashes to_rgba16() before generate_pdq_features (scanner.rs:1393-1410).  (A run of 16-bit
-        // images is consecutive in the RGBA16 buffer: hashed below, all 16-bit images of the chunk at once.)
-        if (out.pixel && a.out_depth != 16)
-            RPH_TRY(rph_launch_pixel_hash(P.hp.data() + a.hp_off, cnt, a.w, a.h, a.hc, a.hstride, istride, r_px + q * 32, s, b3_scratch ? P.b3.data() : nullptr));
-        if (out.want_pdq)
-            RPH_TRY(rph_pdq_hash_batch_dev(ctx, P.hp.data() + a.hp_off, cnt, a.w, a.h, a.hc, a.hstride, istride, r_hash + q * 32, out.quality ? r_q + q * 4 : nullptr,
-                                           out.coeffs ? r_c + q * 1024 : nullptr, out.dihedral ? r_d + q * 256 : nullptr, r_v + q, s));
-        q = e;
-    }
-    // 16-bit pixel hashes: BLAKE3 of the RGBA16 strings, digests into the result slots of those images (in the same order)
-    std::vector<uint8_t> dig16(n16 * 32);
-    if (n16) RPH_TRY(rph_blake3_batch_dev(ctx, P.x16.data(), P.meta.data() + off_b3, (uint32_t)n16, nullptr, P.dig.data(), s));
-    if (n16) RPH_HIP_CHECK(hipMemcpyAsync(dig16.data(), P.dig.data(), n16 * 32, hipMemcpyDeviceToHost, s));
-    RPH_HIP_CHECK(hipMemcpyAsync(P.h_res.data(), R, res_bytes, hipMemcpyDeviceToHost, s));
-    if (out.native) RPH_HIP_CHECK(hipMemcpyAsync(out.native, P.nat.data(), nat_bytes, hipMemcpyDeviceToHost, s));
-    RPH_HIP_CHECK(hipStreamSynchronize(s));
-    const uint8_t *H = P.h_res.data(), *h_hash = H + o_hash, *h_q = H + o_q, *h_c = H + o_c, *h_d = H + o_d, *h_v = H + o_v, *h_px = H + o_px;
-    size_t i16 = 0;
-    for (size_t q = 0; q < g; q++) {
-        const uint32_t f = idx[good[q]];
-        if (out.want_pdq) {
-            memcpy(out.hash + (size_t)f * 32, h_hash + q * 32, 32);
-            if (out.quality) memcpy(out.quality + f, h_q + q * 4, 4);
-            if (out.coeffs) memcpy(out.coeffs + (size_t)f * 256, h_c + q * 1024, 1024);
-            if (out.dihedral) memcpy(out.dihedral + (size_t)f * 256, h_d + q * 256, 256);
-            if (out.valid) out.valid[f] = h_v[q];
-        }
-        if (out.pixel) {
-            if (imgs[good[q]].out_depth == 16)
-                memcpy(out.pixel + (size_t)f * 32, dig16.data() + 32 * i16++, 32);
-            else
-                memcpy(out.pixel + (size_t)f * 32, h_px + q * 32, 32);
-        }
-    }
-    return RPH_OK;
+    return hash_decoded_images(ctx, s, P.hash, imgs, list, reinterpret_cast<uint64_t *>(P.h_meta.data() + off_b3), P.meta.data() + off_b3, st, idx, m, out,
+                               [&](uint32_t g, uint64_t max_px, bool want_hp, uint64_t x16_bytes, uint64_t nat_bytes) -> int {
+                                   RPH_HIP_CHECK(hipMemcpyAsync(P.meta.data(), P.h_meta.data(), meta_bytes, hipMemcpyHostToDevice, s));
+                                   return rph_png_launch_expand(P.raw.data(), P.meta.data() + off_img, (const uint32_t *)(P.meta.data() + off_list), g, max_px,
+                                                                P.meta.data() + off_pal, want_hp ? P.hash.hp.data() : nullptr, x16_bytes ? P.hash.x16.data() : nullptr,
+                                                                nat_bytes ? P.hash.nat.data() : nullptr, s);
+                               });
 }
 
 int run(rph_ctx *ctx, const uint8_t *const *data, const size_t *len, uint32_t n, unsigned threads, const Outputs &out)

@@ -58,6 +58,10 @@ struct rph_ctx {
     std::mutex png_mu;
     void *png = nullptr;
     int png_inflate = RPH_PNG_INFLATE_AUTO;
+    // TIFF path (tiff_pipeline.cpp): the same arrangement; where the strips and tiles are decompressed (RPH_TIFF_DECOMPRESS_*)
+    std::mutex tiff_mu;
+    void *tiff = nullptr;
+    int tiff_decompress = RPH_TIFF_DECOMPRESS_AUTO;
 };
 
 // ---- launchers implemented in the .hip files (all asynchronous on `stream`) ----
@@ -105,6 +109,10 @@ size_t rph_pixel_hash_scratch_bytes(uint32_t n, uint32_t w, uint32_t h);
 int rph_launch_pixel_hash(const uint8_t *d_px, uint32_t n, uint32_t w, uint32_t h, uint32_t channels, size_t row_stride, size_t image_stride,
                           uint8_t *d_hash32, hipStream_t stream, void *d_scratch);
 
+// png_kernels.hip: one wave per zlib stream (rphp::StreamDesc: compressed bytes, destination, the image whose status a refused stream
+// sets); the TIFF path runs its Deflate strips and tiles through it too
+int rph_png_launch_inflate(const uint8_t *d_comp, const void *d_streams, uint32_t n, uint8_t *d_raw, int32_t *d_status, hipStream_t s);
+
 int rph_launch_read_stream(const void *d_buf, size_t bytes, uint32_t *d_sink, hipStream_t stream);
 
 // Runs an entry point's body; no C++ exception crosses the C ABI ("nothing aborts", include/rupphash.h)
@@ -138,6 +146,8 @@ void rph_resize_forget(rph_ctx *ctx);
 void rph_jpeg_forget(rph_ctx *ctx);
 // png_pipeline.cpp
 void rph_png_forget(rph_ctx *ctx);
+// tiff_pipeline.cpp
+void rph_tiff_forget(rph_ctx *ctx);
 void rph_jpeg_forget_threads(rph_ctx *ctx);
 
 // host_grouping.cpp

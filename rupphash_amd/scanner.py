@@ -5,6 +5,7 @@
     group_max_dist                                 scanner.rs:2214-2241 (the per-group max_dist of process_raw_groups)
     load_image_fast ("jpg" | "jpeg" arm)           scanner.rs:461-508
     load_png (the "png" arm, image + png crates)    scanner.rs:461-736 (load_image_fast's generic path for .png)
+    load_tiff (the TiffDecoder arm)                scanner.rs:628-708
     pixel_hash (--pixel-hash)                      scanner.rs:1393-1404
     identical_duplicates                           scanner.rs:1843-1864 (analyze_group steps 1-3)
 File-name logic after the union-find (merge_groups_by_stem, the sorting inside process_raw_groups) stays with the caller.
@@ -41,6 +42,19 @@ def load_png(path, data, engine=None):
     if ext != "png":
         raise ValueError(f"load_png: '{ext}' is not a PNG file name")
     return (engine or default_engine()).png_decode(data)
+
+
+def load_tiff(path, data, engine=None):
+    """The tiff arm of load_image_fast (scanner.rs:628-708): decoded on the device and returned in the native layout of the header's TIFF
+    section -- (h, w) Luma8 / L16, (h, w, 2) LumaA, (h, w, 3) Rgb, (h, w, 4) Rgba; uint8, or uint16 for 16-bit files.  A file the rule
+    refuses raises RphError; status RPH_ERR_UNSUPPORTED (JPEG-in-TIFF, CCITT, palette, ...) means the caller's own decoders take the
+    file.  Extensions other than tif / tiff raise ValueError."""
+    import os
+
+    ext = os.path.splitext(str(path))[1].lstrip(".").lower()
+    if ext not in ("tif", "tiff"):
+        raise ValueError(f"load_tiff: '{ext}' is not a TIFF file name")
+    return (engine or default_engine()).tiff_decode(data)
 
 
 def pixel_hash(image, engine=None):
