@@ -569,6 +569,82 @@ int rph_tiff_set_decompress(rph_ctx *ctx, int where);
 int rph_tiff_release(rph_ctx *ctx);
 
 /* =====================================================================
+ * Lossless WebP decode feeding the hasher: the last arm of load_image_fast, where the image crate guesses the format from the bytes
+ * (scanner.rs:713-734; WebP is the first format it names), followed by the pixel hash and generate_pdq_features.  The host parses the
+ * RIFF container and reads the small serial front of the VP8L stream (transforms with their sub-images, colour table, entropy image,
+ * the prefix codes of every group); the main ARGB stream is decoded by one wave per file on the device (or by the host threads), the
+ * inverse transforms and the expansion to pixels run on the device, the pixels are hashed where they lie; only hashes come back.
+ * What is decoded:
+ *   container    RIFF/WEBP whose image is one VP8L chunk (the simple form), or a VP8X extended container holding a VP8L chunk; ICCP,
+ *                EXIF, XMP and unknown chunks are skipped.
+ *   VP8L         all four transforms in any order the format allows (predictor modes 0-13, and 14 / 15 predicting as mode 0 as libwebp
+ *                does; cross-colour; subtract-green; colour indexing with 1 / 2 / 4 / 8-bit bundling), a colour cache of 1-11 bits, the
+ *                entropy image with any number of groups, simple and normal prefix codes, the 120 short distance codes.
+ * What is not decoded, RPH_ERR_UNSUPPORTED before any pixel memory is allocated: a lossy `VP8 ` chunk (with or without ALPH; a different
+ * codec whose chroma upsampling differs between decoders), animation (the VP8X animation flag, ANIM / ANMF), more than 2^28 pixels (the
+ * PNG bound; 14-bit sizes cannot exceed it), and a stream whose used prefix-code groups need more than 64 MiB of lookup tables (checked
+ * when the entropy image is known, before the codes are read).  Such a file goes to the caller's own decoders, as a CMYK JPEG does.
+ * Native pixels (rph_webp_decode, rph_webp_decode_host): Rgb8 when the image has no alpha, Rgba8 when it has; bit_depth is always 8.
+ * "Has alpha" is the VP8L header's alpha_is_used bit in both container forms: libwebp's VP8LGetInfo has the last word over the VP8X
+ * alpha flag, and Pillow opens the file as RGBA or RGB by it (pinned in the tests on all four combinations).  An image whose bit is 0
+ * loses whatever alpha its pixels carry.
+ * What is hashed follows the PNG section word for word: PDQ through to_luma601 (alpha ignored), pixel hash = blake3 of to_rgba16()
+ * (v -> v * 257, a missing alpha 65535).  A lossless WebP of the pixels of a PNG, a TIFF or a decoded JPEG therefore has that file's PDQ
+ * hash and pixel hash.  Parity with the image-webp crate is UNPINNED (its source is not in the reference tree); for a lossless format
+ * the pixels are fixed by the format text and pinned in the tests against libwebp (Pillow) in both directions.
+ * ONE RULE for damaged or hostile files, the same in the host parser and front (webp_host.cpp) and the shared entropy decoder (vp8l.h:
+ * host threads and device kernel alike): a file's status does not depend on the other files of its call or on the entropy mode.  The
+ * choices below were checked against libwebp only: UNPINNED against the crate.
+ *   REFUSED (RPH_ERR_INVALID_ARG)
+ *     - a bad RIFF or WEBP tag; a RIFF size that reaches past the end of the file (libwebp waits for more data) or is below 4;
+ *     - a chunk (header or payload) that reaches past the RIFF size before the image chunk is found; no image chunk; a VP8X chunk of
+ *       fewer than 10 bytes; a VP8X canvas size that differs from the VP8L image size;
+ *     - a VP8L chunk of fewer than 5 bytes, a signature byte other than 0x2f, a non-zero version;
+ *     - a transform that comes twice; a colour-cache size of 0 or above 11 (in the main image or a sub-image);
+ *     - a prefix code that is over-subscribed or incomplete, or has no symbol at all.  The exception: a code of a single symbol, of any
+ *       length, is complete by definition and read with zero bits (libwebp's rule; zlib's differs).  A simple code's symbol at or past
+ *       its alphabet (only the 40 distance symbols can be passed) does not count as a symbol;
+ *     - a code-length repeat that runs past the alphabet; a max_symbol above the alphabet.  A repeat of the previous length with
+ *       nothing before it is NOT refused: the format defines it (8 is repeated), and libwebp decodes it;
+ *     - a bit pattern the code does not assign; a literal/length symbol at or past the alphabet (280 plus the cache size); a
+ *       colour-cache symbol when no cache is declared (complete codes over the declared alphabet leave no way to write these three;
+ *       the decoder checks them all the same);
+ *     - a distance that reaches before the first pixel; a copy that runs past the last pixel (refused, not clamped: libwebp refuses);
+ *     - a stream that consumes more bits than the chunk holds, anywhere (zero bits are read past the end and the count is checked
+ *       after each element of the front and before each symbol of the pixels: libwebp's end-of-stream flag).
+ *   ACCEPTED
+ *     - bytes after the last pixel inside the chunk; chunks after the image; bytes after the RIFF size (not read: a RIFF size below the
+ *       file length rules, as in libwebp, so a chunk must lie inside it);
+ *     - a colour index past the palette (transparent black, as the format says); a missing pad byte after the image chunk;
+ *     - prefix-code groups that no block of the entropy image uses (read and checked like the others, then dropped).
+ *   Where both apply, the order is: container and chunk walk (a lossy or animated file is UNSUPPORTED as soon as its chunk is met), VP8L
+ *   header, the size limit, then the stream in its own order.  Every refusal inside the stream has one status, so their order does not
+ *   show.  rph_webp_info stops after the size limit.
+ *   VALID BUT SMALL: an image below 5 px gets valid = 0 with status RPH_OK, and still its pixel hash.
+ * ===================================================================== */
+#define RPH_WEBP_ENTROPY_HOST 0   /* n_threads host threads decode the main ARGB stream (vp8l.h); the ARGB residuals cross PCIe */
+#define RPH_WEBP_ENTROPY_DEVICE 1 /* one wave per stream on the device; the compressed bytes and the built tables cross PCIe */
+#define RPH_WEBP_ENTROPY_AUTO 2   /* default: the host: the device won on no measured corpus, 2:1 to 2700:1 */
+/* Container and VP8L header only, host code, no context: the native layout rph_webp_decode will produce (channels 3 or 4, bit_depth 8);
+ * returns the file's status by the rule above as far as the header tells (the stream itself is not read). */
+int rph_webp_info(const uint8_t *data, size_t len, uint32_t *w, uint32_t *h, uint32_t *channels, uint32_t *bit_depth);
+/* The whole decoder on the CPU, no context (tests, tools): native pixels, packed rows, w * h * channels bytes into pixels_out (cap_bytes;
+ * RPH_ERR_CAPACITY if too small). */
+int rph_webp_decode_host(const uint8_t *data, size_t len, void *pixels_out, size_t cap_bytes);
+/* load_image_fast for one lossless WebP, decoded on the device: the same native pixels as rph_webp_decode_host. */
+int rph_webp_decode(rph_ctx *ctx, const uint8_t *data, size_t len, void *pixels_out, size_t cap_bytes);
+/* n WebP files -> n PDQ hashes (+ optional quality, 256 coefficients, 8 dihedral hashes, as rph_pdq_hash_batch) and optional pixel
+ * hashes (32 bytes each); the arguments mean what they mean in rph_png_pdq_hash_batch.  status_out[i] by the rule above (the call itself
+ * returns RPH_OK); a file that cannot be decoded has zero outputs and valid 0. */
+int rph_webp_pdq_hash_batch(rph_ctx *ctx, const uint8_t *const *data, const size_t *len, uint32_t n, uint32_t n_threads, uint8_t *hash32_out,
+                            float *quality_out, float *coeffs_out, uint8_t *dihedral_out, uint8_t *valid_out, int32_t *status_out,
+                            uint8_t *pixel_hash32_out);
+/* Where rph_webp_pdq_hash_batch decodes the main ARGB stream (RPH_WEBP_ENTROPY_*); the results are identical in every mode. */
+int rph_webp_set_entropy(rph_ctx *ctx, int where);
+/* The WebP path keeps its staging and device buffers in the context between calls; this returns them. */
+int rph_webp_release(rph_ctx *ctx);
+
+/* =====================================================================
  * BLAKE3 identity hashes (blake3 crate 1.x, 32-byte output): the two exact hashes the reference computes next to the PDQ hash.
  *   content hash  blake3::keyed_hash(content_key, file_bytes)                     scanner.rs:1343-1347 (the cache key)
  *                 -> rph_blake3_host per file in the scan loop, or rph_blake3_batch(_dev) for a batch of files

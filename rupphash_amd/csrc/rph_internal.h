@@ -62,6 +62,10 @@ struct rph_ctx {
     std::mutex tiff_mu;
     void *tiff = nullptr;
     int tiff_decompress = RPH_TIFF_DECOMPRESS_AUTO;
+    // WebP path (webp_pipeline.cpp): the same arrangement; where the main ARGB streams are entropy-decoded (RPH_WEBP_ENTROPY_*)
+    std::mutex webp_mu;
+    void *webp = nullptr;
+    int webp_entropy = RPH_WEBP_ENTROPY_AUTO;
 };
 
 // ---- launchers implemented in the .hip files (all asynchronous on `stream`) ----
@@ -148,6 +152,8 @@ void rph_jpeg_forget(rph_ctx *ctx);
 void rph_png_forget(rph_ctx *ctx);
 // tiff_pipeline.cpp
 void rph_tiff_forget(rph_ctx *ctx);
+// webp_pipeline.cpp
+void rph_webp_forget(rph_ctx *ctx);
 void rph_jpeg_forget_threads(rph_ctx *ctx);
 
 // host_grouping.cpp

@@ -1,0 +1,325 @@
+// webp_pipeline.cpp -- lossless WebP files -> PDQ hashes and pixel hashes (include/rupphash.h, WebP section).
+//
+// The host threads parse the container and read the serial front of every VP8L stream (webp_host.cpp): transforms with their sub-images,
+// colour table, entropy image, the prefix codes of every group, built into lookup tables.  The built tables cross PCIe rather than the
+// code lengths: the host has to build them anyway to apply the rule's checks to every code, so the kernel starts on the pixels at once
+// and holds no table-building code.  Then either the VP8L chunk's bytes are copied into pinned staging (DEVICE: the compressed bytes
+// cross; one wave per stream decodes the main ARGB image, webp_kernels.hip) or the host threads decode it themselves with the same
+// vp8l.h (HOST: the ARGB residuals cross).  Everything after that runs on the device: the inverse transforms, last read first, one
+// expand kernel, then the pixel hashes and PDQ over runs of equal geometry (decoded_hash.h, shared with the PNG and TIFF paths).
+// A call is processed in chunks whose buffers are kept in the context between calls (rph_webp_release returns them).
+#include <string.h>
+
+#include <algorithm>
+#include <atomic>
+#include <vector>
+
+#include "decoded_hash.h"
+#include "rph_internal.h"
+#include "webp_host.h"
+
+int rph_webp_launch_entropy(const uint8_t *d_comp, const void *d_images, const void *d_codes, uint32_t n, uint32_t *d_argb, int32_t *d_status, hipStream_t s);
+int rph_webp_launch_finish(const void *d_images, const uint32_t *d_list, uint32_t n, uint32_t levels, uint64_t max_pixels, const uint32_t *d_words, uint32_t *d_argb,
+                           uint8_t *d_hp, uint8_t *d_nat, hipStream_t s);
+
+namespace {
+
+struct WebpPipe {
+    hipStream_t s = nullptr;  // (rph_webp_forget: synchronised before the buffers are freed)
+    DevBuf comp, argb, words, codes, meta, status;
+    PinnedBuf h_comp, h_argb, h_words, h_codes, h_meta, h_status;
+    HashStageBufs hash;
+};
+
+// AUTO: the device would decode a chunk whose ARGB bytes are at least this many times its compressed bytes (both unpadded), the host
+// threads the rest.  The ratio is what the host knows before it decodes anything, in both modes; the share of pixels that come from
+// backward references would say more but is known only after a HOST-mode decode.  Measured (profiles/webp_rate.txt):
+// the device loses to 16 host threads at every ratio tried: photographs at 2:1 (1.23 vs 2.99 GB/s of pixels), palette images at 11:1
+// (1.21 vs 1.55), screenshots at 2700:1 (14.9 vs 22.6).  So there is no threshold, and AUTO is HOST
+constexpr uint64_t AUTO_DEVICE_MIN_RATIO = 0;  // 0: AUTO never chooses the device
+// tables (and sub-images) the parsed files of one window, and of one chunk, may hold
+constexpr uint64_t WINDOW_TABLE_BYTES = (uint64_t)1 << 30, CHUNK_TABLE_BYTES = (uint64_t)256 << 20;
+inline uint64_t table_bytes(const rphw::Parsed &p) { return p.codes.size() * 2 + p.words.size() * 4; }
+
+// a stream's bytes in staging: zero bytes behind them for the dwords the bit reader loads past the end before the count of consumed
+// bits stops it (at most 58 bits of one symbol group + 64 buffered + the dword loaded ahead)
+inline uint64_t staged_bytes(const rphw::Parsed &p) { return align_up(p.chunk_len, 4) + 32; }
+inline bool has_palette(const rphw::Image &im)
+{
+    for (uint32_t k = 0; k < im.n_tr; k++)
+        if (im.tr[k].type == rphw::TR_COLOUR_INDEXING) return true;
+    return false;
+}
+
+// one chunk: files[idx[k]] for k in [0, m), all parsed RPH_OK
+int run_chunk(rph_ctx *ctx, WebpPipe &P, std::vector<rphw::Parsed> &parsed, const uint32_t *idx, size_t m, unsigned threads, const FileOutputs &out)
+{
+    hipStream_t s = P.s;
+    auto reserve = [s](auto &buf, size_t bytes) { return reserve_slack(buf, bytes, s); };
+    // placement: coded ARGB images first (the part a HOST-mode chunk uploads), the unbundled images of palette files behind them
+    uint64_t a_words = 0, b_words = 0, comp_bytes = 0, n_words = 0, n_codes = 0, argb_bytes = 0, chunk_bytes = 0;
+    uint32_t levels = 0;
+    std::vector<uint64_t> word_base(m), code_base(m), comp_base(m);
+    for (size_t k = 0; k < m; k++) {
+        rphw::Parsed &pp = parsed[idx[k]];
+        pp.im.a_off = a_words;
+        a_words += align_up((uint64_t)pp.im.xw * pp.im.h, 16);
+        word_base[k] = n_words;
+        n_words += align_up(pp.words.size(), 4);
+        code_base[k] = n_codes;
+        n_codes += align_up(pp.codes.size(), 8);
+        comp_base[k] = comp_bytes;
+        comp_bytes += staged_bytes(pp);
+        argb_bytes += (uint64_t)pp.im.xw * pp.im.h * 4;
+        chunk_bytes += pp.chunk_len;
+        levels = std::max<uint32_t>(levels, pp.im.n_tr);
+    }
+    for (size_t k = 0; k < m; k++) {
+        rphw::Parsed &pp = parsed[idx[k]];
+        if (!has_palette(pp.im)) continue;
+        pp.im.b_off = a_words + b_words;
+        b_words += align_up((uint64_t)pp.im.w * pp.im.h, 16);
+    }
+    int mode = ctx->webp_entropy;
+    if (mode == RPH_WEBP_ENTROPY_AUTO) mode = AUTO_DEVICE_MIN_RATIO && argb_bytes >= AUTO_DEVICE_MIN_RATIO * chunk_bytes ? RPH_WEBP_ENTROPY_DEVICE : RPH_WEBP_ENTROPY_HOST;
+    const bool device = mode == RPH_WEBP_ENTROPY_DEVICE;
+    Layout L;
+    const size_t off_img = L.add(m * sizeof(rphw::Image)), off_list = L.add(m * 4, 256), off_b3 = L.add((m + 1) * 8, 256), meta_bytes = L.end();
+    RPH_TRY(reserve(P.meta, meta_bytes));
+    RPH_TRY(reserve(P.h_meta, meta_bytes));
+    RPH_TRY(reserve(P.argb, (a_words + b_words) * 4));
+    RPH_TRY(reserve(P.words, n_words * 4));
+    RPH_TRY(reserve(P.h_words, n_words * 4));
+    RPH_TRY(reserve(P.status, m * 4));
+    RPH_TRY(reserve(P.h_status, m * 4));
+    uint8_t *M = P.h_meta.data();
+    rphw::Image *imgs = reinterpret_cast<rphw::Image *>(M + off_img);
+    uint32_t *list = reinterpret_cast<uint32_t *>(M + off_list);
+    int32_t *st = reinterpret_cast<int32_t *>(P.h_status.data());
+    uint32_t *h_words = P.h_words.as<uint32_t>();
+    for (size_t k = 0; k < m; k++) {
+        const rphw::Parsed &pp = parsed[idx[k]];
+        imgs[k] = pp.im;
+        for (uint32_t q = 0; q < imgs[k].n_tr; q++) imgs[k].tr[q].off += (uint32_t)word_base[k];
+        imgs[k].ent_off += code_base[k];
+        imgs[k].tab_off += code_base[k];
+        imgs[k].comp_off = comp_base[k];
+        imgs[k].comp_len = pp.chunk_len;
+        st[k] = RPH_OK;
+        if (!pp.words.empty()) memcpy(h_words + word_base[k], pp.words.data(), pp.words.size() * 4);
+    }
+    RPH_HIP_CHECK(hipMemcpyAsync(P.meta.data(), M, meta_bytes, hipMemcpyHostToDevice, s));
+    RPH_HIP_CHECK(hipMemcpyAsync(P.words.data(), h_words, n_words * 4, hipMemcpyHostToDevice, s));
+    if (device) {
+        RPH_TRY(reserve(P.comp, comp_bytes));
+        RPH_TRY(reserve(P.h_comp, comp_bytes));
+        RPH_TRY(reserve(P.codes, n_codes * 2));
+        RPH_TRY(reserve(P.h_codes, n_codes * 2));
+        uint16_t *h_codes = P.h_codes.as<uint16_t>();
+        parallel_for(0, m, threads, [&](size_t k) {
+            const rphw::Parsed &pp = parsed[idx[k]];
+            uint8_t *d = P.h_comp.data() + comp_base[k];
+            memcpy(d, pp.chunk, pp.chunk_len);
+            memset(d + pp.chunk_len, 0, staged_bytes(pp) - pp.chunk_len);
+            memcpy(h_codes + code_base[k], pp.codes.data(), pp.codes.size() * 2);
+        });
+        RPH_HIP_CHECK(hipMemcpyAsync(P.comp.data(), P.h_comp.data(), comp_bytes, hipMemcpyHostToDevice, s));
+        RPH_HIP_CHECK(hipMemcpyAsync(P.codes.data(), h_codes, n_codes * 2, hipMemcpyHostToDevice, s));
+        RPH_HIP_CHECK(hipMemcpyAsync(P.status.data(), st, m * 4, hipMemcpyHostToDevice, s));
+        RPH_TRY(rph_webp_launch_entropy(P.comp.data(), P.meta.data() + off_img, P.codes.data(), (uint32_t)m, P.argb.as<uint32_t>(), P.status.as<int32_t>(), s));
+        RPH_HIP_CHECK(hipMemcpyAsync(st, P.status.data(), m * 4, hipMemcpyDeviceToHost, s));
+        RPH_HIP_CHECK(hipStreamSynchronize(s));
+    } else {
+        RPH_TRY(reserve(P.h_argb, a_words * 4));
+        uint32_t *h_argb = P.h_argb.as<uint32_t>();
+        parallel_for(0, m, threads, [&](size_t k) {
+            if (!rphw::decode_main_host(parsed[idx[k]], h_argb + imgs[k].a_off)) st[k] = RPH_ERR_INVALID_ARG;
+        });
+        RPH_HIP_CHECK(hipMemcpyAsync(P.argb.data(), h_argb, a_words * 4, hipMemcpyHostToDevice, s));
+    }
+    return hash_decoded_images(ctx, s, P.hash, imgs, list, reinterpret_cast<uint64_t *>(M + off_b3), P.meta.data() + off_b3, st, idx, m, out,
+                               [&](uint32_t g, uint64_t max_px, bool want_hp, uint64_t, uint64_t nat_bytes) -> int {
+                                   RPH_HIP_CHECK(hipMemcpyAsync(P.meta.data(), M, meta_bytes, hipMemcpyHostToDevice, s));
+                                   return rph_webp_launch_finish(P.meta.data() + off_img, (const uint32_t *)(P.meta.data() + off_list), g, levels, max_px,
+                                                                 P.words.as<uint32_t>(), P.argb.as<uint32_t>(), want_hp ? P.hash.hp.data() : nullptr,
+                                                                 nat_bytes ? P.hash.nat.data() : nullptr, s);
+                               });
+}
+
+int run(rph_ctx *ctx, const uint8_t *const *data, const size_t *len, uint32_t n, unsigned threads, const FileOutputs &out)
+{
+    std::lock_guard<std::mutex> lock(ctx->webp_mu);
+    RPH_HIP_CHECK(hipSetDevice(ctx->device));
+    WebpPipe *P = static_cast<WebpPipe *>(ctx->webp);
+    if (!P) {
+        P = new WebpPipe();
+        hipError_t e = hipStreamCreateWithFlags(&P->s, hipStreamNonBlocking);
+        if (e != hipSuccess) {
+            delete P;
+            rph_set_error("hipStreamCreate failed: %s", hipGetErrorString(e));
+            return RPH_ERR_HIP;
+        }
+        ctx->webp = P;
+    }
+    if (!threads) threads = rph_host_threads();
+    // The fronts of a window of files at a time: their tables are the bulk of what a parsed file holds.  A window ends early at the first
+    // file that finds the window's tables above their bound (files behind it that were parsed meanwhile are parsed again in the next one)
+    std::vector<rphw::Parsed> parsed(n);
+    for (uint32_t a = 0; a < n;) {
+        uint32_t b = (uint32_t)std::min<uint64_t>(n, (uint64_t)a + CHUNK_FILES);
+        std::atomic<uint64_t> held{0};
+        std::atomic<uint32_t> deferred{b};
+        parallel_for(a, b, threads, [&](size_t i) {
+            if (i > a && (held.load() > WINDOW_TABLE_BYTES || i > deferred.load())) {
+                uint32_t d = deferred.load();
+                while ((uint32_t)i < d && !deferred.compare_exchange_weak(d, (uint32_t)i)) {}
+                return;
+            }
+            out.status[i] = (data[i] && len[i]) ? rphw::front(data[i], len[i], parsed[i]) : RPH_ERR_INVALID_ARG;
+            held += table_bytes(parsed[i]);
+        });
+        for (uint32_t i = deferred.load(); i < b; i++) parsed[i] = rphw::Parsed();
+        b = deferred.load();
+        std::vector<uint32_t> ok;
+        for (uint32_t i = a; i < b; i++)
+            if (out.status[i] == RPH_OK) ok.push_back(i);
+        for (size_t c = 0; c < ok.size();) {
+            size_t e = c;
+            uint64_t comp = 0, px = 0, tab = 0;
+            while (e < ok.size()) {
+                const rphw::Parsed &p = parsed[ok[e]];
+                const uint64_t pix = (uint64_t)p.im.w * p.im.h;
+                if (e > c && (comp + p.chunk_len > CHUNK_COMP || px + pix > CHUNK_PIXELS / 2 || tab + table_bytes(p) > CHUNK_TABLE_BYTES)) break;
+                tab += table_bytes(p);
+                comp += p.chunk_len;
+                px += pix;
+                e++;
+            }
+            RPH_TRY(run_chunk(ctx, *P, parsed, ok.data() + c, e - c, threads, out));
+            c = e;
+        }
+        for (uint32_t i = a; i < b; i++) parsed[i] = rphw::Parsed();
+        a = b;
+    }
+    return RPH_OK;
+}
+
+}  // namespace
+
+void rph_webp_forget(rph_ctx *ctx)
+{
+    WebpPipe *P = static_cast<WebpPipe *>(ctx->webp);
+    if (!P) return;
+    (void)hipStreamSynchronize(P->s);
+    (void)hipStreamDestroy(P->s);
+    delete P;
+    ctx->webp = nullptr;
+}
+
+extern "C" {
+
+int rph_webp_info(const uint8_t *data, size_t len, uint32_t *w, uint32_t *h, uint32_t *channels, uint32_t *bit_depth)
+{
+    return rph_guarded("rph_webp_info", [&]() -> int {
+        if (!data) return RPH_ERR_INVALID_ARG;
+        rphw::Parsed p;
+        const int rc = rphw::parse(data, len, p);
+        if (rc) return rc;
+        if (w) *w = p.im.w;
+        if (h) *h = p.im.h;
+        if (channels) *channels = p.im.out_ch;
+        if (bit_depth) *bit_depth = p.im.out_depth;
+        return RPH_OK;
+    });
+}
+
+int rph_webp_decode_host(const uint8_t *data, size_t len, void *pixels_out, size_t cap_bytes)
+{
+    return rph_guarded("rph_webp_decode_host", [&]() -> int {
+        if (!data || !pixels_out) return RPH_ERR_INVALID_ARG;
+        rphw::Parsed p;
+        std::vector<uint8_t> px;
+        const int rc = rphw::decode_host(data, len, p, px);
+        if (rc) return rc;
+        if (px.size() > cap_bytes) {
+            rph_set_error("rph_webp_decode_host: %zu bytes needed", px.size());
+            return RPH_ERR_CAPACITY;
+        }
+        memcpy(pixels_out, px.data(), px.size());
+        return RPH_OK;
+    });
+}
+
+int rph_webp_decode(rph_ctx *ctx, const uint8_t *data, size_t len, void *pixels_out, size_t cap_bytes)
+{
+    return rph_guarded("rph_webp_decode", [&]() -> int {
+        if (!ctx || !data || !pixels_out) return RPH_ERR_INVALID_ARG;
+        rphw::Parsed p;
+        int rc = rphw::parse(data, len, p);
+        if (rc) return rc;
+        const size_t need = (size_t)p.im.w * p.im.h * p.im.out_ch;
+        if (need > cap_bytes) {
+            rph_set_error("rph_webp_decode: %zu bytes needed", need);
+            return RPH_ERR_CAPACITY;
+        }
+        int32_t status = RPH_OK;
+        FileOutputs o;
+        o.want_pdq = false;
+        o.status = &status;
+        std::vector<uint8_t> staging(align_up(need, 64) + 64);
+        o.native = staging.data();
+        RPH_TRY(run(ctx, &data, &len, 1, 0, o));
+        if (status != RPH_OK) return status;
+        memcpy(pixels_out, staging.data(), need);
+        return RPH_OK;
+    });
+}
+
+int rph_webp_pdq_hash_batch(rph_ctx *ctx, const uint8_t *const *data, const size_t *len, uint32_t n, uint32_t n_threads, uint8_t *hash32_out,
+                            float *quality_out, float *coeffs_out, uint8_t *dihedral_out, uint8_t *valid_out, int32_t *status_out,
+                            uint8_t *pixel_hash32_out)
+{
+    return rph_guarded("rph_webp_pdq_hash_batch", [&]() -> int {
+        if (!ctx || (n && (!data || !len || !hash32_out))) {
+            rph_set_error("rph_webp_pdq_hash_batch: null argument");
+            return RPH_ERR_INVALID_ARG;
+        }
+        if (n == 0) return RPH_OK;
+        std::vector<int32_t> st_local(status_out ? 0 : n);
+        std::vector<uint8_t> v_local(valid_out ? 0 : n);
+        FileOutputs o;
+        o.hash = hash32_out;
+        o.quality = quality_out;
+        o.coeffs = coeffs_out;
+        o.dihedral = dihedral_out;
+        o.valid = valid_out ? valid_out : v_local.data();
+        o.status = status_out ? status_out : st_local.data();
+        o.pixel = pixel_hash32_out;
+        memset(hash32_out, 0, (size_t)n * 32);
+        if (quality_out) memset(quality_out, 0, (size_t)n * 4);
+        if (coeffs_out) memset(coeffs_out, 0, (size_t)n * 1024);
+        if (dihedral_out) memset(dihedral_out, 0, (size_t)n * 256);
+        memset(o.valid, 0, n);
+        if (pixel_hash32_out) memset(pixel_hash32_out, 0, (size_t)n * 32);
+        return run(ctx, data, len, n, n_threads, o);
+    });
+}
+
+int rph_webp_set_entropy(rph_ctx *ctx, int where)
+{
+    if (!ctx || where < RPH_WEBP_ENTROPY_HOST || where > RPH_WEBP_ENTROPY_AUTO) return RPH_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lock(ctx->webp_mu);
+    ctx->webp_entropy = where;
+    return RPH_OK;
+}
+
+int rph_webp_release(rph_ctx *ctx)
+{
+    if (!ctx) return RPH_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lock(ctx->webp_mu);
+    (void)hipSetDevice(ctx->device);
+    rph_webp_forget(ctx);
+    return RPH_OK;
+}
+
+}  // extern "C"
