@@ -7,6 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import deflate_util as du
 import png_util as pu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -101,6 +102,9 @@ def test_host_parser_and_inflate_under_address_and_undefined_behaviour_sanitizer
     variants of it; any report fails the run"""
     for k, (name, data) in enumerate(pu.valid_corpus(5) + [(n, d) for n, d, _ in pu.rule_corpus()]):
         (tmp_path / f"f{k:03d}.png").write_bytes(data)
+    # deflate streams that zlib's encoder never writes (deflate_util's named and refused corpora, in this format's carrier)
+    for k, (name, data, _) in enumerate(f for f in du.carrier_files("png") if not f[0].startswith("random")):
+        (tmp_path / f"g{k:03d}.png").write_bytes(data)
     exe = str(tmp_path / "fuzz_png_host")
     csrc = os.path.join(ROOT, "rupphash_amd", "csrc")
     try:

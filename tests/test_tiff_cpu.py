@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import deflate_util as du
 import tiff_util as tu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -139,6 +140,9 @@ def test_host_parser_and_decompressors_under_address_and_undefined_behaviour_san
     damaged variants of it; any report fails the run"""
     for k, (name, data) in enumerate(tu.valid_corpus(5) + [(n, d) for n, d, _ in tu.rule_corpus()]):
         (tmp_path / f"f{k:03d}.tif").write_bytes(data)
+    # deflate streams that zlib's encoder never writes (deflate_util's named and refused corpora, in this format's carrier)
+    for k, (name, data, _) in enumerate(f for f in du.carrier_files("tiff") if not f[0].startswith("random")):
+        (tmp_path / f"g{k:03d}.tif").write_bytes(data)
     exe = str(tmp_path / "fuzz_tiff_host")
     csrc = os.path.join(ROOT, "rupphash_amd", "csrc")
     try:
