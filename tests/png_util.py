@@ -54,7 +54,7 @@ def filter_row(f, row, prev, bpp):
     b = prev.astype(np.int64)
     a = np.concatenate([np.zeros(min(bpp, len(x)), np.int64), x[:max(0, len(x) - bpp)]])
     c = np.concatenate([np.zeros(min(bpp, len(b)), np.int64), b[:max(0, len(b) - bpp)]])
-    pred = [0 * x, a, b, (a + b) >> 1, _paeth(a, b, c)][f]
+    pred = 0 * x if f == 0 else a if f == 1 else b if f == 2 else (a + b) >> 1 if f == 3 else _paeth(a, b, c)
     return ((x - pred) & 255).astype(np.uint8)
 
 

@@ -31,6 +31,13 @@ def test_fold_and_stack_trees_agree(key):
         assert b3.blake3(data, key) == b3.blake3_stack(data, key), n
 
 
+def test_many_messages_at_once_agree_with_one_at_a_time():
+    rng = np.random.default_rng(5)
+    datas = [b3.test_input(n) for n in LENGTHS] + [rng.integers(0, 256, n, dtype=np.uint8).tobytes() for n in (0, 5, 1024, 3000, 3072, 70000)]
+    assert b3.blake3_many(datas) == [b3.blake3(d) for d in datas]
+    assert b3.blake3_many([]) == [] and b3.blake3_many([b"abc"]) == [b3.blake3(b"abc")]
+
+
 @pytest.mark.parametrize("key", [None, KEY, bytes(range(32))], ids=["hash", "keyed", "key2"])
 def test_host_scalar_matches_helper(key):
     from rupphash_amd import Engine

@@ -9,6 +9,7 @@ import pytest
 
 import deflate_util as du
 import png_util as pu
+import recon_grid as rg
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -105,6 +106,9 @@ def test_host_parser_and_inflate_under_address_and_undefined_behaviour_sanitizer
     # deflate streams that zlib's encoder never writes (deflate_util's named and refused corpora, in this format's carrier)
     for k, (name, data, _) in enumerate(f for f in du.carrier_files("png") if not f[0].startswith("random")):
         (tmp_path / f"g{k:03d}.png").write_bytes(data)
+    # the reconstruction grids (recon_grid.py): every file
+    for k, (name, data) in enumerate(x for files in rg.png_grid().values() for x in files):
+        (tmp_path / f"r{k:04d}.png").write_bytes(data)
     exe = str(tmp_path / "fuzz_png_host")
     csrc = os.path.join(ROOT, "rupphash_amd", "csrc")
     try:

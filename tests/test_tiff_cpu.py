@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import deflate_util as du
+import recon_grid as rg
 import tiff_util as tu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -143,6 +144,9 @@ def test_host_parser_and_decompressors_under_address_and_undefined_behaviour_san
     # deflate streams that zlib's encoder never writes (deflate_util's named and refused corpora, in this format's carrier)
     for k, (name, data, _) in enumerate(f for f in du.carrier_files("tiff") if not f[0].startswith("random")):
         (tmp_path / f"g{k:03d}.tif").write_bytes(data)
+    # the reconstruction grids (recon_grid.py): every file
+    for k, (name, data) in enumerate(x for files in rg.tiff_grid().values() for x in files):
+        (tmp_path / f"r{k:04d}.tif").write_bytes(data)
     exe = str(tmp_path / "fuzz_tiff_host")
     csrc = os.path.join(ROOT, "rupphash_amd", "csrc")
     try:

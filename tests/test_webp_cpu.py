@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import recon_grid as rg
 import webp_util as wu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -155,6 +156,9 @@ def test_host_parser_and_decoder_under_address_and_undefined_behaviour_sanitizer
     variants of it; any report fails the run"""
     for k, (name, data) in enumerate(wu.valid_corpus(4) + [(n, d) for n, d, _ in wu.rule_corpus()]):
         (tmp_path / f"f{k:03d}.webp").write_bytes(data)
+    # the reconstruction grids (recon_grid.py): every file
+    for k, (name, data) in enumerate(x for files in rg.webp_grid().values() for x in files):
+        (tmp_path / f"r{k:04d}.webp").write_bytes(data)
     exe = str(tmp_path / "fuzz_webp_host")
     csrc = os.path.join(ROOT, "rupphash_amd", "csrc")
     # is there a sanitizer runtime at all?  Asked of a trivial program, so that a failure to build the real sources fails the test

@@ -55,6 +55,10 @@ class BitReader:
         self.pos += k
         return v & ((1 << k) - 1)
 
+    def peek(self, k):
+        p = self.pos >> 3
+        return (int.from_bytes(self.d[p:p + 4], "little") >> (self.pos & 7)) & ((1 << k) - 1)
+
     def check(self):
         if self.pos > 8 * len(self.d):
             raise Refused(INVALID, "out of bits")
@@ -72,23 +76,23 @@ class Code:
             return
         if sum(1 << (15 - l) for l, _ in used) != 1 << 15:
             raise Refused(INVALID, "over-subscribed or incomplete code")
-        self.table, code, prev = {}, 0, 0
+        # every pattern of `width` bits as they come out of the stream (least significant first) -> (symbol, length)
+        self.width = max(l for l, _ in used)
+        self.table, code, prev = [None] * (1 << self.width), 0, 0
         for l, s in sorted(used):
             code <<= l - prev
             prev = l
-            self.table[(l, code)] = s
+            first = int(format(code, f"0{l}b")[::-1], 2)
+            for k in range(first, 1 << self.width, 1 << l):
+                self.table[k] = (s, l)
             code += 1
 
     def read(self, br):
         if self.single is not None:
             return self.single
-        code = 0
-        for l in range(1, 16):
-            code = (code << 1) | br.take(1)
-            s = self.table.get((l, code))
-            if s is not None:
-                return s
-        raise Refused(INVALID, "unassigned bit pattern")
+        s, l = self.table[br.peek(self.width)]  # (a complete code assigns every pattern)
+        br.pos += l
+        return s
 
 
 def _read_code(br, n):
@@ -402,6 +406,17 @@ class BitWriter:
             self.acc >>= 8
             self.n -= 8
 
+    def put_many(self, values, counts):
+        """put(values[i], counts[i]) for every i, as one array operation"""
+        values, counts = np.asarray(values, np.uint32).ravel(), np.asarray(counts, np.int64).ravel()
+        ends = np.cumsum(counts)
+        which = np.repeat(np.arange(len(counts)), counts)
+        bit = np.arange(int(ends[-1]) if len(ends) else 0) - (ends - counts)[which]
+        bits = np.concatenate([np.array([(self.acc >> k) & 1 for k in range(self.n)], np.uint8), ((values[which] >> bit) & 1).astype(np.uint8)])
+        whole = len(bits) // 8 * 8
+        self.out += np.packbits(bits[:whole], bitorder="little").tobytes()
+        self.acc, self.n = sum(int(b) << k for k, b in enumerate(bits[whole:])), len(bits) - whole
+
     def bytes(self):
         return bytes(self.out) + (bytes([self.acc]) if self.n else b"")
 
@@ -448,14 +463,14 @@ class CodeWriter:
         used = [s for s, l in enumerate(lens) if l]
         self.single = len(used) == 1
         self.codes = canonical(lens)
+        # the codes as the stream holds them: most significant bit first, so reversed for a writer of least significant bits first
+        self.rev, self.len = np.zeros(len(lens), np.uint32), np.zeros(len(lens), np.int64)
+        for s, (code, l) in self.codes.items():
+            self.rev[s], self.len[s] = int(format(code, f"0{l}b")[::-1], 2), 0 if self.single else l
 
     def put(self, bw, s):
-        if self.single:
-            assert s in self.codes
-            return
-        code, l = self.codes[s]
-        for b in range(l - 1, -1, -1):
-            bw.put((code >> b) & 1, 1)
+        assert s in self.codes
+        bw.put(int(self.rev[s]), int(self.len[s]))
 
 
 def write_code(bw, lens, simple=True, max_symbol=False, repeats=False, hack=None):
@@ -481,7 +496,7 @@ def write_code(bw, lens, simple=True, max_symbol=False, repeats=False, hack=None
     tokens, s = [], 0  # (symbol of the code-length code, extra bits, count of extra bits)
     while s < top:
         run = 1
-        while s + run < top and lens[s + run] == lens[s]:
+        while repeats and s + run < top and lens[s + run] == lens[s]:
             run += 1
         if repeats and lens[s] == 0 and run >= 3:
             run = min(run, 138)
@@ -583,8 +598,19 @@ def token_pixels(t):
 
 
 def write_pixels(bw, tokens, xsize, cache_bits=0, ent=None, meta_bits=0, n_groups=1, code_kw=None, hack=None):
-    """the codes of every group, then the tokens"""
+    """the codes of every group, then the tokens; an array of ARGB values for tokens stands for that many literals of one group"""
     code_kw = code_kw or {}
+    if isinstance(tokens, np.ndarray):
+        assert ent is None and n_groups == 1 and not cache_bits and hack is None
+        c = [(tokens >> 8) & 255, (tokens >> 16) & 255, tokens & 255, tokens >> 24]
+        ws = []
+        for k, n in enumerate((280, 256, 256, 256, 40)):
+            hist = np.bincount(c[k], minlength=n).tolist() if k < 4 else [1] + [0] * 39
+            lens = huffman_lengths(hist)
+            write_code(bw, lens, **code_kw)
+            ws.append(CodeWriter(lens))
+        bw.put_many(np.stack([ws[k].rev[c[k]] for k in range(4)], axis=-1), np.stack([ws[k].len[c[k]] for k in range(4)], axis=-1))
+        return
     green_n = 280 + ((1 << cache_bits) if cache_bits else 0)
     hists = [[[0] * n for n in (green_n, 256, 256, 256, 40)] for _ in range(n_groups)]
     bwid, pos, where = sub(xsize, meta_bits), 0, []
@@ -639,7 +665,7 @@ def write_pixels(bw, tokens, xsize, cache_bits=0, ent=None, meta_bits=0, n_group
 
 def write_sub_image(bw, px, xsize):
     bw.put(0, 1)  # no colour cache
-    write_pixels(bw, [("lit", int(v)) for v in px], xsize)
+    write_pixels(bw, np.asarray(px, np.uint32).ravel(), xsize)
 
 
 def _channels(a):
@@ -652,7 +678,7 @@ def _unchannels(c):
 
 
 def forward_predictor(a, bits, modes):
-    """a: (h, w) uint32; modes: (bh, bw) ints 0 .. 13 -> residuals"""
+    """a: (h, w) uint32; modes: (bh, bw) ints 0 .. 15 (14 and 15 predict as 0) -> residuals"""
     h, w = a.shape
     c = _channels(a)
     flat = c.reshape(-1, 4)
@@ -665,14 +691,14 @@ def forward_predictor(a, bits, modes):
     black = np.zeros_like(L)
     black[..., 0] = 255
     preds = [black, L, T, TR, TL, avg(avg(L, TR), T), avg(L, TL), avg(L, T), avg(TL, T), avg(T, TR), avg(avg(L, TL), avg(T, TR)), np.where(sel, L, T),
-             np.clip(L + T - TL, 0, 255), np.clip(half_a + np.sign(d) * (np.abs(d) // 2), 0, 255)]
+             np.clip(L + T - TL, 0, 255), np.clip(half_a + np.sign(d) * (np.abs(d) // 2), 0, 255), black, black]
     mode_px = np.kron(modes, np.ones((1 << bits, 1 << bits), np.int64))[:h, :w]
     mode_px = mode_px.copy()
     mode_px[:, 0] = 2
     mode_px[0, :] = 1
     mode_px[0, 0] = 0
     pred = np.zeros_like(c)
-    for m in range(14):
+    for m in range(16):
         pred = np.where((mode_px == m)[..., None], preds[m], pred)
     return _unchannels(c - pred)
 
@@ -712,9 +738,11 @@ def to_argb(img):
 
 
 def encode(img, transforms=(), cache_bits=0, meta_bits=None, n_groups=1, refs="none", plane=True, form="simple", alpha=None, vp8x_alpha=None, code_kw=None,
-           tokens=None, hack=None, cache_bits_raw=None, trailing=b"", seed=0):
-    """img: (h, w, 3 or 4) uint8.  transforms, in the order written: ('predictor', bits, mode | 'mixed'), ('cross', bits), ('green',),
-    ('palette',).  tokens: the main stream's tokens as given (the pixels then are what they decode to)."""
+           tokens=None, hack=None, cache_bits_raw=None, trailing=b"", seed=0, ent_map=None):
+    """img: (h, w, 3 or 4) uint8.  transforms, in the order written: ('predictor', bits 2 .. 9, mode 0 .. 15 | 'mixed' (modes 0 .. 13) |
+    'mixed16' (0 .. 15) | an array of modes per block), ('cross', bits 2 .. 9[, an array (bh, bw, 3) of signed coefficients]), ('green',),
+    ('palette'[, declared colours[, the palette as ARGB values]]).  tokens: the main stream's tokens as given (the pixels then are what they decode to).  ent_map: the group of every
+    block of the entropy image, in place of the writer's own pattern."""
     rng = np.random.default_rng(seed)
     a = to_argb(img)
     h, w = a.shape
@@ -731,7 +759,10 @@ def encode(img, transforms=(), cache_bits=0, meta_bits=None, n_groups=1, refs="n
         if tr[0] == "predictor":
             bits = tr[1]
             shape = (sub(hh, bits), sub(ww, bits))
-            modes = rng.integers(0, 14, shape) if tr[2] == "mixed" else np.full(shape, tr[2], np.int64)
+            modes = tr[2]
+            if isinstance(modes, str):
+                modes = rng.integers(0, 14 if modes == "mixed" else 16, shape)
+            modes = np.broadcast_to(np.asarray(modes, np.int64), shape)
             bw.put(0, 2)
             bw.put(bits - 2, 3)
             write_sub_image(bw, (0xff000000 | (modes.astype(np.uint32) << 8)).ravel(), shape[1])
@@ -739,7 +770,7 @@ def encode(img, transforms=(), cache_bits=0, meta_bits=None, n_groups=1, refs="n
         elif tr[0] == "cross":
             bits = tr[1]
             shape = (sub(hh, bits), sub(ww, bits))
-            k = rng.integers(-40, 40, shape + (3,))
+            k = np.broadcast_to(np.asarray(tr[2], np.int64), shape + (3,)) if len(tr) > 2 else rng.integers(-40, 40, shape + (3,))
             bw.put(1, 2)
             bw.put(bits - 2, 3)
             write_sub_image(bw, (0xff000000 | ((k[..., 2] & 255) << 16) | ((k[..., 1] & 255) << 8) | (k[..., 0] & 255)).astype(np.uint32).ravel(), shape[1])
@@ -751,8 +782,13 @@ def encode(img, transforms=(), cache_bits=0, meta_bits=None, n_groups=1, refs="n
             c[..., 3] -= c[..., 2]
             a = _unchannels(c)
         else:
-            pal, index = np.unique(a, return_inverse=True)
-            index = index.reshape(a.shape)
+            if len(tr) > 2:  # (the palette as given: its size does not depend on the colours in use)
+                pal = np.asarray(tr[2], np.uint32)
+                index = (a[..., None] == pal).argmax(-1)
+                assert np.array_equal(pal[index], a)
+            else:
+                pal, index = np.unique(a, return_inverse=True)
+                index = index.reshape(a.shape)
             n = len(pal) if len(tr) < 2 else tr[1]  # (a declared count below the colours in use: indexes past the palette)
             assert len(pal) <= 256
             bits = 0 if n > 16 else 1 if n > 4 else 2 if n > 2 else 3
@@ -780,8 +816,12 @@ def encode(img, transforms=(), cache_bits=0, meta_bits=None, n_groups=1, refs="n
     ent = None
     if meta_bits is not None:
         shape = (sub(h, meta_bits), sub(xsize, meta_bits))
-        ent = [int(v) for v in (np.arange(shape[0] * shape[1]) * 7 % n_groups)]
-        ent[-1] = n_groups - 1
+        if ent_map is None:
+            ent = [int(v) for v in (np.arange(shape[0] * shape[1]) * 7 % n_groups)]
+            ent[-1] = n_groups - 1
+        else:
+            ent = [int(v) for v in np.asarray(ent_map).ravel()]
+            assert len(ent) == shape[0] * shape[1] and max(ent) == n_groups - 1
         bw.put(1, 1)
         bw.put(meta_bits - 2, 3)
         write_sub_image(bw, [0xff000000 | (g << 8) for g in ent], shape[1])
@@ -790,7 +830,8 @@ def encode(img, transforms=(), cache_bits=0, meta_bits=None, n_groups=1, refs="n
     else:
         bw.put(0, 1)
     if tokens is None:
-        tokens = tokenize(px, xsize, cache_bits, refs, plane)
+        plain = refs == "none" and not cache_bits and ent is None and hack is None
+        tokens = a.ravel().astype(np.uint32) if plain else tokenize(px, xsize, cache_bits, refs, plane)
     write_pixels(bw, tokens, xsize, cache_bits, ent, meta_bits or 0, n_groups, code_kw, hack if hack in ("over", "incomplete", "repeat_past", "max_symbol_big", "repeat_first") else None)
     chunk = bw.bytes() + trailing
     if hack == "signature":
