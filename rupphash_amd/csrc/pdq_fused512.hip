@@ -8,9 +8,9 @@
 // in 8 bands of 64 rows x 4 strips of 128 columns (128 px = 384 B = exactly three 128-B cache lines, so
 // no line is ever requested by two tiles).  Per (band, strip) tile:
 //   LOAD   two half tiles of 32 rows; lane (c, g) = 8 columns x 8 rows: two global_load_dwordx3 per row,
-//          Rec.601 luma (exact integers), packed to f16; the 7 luma rows above come from the lane with g-1
-//          through LDS (or from the rows saved by the previous half tile / band), and the vertical 8-row
-//          window sums V (<= 2040, exact in f16) go to a 64x128 f16 tile in LDS.
+//          Rec.601 luma (exact integers), packed to f16 and kept biased (1024 + y); the 7 luma rows above come
+//          from the lane with g-1 through LDS (or from the rows saved by the previous half tile / band), and the
+//          vertical 8-row window sums V (<= 2040, exact in f16, unbiased) go to a 64x128 f16 tile in LDS.
 //   SCAN   lane r = image row: walks the tile left to right keeping the horizontal 8-window sum Hs
 //          of V in f32 (= the pass-1 box value x 64, an exact integer) and the reference's pass-2 row
 //          running sum (sum += in[ri]; sum -= in[li]) in the reference's order; emits the pass-2 row
@@ -127,6 +127,11 @@ __device__ __forceinline__ void luma8(const Px8 &v, float (&l)[8])
 // Bytes become f16 without a conversion: v_perm_b32 pairs each byte with the constant 0x64, and 0x6400 | v is
 // the f16 number 1024 + v.  v_dot2_f32_f16 then forms 299 r + 587 g + 114 b (+ the bias 1024 * 1000, removed by
 // the accumulator constant) with f32 accumulation: all products and sums are integers < 2^24, hence exact.
+// Luma rows are carried BIASED everywhere (L[], the exchange area, the 7 state rows, the prologue): the f16 number 1024 + y, bits
+// 0x6400 | y, exactly what the perm / the conversion leave.  Taking the bias off would cost a v_pk_add_f16 per pair; the window slide
+// v = (v - hist[m-1]) + L[m] cancels it by itself, and only the first V of a lane's eight rows removes it (half_build).  A luma row
+// outside the image is the biased zero.
+constexpr uint32_t BIASED_ZERO = 0x64006400u;
 struct Row8 {
     h2 q[4];
 };
@@ -180,29 +185,28 @@ __device__ __forceinline__ Row8 luma_row(const Pairs12 &pr, bool zero, uint32_t 
         const float n0 = __builtin_amdgcn_fdot2(P[3 * pp], k_rg, dot2_from_zero(P[3 * pp + 1], k_b0, order), false);
         const float n1 = __builtin_amdgcn_fdot2(P[3 * pp + 1], k_0r, dot2_from_zero(P[3 * pp + 2], k_gb, order), false);
         const float y0 = __builtin_fmaf(n0, 0.001f, vhalf), y1 = __builtin_fmaf(n1, 0.001f, vhalf);  // v_fmamk_f32 (VOP2, full rate)
-        packed[pp] = __builtin_bit_cast(h2, __builtin_amdgcn_cvt_pkrtz(y0, y1)) - h2{(_Float16)1024.0f, (_Float16)1024.0f};
+        packed[pp] = __builtin_bit_cast(h2, __builtin_amdgcn_cvt_pkrtz(y0, y1));  // stays biased: 1024 + luma (see BIASED_ZERO)
     }
     order = __builtin_bit_cast(uint32_t, packed[3]);
     Row8 r;
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         r.q[i] = packed[i];
-        if (zero) r.q[i] = h2{(_Float16)0, (_Float16)0};
+        if (zero) r.q[i] = h2_bits(BIASED_ZERO);
     }
     return r;
 }
-// Luma8 input: the bytes are the luma; pairs of them become f16 (1024 + v) by the same v_perm, and the bias leaves exactly
+// Luma8 input: the bytes are the luma; pairs of them become f16 (1024 + v) by the same v_perm, which is the biased row as it is
 __device__ __forceinline__ Row8 luma_row_gray(const Px8 &v, bool zero, uint32_t &order)
 {
-    const h2 bias = h2{(_Float16)1024.0f, (_Float16)1024.0f};
     Row8 r;
-    r.q[0] = byte_pair_lo(v.d[0]) - bias;
-    r.q[1] = byte_pair_hi(v.d[0]) - bias;
-    r.q[2] = byte_pair_lo(v.d[1]) - bias;
-    r.q[3] = byte_pair_hi(v.d[1]) - bias;
+    r.q[0] = byte_pair_lo(v.d[0]);
+    r.q[1] = byte_pair_hi(v.d[0]);
+    r.q[2] = byte_pair_lo(v.d[1]);
+    r.q[3] = byte_pair_hi(v.d[1]);
 #pragma unroll
     for (int i = 0; i < 4; i++)
-        if (zero) r.q[i] = h2{(_Float16)0, (_Float16)0};
+        if (zero) r.q[i] = h2_bits(BIASED_ZERO);
     order = __builtin_bit_cast(uint32_t, r.q[3]);
     return r;
 }
@@ -258,7 +262,7 @@ struct Wave {
     // scan state (lane = row of the band), carried across the 8 strips of a band
     float hs, sum, ring[8];
     uint4 pv;  // previous octet of V (8 x f16)
-    float row_d, row_dinv;  // pass-1 column-window divisor of this lane's row (8 except on the frame)
+    float row_d8, row_dinv8;  // pass-1 column-window divisor d of this lane's row (8 except on the frame) as d / 8 and 8 * fl(1 / d)
     // pass-2 row outputs at the sampled columns of the current half band (lane = row): 8 enter per strip at the
     // top and the file shifts down by 8, so after 4 strips smp[t] is sample slot t of the half band
     float smp[32];
@@ -367,17 +371,19 @@ __device__ __forceinline__ void half_build(Wave &w, int s, int h, const Row8 (&L
     Row8 v;
 #pragma unroll
     for (int i = 0; i < 4; i++) {
-        h2 a = hist[0].q[i] + hist[1].q[i];
-        h2 bb = hist[2].q[i] + hist[3].q[i];
-        h2 cc = hist[4].q[i] + hist[5].q[i];
-        h2 dd = hist[6].q[i] + L[0].q[i];
+        // biased rows: each pair sum is x_b + (y_b - 2048) -- y_b - 2048 in [-1024, -769] and the sum in [0, 510], both exact
+        const h2 two_bias = h2{(_Float16)2048.0f, (_Float16)2048.0f};
+        h2 a = hist[0].q[i] + (hist[1].q[i] - two_bias);
+        h2 bb = hist[2].q[i] + (hist[3].q[i] - two_bias);
+        h2 cc = hist[4].q[i] + (hist[5].q[i] - two_bias);
+        h2 dd = hist[6].q[i] + (L[0].q[i] - two_bias);
         v.q[i] = (a + bb) + (cc + dd);
     }
     *reinterpret_cast<uint4 *>(tile + (row0 + 0) * G::TILE_PITCH + 16 * c) = row_bits(v);
 #pragma unroll
     for (int m = 1; m < 8; m++) {
 #pragma unroll
-        for (int i = 0; i < 4; i++) v.q[i] = (v.q[i] - hist[m - 1].q[i]) + L[m].q[i];  // subtract first: stays <= 2040
+        for (int i = 0; i < 4; i++) v.q[i] = (v.q[i] - hist[m - 1].q[i]) + L[m].q[i];  // both biased: v - hist_b in [-1279, 1016], the sum <= 2040, exact
         *reinterpret_cast<uint4 *>(tile + (row0 + m) * G::TILE_PITCH + 16 * c) = row_bits(v);
     }
     wave_lds_fence();
@@ -427,8 +433,10 @@ __device__ __forceinline__ void row_step(Wave &w, float in2)
 template <bool EDGE_ROWS>
 __device__ __forceinline__ float pass1_value(const Wave &w, float hs)
 {
-    // 64 x pass-1 value at an interior column: Hs (8x8 box sum) for full windows, one IEEE division on the frame rows
-    if (EDGE_ROWS) return div_small(hs * 8.0f, w.row_d, w.row_dinv);
+    // 64 x pass-1 value at an interior column: Hs (8x8 box sum) for full windows, one IEEE division on the frame rows: (8 Hs) / d.
+    // The factor 8 is folded into the Markstein constants (row_d8 = d / 8, exact for d = 4..8, and row_dinv8 = 8 fl(1 / d)): every
+    // intermediate is div_small's scaled by a power of two, so the quotient has the same bits (tools/check_div_small.c) without the multiply.
+    if (EDGE_ROWS) return div_small(hs, w.row_d8, w.row_dinv8);
     return hs;
 }
 
@@ -475,7 +483,7 @@ __device__ __forceinline__ void scan_strip(Wave &w)
         w.hs = hs_sub<0>(w.hs, w.pv.y); row_step<2>(w, e5);
         w.hs = hs_sub<1>(w.hs, w.pv.y);
         {
-            const float in511 = EDGE_ROWS ? div_small(w.hs * 16.0f, w.row_d, w.row_dinv) : w.hs * 2.0f;
+            const float in511 = (EDGE_ROWS ? div_small(w.hs, w.row_d8, w.row_dinv8) : w.hs) * 2.0f;  // (16 Hs) / d = 2 ((8 Hs) / d), same bits
             row_step<3>(w, in511);
         }
         // phase 4, first step: out[508] = (sum - in[504]) / 7   (ring slot of ri = 504 is 0)
@@ -499,8 +507,8 @@ __device__ __forceinline__ void scan_reset(Wave &w, int b)
     const int y = 64 * b + w.lane;
     const int lo = y - 3 < 0 ? 0 : y - 3, hi = y + 4 > 511 ? 511 : y + 4;
     const float d = (float)(hi - lo + 1);
-    w.row_d = d;
-    w.row_dinv = 1.0f / d;
+    w.row_d8 = d * 0.125f;
+    w.row_dinv8 = (1.0f / d) * 8.0f;
 }
 
 // pass-2 column chain over the 64 rows of band b for the sampled columns of one half band.
@@ -755,10 +763,10 @@ __global__ void __launch_bounds__(64, G::WAVES_PER_SIMD) pdq_fused512_kernel(con
 #pragma unroll
     for (int u = 0; u < 8; u++) w.bnew[u] = 0.f;
 
-    // ---- prologue: luma rows 0..3 become the first band's history (rows -3..-1 are outside: zero)
+    // ---- prologue: luma rows 0..3 become the first band's history (rows -3..-1 are outside: biased zero)
     {
         for (int j = 0; j < 3; j++)
-            for (int t = w.lane; t < 64; t += 64) *reinterpret_cast<uint4 *>(lds + G::OFF_STATE + j * 1024 + t * 16) = make_uint4(0, 0, 0, 0);
+            for (int t = w.lane; t < 64; t += 64) *reinterpret_cast<uint4 *>(lds + G::OFF_STATE + j * 1024 + t * 16) = make_uint4(BIASED_ZERO, BIASED_ZERO, BIASED_ZERO, BIASED_ZERO);
         // rows 0..3 x 64 column chunks of 8 px = 256 (row, chunk) slots, 64 per iteration
         uint32_t order = 0;
 #pragma unroll 1
@@ -849,13 +857,13 @@ __global__ void __launch_bounds__(512, 2) pdq_fused512_ll_kernel(const uint8_t *
             for (int k = 0; k < 6; k++) edge_all[k * LL_EDGE_PITCH + 512 + w.lane] = 0.f;
         }
     }
-    // ---- the 7 luma rows above the band's first build step: rows 64 b - 3 .. 64 b + 3 (band 0: rows -3..-1 are outside: zero)
+    // ---- the 7 luma rows above the band's first build step: rows 64 b - 3 .. 64 b + 3 (band 0: rows -3..-1 are outside: biased zero)
     {
         uint32_t order = 0;
 #pragma unroll 1
         for (int it = 0; it < 7; it++) {
             const int row = 64 * band - 3 + it;  // state row `it`; every lane takes one 8-px chunk
-            uint4 bits = make_uint4(0, 0, 0, 0);
+            uint4 bits = make_uint4(BIASED_ZERO, BIASED_ZERO, BIASED_ZERO, BIASED_ZERO);
             if (row >= 0) bits = row_bits(pack_row<G::CH>(load_px8<G::CH>(w.img + (size_t)row * row_stride + (size_t)(8 * w.lane) * G::CH), false, order));
             *reinterpret_cast<uint4 *>(w.lds + G::OFF_STATE + it * 1024 + (8 * w.lane) * 2) = bits;
         }
