@@ -611,7 +611,9 @@ int rph_tiff_release(rph_ctx *ctx);
  *       the decoder checks them all the same);
  *     - a distance that reaches before the first pixel; a copy that runs past the last pixel (refused, not clamped: libwebp refuses);
  *     - a stream that consumes more bits than the chunk holds, anywhere (zero bits are read past the end and the count is checked
- *       after each element of the front and before each symbol of the pixels: libwebp's end-of-stream flag).
+ *       after each element of the front and before each symbol of the pixels: libwebp's end-of-stream flag).  The chunk's own size
+ *       bounds the bits.  libwebp bounds them by the bytes that follow in the file: behind a chunk of odd size it reads the pad byte
+ *       (and whatever chunk comes next), so it decodes some streams that are refused here, never the other way round.
  *   ACCEPTED
  *     - bytes after the last pixel inside the chunk; chunks after the image; bytes after the RIFF size (not read: a RIFF size below the
  *       file length rules, as in libwebp, so a chunk must lie inside it);

@@ -597,8 +597,10 @@ def token_pixels(t):
     return t[1] if t[0] == "ref" else 1
 
 
-def write_pixels(bw, tokens, xsize, cache_bits=0, ent=None, meta_bits=0, n_groups=1, code_kw=None, hack=None):
-    """the codes of every group, then the tokens; an array of ARGB values for tokens stands for that many literals of one group"""
+def write_pixels(bw, tokens, xsize, cache_bits=0, ent=None, meta_bits=0, n_groups=1, code_kw=None, hack=None, lens=None, info=None):
+    """the codes of every group, then the tokens; an array of ARGB values for tokens stands for that many literals of one group.
+    lens: f(group, alphabet 0 .. 4, histogram, the lengths the writer would choose) -> the lengths to use; info: a dict that receives
+    bit_start and bit_end, the writer's bit position in front of the first token and behind the last"""
     code_kw = code_kw or {}
     if isinstance(tokens, np.ndarray):
         assert ent is None and n_groups == 1 and not cache_bits and hack is None
@@ -637,13 +639,16 @@ def write_pixels(bw, tokens, xsize, cache_bits=0, ent=None, meta_bits=0, n_group
         for k, hist in enumerate(hists[g]):
             if not any(hist):
                 hist[0] = 1
-            lens = huffman_lengths(hist)
+            ln = huffman_lengths(hist)
+            ln = lens(g, k, hist, ln) if lens else ln
             hk = hack if (hack and g == 0 and k == (3 if hack in ("max_symbol_big", "repeat_first") else 0)) else None
             if hk == "repeat_first":
-                lens = [8] * 256
-            write_code(bw, lens, hack=hk, **code_kw)
-            ws.append(CodeWriter(lens))
+                ln = [8] * 256
+            write_code(bw, ln, hack=hk, **code_kw)
+            ws.append(CodeWriter(ln))
         writers.append(ws)
+    if info is not None:
+        info["bit_start"] = 8 * len(bw.out) + bw.n
     for t, g in zip(tokens, where):
         ws = writers[g]
         if t[0] == "lit":
@@ -661,6 +666,8 @@ def write_pixels(bw, tokens, xsize, cache_bits=0, ent=None, meta_bits=0, n_group
             s, e, nb = _prefix_encode(t[2])
             ws[4].put(bw, s)
             bw.put(e, nb)
+    if info is not None:
+        info["bit_end"] = 8 * len(bw.out) + bw.n
 
 
 def write_sub_image(bw, px, xsize):
@@ -738,11 +745,11 @@ def to_argb(img):
 
 
 def encode(img, transforms=(), cache_bits=0, meta_bits=None, n_groups=1, refs="none", plane=True, form="simple", alpha=None, vp8x_alpha=None, code_kw=None,
-           tokens=None, hack=None, cache_bits_raw=None, trailing=b"", seed=0, ent_map=None):
+           tokens=None, hack=None, cache_bits_raw=None, trailing=b"", seed=0, ent_map=None, lens=None, info=None):
     """img: (h, w, 3 or 4) uint8.  transforms, in the order written: ('predictor', bits 2 .. 9, mode 0 .. 15 | 'mixed' (modes 0 .. 13) |
     'mixed16' (0 .. 15) | an array of modes per block), ('cross', bits 2 .. 9[, an array (bh, bw, 3) of signed coefficients]), ('green',),
     ('palette'[, declared colours[, the palette as ARGB values]]).  tokens: the main stream's tokens as given (the pixels then are what they decode to).  ent_map: the group of every
-    block of the entropy image, in place of the writer's own pattern."""
+    block of the entropy image, in place of the writer's own pattern.  lens, info: as write_pixels takes them."""
     rng = np.random.default_rng(seed)
     a = to_argb(img)
     h, w = a.shape
@@ -832,7 +839,8 @@ def encode(img, transforms=(), cache_bits=0, meta_bits=None, n_groups=1, refs="n
     if tokens is None:
         plain = refs == "none" and not cache_bits and ent is None and hack is None
         tokens = a.ravel().astype(np.uint32) if plain else tokenize(px, xsize, cache_bits, refs, plane)
-    write_pixels(bw, tokens, xsize, cache_bits, ent, meta_bits or 0, n_groups, code_kw, hack if hack in ("over", "incomplete", "repeat_past", "max_symbol_big", "repeat_first") else None)
+    write_pixels(bw, tokens, xsize, cache_bits, ent, meta_bits or 0, n_groups, code_kw, hack if hack in ("over", "incomplete", "repeat_past", "max_symbol_big", "repeat_first") else None,
+                 lens, info)
     chunk = bw.bytes() + trailing
     if hack == "signature":
         chunk = b"\x2e" + chunk[1:]
