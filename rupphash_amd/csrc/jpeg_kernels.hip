@@ -197,7 +197,8 @@ __device__ __forceinline__ void idct_block(const int16_t *__restrict__ coef, con
                 const int p = unzigzag(n);
                 const uint32_t bit = ((p < 32 ? lo : hi) >> (p & 31)) & 1u;
                 const int32_t v = c[n];
-                c[n] = (bit && (v & p1) == 0) ? (v >= 0 ? v + p1 : v - p1) : v;
+                // (the decoders keep coefficients in 16 bits: -32768 - p1 is 32768 - p1, and the next scan sees that sign)
+                c[n] = (bit && (v & p1) == 0) ? (int32_t)(int16_t)(v >= 0 ? v + p1 : v - p1) : v;
             }
         }
     }
@@ -1016,8 +1017,13 @@ __global__ void __launch_bounds__(64) jpeg_prog_kernel(const uint8_t *__restrict
                     }
                     const uint32_t raw = b.take(s);
                     const int val = raw < (1u << (s - 1)) ? (int)raw - (int)((1u << s) - 1) : (int)raw;
-                    coef[base + zz[k]] = (int16_t)(val * (1 << al));
-                    nz_acc |= 1ull << k;
+                    // History is "the stored coefficient is nonzero": a value whose 16 kept bits are 0 (8 << 13) leaves the zero that is
+                    // there and no history, and a later refinement scan counts it among the zeros of its runs (and may place a value there).
+                    const int16_t st = (int16_t)(val * (1 << al));
+                    if (st) {
+                        coef[base + zz[k]] = st;
+                        nz_acc |= 1ull << k;
+                    }
                     k++;
                     if (k > se) adv = 1;
                 }

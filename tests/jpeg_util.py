@@ -116,12 +116,26 @@ BASELINE_FAULTS = {
 }
 
 
-def encode_baseline(rgb, sampling=((1, 2), (1, 1), (1, 1)), quality_scale=1.0, restart_interval=0, gray=False, sixteen_bit_tables=False, interleaved=True,
-                    fault=None):
-    """A plain baseline (SOF0) encoder: rgb (h, w, 3) uint8 [or (h, w) when gray]; sampling = (H, V) per component.
-    Chroma is box-averaged down.  interleaved=False writes one scan per component (each over the component's own block grid,
-    T.81 A.2.2).  fault: (kind, block[, argument]) of BASELINE_FAULTS, written into that block of the first scan (luma blocks only).
-    Returns the JPEG byte string."""
+QL_STD = np.array([16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62, 18, 22,
+                   37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99])
+QC_STD = np.array([17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99] + [99] * 32)
+
+
+def grid(w, h, sampling):
+    """(hmax, vmax, mcus_x, mcus_y) of a frame; component ci has mcus_y * V by mcus_x * H blocks (the MCU-padded grid)"""
+    hmax = max(s[0] for s in sampling)
+    vmax = max(s[1] for s in sampling)
+    return hmax, vmax, -(-w // (8 * hmax)), -(-h // (8 * vmax))
+
+
+def _i16(v):
+    """v modulo 2^16 into int16's range: what a decoder's (int16_t) store keeps of it"""
+    return ((int(v) + 32768) & 0xFFFF) - 32768
+
+
+def _image_blocks(rgb, sampling, quality_scale, gray, top):
+    """the forward half of the encoders: YCbCr, box-averaged chroma, forward DCT, quantisation.  Returns (h, w, sampling, qts, blocks), blocks
+    per component (blocks high, blocks wide, 8, 8) int64 over the MCU-padded grid, natural order"""
     rgb = np.asarray(rgb)
     if gray:
         h, w = rgb.shape
@@ -131,15 +145,8 @@ def encode_baseline(rgb, sampling=((1, 2), (1, 1), (1, 1)), quality_scale=1.0, r
         h, w, _ = rgb.shape
         r, g, b = [rgb[..., i].astype(np.float64) for i in range(3)]
         comps = [0.299 * r + 0.587 * g + 0.114 * b, -0.168736 * r - 0.331264 * g + 0.5 * b + 128, 0.5 * r - 0.418688 * g - 0.081312 * b + 128]
-    hmax = max(s[0] for s in sampling)
-    vmax = max(s[1] for s in sampling)
-    mcus_x = -(-w // (8 * hmax))
-    mcus_y = -(-h // (8 * vmax))
-    ql = np.array([16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62, 18, 22,
-                   37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99])
-    qc = np.array([17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99] + [99] * 32)
-    top = 65535 if sixteen_bit_tables else 255
-    qts = [np.clip(np.round(q * quality_scale), 1, top).astype(np.int64) for q in (ql, qc)]
+    hmax, vmax, mcus_x, mcus_y = grid(w, h, sampling)
+    qts = [np.clip(np.round(q * quality_scale), 1, top).astype(np.int64) for q in (QL_STD, QC_STD)]
     blocks = []
     for ci, (plane, (H, V)) in enumerate(zip(comps, sampling)):
         fx, fy = hmax // H, vmax // V
@@ -148,127 +155,186 @@ def encode_baseline(rgb, sampling=((1, 2), (1, 1), (1, 1)), quality_scale=1.0, r
         small = full.reshape(ph // fy, fy, pw // fx, fx).mean(axis=(1, 3))
         q = qts[0 if ci == 0 else 1].reshape(8, 8)
         blocks.append(np.round(_fdct_blocks(small) / q).astype(np.int64))
-    out = bytearray(b"\xff\xd8")
+    return h, w, sampling, qts, blocks
 
-    def seg(marker, payload):
-        out.extend(bytes([0xFF, marker]) + (len(payload) + 2).to_bytes(2, "big") + payload)
 
-    for t, q in enumerate(qts if not gray else qts[:1]):
-        zz = q[ZIGZAG]
-        seg(0xDB, bytes([(0x10 if sixteen_bit_tables else 0) | t]) + (b"".join(int(v).to_bytes(2, "big") for v in zz) if sixteen_bit_tables else bytes(int(v) for v in zz)))
-    sof = bytes([8]) + h.to_bytes(2, "big") + w.to_bytes(2, "big") + bytes([len(comps)])
-    for ci, (H, V) in enumerate(sampling):
-        sof += bytes([ci + 1, (H << 4) | V, 0 if ci == 0 else 1])
-    seg(0xC0, sof)
+def _dqt(qts, sixteen_bit_tables):
+    out = b""
+    for t, q in enumerate(qts):
+        zz = np.asarray(q).reshape(64)[ZIGZAG]
+        body = b"".join(int(v).to_bytes(2, "big") for v in zz) if sixteen_bit_tables else bytes(int(v) for v in zz)
+        out += bytes([0xFF, 0xDB]) + (len(body) + 3).to_bytes(2, "big") + bytes([(0x10 if sixteen_bit_tables else 0) | t]) + body
+    return out
+
+
+def _dc_difference(want, pred):
+    """the difference that takes a decoder's prediction `pred` to `want` modulo 2^16, in -32767..32767 (categories 0..15)"""
+    diff = want - pred
+    if not -32767 <= diff <= 32767:
+        diff = _i16(diff)
+        if diff == -32768:
+            raise ValueError(f"DC {want} after {pred}: a difference of 2^15 needs category 16; reach the value over two blocks")
+    return diff
+
+
+def _real_blocks(w, h, sampling, ci, hmax, vmax):
+    """blocks (wide, high) of a component's own grid, what a scan of that component alone covers (T.81 A.2.2)"""
+    H, V = sampling[ci]
+    return -(-(-(-w * H // hmax)) // 8), -(-(-(-h * V // vmax)) // 8)
+
+
+def encode_baseline_coefficients(blocks, qts, w, h, sampling=((1, 2), (1, 1), (1, 1)), restart_interval=0, interleaved=True, sixteen_bit_tables=False, gray=False,
+                                 tables="used", fault=None):
+    """The entropy half of a baseline (SOF0) encoder.  blocks: per component an integer array (blocks high, blocks wide, 8, 8) or (.., 64) over
+    the MCU-padded grid, natural order, quantised; qts: the quantisation tables (64 entries, natural order) of luma and chroma.
+    AC values are int16 except -32768 (categories 1..15).  DC values are what the block is AIMED at: each is coded as the difference from the
+    decoder's prediction modulo 2^16, so a chain 32767, -32768, 32767 costs differences of 1, and values beyond int16 are allowed (the decoders
+    keep the prediction in 32 bits and narrow at the store).  A difference of exactly 2^15 has no category below 16: ValueError.
+    tables: "used" = one table per class and slot, fixed-length codes for the symbols that occur (DC categories to 15 and AC sizes to 15 become
+    codable); "annex_k" = T.81 K.3's tables.  fault: as encode_baseline (Annex K tables only).
+    Returns (bytes, expected): expected = the (total blocks, 64) int16 coefficients a decoder holds afterwards, component-major, raster over the
+    padded grid, natural order -- plain int16 arithmetic on `blocks` (blocks a scan of one component does not cover stay 0)."""
+    if gray:
+        sampling = ((1, 1),)
+    ncomp = len(sampling)
+    assert len(blocks) == ncomp and (tables == "annex_k" or not fault)
+    hmax, vmax, mcus_x, mcus_y = grid(w, h, sampling)
+    blocks = [np.asarray(b).astype(np.int64).reshape(mcus_y * V, mcus_x * H, 64) for b, (H, V) in zip(blocks, sampling)]
+    expected = [np.zeros(b.shape, np.int16) for b in blocks]
     dc_l = DC_L_WIDE if fault and fault[0] in ("dc_cat", "dc_cat_16") else DC_L
-    tables = [(0x00, dc_l), (0x10, AC_L)] + ([] if gray else [(0x01, DC_C), (0x11, AC_C)])
-    for tid, (counts, symbols) in tables:
-        seg(0xC4, bytes([tid]) + bytes(counts) + bytes(symbols))
-    if restart_interval:
-        seg(0xDD, restart_interval.to_bytes(2, "big"))
-    dc_codes = [_codes(*dc_l), _codes(*DC_C)]
-    ac_codes = [_codes(*AC_L), _codes(*AC_C)]
-    pred = [0] * len(comps)
+    pred = [0] * ncomp
     luma_blocks = [0]
+    scans = []  # (component indices, tokens): ("s", "dc" | "ac", slot, symbol) | ("b", value, nbits) | ("rst", n)
 
-    def put_fault(bits, kind, arg):
-        ac = ac_codes[0]
+    def put_fault(toks, kind, arg):
         if kind == "dc_cat":  # the block's DC: the largest difference of the category, the prediction follows it
-            bits.put(*dc_codes[0][arg])
-            bits.put((1 << arg) - 1, arg)
+            toks += [("s", "dc", 0, arg), ("b", (1 << arg) - 1, arg), ("s", "ac", 0, 0x00)]
             pred[0] += (1 << arg) - 1
-            bits.put(*ac[0x00])
         elif kind == "dc_cat_16":  # (refused at the code: no magnitude bits follow)
-            bits.put(*dc_codes[0][16])
+            toks.append(("s", "dc", 0, 16))
         elif kind == "bad_code":
-            bits.put(0xFFFF, 16)
+            toks.append(("b", 0xFFFF, 16))
         elif kind == "run_past_63":
-            for _ in range(3):
-                bits.put(*ac[0xF0])
-            bits.put(*ac[0xF1])
-            bits.put(1, 1)
+            toks += [("s", "ac", 0, 0xF0)] * 3 + [("s", "ac", 0, 0xF1), ("b", 1, 1)]
         elif kind == "zrl_past_63":
-            for _ in range(4):
-                bits.put(*ac[0xF0])
+            toks += [("s", "ac", 0, 0xF0)] * 4
         elif kind == "zrl_to_64":
-            for _ in range(2):
-                bits.put(*ac[0xF0])
-            bits.put(*ac[0xE1])
-            bits.put(1, 1)
-            bits.put(*ac[0xF0])
+            toks += [("s", "ac", 0, 0xF0)] * 2 + [("s", "ac", 0, 0xE1), ("b", 1, 1), ("s", "ac", 0, 0xF0)]
         else:
             raise ValueError(kind)
 
-    def put_block(bits, blk, ci):
+    def put_block(toks, ci, by, bx):
         t = 0 if ci == 0 else 1
-        zz = blk.reshape(64)[ZIGZAG]
+        zz = blocks[ci][by, bx][ZIGZAG].tolist()
         if ci == 0:
             luma_blocks[0] += 1
             if fault and luma_blocks[0] - 1 == fault[1]:
                 if fault[0] not in ("dc_cat", "dc_cat_16"):
-                    bits.put(*dc_codes[0][0])  # DC difference 0
-                put_fault(bits, fault[0], fault[2] if len(fault) > 2 else 12)
+                    toks.append(("s", "dc", 0, 0))  # DC difference 0
+                put_fault(toks, fault[0], fault[2] if len(fault) > 2 else 12)
                 return
-        diff = int(zz[0]) - pred[ci]
-        pred[ci] = int(zz[0])
+        diff = _dc_difference(zz[0], pred[ci])
+        pred[ci] += diff
         s = abs(diff).bit_length()
-        bits.put(*dc_codes[t][s])
+        toks.append(("s", "dc", t, s))
         if s:
-            bits.put(diff if diff >= 0 else diff + (1 << s) - 1, s)
+            toks.append(("b", diff if diff >= 0 else diff + (1 << s) - 1, s))
         run = 0
-        last = np.nonzero(zz[1:])[0]
-        end = (last[-1] + 1) if len(last) else 0
+        end = max([k for k in range(1, 64) if zz[k]], default=0)
         for k in range(1, end + 1):
-            v = int(zz[k])
+            v = zz[k]
             if v == 0:
                 run += 1
                 continue
             while run > 15:
-                bits.put(*ac_codes[t][0xF0])
+                toks.append(("s", "ac", t, 0xF0))
                 run -= 16
             s = abs(v).bit_length()
-            bits.put(*ac_codes[t][(run << 4) | s])
-            bits.put(v if v >= 0 else v + (1 << s) - 1, s)
+            if s > 15:
+                raise ValueError(f"AC {v}: no category below 16")
+            toks.append(("s", "ac", t, (run << 4) | s))
+            toks.append(("b", v if v >= 0 else v + (1 << s) - 1, s))
             run = 0
         if end < 63:
-            bits.put(*ac_codes[t][0x00])
+            toks.append(("s", "ac", t, 0x00))
+        expected[ci][by, bx] = [_i16(pred[ci])] + [_i16(v) for v in blocks[ci][by, bx][1:].tolist()]
 
-    def write_scan(cis):
+    def scan(cis):
         nonlocal pred
-        sos = bytes([len(cis)])
-        for ci in cis:
-            sos += bytes([ci + 1, 0x00 if ci == 0 else 0x11])
-        seg(0xDA, sos + bytes([0, 63, 0]))
-        bits = _Bits()
-        pred = [0] * len(comps)
-        if len(cis) == 1 and len(comps) > 1:  # the component's own grid: ceil(samples / 8) blocks each way, one block per MCU
-            ci = cis[0]
-            H, V = sampling[ci]
-            bw = -(-(-(-w * H // hmax)) // 8)
-            bh = -(-(-(-h * V // vmax)) // 8)
-            units = [[(ci, by, bx)] for by in range(bh) for bx in range(bw)]
+        toks = []
+        pred = [0] * ncomp
+        if len(cis) == 1 and ncomp > 1:  # the component's own grid: ceil(samples / 8) blocks each way, one block per MCU
+            bw, bh = _real_blocks(w, h, sampling, cis[0], hmax, vmax)
+            units = [[(cis[0], by, bx)] for by in range(bh) for bx in range(bw)]
         else:
             units = [[(ci, my * sampling[ci][1] + v, mx * sampling[ci][0] + hh) for ci in cis for v in range(sampling[ci][1]) for hh in range(sampling[ci][0])]
                      for my in range(mcus_y) for mx in range(mcus_x)]
         rst = 0
         for count, unit in enumerate(units):
             if restart_interval and count and count % restart_interval == 0:
-                bits.flush()
-                bits.out.extend(bytes([0xFF, 0xD0 + (rst & 7)]))
+                toks.append(("rst", rst & 7))
                 rst += 1
-                pred = [0] * len(comps)
+                pred = [0] * ncomp
             for ci, by, bx in unit:
-                put_block(bits, blocks[ci][by, bx], ci)
+                put_block(toks, ci, by, bx)
+        scans.append((cis, toks))
+
+    if interleaved or ncomp == 1:
+        scan(list(range(ncomp)))
+    else:
+        for ci in range(ncomp):
+            scan([ci])
+
+    slots = [0] if ncomp == 1 else [0, 1]
+    if tables == "annex_k":
+        defs = {("dc", 0): dc_l, ("ac", 0): AC_L, ("dc", 1): DC_C, ("ac", 1): AC_C}
+    else:
+        defs = {(cls, t): _table_for({k[3] for _, toks in scans for k in toks if k[0] == "s" and k[1] == cls and k[2] == t}, False) for t in slots for cls in ("dc", "ac")}
+    out = bytearray(b"\xff\xd8")
+
+    def seg(marker, payload):
+        out.extend(bytes([0xFF, marker]) + (len(payload) + 2).to_bytes(2, "big") + payload)
+
+    out.extend(_dqt(qts[:len(slots)], sixteen_bit_tables))
+    sof = bytes([8]) + h.to_bytes(2, "big") + w.to_bytes(2, "big") + bytes([ncomp])
+    for ci, (H, V) in enumerate(sampling):
+        sof += bytes([ci + 1, (H << 4) | V, 0 if ci == 0 else 1])
+    seg(0xC0, sof)
+    for t in slots:
+        for cls in ("dc", "ac"):
+            counts, symbols = defs[cls, t]
+            seg(0xC4, bytes([(0x10 if cls == "ac" else 0) | t]) + bytes(counts) + bytes(symbols))
+    if restart_interval:
+        seg(0xDD, restart_interval.to_bytes(2, "big"))
+    codes = {key: _codes(*d) for key, d in defs.items()}
+    for cis, toks in scans:
+        sos = bytes([len(cis)])
+        for ci in cis:
+            sos += bytes([ci + 1, 0x00 if ci == 0 else 0x11])
+        seg(0xDA, sos + bytes([0, 63, 0]))
+        bits = _Bits()
+        for k in toks:
+            if k[0] == "s":
+                bits.put(*codes[k[1], k[2]][k[3]])
+            elif k[0] == "b":
+                bits.put(k[1], k[2])
+            else:
+                bits.flush()
+                bits.out.extend(bytes([0xFF, 0xD0 + k[1]]))
         bits.flush()
         out.extend(bits.out)
-
-    if interleaved or len(comps) == 1:
-        write_scan(list(range(len(comps))))
-    else:
-        for ci in range(len(comps)):
-            write_scan([ci])
     out.extend(b"\xff\xd9")
-    return bytes(out)
+    return bytes(out), np.concatenate([e.reshape(-1, 64) for e in expected])
+
+
+def encode_baseline(rgb, sampling=((1, 2), (1, 1), (1, 1)), quality_scale=1.0, restart_interval=0, gray=False, sixteen_bit_tables=False, interleaved=True,
+                    fault=None):
+    """A plain baseline (SOF0) encoder: rgb (h, w, 3) uint8 [or (h, w) when gray]; sampling = (H, V) per component.
+    Chroma is box-averaged down.  interleaved=False writes one scan per component (each over the component's own block grid,
+    T.81 A.2.2).  fault: (kind, block[, argument]) of BASELINE_FAULTS, written into that block of the first scan (luma blocks only).
+    Returns the JPEG byte string."""
+    h, w, sampling, qts, blocks = _image_blocks(rgb, sampling, quality_scale, gray, 65535 if sixteen_bit_tables else 255)
+    return encode_baseline_coefficients(blocks, qts, w, h, sampling, restart_interval, interleaved, sixteen_bit_tables, gray, tables="annex_k", fault=fault)[0]
 
 
 # ---- a progressive (SOF2) encoder with an arbitrary scan script --------------------------------------------------------------------
@@ -276,36 +342,6 @@ def encode_baseline(rgb, sampling=((1, 2), (1, 1), (1, 1)), quality_scale=1.0, r
 # were first coded, deep successive approximation, end-of-band runs that carry correction bits, sixteen zero-history coefficients stepped
 # over inside a refinement scan, codes longer than the lookup tables.  T.81 G.1.2 procedures as libjpeg's encoder arranges them (correction
 # bits are held back until the symbol they follow is out).
-
-def _quantised_blocks(rgb, sampling, quality_scale, gray):
-    rgb = np.asarray(rgb)
-    if gray:
-        h, w = rgb.shape
-        comps = [rgb.astype(np.float64)]
-        sampling = ((1, 1),)
-    else:
-        h, w, _ = rgb.shape
-        r, g, b = [rgb[..., i].astype(np.float64) for i in range(3)]
-        comps = [0.299 * r + 0.587 * g + 0.114 * b, -0.168736 * r - 0.331264 * g + 0.5 * b + 128, 0.5 * r - 0.418688 * g - 0.081312 * b + 128]
-    hmax = max(s[0] for s in sampling)
-    vmax = max(s[1] for s in sampling)
-    mcus_x = -(-w // (8 * hmax))
-    mcus_y = -(-h // (8 * vmax))
-    ql = np.array([16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62, 18, 22,
-                   37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99])
-    qc = np.array([17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99] + [99] * 32)
-    qts = [np.clip(np.round(q * quality_scale), 1, 255).astype(np.int64) for q in (ql, qc)]
-    blocks = []
-    for ci, (plane, (H, V)) in enumerate(zip(comps, sampling)):
-        fx, fy = hmax // H, vmax // V
-        pw, ph = mcus_x * 8 * hmax, mcus_y * 8 * vmax
-        full = np.pad(plane, ((0, ph - h), (0, pw - w)), mode="edge")
-        small = full.reshape(ph // fy, fy, pw // fx, fx).mean(axis=(1, 3))
-        q = qts[0 if ci == 0 else 1].reshape(8, 8)
-        blk = np.round(_fdct_blocks(small) / q).astype(np.int64)
-        blocks.append(blk.reshape(blk.shape[0], blk.shape[1], 64)[:, :, ZIGZAG])  # zigzag order
-    return h, w, sampling, hmax, vmax, mcus_x, mcus_y, qts, blocks
-
 
 def _table_for(used, long_codes):
     """a Huffman table (counts[16], symbols) for the symbols in `used`: fixed-length codes (the all-ones code stays free), or -- long_codes --
@@ -331,19 +367,30 @@ PROGRESSIVE_FAULTS = {
 }
 
 
-def encode_progressive(rgb, script, sampling=((2, 2), (1, 1), (1, 1)), quality_scale=1.0, gray=False, long_codes=False, fault=None):
-    """script: list of (components, Ss, Se, Ah, Al), components a tuple of indices (several only for DC scans).  Every scan gets its own
-    Huffman table (written in front of it, slot 0 / 1 alternating so that slots are redefined between scans).  fault: (kind, scan) of
-    PROGRESSIVE_FAULTS, put in front of that scan's symbols."""
-    h, w, sampling, hmax, vmax, mcus_x, mcus_y, qts, blocks = _quantised_blocks(rgb, sampling, quality_scale, gray)
-    ncomp = len(blocks)
+def encode_progressive_coefficients(blocks, qts, w, h, script, sampling=((2, 2), (1, 1), (1, 1)), gray=False, sixteen_bit_tables=False, long_codes=False,
+                                    max_corr_bits=900, fault=None):
+    """The entropy half of a progressive (SOF2) encoder.  blocks, qts: as encode_baseline_coefficients, but every value -- AC too -- is what
+    the scans AIM at and may lie beyond int16: a first scan codes sign and magnitude >> Al (below 2^15: ValueError otherwise), a refinement
+    scan sends bit Al of the magnitude.  What a decoder then holds is worked out alongside, in int16 arithmetic by T.81 G.1.2's rules as
+    libjpeg applies them: a first scan stores (int16)(value << Al); a correction bit moves a coefficient that is not 0 away from zero by
+    1 << Al unless its bit Al is set already, wrapping at 16 bits; a coefficient that is 0 when a refinement scan passes it -- never coded,
+    or wrapped to 0 -- is a zero of the run, or becomes +-(1 << Al) when the bit sent for it is 1.  For values within int16 and scripts
+    that refine each band one bit at a time, that is the value itself.  DC: the first scan codes differences of value >> Al modulo 2^16.
+    max_corr_bits: an end-of-band run is cut when this many correction bits wait behind it (libjpeg's encoder: 900 of its 1000-bit buffer).
+    Returns (bytes, expected) as encode_baseline_coefficients."""
+    if gray:
+        sampling = ((1, 1),)
+    ncomp = len(sampling)
+    assert len(blocks) == ncomp
+    hmax, vmax, mcus_x, mcus_y = grid(w, h, sampling)
+    blocks = [np.asarray(b).astype(np.int64).reshape(mcus_y * V, mcus_x * H, 64)[:, :, ZIGZAG] for b, (H, V) in zip(blocks, sampling)]  # zigzag order
+    held = [np.zeros(b.shape, np.int64) for b in blocks]  # the decoder's coefficients, zigzag order
     out = bytearray(b"\xff\xd8")
 
     def seg(marker, payload):
         out.extend(bytes([0xFF, marker]) + (len(payload) + 2).to_bytes(2, "big") + payload)
 
-    for t, q in enumerate(qts if ncomp > 1 else qts[:1]):
-        seg(0xDB, bytes([t]) + bytes(int(v) for v in q[ZIGZAG]))
+    out.extend(_dqt(qts if ncomp > 1 else qts[:1], sixteen_bit_tables))
     sof = bytes([8]) + h.to_bytes(2, "big") + w.to_bytes(2, "big") + bytes([ncomp])
     for ci, (H, V) in enumerate(sampling):
         sof += bytes([ci + 1, (H << 4) | V, 0 if ci == 0 else 1])
@@ -352,29 +399,29 @@ def encode_progressive(rgb, script, sampling=((2, 2), (1, 1), (1, 1)), quality_s
     def units_of(cis):
         if len(cis) == 1:  # the component's own grid (T.81 A.2.2)
             ci = cis[0]
-            H, V = sampling[ci]
-            bw = -(-(-(-w * H // hmax)) // 8) if ncomp > 1 else -(-w // 8)
-            bh = -(-(-(-h * V // vmax)) // 8) if ncomp > 1 else -(-h // 8)
+            bw, bh = _real_blocks(w, h, sampling, ci, hmax, vmax) if ncomp > 1 else (-(-w // 8), -(-h // 8))
             return [(ci, by, bx) for by in range(bh) for bx in range(bw)]
         return [(ci, my * sampling[ci][1] + v, mx * sampling[ci][0] + hh) for my in range(mcus_y) for mx in range(mcus_x) for ci in cis
                 for v in range(sampling[ci][1]) for hh in range(sampling[ci][0])]
 
     for scan_no, (cis, ss, se, ah, al) in enumerate(script):
         toks = []  # ('s', component, symbol) | ('b', value, nbits)
+        p1 = 1 << al
         if ss == 0:
             pred = [0] * ncomp
             for ci, by, bx in units_of(cis):
                 c0 = int(blocks[ci][by, bx, 0])
                 if ah == 0:
-                    v = c0 >> al  # arithmetic shift: the DC point transform
-                    diff = v - pred[ci]
-                    pred[ci] = v
+                    diff = _dc_difference(c0 >> al, pred[ci])  # arithmetic shift: the DC point transform
+                    pred[ci] += diff
+                    held[ci][by, bx, 0] = _i16(pred[ci] << al)
                     s = abs(diff).bit_length()
                     toks.append(("s", ci, s))
                     if s:
                         toks.append(("b", diff if diff >= 0 else diff + (1 << s) - 1, s))
                 else:
                     toks.append(("b", (c0 >> al) & 1, 1))
+                    held[ci][by, bx, 0] |= ((c0 >> al) & 1) << al
         else:
             ci = cis[0]
             eobrun = 0
@@ -393,8 +440,9 @@ def encode_progressive(rgb, script, sampling=((2, 2), (1, 1), (1, 1)), quality_s
                 be = []
 
             for _, by, bx in units_of(cis):
-                zz = blocks[ci][by, bx]
-                mag = [abs(int(v)) >> al for v in zz]  # magnitudes are shifted, not the signed values
+                zz = blocks[ci][by, bx].tolist()
+                cur = held[ci][by, bx].tolist()
+                mag = [abs(v) >> al for v in zz]  # magnitudes are shifted, not the signed values
                 if ah == 0:
                     r = 0
                     for k in range(ss, se + 1):
@@ -407,8 +455,11 @@ def encode_progressive(rgb, script, sampling=((2, 2), (1, 1), (1, 1)), quality_s
                             toks.append(("s", ci, 0xF0))
                             r -= 16
                         s = t.bit_length()
+                        if s > 15:
+                            raise ValueError(f"AC {zz[k]} at Al {al}: no category below 16")
                         toks.append(("s", ci, (r << 4) | s))
                         toks.append(("b", t if zz[k] >= 0 else (~t) & ((1 << s) - 1), s))
+                        cur[k] = _i16((t if zz[k] >= 0 else -t) << al)
                         r = 0
                     if r > 0:
                         eobrun += 1
@@ -417,13 +468,13 @@ def encode_progressive(rgb, script, sampling=((2, 2), (1, 1), (1, 1)), quality_s
                 else:
                     eob = 0
                     for k in range(ss, se + 1):
-                        if mag[k] == 1:
+                        if cur[k] == 0 and mag[k] & 1:
                             eob = k
                     r = 0
                     br = []
                     for k in range(ss, se + 1):
                         t = mag[k]
-                        if t == 0:
+                        if cur[k] == 0 and not t & 1:
                             r += 1
                             continue
                         while r > 15 and k <= eob:
@@ -432,20 +483,24 @@ def encode_progressive(rgb, script, sampling=((2, 2), (1, 1), (1, 1)), quality_s
                             r -= 16
                             toks.extend(("b", bit, 1) for bit in br)
                             br = []
-                        if t > 1:
+                        if cur[k] != 0:
                             br.append(t & 1)
+                            if t & 1 and cur[k] & p1 == 0:
+                                cur[k] = _i16(cur[k] + p1 if cur[k] >= 0 else cur[k] - p1)
                             continue
                         flush_eobrun()
                         toks.append(("s", ci, (r << 4) | 1))
                         toks.append(("b", 0 if zz[k] < 0 else 1, 1))
                         toks.extend(("b", bit, 1) for bit in br)
+                        cur[k] = -p1 if zz[k] < 0 else p1
                         br = []
                         r = 0
                     if r > 0 or br:
                         eobrun += 1
                         be.extend(br)
-                        if eobrun == 0x7FFF or len(be) > 900:
+                        if eobrun == 0x7FFF or len(be) > max_corr_bits:
                             flush_eobrun()
+                held[ci][by, bx] = cur
             flush_eobrun()
             if fault and fault[1] == scan_no:
                 kind = fault[0]
@@ -484,7 +539,16 @@ def encode_progressive(rgb, script, sampling=((2, 2), (1, 1), (1, 1)), quality_s
         bits.flush()
         out.extend(bits.out)
     out.extend(b"\xff\xd9")
-    return bytes(out)
+    unzig = np.argsort(ZIGZAG)
+    return bytes(out), np.concatenate([e[:, :, unzig].reshape(-1, 64) for e in held]).astype(np.int16)
+
+
+def encode_progressive(rgb, script, sampling=((2, 2), (1, 1), (1, 1)), quality_scale=1.0, gray=False, long_codes=False, fault=None):
+    """script: list of (components, Ss, Se, Ah, Al), components a tuple of indices (several only for DC scans).  Every scan gets its own
+    Huffman table (written in front of it, slot 0 / 1 alternating so that slots are redefined between scans).  fault: (kind, scan) of
+    PROGRESSIVE_FAULTS, put in front of that scan's symbols."""
+    h, w, sampling, qts, blocks = _image_blocks(rgb, sampling, quality_scale, gray, 255)
+    return encode_progressive_coefficients(blocks, qts, w, h, script, sampling, gray, long_codes=long_codes, fault=fault)[0]
 
 
 # scan scripts for encode_progressive (three components unless noted)
