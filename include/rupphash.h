@@ -647,6 +647,86 @@ int rph_webp_set_entropy(rph_ctx *ctx, int where);
 int rph_webp_release(rph_ctx *ctx);
 
 /* =====================================================================
+ * GIF decode feeding the hasher: GIF is in the reference's is_image_ext list (scanner.rs:2278) and goes through the image-crate arm of
+ * load_image_fast (scanner.rs:713-734: image 0.25's GifDecoder over the gif crate), followed by the pixel hash and
+ * generate_pdq_features.  The host parses the container up to the end of the first frame's data and joins that frame's sub-blocks into
+ * one stream; one wave per file decodes its LZW codes into palette indices on the device (or the host threads do), one expand kernel
+ * undoes the interlacing, looks up the palette, places the frame on the logical screen and sets alpha, and the pixels are hashed where
+ * they lie; only hashes come back.
+ * What is decoded:
+ *   container    GIF87a and GIF89a: logical screen descriptor, global colour table, every extension before the first image descriptor
+ *                skipped by its sub-blocks.  Of the Graphic Control Extensions (label 0xF9, one sub-block of 4 bytes) the last one before
+ *                the first image descriptor counts: its transparency flag and index.  Disposal, delay, the background colour index, the
+ *                pixel aspect ratio, comments, application blocks (NETSCAPE2.0 loops) and plain text are not used.
+ *   first frame  position and size, local colour table (else the global one), interlace flag.  Nothing after the first frame's data is
+ *                examined: an animated file yields its first frame, as GifDecoder does.
+ *   LZW          codes least significant bit first, minimum code size m of 2 .. 8, Clear 1 << m, EOI Clear + 1, widths m + 1 .. 12
+ *                growing when the next free entry reaches 1 << width; a table of 4096 entries is full: nothing is added and the width
+ *                stays 12 until a Clear ("deferred clear"); a stream whose first code is not a Clear starts from the initial table.
+ * Native pixels (rph_gif_decode, rph_gif_decode_host): always Rgba8 at the size of the logical screen, as image 0.25 reports a GIF:
+ *   a pixel inside the frame has the palette's RGB and alpha 255; one whose index is the transparent index has the palette's RGB and
+ *   alpha 0; an index past the palette's last entry gives (0, 0, 0, 0); a screen pixel outside the frame is (0, 0, 0, 0); the part of a
+ *   frame that reaches past the screen is cut off.
+ *   These rules follow the gif and image crates as recollected: their sources are not in the reference tree, so parity with them is
+ *   UNPINNED (the RGB kept under alpha 0, the transparent black of an out-of-range index and of the screen around a small frame, the
+ *   screen rather than the frame as the image's size).  Where the rules and Pillow (frame 0, convert("RGBA")) must agree -- LZW,
+ *   interlacing, palettes, the transparent index, on files whose frame fills the screen and whose indices lie in the palette -- the
+ *   arithmetic is pinned against Pillow in the tests.
+ * What is hashed follows the PNG section word for word: PDQ through to_luma601 (alpha ignored), pixel hash = blake3 of to_rgba16()
+ * little-endian (v -> v * 257); the pixels are hashed where they lie.  A GIF of the pixels of a palette PNG therefore has that PNG's PDQ
+ * hash and pixel hash (a PNG without tRNS is Rgb8, whose to_rgba16() supplies the same alpha 65535).
+ * ONE RULE for damaged or hostile files, the same in the host parser (gif_host.cpp) and the shared decoder (gif_lzw.h: host threads and
+ * device kernel alike): a file's status does not depend on the other files of its call or on where it was decompressed.  Parity with
+ * the gif crate on damaged input is UNPINNED.
+ *   REFUSED (RPH_ERR_INVALID_ARG)
+ *     - a signature other than GIF87a / GIF89a;
+ *     - a screen descriptor, colour table, extension (label or sub-block), image descriptor, code size byte or data sub-block that
+ *       reaches outside the file;
+ *     - no image descriptor before the trailer or the end of the file; a block introducer other than 0x21 / 0x2C before it;
+ *     - a zero screen width or height; a zero frame width or height;
+ *     - no colour table at all for the first frame;
+ *     - a code above the next free entry;
+ *     - the first code of the stream or after a Clear being above Clear (a Clear after a Clear is accepted);
+ *     - a stream that runs out of bits, or sends EOI, before the frame's w * h indices are produced.
+ *   ACCEPTED
+ *     - decoding stops when the frame is full: further codes, a missing EOI, and a missing block terminator (a file that ends on a
+ *       sub-block boundary) are not examined;
+ *     - a full table without a Clear;
+ *     - anything after the first frame's data; a transparent index past the palette (it matches no pixel that has a colour).
+ *   RPH_ERR_UNSUPPORTED, before any pixel memory is allocated
+ *     - a minimum code size outside 2 .. 8;
+ *     - a screen, or a frame, of more than 2^28 pixels (the PNG bound);
+ *     - a frame whose w * h exceeds the most its joined stream of n bytes can expand to: (4095 - (1 << m)) indices from every m + 1 bits,
+ *       (4095 - (1 << m)) * floor(8 n / (m + 1)) (gif_lzw.h); a frame without data bytes lands here.
+ *   The checks run in file order and the first that fails decides: signature; screen descriptor inside the file, non-zero, its size
+ *   limit; global table; blocks up to the image descriptor; the descriptor inside the file, non-zero frame; local table; a table at all;
+ *   the code size byte present, its range; the sub-block chain; the frame's size limit; the expansion bound.  rph_gif_info stops there;
+ *   every refusal inside the stream has one status.
+ *   VALID BUT SMALL: a screen below 5 px gets valid = 0 with status RPH_OK, and still its pixel hash.
+ * ===================================================================== */
+#define RPH_GIF_DECOMPRESS_HOST 0   /* n_threads host threads decode the LZW streams (gif_lzw.h); the palette indices cross PCIe */
+#define RPH_GIF_DECOMPRESS_DEVICE 1 /* one wave per file on the device; the joined compressed bytes cross PCIe */
+#define RPH_GIF_DECOMPRESS_AUTO 2   /* default: the host: the device won on no measured corpus, 1.2:1 to 164:1 */
+/* Container only, host code, no context: the native layout rph_gif_decode will produce (the logical screen's size, channels 4, bit_depth
+ * 8); returns the file's status by the rule above (the codes themselves are not read). */
+int rph_gif_info(const uint8_t *data, size_t len, uint32_t *w, uint32_t *h, uint32_t *channels, uint32_t *bit_depth);
+/* The whole decoder on the CPU, no context (tests, tools): native pixels, packed rows, w * h * 4 bytes into pixels_out (cap_bytes;
+ * RPH_ERR_CAPACITY if too small). */
+int rph_gif_decode_host(const uint8_t *data, size_t len, void *pixels_out, size_t cap_bytes);
+/* The first frame of one GIF on its screen, decoded on the device: the same native pixels as rph_gif_decode_host. */
+int rph_gif_decode(rph_ctx *ctx, const uint8_t *data, size_t len, void *pixels_out, size_t cap_bytes);
+/* n GIF files -> n PDQ hashes (+ optional quality, 256 coefficients, 8 dihedral hashes, as rph_pdq_hash_batch) and optional pixel
+ * hashes (32 bytes each); the arguments mean what they mean in rph_png_pdq_hash_batch.  status_out[i] by the rule above (the call itself
+ * returns RPH_OK); a file that cannot be decoded has zero outputs and valid 0. */
+int rph_gif_pdq_hash_batch(rph_ctx *ctx, const uint8_t *const *data, const size_t *len, uint32_t n, uint32_t n_threads, uint8_t *hash32_out,
+                           float *quality_out, float *coeffs_out, uint8_t *dihedral_out, uint8_t *valid_out, int32_t *status_out,
+                           uint8_t *pixel_hash32_out);
+/* Where rph_gif_pdq_hash_batch decodes the LZW streams (RPH_GIF_DECOMPRESS_*); the results are identical in every mode. */
+int rph_gif_set_decompress(rph_ctx *ctx, int where);
+/* The GIF path keeps its staging and device buffers in the context between calls; this returns them. */
+int rph_gif_release(rph_ctx *ctx);
+
+/* =====================================================================
  * BLAKE3 identity hashes (blake3 crate 1.x, 32-byte output): the two exact hashes the reference computes next to the PDQ hash.
  *   content hash  blake3::keyed_hash(content_key, file_bytes)                     scanner.rs:1343-1347 (the cache key)
  *                 -> rph_blake3_host per file in the scan loop, or rph_blake3_batch(_dev) for a batch of files

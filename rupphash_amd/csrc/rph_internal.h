@@ -66,6 +66,10 @@ struct rph_ctx {
     std::mutex webp_mu;
     void *webp = nullptr;
     int webp_entropy = RPH_WEBP_ENTROPY_AUTO;
+    // GIF path (gif_pipeline.cpp): the same arrangement; where the frames' LZW streams are decoded (RPH_GIF_DECOMPRESS_*)
+    std::mutex gif_mu;
+    void *gif = nullptr;
+    int gif_decompress = RPH_GIF_DECOMPRESS_AUTO;
 };
 
 // ---- launchers implemented in the .hip files (all asynchronous on `stream`) ----
@@ -154,6 +158,8 @@ void rph_png_forget(rph_ctx *ctx);
 void rph_tiff_forget(rph_ctx *ctx);
 // webp_pipeline.cpp
 void rph_webp_forget(rph_ctx *ctx);
+// gif_pipeline.cpp
+void rph_gif_forget(rph_ctx *ctx);
 void rph_jpeg_forget_threads(rph_ctx *ctx);
 
 // host_grouping.cpp

@@ -13,6 +13,7 @@
 // Every loop is bounded by the segment's input bits or output bytes (tiff_lzw.h), and the host has checked every offset and size.
 #include "rph_internal.h"
 #include "tiff_host.h"
+#include "wave_sink.h"
 
 namespace {
 
@@ -21,41 +22,7 @@ using rpht::Segment;
 
 constexpr uint32_t LDS_SEG = 16384;
 
-// The segment's output through one pointer: LDS or global memory (flat addressing).  Lanes read what other lanes wrote, so a copy
-// begins behind a workgroup fence (the block is one wave).
-struct DevSegSink {
-    uint8_t *out;
-    uint64_t cap_, n;
-    uint32_t lane;
-    __device__ uint64_t pos() const { return n; }
-    __device__ uint64_t cap() const { return cap_; }
-    __device__ __forceinline__ void lit(uint32_t b)
-    {
-        if (lane == 0) out[n] = (uint8_t)b;
-        n++;
-    }
-    __device__ __forceinline__ void copy(uint64_t from, uint32_t len)
-    {
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        const uint64_t dist = n - from;
-        for (uint32_t base = 0; base < len; base += 64) {
-            const uint32_t i = base + lane;
-            // (every source byte lies below n: no step of a copy reads what an earlier step of it wrote)
-            if (i < len) out[n + i] = out[from + (dist >= len ? i : i % dist)];
-        }
-        n += len;
-    }
-    __device__ __forceinline__ void span(const uint8_t *p, uint32_t len)
-    {
-        for (uint32_t i = lane; i < len; i += 64) out[n + i] = p[i];
-        n += len;
-    }
-    __device__ __forceinline__ void fill(uint8_t b, uint32_t len)
-    {
-        for (uint32_t i = lane; i < len; i += 64) out[n + i] = b;
-        n += len;
-    }
-};
+using DevSegSink = WaveSink;  // the segment's output, LDS or global memory, written by the whole wave
 
 __global__ void __launch_bounds__(64) tiff_lzw_kernel(const uint8_t *__restrict__ comp, const Segment *__restrict__ segs, uint8_t *dec, int32_t *__restrict__ status)
 {

@@ -345,6 +345,60 @@ class Engine:
               "rph_webp_pdq_hash_batch")
         return out
 
+    # ---- GIF (include/rupphash.h, GIF section) ----
+    @staticmethod
+    def gif_info(data):
+        """(w, h, channels, bit_depth) of the native pixels (host code), or raises RphError by the damaged-file rule."""
+        w, h, c, d = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        check(_lib.load().rph_gif_info(data, len(data), C.byref(w), C.byref(h), C.byref(c), C.byref(d)), "rph_gif_info")
+        return w.value, h.value, c.value, d.value
+
+    @staticmethod
+    def _gif_array(data):
+        w, h, c, _ = Engine.gif_info(data)
+        return np.zeros((h, w, c), np.uint8)  # (always 4 channels)
+
+    @staticmethod
+    def gif_decode_host(data):
+        """The whole decoder on the CPU: (h, w, 4) Rgba8 at the logical screen's size, uint8."""
+        out = Engine._gif_array(data)
+        check(_lib.load().rph_gif_decode_host(data, len(data), _ptr(out), out.nbytes), "rph_gif_decode_host")
+        return out
+
+    def gif_decode(self, data):
+        """The first frame of one GIF byte string on its screen, decoded on the device: the same array as gif_decode_host."""
+        out = self._gif_array(data)
+        check(self.L.rph_gif_decode(self.ctx, data, len(data), _ptr(out), out.nbytes), "rph_gif_decode")
+        return out
+
+    def gif_set_decompress(self, where):
+        """0 = host threads decode the LZW streams, 1 = the device (one wave per file), 2 = automatic (default)"""
+        check(self.L.rph_gif_set_decompress(self.ctx, int(where)), "rph_gif_set_decompress")
+
+    def gif_release(self):
+        """give the GIF path's cached staging / device buffers back"""
+        check(self.L.rph_gif_release(self.ctx), "rph_gif_release")
+
+    def gif_pdq_hash_batch(self, files, threads=0, want_quality=True, want_coeffs=False, want_dihedral=False, want_pixel_hash=False):
+        """files: list of GIF byte strings (any mix), or the tuple jpeg_file_list() made of one.  Returns dict(hash, quality, coeffs,
+        dihedral, valid, status[, pixel_hash]) as jpeg_pdq_hash_batch: status[i] != 0 for a file the rule refuses (zero outputs),
+        valid[i] = 0 with status 0 for an image below 5 px (which still has its pixel hash)."""
+        arr, lens, n = files if isinstance(files, tuple) else self.jpeg_file_list(files)
+        out = {
+            "hash": np.zeros((n, 32), np.uint8),
+            "quality": np.zeros(n, np.float32) if want_quality else None,
+            "coeffs": np.zeros((n, 256), np.float32) if want_coeffs else None,
+            "dihedral": np.zeros((n, 8, 32), np.uint8) if want_dihedral else None,
+            "valid": np.zeros(n, np.uint8),
+            "status": np.zeros(n, np.int32),
+        }
+        if want_pixel_hash:
+            out["pixel_hash"] = np.zeros((n, 32), np.uint8)
+        check(self.L.rph_gif_pdq_hash_batch(self.ctx, arr, lens, n, int(threads), _ptr(out["hash"]), _ptr(out["quality"]), _ptr(out["coeffs"]),
+                                            _ptr(out["dihedral"]), _ptr(out["valid"]), _ptr(out["status"]), _ptr(out.get("pixel_hash"))),
+              "rph_gif_pdq_hash_batch")
+        return out
+
     # ---- BLAKE3 identity hashes ----
     @staticmethod
     def blake3_host(data, key=None):

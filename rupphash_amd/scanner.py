@@ -6,6 +6,7 @@
     load_image_fast ("jpg" | "jpeg" arm)           scanner.rs:461-508
     load_png (the "png" arm, image + png crates)    scanner.rs:461-736 (load_image_fast's generic path for .png)
     load_tiff (the TiffDecoder arm)                scanner.rs:628-708
+    load_gif (the image-crate arm for .gif)        scanner.rs:713-734
     pixel_hash (--pixel-hash)                      scanner.rs:1393-1404
     identical_duplicates                           scanner.rs:1843-1864 (analyze_group steps 1-3)
 File-name logic after the union-find (merge_groups_by_stem, the sorting inside process_raw_groups) stays with the caller.
@@ -55,6 +56,18 @@ def load_tiff(path, data, engine=None):
     if ext not in ("tif", "tiff"):
         raise ValueError(f"load_tiff: '{ext}' is not a TIFF file name")
     return (engine or default_engine()).tiff_decode(data)
+
+
+def load_gif(path, data, engine=None):
+    """The image-crate arm of load_image_fast for a .gif (scanner.rs:713-734): the first frame on its logical screen, decoded on the
+    device and returned as (h, w, 4) uint8 Rgba8, the native layout of the header's GIF section.  A file the rule refuses raises
+    RphError; extensions other than gif raise ValueError.  load_image_fast itself stays JPEG-only."""
+    import os
+
+    ext = os.path.splitext(str(path))[1].lstrip(".").lower()
+    if ext != "gif":
+        raise ValueError(f"load_gif: '{ext}' is not a GIF file name")
+    return (engine or default_engine()).gif_decode(data)
 
 
 def pixel_hash(image, engine=None):
