@@ -66,6 +66,10 @@ struct Geo {
     static constexpr int OFF_PARK_E = OFF_PARK_C + (PARK ? 9 * 64 * 4 : 0);  // [9][6] floats
     static constexpr int LDS_BYTES = OFF_PARK_E + (PARK ? 9 * 6 * 4 : 0);    // SW 64: 20440 B (17920 without the parked states), SW 128: 26112 B
     static constexpr int WAVES_PER_SIMD = 2;
+    // Loads that used to be issued where their data is needed -- rows 0..3 of the image, the edge pixels of every band -- go out ahead
+    // (kernel head; col_pass of the band before).  The 128-px build sits at 256 VGPRs and answers either with a spilled register, so
+    // it keeps the serial prologue and loads a band's edge pixels at the band's start.
+    static constexpr bool AHEAD = SW == 64;
     static_assert(64 * 33 * 4 <= TILE_BYTES, "sample transpose buffer must fit in the dead V tile");
     static_assert((NG - 1) * 7 * CL * 16 <= (NH == 2 ? 32 : 64) * TILE_PITCH, "exchange area must fit");
     static_assert(rph::TAIL_LDS_FLOATS * 4 <= TILE_BYTES, "tail scratch must fit in the dead V tile");
@@ -514,14 +518,17 @@ __device__ __forceinline__ void scan_reset(Wave &w, int b)
 // pass-2 column chain over the 64 rows of band b for the sampled columns of one half band.
 // First half: sample slots 0..31 = [dummy, j = 0..30] -> lanes j = 0..30 read slot j + 1.
 // Second half: slots 0..31 = j = 31..62, slot 32 = j = 63      -> lanes j = 31..63 read slot j - 31.
-template <class G>
-__device__ __forceinline__ void col_pass(Wave &w, int b, bool second_half)
+// NEXT_EDGE: the edge pixels of band b + 1 are requested here, once the samples have left their registers; the chain below and the
+// band's tail rows cover the round trip (the fence keeps the loads from sinking to their use in the next band's edge_band)
+template <class G, bool NEXT_EDGE = false>
+__device__ __forceinline__ void col_pass(Wave &w, int b, bool second_half, Px8 (*epx)[2] = nullptr)
 {
     // transpose through the V tile, which is dead between the last scan of the half band and the next tile build
     float *tb = reinterpret_cast<float *>(w.lds + G::OFF_TILE);
 #pragma unroll
     for (int t = 0; t < 32; t++) tb[w.lane * SAMP_PITCH + t] = w.smp[t];
     tb[w.lane * SAMP_PITCH + 32] = w.smp_last;
+    if (NEXT_EDGE) edge_band_issue<G>(w, b + 1, *epx);
     wave_lds_fence();
     const bool active = second_half ? (w.lane >= 31) : (w.lane < 31);
     if (active) {
@@ -557,17 +564,19 @@ __device__ __forceinline__ void col_pass(Wave &w, int b, bool second_half)
 
 // edge pre-pass: pass-1 values (x64) of columns 0,1,2,508,509,510 for V rows 64b .. 64b+63
 //   (FIRST: also consumes the chain's phase 1 = luma rows 0..3)
+// The two loads of luma row y (columns 0..7 and 504..511) are issued apart from their use: the wave that walks a whole image has them
+// in flight long before edge_band needs them (band 0: with the image head, band b + 1: during band b's second column chain)
 template <int CH>
-__device__ __forceinline__ void edge_rowvals(const Wave &w, int y, bool live, float (&rv)[6])
+__device__ __forceinline__ void edge_issue(const Wave &w, int y, Px8 (&e)[2])
+{
+    const int yc = y > 511 ? 511 : y;
+    e[0] = load_px8<CH>(w.img + (size_t)yc * w.row_stride);
+    e[1] = load_px8<CH>(w.img + (size_t)yc * w.row_stride + 504 * CH);
+}
+__device__ __forceinline__ void edge_values(const float (&l)[8], const float (&r)[8], bool live, float (&rv)[6])
 {
     // lane = luma row y: R = horizontal clipped window sum of luma (exact), rowval x 64 = (64 R) / window; the numerators are
     // multiples of 64 below 2^17 and the divisors 5, 6, 7, so div_small gives the IEEE quotient
-    const int yc = y > 511 ? 511 : y;
-    const Px8 pl = load_px8<CH>(w.img + (size_t)yc * w.row_stride);
-    const Px8 pr = load_px8<CH>(w.img + (size_t)yc * w.row_stride + 504 * CH);
-    float l[8], r[8];
-    luma8<CH>(pl, l);
-    luma8<CH>(pr, r);
     const float r0 = (((l[0] + l[1]) + l[2]) + l[3]) + l[4];
     const float r1 = r0 + l[5];
     const float r2 = r1 + l[6];
@@ -585,13 +594,39 @@ __device__ __forceinline__ void edge_rowvals(const Wave &w, int y, bool live, fl
         for (int k = 0; k < 6; k++) rv[k] = 0.f;
     }
 }
+template <int CH>
+__device__ __forceinline__ void edge_compute(const Px8 (&e)[2], bool live, float (&rv)[6])
+{
+    float l[8], r[8];
+    luma8<CH>(e[0], l);
+    luma8<CH>(e[1], r);
+    edge_values(l, r, live, rv);
+}
+template <int CH>
+__device__ __forceinline__ void edge_rowvals(const Wave &w, int y, bool live, float (&rv)[6])
+{
+    Px8 e[2];
+    edge_issue<CH>(w, y, e);
+    edge_compute<CH>(e, live, rv);
+}
 
 template <class G>
 __device__ __forceinline__ void edge_prologue(Wave &w)
 {
     float *edge = reinterpret_cast<float *>(w.lds + G::OFF_EDGE);
     float rv[6];
-    edge_rowvals<G::CH>(w, w.lane & 3, true, rv);
+    {
+        // luma rows 0..3 are already in the band history (state rows 3..6) as biased f16: columns 0..7 and 504..511 of row lane & 3
+        const uint8_t *row = w.lds + G::OFF_STATE + (3 + (w.lane & 3)) * 1024;
+        const h8 hl = *reinterpret_cast<const h8 *>(row), hr = *reinterpret_cast<const h8 *>(row + 504 * 2);
+        float l[8], r[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            l[i] = (float)hl[i] - 1024.0f;
+            r[i] = (float)hr[i] - 1024.0f;
+        }
+        edge_values(l, r, true, rv);
+    }
     if (w.lane < 4) {
 #pragma unroll
         for (int k = 0; k < 6; k++) edge[k * 64 + w.lane] = rv[k];
@@ -617,14 +652,17 @@ __device__ __forceinline__ void edge_prologue(Wave &w)
     wave_lds_fence();
 }
 
-template <class G, int KIND>  // 0 = first band, 1 = middle, 2 = last band
-__device__ __forceinline__ void edge_band(Wave &w, int b)
+template <class G>
+__device__ __forceinline__ void edge_band_issue(const Wave &w, int b, Px8 (&epx)[2]) { edge_issue<G::CH>(w, 64 * b + 4 + w.lane, epx); }
+
+template <class G, int KIND>  // 0 = first band, 1 = middle, 2 = last band; epx: the band's edge pixels (edge_band_issue), in flight
+__device__ __forceinline__ void edge_band(Wave &w, int b, const Px8 (&epx)[2])
 {
     float *edge = reinterpret_cast<float *>(w.lds + G::OFF_EDGE);
     {
         float rv[6];
         const int y = 64 * b + 4 + w.lane;
-        edge_rowvals<G::CH>(w, y, y < 512, rv);
+        edge_compute<G::CH>(epx, y < 512, rv);
 #pragma unroll
         for (int k = 0; k < 6; k++) edge[k * 64 + w.lane] = rv[k];
     }
@@ -688,11 +726,16 @@ __device__ __forceinline__ void store_samples(const Wave &w, float *band_samples
 // LL = false: the band of a wave that walks the whole image (edge chains, column chain and tail carried from band to band).
 // LL = true: the band of one of the eight waves that share an image (pdq_fused512_ll_kernel): the edge values of the band are already
 // in the wave's edge area, the prefetch stops at the band's end, and the pass-2 row samples go to `samples` for the final chain.
+// epx (LL = false, Geo::AHEAD): in, the edge pixels of this band, in flight; out, those of band b + 1 (nothing for the last band).
+// Without Geo::AHEAD the band loads them itself, here, and waits.
 template <class G, int KIND, bool LL = false>
-__device__ __forceinline__ void do_band(Wave &w, int b, Px8 (&pre)[8], float *samples = nullptr)
+__device__ __forceinline__ void do_band(Wave &w, int b, Px8 (&pre)[8], float *samples, Px8 (&epx)[2])
 {
     constexpr bool EDGE_ROWS = KIND != 1;
-    if (!LL) edge_band<G, KIND>(w, b);
+    if (!LL) {
+        if (!G::AHEAD) edge_band_issue<G>(w, b, epx);
+        edge_band<G, KIND>(w, b, epx);
+    }
     scan_reset(w, b);
 #pragma unroll 1
     for (int s = 0; s < G::NSTRIP; s++) {
@@ -724,11 +767,17 @@ __device__ __forceinline__ void do_band(Wave &w, int b, Px8 (&pre)[8], float *sa
             if (s == G::NSTRIP - 1) store_samples<G>(w, samples, true);
         } else {
             if (s == G::NSTRIP / 2 - 1) col_pass<G>(w, b, false);
-            if (s == G::NSTRIP - 1) col_pass<G>(w, b, true);
+            if (!G::AHEAD && s == G::NSTRIP - 1) col_pass<G>(w, b, true);
         }
         wave_lds_fence();
     }
     if (LL) return;
+    if (G::AHEAD) {
+        // after the strip loop, not in its last trip: the pixels requested here are then live only from this point to the next band's
+        // edge_band, not around the strip loop
+        col_pass<G, KIND != 2>(w, b, true, &epx);
+        wave_lds_fence();
+    }
     // band b completed decimated rows i = 8 b + u - 1 (u = 0 of band 0 is a dummy): feed them to the tail in order
 #pragma unroll
     for (int u = 0; u < 8; u++)
@@ -748,6 +797,17 @@ __global__ void __launch_bounds__(64, G::WAVES_PER_SIMD) pdq_fused512_kernel(con
     w.row_stride = row_stride;
     w.rs32 = (uint32_t)row_stride;
     w.lane = threadIdx.x;
+    // ---- every load of the image head goes out before anything waits for one: rows 0..3 (lane = 8-px chunk), the edge pixels of
+    // band 0, the first half tile.  One round trip instead of six; the scan state is not live yet, so the registers are there.
+    // (Without Geo::AHEAD only the first half tile goes out here.)
+    Px8 head[4], epx[2], pre[8];
+    if (G::AHEAD) {
+#pragma unroll
+        for (int row = 0; row < 4; row++) head[row] = load_px8<G::CH>(w.img + (size_t)row * row_stride + (size_t)(8 * w.lane) * G::CH);
+        edge_band_issue<G>(w, 0, epx);
+    }
+    half_issue<G>(w, 0, 0, 0, pre);
+    wave_lds_fence();  // the loads stay above everything that follows
     w.csum = 0.f;
     w.smp_last = 0.f;
 #pragma unroll
@@ -767,24 +827,28 @@ __global__ void __launch_bounds__(64, G::WAVES_PER_SIMD) pdq_fused512_kernel(con
     {
         for (int j = 0; j < 3; j++)
             for (int t = w.lane; t < 64; t += 64) *reinterpret_cast<uint4 *>(lds + G::OFF_STATE + j * 1024 + t * 16) = make_uint4(BIASED_ZERO, BIASED_ZERO, BIASED_ZERO, BIASED_ZERO);
-        // rows 0..3 x 64 column chunks of 8 px = 256 (row, chunk) slots, 64 per iteration
         uint32_t order = 0;
+        if (G::AHEAD) {
+#pragma unroll
+            for (int row = 0; row < 4; row++)
+                *reinterpret_cast<uint4 *>(lds + G::OFF_STATE + (3 + row) * 1024 + (8 * w.lane) * 2) = row_bits(pack_row<G::CH>(head[row], false, order));
+        } else {
 #pragma unroll 1
-        for (int it = 0; it < 4; it++) {
-            const int slot = it * 64 + w.lane;
-            const int chunk = slot & 63, row = slot >> 6;
-            const Px8 p = load_px8<G::CH>(w.img + (size_t)row * row_stride + (size_t)(8 * chunk) * G::CH);
-            *reinterpret_cast<uint4 *>(lds + G::OFF_STATE + (3 + row) * 1024 + (8 * chunk) * 2) = row_bits(pack_row<G::CH>(p, false, order));
+            for (int it = 0; it < 4; it++) {  // rows 0..3 x 64 column chunks of 8 px = 256 (row, chunk) slots, 64 per iteration: a round trip each
+                const int slot = it * 64 + w.lane;
+                const int chunk = slot & 63, row = slot >> 6;
+                const Px8 p = load_px8<G::CH>(w.img + (size_t)row * row_stride + (size_t)(8 * chunk) * G::CH);
+                *reinterpret_cast<uint4 *>(lds + G::OFF_STATE + (3 + row) * 1024 + (8 * chunk) * 2) = row_bits(pack_row<G::CH>(p, false, order));
+            }
         }
     }
+    wave_lds_fence();
     edge_prologue<G>(w);
 
-    Px8 pre[8];
-    half_issue<G>(w, 0, 0, 0, pre);
-    do_band<G, 0>(w, 0, pre);
+    do_band<G, 0>(w, 0, pre, nullptr, epx);
 #pragma unroll 1
-    for (int b = 1; b < 7; b++) do_band<G, 1>(w, b, pre);
-    do_band<G, 2>(w, 7, pre);
+    for (int b = 1; b < 7; b++) do_band<G, 1>(w, b, pre, nullptr, epx);
+    do_band<G, 2>(w, 7, pre, nullptr, epx);
 
     // pass-2 column chain, phase 4 first step: out[508] = (csum - in[504]) / 7  (ring slot 0), unscale by 64
     if (G::PARK) {
@@ -821,7 +885,8 @@ __device__ __forceinline__ void ll_band(Wave &w, int b, float *samples)
 {
     Px8 pre[8];
     half_issue<G>(w, b, 0, 0, pre);
-    do_band<G, KIND, true>(w, b, pre, samples);
+    Px8 none[2];  // the band's edge values are already in the wave's edge area
+    do_band<G, KIND, true>(w, b, pre, samples, none);
 }
 
 template <class G>
