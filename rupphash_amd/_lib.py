@@ -186,6 +186,11 @@ SIGNATURES = {
     "rph_stream": (C.c_void_p, [_vp]),
 }
 
+# exports that are NOT in include/rupphash.h (debug / tests only), bound the same way
+DEBUG_SIGNATURES = {
+    "rph_debug_copy_thumbnails": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32]),
+}
+
 _lib = None
 
 
@@ -224,7 +229,7 @@ def load():
                 "rupphash_amd has no CPU fallback.")
         _one_hip_runtime()
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(DEBUG_SIGNATURES.items()):
             f = getattr(L, name)  # AttributeError if the library does not export what the header declares
             f.restype = res
             f.argtypes = args

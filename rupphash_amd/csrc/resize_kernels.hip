@@ -574,6 +574,11 @@ int rph_launch_pdq_resized(rph_ctx *ctx, const uint8_t *d_px, uint32_t n, uint32
     const size_t need = (full + tmp + small) * chunk;
     RPH_TRY(ctx->rz_scratch.acquire(stream, need));
     uint8_t *p_luma = ctx->rz_scratch.data(), *p_tmp = p_luma + full * chunk, *p_small = p_tmp + tmp * chunk;
+    ctx->rz_last.offset = (size_t)(p_small - p_luma);
+    ctx->rz_last.n = chunk >= n ? n : 0;
+    ctx->rz_last.nw = nw;
+    ctx->rz_last.nh = nh;
+    ctx->rz_last.pitch = np;
     for (uint32_t first = 0; first < n; first += chunk) {
         const uint32_t m = std::min(chunk, n - first);
         if (fused) {
@@ -610,11 +615,24 @@ int rph_launch_pdq_resized(rph_ctx *ctx, const uint8_t *d_px, uint32_t n, uint32
     return ctx->rz_scratch.publish(stream);
 }
 
-// debug / tests: the thumbnails the last pre-downsample call of this context left in its scratch (first `bytes` bytes, rows of align16(new_w))
-extern "C" int rph_debug_copy_thumbnails(rph_ctx *ctx, void *host_dst, size_t bytes)
+// debug / tests: the n thumbnails of new_w x new_h the last pre-downsample call of this context left in its scratch, packed into host_dst
+// ([n][new_h][new_w] bytes).  The fused forms keep rows of align16(new_w) and the two-pass form keeps the thumbnails behind its luma and
+// half-resized planes: both are recorded by the call, and a request for another count or size than the call's is refused.  ONLY VALID
+// after a call of at most one chunk (a call of several chunks reuses the scratch for each, and is refused here), and with no other
+// pre-downsample call of this context in between.  Not part of include/rupphash.h.
+extern "C" int rph_debug_copy_thumbnails(rph_ctx *ctx, void *host_dst, uint32_t n, uint32_t new_w, uint32_t new_h)
 {
-    if (!ctx || !host_dst || bytes > ctx->rz_scratch.capacity()) return RPH_ERR_INVALID_ARG;
+    if (!ctx || !host_dst || n == 0) return RPH_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    const auto &L = ctx->rz_last;
+    if (n != L.n || new_w != L.nw || new_h != L.nh || L.offset + (size_t)L.pitch * L.nh * L.n > ctx->rz_scratch.capacity()) {
+        rph_set_error("rph_debug_copy_thumbnails: the last pre-downsample call left %u thumbnails of %ux%u in one chunk, not %u of %ux%u", L.n, L.nw, L.nh, n, new_w,
+                      new_h);
+        return RPH_ERR_INVALID_ARG;
+    }
+    RPH_HIP_CHECK(hipSetDevice(ctx->device));
     RPH_HIP_CHECK(hipDeviceSynchronize());
-    RPH_HIP_CHECK(hipMemcpy(host_dst, ctx->rz_scratch.data(), bytes, hipMemcpyDeviceToHost));
+    // (images follow each other at pitch * new_h: n * new_h rows of one pitch)
+    RPH_HIP_CHECK(hipMemcpy2D(host_dst, new_w, ctx->rz_scratch.data() + L.offset, L.pitch, new_w, (size_t)n * new_h, hipMemcpyDeviceToHost));
     return RPH_OK;
 }

@@ -30,6 +30,11 @@ struct rph_ctx {
     std::mutex pipe_mu;
     void *pipe = nullptr;
     void *axis_cache = nullptr;  // per-geometry coefficient tables of the pre-downsample, kept across calls (resize_kernels.hip)
+    // where the last pre-downsample call left its thumbnails in rz_scratch (rph_debug_copy_thumbnails; n = 0: the call took several chunks)
+    struct {
+        size_t offset = 0;
+        uint32_t n = 0, nw = 0, nh = 0, pitch = 0;
+    } rz_last;
     // 2 = fp4 MFMA formulation of the sweep's fast path, popcount-sorted {0,1} operands for plain all-pairs sweeps (default),
     // 3 = fp4 MFMA with +-1 operands everywhere, 4 = sorted {0,1} at every size, 1 = int8 MFMA, 0 = VALU xor + popcount
     int hamming_kernel = 2;

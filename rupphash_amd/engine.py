@@ -461,6 +461,15 @@ class Engine:
         check(self.L.rph_pdq_hash_batch_dev(self.ctx, d_px, n, w, h, channels, row_stride, image_stride, d_hash, d_quality,
                                             d_coeffs, d_dihedral, d_valid, stream), "rph_pdq_hash_batch_dev")
 
+    def debug_thumbnails(self, n, nw, nh):
+        """The thumbnails the last pre-downsample call (a side > 512 px) of this context left in its scratch: (n, nh, nw) uint8, the
+        align16(nw) row pitch of the fused forms cut away, the two-pass form's planes in front of them skipped.  Debug / tests only: ONLY
+        VALID after a call of at most one chunk (the library refuses the read-back after a call of several), with no other
+        pre-downsample call on this context in between -- so after pdq_hash_batch_dev, or a pdq_hash_batch of at most 64 MiB of pixels."""
+        out = np.zeros((n, nh, nw), np.uint8)
+        check(self.L.rph_debug_copy_thumbnails(self.ctx, _ptr(out), n, nw, nh), "rph_debug_copy_thumbnails")
+        return out
+
     def pdq_hashes_from_coeffs(self, coeffs, want_hash=True, want_dihedral=True):
         coeffs = np.ascontiguousarray(coeffs, np.float32).reshape(-1, 256)
         n = len(coeffs)

@@ -351,6 +351,16 @@ def valid_files():
     add("small_1x1", image_gif([[1]], colour_palette(2, 36)))
     add("small_4x9", image_gif(rng.integers(0, 4, (9, 4)), colour_palette(4, 36)))
     add("small_screen_large_frame", image_gif(rng.integers(0, 4, (9, 9)), colour_palette(4, 36), screen=(3, 3), pos=(0, 0)))
+    # screens with a side above 512 px: the hasher box-downsamples them to a thumbnail first (Rgba8 at the screen's pitch)
+    big = np.random.default_rng(37)  # (a generator of their own: the files above stay what they were)
+
+    def scene(fh, fw, colours):
+        yy, xx = np.mgrid[0:fh, 0:fw]
+        return ((xx // 23 + 2 * (yy // 17) + (xx * yy) // 4099 + big.integers(0, 2, (fh, fw))) % colours).astype(np.uint8)
+
+    add("above_512_700x90", image_gif(scene(90, 700, 64), colour_palette(64, 38)))
+    add("above_512_90x700", image_gif(scene(700, 90, 64), colour_palette(64, 39), interlace=True))
+    add("above_512_1024x600_frame_at_offset_transparent", image_gif(scene(500, 900, 32), colour_palette(32, 40), screen=(1024, 600), pos=(61, 37), trans=5))
     return out
 
 

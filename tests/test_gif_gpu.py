@@ -112,10 +112,20 @@ def test_one_mixed_call_gives_every_file_what_it_gets_alone(eng, alone, mode):
     assert small >= 5
 
 
-def test_hashes_are_those_of_the_decoded_pixels(eng):
-    """hash, quality, coefficients and dihedral = rph_pdq_hash_batch, pixel hashes = rph_pixel_hash_batch, on the Rgba8 pixels"""
+def test_hashes_are_those_of_the_decoded_pixels(eng, oracle):
+    """hash, quality, coefficients and dihedral = rph_pdq_hash_batch, pixel hashes = rph_pixel_hash_batch, on the Rgba8 pixels; files with
+    a side above 512 px (pre-downsampled from Rgba8 rows at the screen's pitch) are held to the CPU oracle on the host-decoded pixels too"""
     out = _batch(eng, [d for _, d in good_files()], DEVICE)
     assert not out["status"].any()
+    large = [k for k, px in enumerate(host_pixels()) if max(px.shape[:2]) > 512]
+    assert sorted(host_pixels()[k].shape[:2] for k in large) == [(90, 700), (600, 1024), (700, 90)]
+    for k in large:
+        name = good_files()[k][0]
+        rc, coeffs, q = oracle.pdq_features(host_pixels()[k])
+        assert rc == 0 and out["valid"][k] == 1, name
+        assert out["coeffs"][k].tobytes() == coeffs.tobytes(), name
+        assert out["quality"][k].tobytes() == np.float32(q).tobytes(), name
+        assert np.array_equal(out["hash"][k], oracle.to_hash(coeffs)) and np.array_equal(out["dihedral"][k], oracle.dihedral_hashes(coeffs)), name
     for k, ((name, _), px) in enumerate(zip(good_files(), host_pixels())):
         assert np.array_equal(out["pixel_hash"][k], eng.pixel_hash_batch(px[None])[0]), name
         ref = eng.pdq_hash_batch(px[None], want_coeffs=True, want_dihedral=True)
