@@ -102,6 +102,33 @@ int rph_pdq_hash_batch_dev(rph_ctx *ctx, const void *d_px, uint32_t n, uint32_t 
                            void *d_valid, void *stream);
 
 /*
+ * generate_pdq_features for n images of ANY mix of geometries and channel counts, one call.
+ * px[i]: image i, w[i] x h[i] pixels, channels[i] in {1,3,4} interleaved u8, row_stride[i] bytes between rows.
+ * Outputs as rph_pdq_hash_batch (index i = image i; all but hash32_out nullable).
+ *  - Every input rph_pdq_hash_batch accepts with n = 1 is accepted per image, w[i] or h[i] < 5 (valid 0, outputs zeroed) and
+ *    4000 x 5 among them.
+ *  - The result for image i is bit for bit what rph_pdq_hash_batch returns for that image alone: hash, quality, coefficients
+ *    and dihedral hashes.
+ *  - channels[i] outside {1,3,4}, row_stride[i] < w[i] * channels[i] or a null required pointer (ctx, px, px[i], w, h, channels,
+ *    row_stride, hash32_out) gives RPH_ERR_INVALID_ARG for the whole call, with nothing launched.  n = 0 is RPH_OK.
+ *  - A call whose images all share one (w, h, channels, row_stride) goes to the uniform path of rph_pdq_hash_batch(_dev) (the
+ *    device form: when the images also lie at one distance from each other, as that path's image_stride wants them).
+ *  - Images with both sides 128..512, and larger ones whose <= 512 px thumbnail has both sides >= 128, are hashed by kernels that
+ *    take each image's geometry from a descriptor: the number of launches does not depend on the number of geometries.  The
+ *    rest (a side < 128, thumbnails thinner than 128, w or h < 5), and every image under rph_pdq_set_kernel modes 0 and 5, go
+ *    through rph_pdq_hash_batch_dev in runs of equal geometry.
+ */
+int rph_pdq_hash_ragged(rph_ctx *ctx, const uint8_t *const *px, const uint32_t *w, const uint32_t *h, const uint32_t *channels,
+                        const size_t *row_stride, uint32_t n, uint8_t *hash32_out, float *quality_out, float *coeffs_out,
+                        uint8_t *dihedral_out, uint8_t *valid_out);
+/* Pixels already on the device: image i starts at (uint8_t *)d_px + offset[i]; the descriptor arrays are HOST arrays
+ * (the host plans the call).  Asynchronous on `stream` like rph_pdq_hash_batch_dev; the host arrays may be reused when the
+ * call returns. */
+int rph_pdq_hash_ragged_dev(rph_ctx *ctx, const void *d_px, const uint64_t *offset, const uint32_t *w, const uint32_t *h,
+                            const uint32_t *channels, const size_t *row_stride, uint32_t n, void *d_hash32, void *d_quality,
+                            void *d_coeffs, void *d_dihedral, void *d_valid, void *stream);
+
+/*
  * generate_pdq_features for ONE image, as scanner.rs:1410 calls it from many rayon workers at once: thread-safe and
  * blocking; concurrent callers are coalesced into GPU batches (images of any mix of sizes) whose transfers are pipelined
  * over three slots.  A batch goes as soon as nobody is still copying into it and a pipeline slot is free, so its size

@@ -101,6 +101,34 @@ inline std::optional<std::pair<Hash, float>> generate_pdq(const ImageView &img)
     if (!valid) return std::nullopt;
     return std::make_pair(h, q);
 }
+// generate_pdq_features of many images of any mix of sizes and channel counts in one call (rph_pdq_hash_ragged): what a caller with
+// its own decoders hands over instead of one generate_pdq_features per image.  Entry i: nullopt <=> None for image i.
+inline std::vector<std::optional<std::pair<PdqFeatures, float>>> generate_pdq_features_many(const std::vector<ImageView> &imgs)
+{
+    const uint32_t n = (uint32_t)imgs.size();
+    std::vector<const uint8_t *> px(n);
+    std::vector<uint32_t> w(n), h(n), ch(n);
+    std::vector<size_t> rs(n);
+    for (uint32_t i = 0; i < n; i++) {
+        px[i] = imgs[i].data;
+        w[i] = imgs[i].width;
+        h[i] = imgs[i].height;
+        ch[i] = imgs[i].channels;
+        rs[i] = (size_t)imgs[i].width * imgs[i].channels;
+    }
+    std::vector<uint8_t> hash((size_t)n * 32 + 1), valid(n + 1);
+    std::vector<float> q(n + 1), c((size_t)n * 256 + 1);
+    check(rph_pdq_hash_ragged(Context::get(), px.data(), w.data(), h.data(), ch.data(), rs.data(), n, hash.data(), q.data(), c.data(), nullptr, valid.data()),
+          "generate_pdq_features_many");
+    std::vector<std::optional<std::pair<PdqFeatures, float>>> out(n);
+    for (uint32_t i = 0; i < n; i++) {
+        if (!valid[i]) continue;
+        PdqFeatures f{};
+        std::copy(c.begin() + (size_t)i * 256, c.begin() + (size_t)(i + 1) * 256, f.coefficients.begin());
+        out[i] = std::make_pair(f, q[i]);
+    }
+    return out;
+}
 // pdqhash.rs:224-235
 inline std::pair<uint32_t, uint32_t> calculate_target_dimensions(uint32_t w, uint32_t h, uint32_t max_dim)
 {

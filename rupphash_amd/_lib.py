@@ -66,6 +66,8 @@ SIGNATURES = {
                                      _f32p, _u8p, _u8p]),
     "rph_pdq_hash_batch_dev": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _sz, _sz, _vp, _vp, _vp,
                                          _vp, _vp, _vp]),
+    "rph_pdq_hash_ragged": (C.c_int, [_vp, C.POINTER(C.c_void_p), _u32p, _u32p, _u32p, C.POINTER(C.c_size_t), C.c_uint32, _u8p, _f32p, _f32p, _u8p, _u8p]),
+    "rph_pdq_hash_ragged_dev": (C.c_int, [_vp, _vp, _u64p, _u32p, _u32p, _u32p, C.POINTER(C.c_size_t), C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rph_pdq_hash_one": (C.c_int, [_vp, _u8p, C.c_uint32, C.c_uint32, C.c_uint32, _sz, _u8p, _f32p, _f32p, _u8p]),
     "rph_pdq_batcher_config": (C.c_int, [_vp, C.c_uint32, C.c_uint32]),
     "rph_pdq_batcher_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

@@ -230,6 +230,8 @@ int rph_init(int device, rph_ctx **out)
         ctx->serial = next_serial.fetch_add(1);
         ctx->device = device;
         ctx->compute_units = prop.multiProcessorCount;
+        if (const char *e = getenv("RPH_RAGGED_CHUNK_BYTES"))  // tests: several staging chunks from a few small images
+            if (const long long v = atoll(e); v > 0) ctx->ragged_chunk_bytes = (size_t)v;
         hipError_t e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
         if (e != hipSuccess) {
             rph_set_error("hipStreamCreate failed: %s", hipGetErrorString(e));
@@ -248,6 +250,7 @@ int rph_shutdown(rph_ctx *ctx)
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     rph_pipe_forget(ctx);
+    rph_ragged_forget(ctx);
     rph_resize_forget(ctx);
     rph_jpeg_forget(ctx);
     rph_png_forget(ctx);
@@ -425,6 +428,101 @@ int rph_pdq_hash_batch_keep(rph_ctx *ctx, const uint8_t *px, uint32_t n, uint32_
         }
         RPH_TRY(finish(k & 1));
         RPH_TRY(finish((k + 1) & 1));
+        return RPH_OK;
+    });
+}
+
+// Host form of the ragged call: the images are packed into the pinned staging sets of rph_pdq_hash_batch -- each at a 16-byte aligned
+// offset, rows at a pitch that is a multiple of 4 (the streaming kernel reads Luma8 images of 128..512 px straight from there) -- in
+// chunks of ctx->ragged_chunk_bytes; chunk k is hashed while the host threads pack chunk k + 1 into the other set.
+extern "C" int rph_pdq_hash_ragged(rph_ctx *ctx, const uint8_t *const *px, const uint32_t *w, const uint32_t *h, const uint32_t *channels, const size_t *row_stride,
+                                   uint32_t n, uint8_t *hash32_out, float *quality_out, float *coeffs_out, uint8_t *dihedral_out, uint8_t *valid_out)
+{
+    return rph_guarded("rph_pdq_hash_ragged", [&]() -> int {
+        if (ctx && n == 0) return RPH_OK;
+        if (!ctx || !hash32_out || !px || !w || !h || !channels || !row_stride) {
+            rph_set_error("rph_pdq_hash_ragged: null argument");
+            return RPH_ERR_INVALID_ARG;
+        }
+        for (uint32_t i = 0; i < n; i++)
+            if (!px[i] || (channels[i] != 1 && channels[i] != 3 && channels[i] != 4) || row_stride[i] < (size_t)w[i] * channels[i]) {
+                rph_set_error("rph_pdq_hash_ragged: invalid argument (image %u: %ux%ux%u row_stride=%zu)", i, w[i], h[i], channels[i], px[i] ? row_stride[i] : (size_t)0);
+                return RPH_ERR_INVALID_ARG;
+            }
+        RPH_HIP_CHECK(hipSetDevice(ctx->device));
+        // the packed form of every image, and the chunks
+        constexpr uint32_t kMaxChunkImages = 16384;
+        std::vector<size_t> pitch(n);
+        std::vector<uint64_t> offset(n);
+        std::vector<uint32_t> chunk_first;  // + the end
+        size_t max_bytes = 0, bytes = 0;
+        uint32_t max_images = 0;
+        for (uint32_t i = 0; i < n; i++) {
+            pitch[i] = align_up((size_t)w[i] * channels[i], 4);
+            const size_t size = pitch[i] * h[i];
+            // (an image larger than a chunk gets one of its own)
+            if (chunk_first.empty() || (i > chunk_first.back() && (align_up(bytes, 16) + size > ctx->ragged_chunk_bytes || i - chunk_first.back() >= kMaxChunkImages))) {
+                chunk_first.push_back(i);
+                bytes = 0;
+            }
+            offset[i] = align_up(bytes, 16);
+            bytes = offset[i] + size;
+            max_bytes = std::max(max_bytes, bytes);
+            max_images = std::max(max_images, i - chunk_first.back() + 1);
+        }
+        chunk_first.push_back(n);
+        std::lock_guard<std::mutex> pipe_lock(ctx->pipe_mu);
+        HostPipe *P = nullptr;
+        RPH_TRY(pipe_of(ctx, max_bytes + 16, max_images, &P));
+        struct Pending {
+            uint32_t first = 0, m = 0;
+            bool active = false;
+        } pend[2];
+        auto finish = [&](int b) -> int {  // results of the chunk that used set b -> the caller's arrays
+            if (!pend[b].active) return RPH_OK;
+            const PipeSet &S = P->set[b];
+            RPH_HIP_CHECK(hipStreamSynchronize(S.stream));
+            const uint32_t first = pend[b].first, m = pend[b].m;
+            std::memcpy(hash32_out + (size_t)first * 32, S.h_hash.data(), (size_t)m * 32);
+            if (quality_out) std::memcpy(quality_out + first, S.h_q.data(), (size_t)m * 4);
+            if (coeffs_out) std::memcpy(coeffs_out + (size_t)first * 256, S.h_c.data(), (size_t)m * 1024);
+            if (dihedral_out) std::memcpy(dihedral_out + (size_t)first * 256, S.h_d.data(), (size_t)m * 256);
+            if (valid_out) std::memcpy(valid_out + first, S.h_v.data(), m);
+            pend[b].active = false;
+            return RPH_OK;
+        };
+        const unsigned nt = std::min(8u, rph_host_threads());
+        for (size_t k = 0; k + 1 < chunk_first.size(); k++) {
+            const int b = (int)(k & 1);
+            RPH_TRY(finish(b));
+            PipeSet &S = P->set[b];
+            const uint32_t first = chunk_first[k], m = chunk_first[k + 1] - first;
+            parallel_for(first, first + m, nt, [&](size_t i) {
+                uint8_t *to = S.h_px.data() + offset[i];
+                const size_t row = (size_t)w[i] * channels[i];
+                if (row_stride[i] == pitch[i]) {
+                    if (h[i]) std::memcpy(to, px[i], pitch[i] * (h[i] - 1) + row);
+                } else {
+                    for (uint32_t y = 0; y < h[i]; y++) std::memcpy(to + y * pitch[i], px[i] + (size_t)y * row_stride[i], row);
+                }
+            });
+            const size_t used = (size_t)offset[first + m - 1] + pitch[first + m - 1] * h[first + m - 1];
+            hipStream_t s = S.stream;
+            if (used) RPH_HIP_CHECK(hipMemcpyAsync(S.d_px.data(), S.h_px.data(), used, hipMemcpyHostToDevice, s));
+            RPH_TRY(rph_pdq_ragged_run(ctx, S.d_px.data(), offset.data() + first, w + first, h + first, channels + first, pitch.data() + first, m, S.d_hash.data(),
+                                       quality_out ? S.d_q.as<float>() : nullptr, coeffs_out ? S.d_c.as<float>() : nullptr, dihedral_out ? S.d_d.data() : nullptr,
+                                       valid_out ? S.d_v.data() : nullptr, s));
+            RPH_HIP_CHECK(hipMemcpyAsync(S.h_hash.data(), S.d_hash.data(), (size_t)m * 32, hipMemcpyDeviceToHost, s));
+            if (quality_out) RPH_HIP_CHECK(hipMemcpyAsync(S.h_q.data(), S.d_q.data(), (size_t)m * 4, hipMemcpyDeviceToHost, s));
+            if (coeffs_out) RPH_HIP_CHECK(hipMemcpyAsync(S.h_c.data(), S.d_c.data(), (size_t)m * 1024, hipMemcpyDeviceToHost, s));
+            if (dihedral_out) RPH_HIP_CHECK(hipMemcpyAsync(S.h_d.data(), S.d_d.data(), (size_t)m * 256, hipMemcpyDeviceToHost, s));
+            if (valid_out) RPH_HIP_CHECK(hipMemcpyAsync(S.h_v.data(), S.d_v.data(), m, hipMemcpyDeviceToHost, s));
+            pend[b].first = first;
+            pend[b].m = m;
+            pend[b].active = true;
+        }
+        RPH_TRY(finish(0));
+        RPH_TRY(finish(1));
         return RPH_OK;
     });
 }

@@ -29,6 +29,10 @@ struct rph_ctx {
     // copy / H2D of one chunk overlaps the transfer and kernels of the other (rph_api.cpp); one host-batch call at a time
     std::mutex pipe_mu;
     void *pipe = nullptr;
+    // rph_pdq_hash_ragged (pdq_ragged.hip): pinned descriptor buffers; the pixel bytes of one staging chunk of its host form
+    // (RPH_RAGGED_CHUNK_BYTES, tests only: read once, by rph_init)
+    void *ragged = nullptr;
+    size_t ragged_chunk_bytes = (size_t)64 << 20;
     void *axis_cache = nullptr;  // per-geometry coefficient tables of the pre-downsample, kept across calls (resize_kernels.hip)
     // where the last pre-downsample call left its thumbnails in rz_scratch (rph_debug_copy_thumbnails; n = 0: the call took several chunks)
     struct {
@@ -97,6 +101,14 @@ int rph_launch_pdq_stream_color(rph_ctx *ctx, const uint8_t *d_px, uint32_t n, u
 int rph_launch_pdq_resized(rph_ctx *ctx, const uint8_t *d_px, uint32_t n, uint32_t w, uint32_t h, uint32_t channels,
                            size_t row_stride, size_t image_stride, uint8_t *d_hash, float *d_quality, float *d_coeffs,
                            uint8_t *d_dihedral, uint8_t *d_valid, hipStream_t stream);
+// resize_kernels.hip: the box windows of one axis of the pre-downsample as resize_mfma_kernel reads them (start, size and the one
+// coefficient of every output); false: the taps of some output differ (the matrix-pipe form does not apply)
+bool rph_resize_axis_tables(uint32_t in_size, uint32_t out_size, std::vector<uint32_t> &start, std::vector<uint32_t> &size, std::vector<int32_t> &c1, int *precision);
+// pdq_ragged.hip: images of any mix of geometries, validated by the caller (rph_api.cpp); d_px + offset[i] = image i
+int rph_pdq_ragged_run(rph_ctx *ctx, const uint8_t *d_px, const uint64_t *offset, const uint32_t *w, const uint32_t *h, const uint32_t *channels,
+                       const size_t *row_stride, uint32_t n, uint8_t *d_hash, float *d_quality, float *d_coeffs, uint8_t *d_dihedral, uint8_t *d_valid,
+                       hipStream_t stream);
+void rph_ragged_forget(rph_ctx *ctx);
 int rph_launch_pdq_from_coeffs(const float *d_coeffs, uint32_t n, uint8_t *d_hash, uint8_t *d_dihedral, hipStream_t stream);
 int rph_launch_lowconf_from_quality(const float *d_quality, const uint8_t *d_valid, uint64_t n, uint8_t *d_low, hipStream_t stream);
 int rph_launch_featureless_variants(const uint8_t *d_hashes, const uint8_t *d_has_features, uint64_t n, uint8_t *d_variants, hipStream_t stream);

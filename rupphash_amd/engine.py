@@ -18,6 +18,41 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _ragged_view(image):
+    """(h, w), (h, w, 3) or (h, w, 4) uint8 -> (array, h, w, channels, row stride): the array as it is if its pixels are interleaved
+    bytes and its rows lie at one non-negative distance >= w * channels (a slice of a larger array), else a contiguous copy."""
+    a = np.asarray(image, np.uint8)
+    if a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] not in (3, 4)):
+        raise ValueError(f"image of shape {a.shape}: (h, w), (h, w, 3) or (h, w, 4) wanted")
+    h, w = a.shape[:2]
+    ch = 1 if a.ndim == 2 else a.shape[2]
+    inner = (1,) if a.ndim == 2 else (ch, 1)
+    if h and w and (a.strides[1:] != inner or (h > 1 and a.strides[0] < w * ch)):
+        a = np.ascontiguousarray(a)
+    return a, h, w, ch, (a.strides[0] if h > 1 and w else w * ch)
+
+
+def ragged_pack(images, align=16, pitch_align=4, fill=0):
+    """The packed form of a list of images for Engine.pdq_hash_ragged_dev: one uint8 buffer with image i at offset[i] (a multiple of
+    `align`), its rows row_stride[i] = w * channels rounded up to `pitch_align` bytes apart; gaps and row padding hold `fill`.
+    Returns (buffer, offset uint64, w uint32, h uint32, channels uint32, row_stride uintp)."""
+    views = [_ragged_view(im) for im in images]
+    n = len(views)
+    offset, ws, hs, chs, rs = np.zeros(n, np.uint64), np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uintp)
+    end = 0
+    for i, (a, h, w, ch, _) in enumerate(views):
+        pitch = -(-(w * ch) // pitch_align) * pitch_align
+        at = -(-end // align) * align
+        offset[i], ws[i], hs[i], chs[i], rs[i] = at, w, h, ch, pitch
+        end = at + pitch * h
+    buf = np.full(max(end, 1), fill, np.uint8)
+    for i, (a, h, w, ch, _) in enumerate(views):
+        if h and w:
+            rows = np.lib.stride_tricks.as_strided(buf[int(offset[i]):], (h, w * ch), (int(rs[i]), 1), writeable=True)
+            rows[...] = a.reshape(h, w * ch) if a.flags.c_contiguous else np.ascontiguousarray(a).reshape(h, w * ch)
+    return buf, offset, ws, hs, chs, rs
+
+
 class Engine:
     def __init__(self, device=0):
         self.L = _lib.load()
@@ -78,6 +113,41 @@ class Engine:
                                         _ptr(out["quality"]), _ptr(out["coeffs"]), _ptr(out["dihedral"]), _ptr(out["valid"])),
               "rph_pdq_hash_batch")
         return out
+
+    def pdq_hash_ragged(self, images, want_quality=True, want_coeffs=False, want_dihedral=False):
+        """images: a list of uint8 arrays (h, w) [Luma8], (h, w, 3) or (h, w, 4) of ANY mix of sizes, rows possibly non-contiguous (slices
+        of larger arrays are read where they are).  One call; returns dict(hash, quality, coeffs, dihedral, valid) like pdq_hash_batch,
+        entry i for image i (valid 0 and zeros for an image with a side < 5)."""
+        views = [_ragged_view(im) for im in images]
+        n = len(views)
+        px = (C.c_void_p * max(n, 1))(*[v[0].ctypes.data for v in views])
+        h = np.array([v[1] for v in views], np.uint32)
+        w = np.array([v[2] for v in views], np.uint32)
+        ch = np.array([v[3] for v in views], np.uint32)
+        rs = (C.c_size_t * max(n, 1))(*[v[4] for v in views])
+        out = {
+            "hash": np.zeros((n, 32), np.uint8),
+            "quality": np.zeros(n, np.float32) if want_quality else None,
+            "coeffs": np.zeros((n, 256), np.float32) if want_coeffs else None,
+            "dihedral": np.zeros((n, 8, 32), np.uint8) if want_dihedral else None,
+            "valid": np.zeros(n, np.uint8),
+        }
+        check(self.L.rph_pdq_hash_ragged(self.ctx, px, _ptr(w), _ptr(h), _ptr(ch), rs, n, _ptr(out["hash"]), _ptr(out["quality"]), _ptr(out["coeffs"]),
+                                         _ptr(out["dihedral"]), _ptr(out["valid"])), "rph_pdq_hash_ragged")
+        return out
+
+    def pdq_hash_ragged_dev(self, d_px, offset, w, h, channels, row_stride, d_hash, d_quality=None, d_coeffs=None, d_dihedral=None, d_valid=None,
+                            stream=None):
+        """Images on the device: image i at d_px + offset[i]; the descriptor arrays are host arrays (ragged_pack() makes them).
+        Asynchronous on `stream`; results in slot i of the device output arrays."""
+        offset = np.ascontiguousarray(offset, np.uint64)
+        w, h, channels = (np.ascontiguousarray(a, np.uint32) for a in (w, h, channels))
+        row_stride = np.ascontiguousarray(row_stride, np.uintp)
+        n = len(offset)
+        if not (len(w) == len(h) == len(channels) == len(row_stride) == n):
+            raise ValueError("descriptor arrays of different lengths")
+        check(self.L.rph_pdq_hash_ragged_dev(self.ctx, d_px, _ptr(offset), _ptr(w), _ptr(h), _ptr(channels), row_stride.ctypes.data_as(C.POINTER(C.c_size_t)), n,
+                                             d_hash, d_quality, d_coeffs, d_dihedral, d_valid, stream), "rph_pdq_hash_ragged_dev")
 
     def pdq_hash_one(self, image, want_coeffs=True):
         """One image through the batching queue (thread-safe; concurrent callers share a GPU batch).

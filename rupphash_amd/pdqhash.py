@@ -60,6 +60,13 @@ def generate_pdq_features_batch(images, engine=None, want_dihedral=False):
     return (engine or default_engine()).pdq_hash_batch(images, want_quality=True, want_coeffs=True, want_dihedral=want_dihedral)
 
 
+def generate_pdq_features_many(images, engine=None):
+    """generate_pdq_features of a list of images of any mix of sizes and channel counts in one GPU call (rph_pdq_hash_ragged):
+    [(PdqFeatures, quality) or None], None for an image that is too small, like the single form."""
+    out = (engine or default_engine()).pdq_hash_ragged(list(images), want_quality=True, want_coeffs=True)
+    return [(PdqFeatures(out["coeffs"][i]), float(out["quality"][i])) if out["valid"][i] else None for i in range(len(out["valid"]))]
+
+
 def calculate_target_dimensions(w, h, max_dim=DOWNSAMPLE_DIMS):
     """pdqhash.rs:224-235"""
     import ctypes as C
