@@ -182,7 +182,8 @@ uint16_t rph_get_chunk64(uint64_t h, uint32_t chunk_idx);
 /* Which formulation the sweep's fast path uses: 2 = fp4 MFMA (default: bits as e2m1 +-1; plain all-pairs sweeps of >= 32768
  * hashes run on a popcount-sorted copy with bits as {0, 1}, which the power-limited chip clocks ~10 % higher), 3 = fp4 MFMA with
  * +-1 operands everywhere, 4 = the sorted {0, 1} form at every size (tests), 1 = int8 MFMA, 0 = VALU xor + popcount.  All feed the same exact completion and report the same edge
- * set.  Debug/bench. */
+ * set.  Debug/bench.  Cross sweeps (rph_hamming_cross_pairs ...) have no sorted {0, 1} form -- it sorts one array and needs
+ * rows == columns -- so settings 2, 3 and 4 all select the +-1 fp4 form there; 1 and 0 as above. */
 int rph_hamming_set_kernel(rph_ctx *ctx, int which);
 /* Width (in 32-bit words, 4..8) of the hash prefix the sweep's fast path examines for `threshold` under formulation `kernel`
  * (as in rph_hamming_set_kernel).  Informational (bench.py prices the fast path with it): results never depend on it. */
@@ -190,7 +191,7 @@ int rph_hamming_prefix_dwords(uint32_t threshold, int kernel);
 
 /* One reported pair of the all-pairs sweep. */
 typedef struct rph_edge {
-    uint32_t i, j;  /* i < j (indices into the hash array; for variant sweeps i is the owning file) */
+    uint32_t i, j;  /* i < j (indices into the hash array; for variant sweeps i is the owning file); cross sweeps: i in A, j in B */
     uint16_t d;     /* Hamming distance, <= threshold */
     uint16_t flags; /* RPH_EDGE_* */
 } rph_edge;
@@ -237,6 +238,32 @@ int rph_hamming_variant_pairs_dev(rph_ctx *ctx, const void *d_variants, uint32_t
                                   uint64_t cap, void *d_count, void *stream);
 
 /*
+ * Cross sweeps: set A against a DIFFERENT set B (new files against a library, queries against a resident collection, two
+ * collections against each other) without the pairs inside either set.  Every pair (a, b) with
+ * hamming_distance(variant_v(a), hash(b)) <= limit(a, b) is reported, e.i indexing A and e.j indexing B; there is no i < j rule,
+ * so a hash present in both sets at the same index is reported as (k, k).  limit = 0 if low_conf_a[a] or low_conf_b[b], else
+ * the threshold; both flag arrays nullable.  flags as in the square sweeps (variant slot, RPH_EDGE_MIH_R1 and the probe key: all
+ * symmetric in the pair).  Capacity protocol as above: the total is always reported, RPH_ERR_CAPACITY if it exceeds `cap`.
+ * n_a == 0 or n_b == 0: RPH_OK, no edges; either count above 2^32 - 1: RPH_ERR_INVALID_ARG.  part/nparts shard the blocks of the
+ * (row tile x column segment) rectangle round-robin: the parts are disjoint and their union is the whole edge set.
+ */
+int rph_hamming_cross_pairs(rph_ctx *ctx, const uint8_t *a32, uint64_t n_a, const uint8_t *b32, uint64_t n_b,
+                            uint32_t threshold, uint32_t part, uint32_t nparts, rph_edge *edges, uint64_t cap,
+                            uint64_t *n_edges_out);
+int rph_hamming_cross_pairs_dev(rph_ctx *ctx, const void *d_a32, uint64_t n_a, const void *d_b32, uint64_t n_b,
+                                uint32_t threshold, uint32_t part, uint32_t nparts, void *d_edges, uint64_t cap,
+                                void *d_count, void *stream);
+/* variants_a: n_a x n_variants x 32 bytes (n_variants 1 or 8), hashes_b: n_b x 32 bytes. */
+int rph_hamming_variant_cross_pairs(rph_ctx *ctx, const uint8_t *variants_a, uint32_t n_variants,
+                                    const uint8_t *low_conf_a, uint64_t n_a, const uint8_t *hashes_b,
+                                    const uint8_t *low_conf_b, uint64_t n_b, uint32_t similarity, uint32_t part,
+                                    uint32_t nparts, rph_edge *edges, uint64_t cap, uint64_t *n_edges_out);
+int rph_hamming_variant_cross_pairs_dev(rph_ctx *ctx, const void *d_variants_a, uint32_t n_variants,
+                                        const void *d_low_conf_a, uint64_t n_a, const void *d_hashes_b,
+                                        const void *d_low_conf_b, uint64_t n_b, uint32_t similarity, uint32_t part,
+                                        uint32_t nparts, void *d_edges, uint64_t cap, void *d_count, void *stream);
+
+/*
  * find_groups::<[u8;32]> (hamminghash.rs:191-271), bit-exact including member
  * order: adjacency = pairs with d <= max_dist that R<=1 probing reaches, in
  * first-seen order, then the serial greedy star clustering.
@@ -276,6 +303,30 @@ int rph_group_files_pdq(rph_ctx *ctx, const uint8_t *hashes32, const float *coef
 /* Union-find part alone (scanner.rs:1781-1817) over an edge list. */
 int rph_union_find_groups(const rph_edge *edges, uint64_t n_edges, uint64_t n, uint32_t *members,
                           uint32_t *offsets, uint32_t *n_groups_out);
+
+/*
+ * Incremental rph_group_files_pdq: a library of n_old files that an earlier call grouped (old_members / old_offsets /
+ * n_old_groups exactly as that call returned them) plus n_new new files.  Files are numbered as the concatenation: library
+ * 0 .. n_old-1, new n_old .. n_old+n_new-1.  Only the pairs the new files add are swept -- (library variants x new hashes) by the
+ * cross sweep, (new variants x new hashes, i < j) by the triangular one -- and the union-find starts from the old components.
+ * members / offsets / *n_groups_out are identical to rph_group_files_pdq on the concatenated arrays;
+ * *new_comparisons_out = that call's comparison count minus the library's own.
+ * Per side, the nullable arguments are those of rph_group_files_pdq: coeffs NULL = that side has one variant per file;
+ * has_features only counts next to coeffs; quality NULL = no low-confidence files on that side.
+ * members capacity n_old + n_new, offsets capacity (n_old + n_new) / 2 + 2.  Malformed old groups: RPH_ERR_INVALID_ARG.
+ */
+int rph_group_files_pdq_append(rph_ctx *ctx, const uint8_t *old_hashes32, const float *old_coeffs,
+                               const uint8_t *old_has_features, const int32_t *old_quality, uint64_t n_old,
+                               const uint32_t *old_members, const uint32_t *old_offsets, uint32_t n_old_groups,
+                               const uint8_t *new_hashes32, const float *new_coeffs, const uint8_t *new_has_features,
+                               const int32_t *new_quality, uint64_t n_new, uint32_t similarity, uint32_t *members,
+                               uint32_t *offsets, uint32_t *n_groups_out, uint64_t *new_comparisons_out);
+/* Its host part alone: union-find over n_total files that starts from the groups of an earlier call and adds `edges`.  The old
+ * groups are checked (a member >= n_total, a member listed twice, offsets that do not start at 0 or are not ascending:
+ * RPH_ERR_INVALID_ARG); nothing is written outside members[0 .. n_total) and offsets[0 .. n_total / 2 + 2). */
+int rph_union_find_groups_append(const uint32_t *old_members, const uint32_t *old_offsets, uint32_t n_old_groups,
+                                 const rph_edge *edges, uint64_t n_edges, uint64_t n_total, uint32_t *members,
+                                 uint32_t *offsets, uint32_t *n_groups_out);
 
 /* is_low_pdq_quality (scanner.rs:1592-1594); quality < 0 encodes None. */
 int rph_is_low_pdq_quality(int32_t quality);

@@ -371,6 +371,68 @@ inline std::pair<std::vector<std::vector<uint32_t>>, size_t> group_with_pdqhash(
         for (uint32_t t = offsets[g]; t < offsets[g + 1]; t++) out[g].push_back(dense_to_sparse[members[t]]);
     return {out, (size_t)cmp};
 }
+
+// The incremental form (rph_group_files_pdq_append): `library` was grouped by an earlier call whose DENSE result the caller kept
+// (files without a hash skipped, numbered in order), `added` are the new files.  Returns the groups of the concatenation
+// library ++ added as indices into it, the dense state to keep for the next run, and the comparisons the new files added.
+struct DenseGroups {  // members / offsets as rph_group_files_pdq returns them, over the files that have a hash
+    std::vector<uint32_t> members, offsets{0};
+};
+struct AppendResult {
+    std::vector<std::vector<uint32_t>> groups;
+    DenseGroups state;
+    size_t new_comparisons = 0;
+};
+inline AppendResult group_with_pdqhash_append(const std::vector<ScannedFile> &library, const DenseGroups &library_groups,
+                                              const std::vector<ScannedFile> &added, uint32_t similarity)
+{
+    if (similarity > hamminghash::MAX_SIMILARITY_256)  // scanner.rs:1650-1655 (assert!)
+        throw std::runtime_error("Similarity distances above 63 require R=4 bit-flip checks, which are not implemented.");
+    struct Side {
+        std::vector<uint8_t> hashes, has;
+        std::vector<float> coeffs;
+        std::vector<int32_t> quality;
+        bool any_features = false;
+        size_t n = 0;
+    } side[2];
+    std::vector<uint32_t> dense_to_sparse;
+    const std::vector<ScannedFile> *sets[2] = {&library, &added};
+    for (int k = 0; k < 2; k++)
+        for (size_t i = 0; i < sets[k]->size(); i++) {
+            const auto &f = (*sets[k])[i];
+            if (!f.pdqhash) continue;
+            Side &d = side[k];
+            dense_to_sparse.push_back((uint32_t)(i + (k ? library.size() : 0)));
+            d.hashes.insert(d.hashes.end(), f.pdqhash->begin(), f.pdqhash->end());
+            d.has.push_back(f.pdq_features ? 1 : 0);
+            d.any_features |= f.pdq_features.has_value();
+            const size_t at = d.coeffs.size();
+            d.coeffs.resize(at + 256, 0.0f);
+            if (f.pdq_features) std::memcpy(&d.coeffs[at], f.pdq_features->coefficients.data(), 1024);
+            d.quality.push_back(f.pdq_quality ? (int32_t)*f.pdq_quality : -1);
+            d.n++;
+        }
+    const size_t n = side[0].n + side[1].n;
+    AppendResult r;
+    r.state.members.resize(n ? n : 1);
+    r.state.offsets.resize(n / 2 + 2);
+    uint32_t ng = 0;
+    uint64_t cmp = 0;
+    const Side &o = side[0], &w = side[1];
+    check(rph_group_files_pdq_append(Context::get(), o.hashes.data(), o.any_features ? o.coeffs.data() : nullptr, o.any_features ? o.has.data() : nullptr,
+                                     o.quality.data(), o.n, library_groups.members.data(), library_groups.offsets.data(),
+                                     (uint32_t)(library_groups.offsets.size() - 1), w.hashes.data(), w.any_features ? w.coeffs.data() : nullptr,
+                                     w.any_features ? w.has.data() : nullptr, w.quality.data(), w.n, similarity, r.state.members.data(),
+                                     r.state.offsets.data(), &ng, &cmp),
+          "group_with_pdqhash_append");
+    r.state.offsets.resize(ng + 1);
+    r.state.members.resize(r.state.offsets[ng]);
+    r.groups.resize(ng);
+    for (uint32_t g = 0; g < ng; g++)
+        for (uint32_t t = r.state.offsets[g]; t < r.state.offsets[g + 1]; t++) r.groups[g].push_back(dense_to_sparse[r.state.members[t]]);
+    r.new_comparisons = (size_t)cmp;
+    return r;
+}
 }  // namespace scanner
 
 }  // namespace rupphash

@@ -90,6 +90,13 @@ SIGNATURES = {
                                             C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "rph_hamming_variant_pairs_dev": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32,
                                                 C.c_uint32, _vp, C.c_uint64, _vp, _vp]),
+    "rph_hamming_cross_pairs": (C.c_int, [_vp, _u8p, C.c_uint64, _u8p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint64,
+                                          C.POINTER(C.c_uint64)]),
+    "rph_hamming_cross_pairs_dev": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _vp, _vp]),
+    "rph_hamming_variant_cross_pairs": (C.c_int, [_vp, _u8p, C.c_uint32, _u8p, C.c_uint64, _u8p, _u8p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                                  C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "rph_hamming_variant_cross_pairs_dev": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint64, _vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32,
+                                                      C.c_uint32, _vp, C.c_uint64, _vp, _vp]),
     "rph_find_groups256": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_uint32, _u32p, _u32p, C.POINTER(C.c_uint32)]),
     "rph_hamming_all_pairs64": (C.c_int, [_vp, _u64p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint64,
                                           C.POINTER(C.c_uint64)]),
@@ -99,6 +106,9 @@ SIGNATURES = {
     "rph_group_files_pdq": (C.c_int, [_vp, _u8p, _f32p, _u8p, _i32p, C.c_uint64, C.c_uint32, _u32p, _u32p,
                                       C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "rph_union_find_groups": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _u32p, _u32p, C.POINTER(C.c_uint32)]),
+    "rph_group_files_pdq_append": (C.c_int, [_vp, _u8p, _f32p, _u8p, _i32p, C.c_uint64, _u32p, _u32p, C.c_uint32, _u8p, _f32p, _u8p, _i32p,
+                                             C.c_uint64, C.c_uint32, _u32p, _u32p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "rph_union_find_groups_append": (C.c_int, [_u32p, _u32p, C.c_uint32, _vp, C.c_uint64, C.c_uint64, _u32p, _u32p, C.POINTER(C.c_uint32)]),
     "rph_is_low_pdq_quality": (C.c_int, [C.c_int32]),
     "rph_mih_build256": (C.c_int, [_vp, _u8p, C.c_uint64, _u32p, _u32p]),
     "rph_mih_build64": (C.c_int, [_vp, _u64p, C.c_uint64, _u32p, _u32p]),
@@ -191,6 +201,8 @@ SIGNATURES = {
 # exports that are NOT in include/rupphash.h (debug / tests only), bound the same way
 DEBUG_SIGNATURES = {
     "rph_debug_copy_thumbnails": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "rph_debug_hamming_cross_layout": (None, [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                              C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
 }
 
 _lib = None

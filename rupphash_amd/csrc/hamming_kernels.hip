@@ -64,6 +64,13 @@ struct SweepArgs {
     // pcs[k] that popcount (ascending), perm[k] the index of sorted hash k in the caller's array
     const uint32_t *perm;
     const uint16_t *pcs;
+    // cross sweeps (CROSS instantiations only; nothing else reads these): rows are one set (n of them, with low_conf and
+    // has_features), columns another of n_cols hashes with flags of their own.  Blocks enumerate the rectangle row-major:
+    // block p = row tile p / n_col_segs against the column tiles [(p % n_col_segs) * seg_tiles, + seg_tiles).
+    unsigned long long n_cols = 0;
+    const uint8_t *low_conf_cols = nullptr;  // [n_cols] or nullptr
+    uint32_t n_col_segs = 0;
+    uint32_t swap_ij = 0;  // the caller's set A rides on the column side: an edge is reported as (column, row)
 };
 
 __device__ __forceinline__ uint32_t bcnt_acc(uint32_t x, uint32_t acc) { return (uint32_t)__builtin_popcount(x) + acc; }
@@ -122,7 +129,9 @@ __device__ __forceinline__ uint32_t first_half_distance(const uint32_t *__restri
     return d;
 }
 
-// Step 2, for a pair whose first-half distance d (differences x0) is within the threshold.
+// Step 2, for a pair whose first-half distance d (differences x0) is within the threshold.  CROSS: rows and columns are different
+// sets, so every pair in bounds is reported (no i < j rule) and the two sides have their own low-confidence flags.
+template <bool CROSS = false>
 __device__ __forceinline__ void complete_rest(const SweepArgs &a, const uint32_t *__restrict__ rowp, const uint32_t *colp, const uint32_t x0[4],
                                               uint32_t d, unsigned long long owner, unsigned long long col, uint32_t variant)
 {
@@ -136,10 +145,15 @@ __device__ __forceinline__ void complete_rest(const SweepArgs &a, const uint32_t
         for (int w = 4; w < 8; w++) d += (uint32_t)__builtin_popcount(x[w]);
     }
     if (variant > 0 && a.has_features && !a.has_features[owner]) return;
-    if (col >= a.n) return;
-    if (col <= owner) return;  // i < j only (scanner.rs:1716 `cand_idx <= i`, hamminghash.rs:216 `dense_idx == i`)
     uint32_t limit = a.threshold;
-    if (a.low_conf && (a.low_conf[owner] | a.low_conf[col])) limit = 0;  // scanner.rs:1699,1721
+    if (CROSS) {  // (every caller has bounded col by the live columns of its segment: n_cols is not needed here)
+        if (a.low_conf && a.low_conf[owner]) limit = 0;
+        if (a.low_conf_cols && a.low_conf_cols[col]) limit = 0;
+    } else {
+        if (col >= a.n) return;
+        if (col <= owner) return;  // i < j only (scanner.rs:1716 `cand_idx <= i`, hamminghash.rs:216 `dense_idx == i`)
+        if (a.low_conf && (a.low_conf[owner] | a.low_conf[col])) limit = 0;  // scanner.rs:1699,1721
+    }
     if (d > limit) return;
     // find_groups reachability (hamminghash.rs:206-238): first chunk k (ascending) whose 16-bit
     // difference has popcount <= tol; slot 0 = exact bucket, 1 + b = flip of bit b.
@@ -158,7 +172,12 @@ __device__ __forceinline__ void complete_rest(const SweepArgs &a, const uint32_t
         rph_edge e;
         e.i = (uint32_t)owner;
         e.j = (uint32_t)col;
-        if (a.perm) {  // sorted sweep: back to the caller's indices, i < j (distance and probe key are symmetric)
+        if (CROSS) {
+            if (a.swap_ij) {  // (distance and probe key are symmetric)
+                e.i = (uint32_t)col;
+                e.j = (uint32_t)owner;
+            }
+        } else if (a.perm) {  // sorted sweep: back to the caller's indices, i < j (distance and probe key are symmetric)
             const uint32_t pi = a.perm[owner], pj = a.perm[col];
             e.i = pi < pj ? pi : pj;
             e.j = pi < pj ? pj : pi;
@@ -169,15 +188,17 @@ __device__ __forceinline__ void complete_rest(const SweepArgs &a, const uint32_t
     }
 }
 
+template <bool CROSS = false>
 __device__ __forceinline__ void complete_pair(const SweepArgs &a, const uint32_t *__restrict__ rowp, const uint32_t *colp,
                                               unsigned long long owner, unsigned long long col, uint32_t variant)
 {
     uint32_t x[4];
     const uint32_t d = first_half_distance(rowp, colp, x);
-    if (d <= a.threshold) complete_rest(a, rowp, colp, x, d, owner, col, variant);
+    if (d <= a.threshold) complete_rest<CROSS>(a, rowp, colp, x, d, owner, col, variant);
 }
 
-template <int PW>
+// CROSS: the rectangle of (row tile, column tile) pairs of two different sets instead of the upper triangle of one.
+template <int PW, bool CROSS = false>
 __global__ void __launch_bounds__(BLOCK) hamming_sweep_kernel(SweepArgs a)
 {
     __shared__ uint4 s_cols[T_FILES * 2];  // [column][2 x uint4] = 32 KiB
@@ -185,11 +206,17 @@ __global__ void __launch_bounds__(BLOCK) hamming_sweep_kernel(SweepArgs a)
     const unsigned long long p = (unsigned long long)a.part + (a.block0 + blockIdx.x) * a.nparts;
     if (p >= a.n_tile_pairs) return;
     uint32_t I, J;
-    tile_pair(p, a.n_tiles, I, J);
+    if (CROSS) {
+        I = (uint32_t)(p / a.n_col_segs);
+        J = (uint32_t)(p % a.n_col_segs);
+    } else {
+        tile_pair(p, a.n_tiles, I, J);
+    }
 
     const unsigned long long col0 = (unsigned long long)J * T_FILES;
     const unsigned long long row0 = (unsigned long long)I * T_FILES;
-    const uint32_t ncols = (uint32_t)((a.n - col0) < (unsigned long long)T_FILES ? (a.n - col0) : T_FILES);
+    const unsigned long long n_col_set = CROSS ? a.n_cols : a.n;
+    const uint32_t ncols = (uint32_t)((n_col_set - col0) < (unsigned long long)T_FILES ? (n_col_set - col0) : T_FILES);
 
     // stage the column tile: 2048 x 16 B, coalesced
     {
@@ -203,6 +230,7 @@ __global__ void __launch_bounds__(BLOCK) hamming_sweep_kernel(SweepArgs a)
     __syncthreads();
 
     const uint32_t nv = a.n_variants;
+    if (CROSS && row0 + threadIdx.x >= a.n) return;  // a short row tile: every row of this lane is past the end (no barrier follows)
     for (uint32_t v = 0; v < nv; v++) {
         // this lane's R row hashes: files row0 + r*BLOCK + tid, variant v (first PW dwords kept in VGPRs)
         uint32_t rw[R][PW];
@@ -242,7 +270,7 @@ __global__ void __launch_bounds__(BLOCK) hamming_sweep_kernel(SweepArgs a)
 #pragma unroll 1
                 for (int r = 0; r < R; r++) {
                     const unsigned long long owner = row0 + (unsigned long long)r * BLOCK + threadIdx.x;
-                    if (owner < a.n) complete_pair(a, a.rows + (owner * nv + v) * 8, colp, owner, col0 + c, v);
+                    if (owner < a.n) complete_pair<CROSS>(a, a.rows + (owner * nv + v) * 8, colp, owner, col0 + c, v);
                 }
             }
         }
@@ -416,7 +444,10 @@ __device__ __forceinline__ void complete_pair_u64(const SweepArgs &a, unsigned l
 }
 
 // U64: the hashes are 64-bit (stride 2 dwords, PW = 2: the whole hash is one fp4 MFMA slice) and pairs are completed by complete_pair_u64.
-template <class F, int PW, bool U64 = false>
+// CROSS: rows and columns are different sets (SweepArgs::n_cols ...): the blocks enumerate a rectangle, passes and waves whose rows
+// all lie past the end of the row set are skipped, and the completion applies the cross rules.  Only the block prologue, one
+// wave-uniform test per pass and the exact completion differ; the MFMA loop is the same text.
+template <class F, int PW, bool U64 = false, bool CROSS = false>
 __global__ void __launch_bounds__(MF_BLOCK, F::blocks_per_cu(PW)) hamming_mfma_kernel(SweepArgs a)
 {
     constexpr int HS = U64 ? 2 : 8;               // dwords per hash
@@ -427,6 +458,7 @@ __global__ void __launch_bounds__(MF_BLOCK, F::blocks_per_cu(PW)) hamming_mfma_k
     constexpr int MF_RB = F::row_blocks(PW);      // 32-row blocks per wave and pass
     constexpr int PASS_ROWS = 4 * 32 * MF_RB;     // rows one pass of the 4 waves covers; T_FILES / PASS_ROWS passes per tile
     static_assert(!U64 || PW == 2, "u64 hashes are swept at full width");
+    static_assert(!(U64 && CROSS) && !(CROSS && is_zero_one<F>::value), "cross sweeps: 256-bit hashes, +-1 operands");
     constexpr int NCB = CHUNK / 32;               // 32-column blocks per chunk
     constexpr int NRP = MF_RB / 2;                // row-block pairs per wave and pass
     constexpr int NCG = RPH_SWEEP_NCG < NCB ? RPH_SWEEP_NCG : NCB;  // column-block groups per chunk (cb % NCG): one running maximum per (row-block pair, group)
@@ -442,11 +474,17 @@ __global__ void __launch_bounds__(MF_BLOCK, F::blocks_per_cu(PW)) hamming_mfma_k
     const unsigned long long p = (unsigned long long)a.part + (a.block0 + blockIdx.x) * a.nparts;
     if (p >= a.n_tile_pairs) return;  // (for this kernel: the number of segment blocks)
     uint32_t I, J;
-    seg_block(p, a.n_tiles, a.seg_tiles, I, J);
+    if (CROSS) {
+        I = (uint32_t)(p / a.n_col_segs);
+        J = (uint32_t)(p % a.n_col_segs) * a.seg_tiles;
+    } else {
+        seg_block(p, a.n_tiles, a.seg_tiles, I, J);
+    }
     const unsigned long long col0 = (unsigned long long)J * T_FILES;
     const unsigned long long row0 = (unsigned long long)I * T_FILES;
     const unsigned long long seg_cols = (unsigned long long)a.seg_tiles * T_FILES;
-    const uint32_t ncols = (uint32_t)((a.n - col0) < seg_cols ? (a.n - col0) : seg_cols);  // <= 8192: queue entries keep 16 bits for it
+    const unsigned long long n_col_set = CROSS ? a.n_cols : a.n;
+    const uint32_t ncols = (uint32_t)((n_col_set - col0) < seg_cols ? (n_col_set - col0) : seg_cols);  // <= 8192: queue entries keep 16 bits for it
 
     s_lut[threadIdx.x] = F::lut_entry(threadIdx.x);
     if (threadIdx.x < 4) s_qn[threadIdx.x] = 0;
@@ -460,13 +498,18 @@ __global__ void __launch_bounds__(MF_BLOCK, F::blocks_per_cu(PW)) hamming_mfma_k
 
     for (uint32_t vp = 0; vp < nv * (T_FILES / PASS_ROWS); vp++) {
         const uint32_t v = vp / (T_FILES / PASS_ROWS);
+        // a short row tile (cross sweeps: the row set may be a handful of files): a pass whose rows are all past the end is not run
+        // (the same decision in every wave of the block, so the barriers below stay matched)
+        if (CROSS && row0 + (vp % (T_FILES / PASS_ROWS)) * PASS_ROWS >= a.n) continue;
         auto complete = [&](unsigned long long owner, unsigned long long col) {
             if (U64)
                 complete_pair_u64(a, owner, col);
             else
-                complete_pair(a, a.rows + (owner * nv + v) * 8, a.cols + col * 8, owner, col, v);
+                complete_pair<CROSS>(a, a.rows + (owner * nv + v) * 8, a.cols + col * 8, owner, col, v);
         };
         const uint32_t wrow = (vp % (T_FILES / PASS_ROWS)) * PASS_ROWS + wave * 32 * MF_RB;  // first tile row of this wave in this pass
+        // ... and a wave whose rows are all past the end still expands columns and meets the barriers, but issues no MFMA
+        const uint32_t sweep_cols = (!CROSS || row0 + wrow < a.n) ? ncols : 0u;
         // A fragments: this lane holds, for row block rb and fragment f, the operand bytes of row c32 for k-half h
         v4i A[MF_RB][NF];
 #pragma unroll
@@ -541,7 +584,7 @@ __global__ void __launch_bounds__(MF_BLOCK, F::blocks_per_cu(PW)) hamming_mfma_k
                 for (int p = 0; p < NRP; p++) runmax[g][p] = (int)0x80000000;
 #pragma unroll 1
             for (int cb0 = 0; cb0 < NCB; cb0 += NCG) {
-                if (cbase + cb0 * 32 >= ncols) break;
+                if (cbase + cb0 * 32 >= sweep_cols) break;
 #pragma unroll
               for (int g = 0; g < NCG; g++) {
                 const int cb = cb0 + g;  // (columns past the end of the segment were expanded as zeros: dot 0)
@@ -653,7 +696,7 @@ __global__ void __launch_bounds__(MF_BLOCK, F::blocks_per_cu(PW)) hamming_mfma_k
                                     if (d[u][k] <= a.threshold) {
                                         unsigned long long owner, col;
                                         item_of(e[u], (uint32_t)__builtin_ctz(e[u].x), k, owner, col);
-                                        complete_rest(a, a.rows + (owner * nv + v) * 8, a.cols + col * 8, x[u][k], d[u][k], owner, col, v);
+                                        complete_rest<CROSS>(a, a.rows + (owner * nv + v) * 8, a.cols + col * 8, x[u][k], d[u][k], owner, col, v);
                                     }
 #pragma unroll
                             for (int u = 0; u < U; u++) e[u].x &= e[u].x - 1;  // (0 stays 0)
@@ -923,6 +966,112 @@ int rph_launch_hamming_sweep(rph_ctx *ctx, const uint8_t *d_rows, uint32_t n_var
         RPH_HIP_CHECK(hipGetLastError());
     }
     if (zero_one) RPH_TRY(ctx->sweep_scratch.publish(stream));
+    return RPH_OK;
+}
+
+// Block layout of a cross sweep (exported for the tests: Engine.hamming_cross_layout).  Set A becomes the row side unless it has one
+// variant per file and is the smaller set: rows are what a block holds in registers, a full tile of 1024 of them shared by its four
+// waves, while columns stream through LDS in chunks of 128 or 256 and a block stops after the last live chunk.  A small set therefore
+// costs little as columns (one chunk, all four waves busy on it) and much as rows (a pass over every column of the segment for a few
+// live rows, three of the four waves idle), so the larger set goes to the rows.  Variants are laid out per row and always stay there.
+// Segments: as many column tiles per block (up to 8) as leave ~8 blocks per resident block slot, from the rectangle's tile count.
+extern "C" void rph_debug_hamming_cross_layout(uint64_t n_a, uint32_t n_variants, uint64_t n_b, uint32_t nparts, int kernel, uint32_t *swap_out,
+                                         uint32_t *seg_tiles_out, uint32_t *n_col_segs_out, uint64_t *n_blocks_out)
+{
+    const bool swap = n_variants == 1 && n_a < n_b;
+    const uint64_t n_rows = swap ? n_b : n_a, n_cols = swap ? n_a : n_b;
+    const uint64_t rt = (n_rows + T_FILES - 1) / T_FILES, ct = (n_cols + T_FILES - 1) / T_FILES;
+    uint64_t S = 1;
+    if (kernel >= 1) {
+        S = rt * ct / (8ull * 512ull * (nparts ? nparts : 1));
+        S = S < 1 ? 1 : (S > 8 ? 8 : S);
+    }
+    const uint64_t segs = (ct + S - 1) / S;
+    if (swap_out) *swap_out = swap ? 1u : 0u;
+    if (seg_tiles_out) *seg_tiles_out = (uint32_t)S;
+    if (n_col_segs_out) *n_col_segs_out = (uint32_t)segs;
+    if (n_blocks_out) *n_blocks_out = rt * segs;
+}
+
+template <class F>
+static void launch_cross_mfma(int pw, dim3 grid, hipStream_t stream, const SweepArgs &a)
+{
+    const dim3 mblock(MF_BLOCK);
+    if (pw == 4)
+        hipLaunchKernelGGL((hamming_mfma_kernel<F, 4, false, true>), grid, mblock, 0, stream, a);
+    else if (pw == 6)
+        hipLaunchKernelGGL((hamming_mfma_kernel<F, 6, false, true>), grid, mblock, 0, stream, a);
+    else if (pw == 8)
+        hipLaunchKernelGGL((hamming_mfma_kernel<F, 8, false, true>), grid, mblock, 0, stream, a);
+    else if constexpr (F::nfrag(5) == 5) {  // odd widths: the int8 format only
+        if (pw == 5)
+            hipLaunchKernelGGL((hamming_mfma_kernel<F, 5, false, true>), grid, mblock, 0, stream, a);
+        else
+            hipLaunchKernelGGL((hamming_mfma_kernel<F, 7, false, true>), grid, mblock, 0, stream, a);
+    }
+}
+
+// Cross form of rph_launch_hamming_sweep: every pair (a, b) of two different sets, a's variants against b's hash; e.i indexes A and
+// e.j indexes B.  Kernel settings 2, 3 and 4 all run the +-1 fp4 form here (the popcount-sorted {0,1} form sorts ONE array and
+// needs rows == columns).
+int rph_launch_hamming_cross_sweep(rph_ctx *ctx, const uint8_t *d_a, uint32_t n_variants, const uint8_t *d_low_conf_a, const uint8_t *d_has_features_a,
+                                   uint64_t n_a, const uint8_t *d_b, const uint8_t *d_low_conf_b, uint64_t n_b, uint32_t threshold, uint32_t part,
+                                   uint32_t nparts, rph_edge *d_edges, uint64_t cap, unsigned long long *d_count, hipStream_t stream, int use_mfma)
+{
+    (void)ctx;
+    if (nparts == 0 || part >= nparts || (n_variants != 1 && n_variants != 8) || n_a > 0xFFFFFFFFull || n_b > 0xFFFFFFFFull) {
+        rph_set_error("hamming cross sweep: bad arguments (n_a=%llu n_b=%llu variants=%u part=%u/%u)", (unsigned long long)n_a,
+                      (unsigned long long)n_b, n_variants, part, nparts);
+        return RPH_ERR_INVALID_ARG;
+    }
+    if (n_a == 0 || n_b == 0) return RPH_OK;
+    uint32_t swap = 0;
+    uint64_t n_blocks = 0;
+    SweepArgs a;
+    rph_debug_hamming_cross_layout(n_a, n_variants, n_b, nparts, use_mfma, &swap, &a.seg_tiles, &a.n_col_segs, &n_blocks);
+    a.rows = reinterpret_cast<const uint32_t *>(swap ? d_b : d_a);
+    a.cols = reinterpret_cast<const uint32_t *>(swap ? d_a : d_b);
+    a.low_conf = swap ? d_low_conf_b : d_low_conf_a;
+    a.low_conf_cols = swap ? d_low_conf_a : d_low_conf_b;
+    a.has_features = n_variants > 1 ? d_has_features_a : nullptr;
+    a.n = swap ? n_b : n_a;
+    a.n_cols = swap ? n_a : n_b;
+    a.swap_ij = swap;
+    a.n_variants = n_variants;
+    a.threshold = threshold > 256 ? 256 : threshold;
+    a.mih_tol = (threshold / 16u) >= 1 ? 1 : 0;
+    a.part = part;
+    a.nparts = nparts;
+    a.n_tiles = (uint32_t)((a.n + T_FILES - 1) / T_FILES);
+    a.n_tile_pairs = n_blocks;
+    a.edges = d_edges;
+    a.cap = cap;
+    a.count = d_count;
+    a.perm = nullptr;
+    a.pcs = nullptr;
+    const unsigned long long mine = (a.n_tile_pairs > part) ? (a.n_tile_pairs - part + nparts - 1) / nparts : 0;
+    const int pw = rph_hamming_prefix_dwords(a.threshold, use_mfma);
+    for (unsigned long long b0 = 0; b0 < mine; b0 += MAX_GRID) {  // one launch carries at most MAX_GRID blocks
+        a.block0 = b0;
+        const dim3 grid((unsigned)((mine - b0) < MAX_GRID ? (mine - b0) : MAX_GRID)), block(BLOCK);
+        if (use_mfma >= 2) {
+            launch_cross_mfma<FmtFp4>(pw, grid, stream, a);
+        } else if (use_mfma) {
+            launch_cross_mfma<FmtI8>(pw, grid, stream, a);
+        } else {
+            if (pw == 4)
+                hipLaunchKernelGGL((hamming_sweep_kernel<4, true>), grid, block, 0, stream, a);
+            else if (pw == 5)
+                hipLaunchKernelGGL((hamming_sweep_kernel<5, true>), grid, block, 0, stream, a);
+            else if (pw == 6)
+                hipLaunchKernelGGL((hamming_sweep_kernel<6, true>), grid, block, 0, stream, a);
+            else if (pw == 7)
+                hipLaunchKernelGGL((hamming_sweep_kernel<7, true>), grid, block, 0, stream, a);
+            else
+                hipLaunchKernelGGL((hamming_sweep_kernel<8, true>), grid, block, 0, stream, a);
+        }
+        RPH_HIP_CHECK(hipGetLastError());
+    }
     return RPH_OK;
 }
 

@@ -98,13 +98,11 @@ inline uint32_t uf_find(std::vector<uint32_t> &parent, uint32_t i)
     }
     return root;
 }
-}  // namespace
 
-int rph_host_union_find(const rph_edge *edges, uint64_t n_edges, uint64_t n, uint32_t *members, uint32_t *offsets,
-                        uint32_t *n_groups_out)
+// union of the edges' ends (scanner.rs:1797-1803)
+int uf_apply_edges(std::vector<uint32_t> &parent, const rph_edge *edges, uint64_t n_edges)
 {
-    std::vector<uint32_t> parent(n);
-    for (uint64_t i = 0; i < n; i++) parent[i] = (uint32_t)i;
+    const uint64_t n = parent.size();
     for (uint64_t e = 0; e < n_edges; e++) {
         if (edges[e].i >= n || edges[e].j >= n) {
             rph_set_error("union-find: edge %llu references file %u/%u outside n=%llu", (unsigned long long)e, edges[e].i,
@@ -112,10 +110,16 @@ int rph_host_union_find(const rph_edge *edges, uint64_t n_edges, uint64_t n, uin
             return RPH_ERR_INVALID_ARG;
         }
         const uint32_t ri = uf_find(parent, edges[e].i), rj = uf_find(parent, edges[e].j);
-        if (ri != rj) parent[ri] = rj;  // scanner.rs:1797-1803
+        if (ri != rj) parent[ri] = rj;
     }
-    // Components with more than one member; members ascending (the reference pushes i in 0..n order,
-    // scanner.rs:1810-1814), groups ordered by their first member.
+    return RPH_OK;
+}
+
+// Components with more than one member; members ascending (the reference pushes i in 0..n order,
+// scanner.rs:1810-1814), groups ordered by their first member.
+void uf_list_groups(std::vector<uint32_t> &parent, uint32_t *members, uint32_t *offsets, uint32_t *n_groups_out)
+{
+    const uint64_t n = parent.size();
     std::vector<uint32_t> root(n), count(n, 0), slot(n, UINT32_MAX);
     for (uint64_t i = 0; i < n; i++) {
         root[i] = uf_find(parent, (uint32_t)i);
@@ -140,6 +144,53 @@ int rph_host_union_find(const rph_edge *edges, uint64_t n_edges, uint64_t n, uin
         }
     }
     *n_groups_out = ng;
+}
+}  // namespace
+
+int rph_host_union_find(const rph_edge *edges, uint64_t n_edges, uint64_t n, uint32_t *members, uint32_t *offsets,
+                        uint32_t *n_groups_out)
+{
+    std::vector<uint32_t> parent(n);
+    for (uint64_t i = 0; i < n; i++) parent[i] = (uint32_t)i;
+    RPH_TRY(uf_apply_edges(parent, edges, n_edges));
+    uf_list_groups(parent, members, offsets, n_groups_out);
+    return RPH_OK;
+}
+
+// The components an earlier call reported are joined first, then the new edges: connected components do not depend on the order of
+// the unions, so the result is that of one union-find over the old edges and the new ones.  The old groups come from a file the
+// caller kept between runs: every index is checked before it is used.
+int rph_host_union_find_append(const uint32_t *old_members, const uint32_t *old_offsets, uint32_t n_old_groups, const rph_edge *edges,
+                               uint64_t n_edges, uint64_t n, uint32_t *members, uint32_t *offsets, uint32_t *n_groups_out)
+{
+    if (n > 0xFFFFFFFFull) {
+        rph_set_error("union-find: %llu files, at most 2^32 - 1", (unsigned long long)n);
+        return RPH_ERR_INVALID_ARG;
+    }
+    if (n_old_groups && old_offsets[0] != 0) {
+        rph_set_error("union-find: old offsets start at %u, not 0", old_offsets[0]);
+        return RPH_ERR_INVALID_ARG;
+    }
+    for (uint32_t g = 0; g < n_old_groups; g++)
+        if (old_offsets[g + 1] < old_offsets[g] || old_offsets[g + 1] > n) {  // (distinct members: no more than n of them)
+            rph_set_error("union-find: old offsets are not ascending within n=%llu at group %u", (unsigned long long)n, g);
+            return RPH_ERR_INVALID_ARG;
+        }
+    std::vector<uint32_t> parent(n);
+    for (uint64_t i = 0; i < n; i++) parent[i] = (uint32_t)i;
+    std::vector<uint8_t> seen(n, 0);
+    for (uint32_t g = 0; g < n_old_groups; g++)
+        for (uint32_t t = old_offsets[g]; t < old_offsets[g + 1]; t++) {
+            const uint32_t m = old_members[t];
+            if (m >= n || seen[m]) {
+                rph_set_error("union-find: old group %u lists file %u %s", g, m, m >= n ? "outside n" : "twice");
+                return RPH_ERR_INVALID_ARG;
+            }
+            seen[m] = 1;
+            if (t > old_offsets[g]) parent[uf_find(parent, m)] = uf_find(parent, old_members[old_offsets[g]]);
+        }
+    RPH_TRY(uf_apply_edges(parent, edges, n_edges));
+    uf_list_groups(parent, members, offsets, n_groups_out);
     return RPH_OK;
 }
 

@@ -614,6 +614,94 @@ int rph_hamming_variant_pairs(rph_ctx *ctx, const uint8_t *variants, uint32_t n_
     });
 }
 
+// ---- cross sweeps: set A (variants, flags) against set B (hashes, flags), every pair ----
+int rph_hamming_variant_cross_pairs_dev(rph_ctx *ctx, const void *d_variants_a, uint32_t n_variants, const void *d_low_conf_a, uint64_t n_a,
+                                        const void *d_hashes_b, const void *d_low_conf_b, uint64_t n_b, uint32_t similarity, uint32_t part,
+                                        uint32_t nparts, void *d_edges, uint64_t cap, void *d_count, void *stream)
+{
+    if (!ctx || (!d_variants_a && n_a) || (!d_hashes_b && n_b) || !d_count || (!d_edges && cap)) {
+        rph_set_error("rph_hamming_variant_cross_pairs: null argument");
+        return RPH_ERR_INVALID_ARG;
+    }
+    RPH_HIP_CHECK(hipSetDevice(ctx->device));
+    return rph_launch_hamming_cross_sweep(ctx, (const uint8_t *)d_variants_a, n_variants, (const uint8_t *)d_low_conf_a, nullptr, n_a,
+                                          (const uint8_t *)d_hashes_b, (const uint8_t *)d_low_conf_b, n_b, similarity, part, nparts,
+                                          (rph_edge *)d_edges, cap, (unsigned long long *)d_count, pick(ctx, stream), ctx->hamming_kernel);
+}
+
+int rph_hamming_cross_pairs_dev(rph_ctx *ctx, const void *d_a32, uint64_t n_a, const void *d_b32, uint64_t n_b, uint32_t threshold, uint32_t part,
+                                uint32_t nparts, void *d_edges, uint64_t cap, void *d_count, void *stream)
+{
+    return rph_hamming_variant_cross_pairs_dev(ctx, d_a32, 1, nullptr, n_a, d_b32, nullptr, n_b, threshold, part, nparts, d_edges, cap, d_count,
+                                               stream);
+}
+
+static int cross_host(rph_ctx *ctx, const uint8_t *variants_a, uint32_t n_variants, const uint8_t *low_conf_a, uint64_t n_a, const uint8_t *hashes_b,
+                      const uint8_t *low_conf_b, uint64_t n_b, uint32_t thr, uint32_t part, uint32_t nparts, rph_edge *edges, uint64_t cap,
+                      uint64_t *n_edges_out)
+{
+    if (!ctx || (!variants_a && n_a) || (!hashes_b && n_b) || !n_edges_out || (!edges && cap)) {
+        rph_set_error("hamming cross sweep: null argument");
+        return RPH_ERR_INVALID_ARG;
+    }
+    *n_edges_out = 0;
+    if (nparts == 0 || part >= nparts || (n_variants != 1 && n_variants != 8) || n_a > 0xFFFFFFFFull || n_b > 0xFFFFFFFFull) {
+        rph_set_error("hamming cross sweep: bad arguments (n_a=%llu n_b=%llu variants=%u part=%u/%u)", (unsigned long long)n_a,
+                      (unsigned long long)n_b, n_variants, part, nparts);
+        return RPH_ERR_INVALID_ARG;
+    }
+    if (n_a == 0 || n_b == 0) return RPH_OK;
+    RPH_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    DevBuf d_a, d_b, d_la, d_lb, d_e, d_cnt;
+    RPH_TRY(d_a.alloc(n_a * 32 * n_variants));
+    RPH_HIP_CHECK(hipMemcpyAsync(d_a.data(), variants_a, n_a * 32 * n_variants, hipMemcpyHostToDevice, s));
+    RPH_TRY(d_b.alloc(n_b * 32));
+    RPH_HIP_CHECK(hipMemcpyAsync(d_b.data(), hashes_b, n_b * 32, hipMemcpyHostToDevice, s));
+    if (low_conf_a) {
+        RPH_TRY(d_la.alloc(n_a));
+        RPH_HIP_CHECK(hipMemcpyAsync(d_la.data(), low_conf_a, n_a, hipMemcpyHostToDevice, s));
+    }
+    if (low_conf_b) {
+        RPH_TRY(d_lb.alloc(n_b));
+        RPH_HIP_CHECK(hipMemcpyAsync(d_lb.data(), low_conf_b, n_b, hipMemcpyHostToDevice, s));
+    }
+    RPH_TRY(d_e.alloc(cap * sizeof(rph_edge)));
+    RPH_TRY(d_cnt.alloc(8));
+    RPH_HIP_CHECK(hipMemsetAsync(d_cnt.data(), 0, 8, s));
+    RPH_TRY(rph_launch_hamming_cross_sweep(ctx, d_a.data(), n_variants, d_la.data(), nullptr, n_a, d_b.data(), d_lb.data(), n_b, thr, part, nparts,
+                                           d_e.as<rph_edge>(), cap, d_cnt.as<unsigned long long>(), s, ctx->hamming_kernel));
+    unsigned long long cnt = 0;
+    RPH_HIP_CHECK(hipMemcpyAsync(&cnt, d_cnt.data(), 8, hipMemcpyDeviceToHost, s));
+    RPH_HIP_CHECK(hipStreamSynchronize(s));
+    *n_edges_out = cnt;
+    const uint64_t take = std::min<uint64_t>(cnt, cap);
+    if (take) RPH_HIP_CHECK(hipMemcpy(edges, d_e.data(), take * sizeof(rph_edge), hipMemcpyDeviceToHost));
+    if (cnt > cap) {
+        rph_set_error("hamming cross sweep: %llu edges found, capacity %llu", cnt, (unsigned long long)cap);
+        return RPH_ERR_CAPACITY;
+    }
+    return RPH_OK;
+}
+
+int rph_hamming_cross_pairs(rph_ctx *ctx, const uint8_t *a32, uint64_t n_a, const uint8_t *b32, uint64_t n_b, uint32_t threshold, uint32_t part,
+                            uint32_t nparts, rph_edge *edges, uint64_t cap, uint64_t *n_edges_out)
+{
+    return rph_guarded("rph_hamming_cross_pairs", [&]() -> int {
+        return cross_host(ctx, a32, 1, nullptr, n_a, b32, nullptr, n_b, threshold, part, nparts, edges, cap, n_edges_out);
+    });
+}
+
+int rph_hamming_variant_cross_pairs(rph_ctx *ctx, const uint8_t *variants_a, uint32_t n_variants, const uint8_t *low_conf_a, uint64_t n_a,
+                                    const uint8_t *hashes_b, const uint8_t *low_conf_b, uint64_t n_b, uint32_t similarity, uint32_t part,
+                                    uint32_t nparts, rph_edge *edges, uint64_t cap, uint64_t *n_edges_out)
+{
+    return rph_guarded("rph_hamming_variant_cross_pairs", [&]() -> int {
+        return cross_host(ctx, variants_a, n_variants, low_conf_a, n_a, hashes_b, low_conf_b, n_b, similarity, part, nparts, edges, cap,
+                          n_edges_out);
+    });
+}
+
 int rph_hamming_all_pairs64_dev(rph_ctx *ctx, const void *d_hashes64, uint64_t n, uint32_t threshold, uint32_t part,
                                 uint32_t nparts, void *d_edges, uint64_t cap, void *d_count, void *stream)
 {
@@ -795,6 +883,139 @@ int rph_group_files_pdq(rph_ctx *ctx, const uint8_t *hashes32, const float *coef
         }
         if (comparison_count_out) *comparison_count_out = edges.size();
         return rph_host_union_find(edges.data(), edges.size(), n, members, offsets, n_groups_out);
+    });
+}
+
+int rph_union_find_groups_append(const uint32_t *old_members, const uint32_t *old_offsets, uint32_t n_old_groups, const rph_edge *edges,
+                                 uint64_t n_edges, uint64_t n_total, uint32_t *members, uint32_t *offsets, uint32_t *n_groups_out)
+{
+    return rph_guarded("rph_union_find_groups_append", [&]() -> int {
+        if ((!edges && n_edges) || ((!old_members || !old_offsets) && n_old_groups) || !members || !offsets || !n_groups_out) {
+            rph_set_error("rph_union_find_groups_append: null argument");
+            return RPH_ERR_INVALID_ARG;
+        }
+        return rph_host_union_find_append(old_members, old_offsets, n_old_groups, edges, n_edges, n_total, members, offsets, n_groups_out);
+    });
+}
+
+namespace {
+// One side (library or new files) of rph_group_files_pdq_append on the device: hashes, the variants its files own as rows (8 per file
+// from the coefficients, else the hash itself), has_features and low-confidence flags -- what rph_group_files_pdq builds for its one set.
+struct GroupSide {
+    DevBuf d_h, d_var, d_lc, d_hf, d_stage;
+    uint64_t n = 0;
+    uint32_t n_variants = 1;
+    bool use_hf = false;
+    const uint8_t *rows() const { return n_variants == 8 ? d_var.data() : d_h.data(); }
+    const uint8_t *low_conf() const { return d_lc.data(); }
+    const uint8_t *has_features() const { return use_hf ? d_hf.data() : nullptr; }
+    int upload(const uint8_t *hashes32, const float *coeffs, const uint8_t *hf, const int32_t *quality, uint64_t count, bool want_rows,
+               std::vector<uint8_t> &low_conf_host, hipStream_t s)
+    {
+        n = count;
+        if (n == 0) return RPH_OK;
+        RPH_TRY(d_h.alloc(n * 32));
+        RPH_HIP_CHECK(hipMemcpyAsync(d_h.data(), hashes32, n * 32, hipMemcpyHostToDevice, s));
+        if (quality) {
+            low_conf_host.resize(n);
+            for (uint64_t i = 0; i < n; i++) low_conf_host[i] = (uint8_t)rph_is_low_pdq_quality(quality[i]);
+            RPH_TRY(d_lc.alloc(n));
+            RPH_HIP_CHECK(hipMemcpyAsync(d_lc.data(), low_conf_host.data(), n, hipMemcpyHostToDevice, s));
+        }
+        if (!coeffs || !want_rows) return RPH_OK;
+        n_variants = 8;
+        use_hf = hf != nullptr;
+        if (use_hf) {
+            RPH_TRY(d_hf.alloc(n));
+            RPH_HIP_CHECK(hipMemcpyAsync(d_hf.data(), hf, n, hipMemcpyHostToDevice, s));
+        }
+        RPH_TRY(d_var.alloc(n * 256));
+        const uint64_t step = 1u << 18;  // 256 MiB of coefficients per piece
+        RPH_TRY(d_stage.alloc(std::min<uint64_t>(step, n) * 1024));
+        for (uint64_t first = 0; first < n; first += step) {
+            const uint32_t m = (uint32_t)std::min<uint64_t>(step, n - first);
+            RPH_HIP_CHECK(hipMemcpyAsync(d_stage.data(), coeffs + first * 256, (size_t)m * 1024, hipMemcpyHostToDevice, s));
+            RPH_TRY(rph_launch_pdq_from_coeffs((const float *)d_stage.data(), m, nullptr, d_var.as<uint8_t>() + first * 256, s));
+        }
+        if (use_hf) RPH_TRY(rph_launch_featureless_variants(d_h.as<uint8_t>(), d_hf.as<uint8_t>(), n, d_var.as<uint8_t>(), s));
+        return RPH_OK;
+    }
+};
+}  // namespace
+
+int rph_group_files_pdq_append(rph_ctx *ctx, const uint8_t *old_hashes32, const float *old_coeffs, const uint8_t *old_has_features,
+                               const int32_t *old_quality, uint64_t n_old, const uint32_t *old_members, const uint32_t *old_offsets,
+                               uint32_t n_old_groups, const uint8_t *new_hashes32, const float *new_coeffs, const uint8_t *new_has_features,
+                               const int32_t *new_quality, uint64_t n_new, uint32_t similarity, uint32_t *members, uint32_t *offsets,
+                               uint32_t *n_groups_out, uint64_t *new_comparisons_out)
+{
+    return rph_guarded("rph_group_files_pdq_append", [&]() -> int {
+        if (!ctx || (!old_hashes32 && n_old) || (!new_hashes32 && n_new) || ((!old_members || !old_offsets) && n_old_groups) || !members ||
+            !offsets || !n_groups_out) {
+            rph_set_error("rph_group_files_pdq_append: null argument");
+            return RPH_ERR_INVALID_ARG;
+        }
+        if (similarity > RPH_MAX_SIMILARITY_256) {
+            // scanner.rs:1650-1655 asserts this
+            rph_set_error("Similarity distances above %u require R=4 bit-flip checks, which are not implemented.",
+                          RPH_MAX_SIMILARITY_256);
+            return RPH_ERR_INVALID_ARG;
+        }
+        const uint64_t n_total = n_old + n_new;
+        if (n_total > 0xFFFFFFFFull) {
+            rph_set_error("rph_group_files_pdq_append: %llu files, at most 2^32 - 1", (unsigned long long)n_total);
+            return RPH_ERR_INVALID_ARG;
+        }
+        *n_groups_out = 0;
+        offsets[0] = 0;
+        if (new_comparisons_out) *new_comparisons_out = 0;
+        std::vector<rph_edge> edges;
+        if (n_new) {
+            RPH_HIP_CHECK(hipSetDevice(ctx->device));
+            hipStream_t s = ctx->stream;
+            // group_files_generic tests the variants of the lower-indexed file against the hash of the higher one (scanner.rs:1716), and
+            // the library comes first: the pairs the new files add are (library variants x new hashes), all of them, and
+            // (new variants x new hashes, i < j).  The library's variants are only needed as rows; the new files are rows and columns.
+            GroupSide lib, add;
+            std::vector<uint8_t> lc_old, lc_new;
+            RPH_TRY(lib.upload(old_hashes32, old_coeffs, old_has_features, old_quality, n_old, true, lc_old, s));
+            RPH_TRY(add.upload(new_hashes32, new_coeffs, new_has_features, new_quality, n_new, n_new > 1, lc_new, s));
+            DevBuf d_e, d_cnt;
+            uint64_t cap = std::max<uint64_t>(1u << 20, 32 * n_new);
+            RPH_TRY(d_cnt.alloc(8));
+            for (int attempt = 0;; attempt++) {
+                RPH_TRY(d_e.alloc(cap * sizeof(rph_edge)));
+                RPH_HIP_CHECK(hipMemsetAsync(d_cnt.data(), 0, 8, s));
+                unsigned long long n_cross = 0, found = 0;
+                if (n_old)
+                    RPH_TRY(rph_launch_hamming_cross_sweep(ctx, lib.rows(), lib.n_variants, lib.low_conf(), lib.has_features(), n_old, add.d_h.data(),
+                                                           add.low_conf(), n_new, similarity, 0, 1, d_e.as<rph_edge>(), cap,
+                                                           d_cnt.as<unsigned long long>(), s, ctx->hamming_kernel));
+                RPH_HIP_CHECK(hipMemcpyAsync(&n_cross, d_cnt.data(), 8, hipMemcpyDeviceToHost, s));
+                // the triangular sweep of the new files appends behind the cross edges (one cursor); its indices are local to the new set
+                RPH_TRY(rph_launch_hamming_sweep(ctx, add.rows(), add.n_variants, add.d_h.data(), add.low_conf(), add.has_features(), n_new, similarity,
+                                                 0, 1, d_e.as<rph_edge>(), cap, d_cnt.as<unsigned long long>(), s, ctx->hamming_kernel));
+                RPH_HIP_CHECK(hipMemcpyAsync(&found, d_cnt.data(), 8, hipMemcpyDeviceToHost, s));
+                RPH_HIP_CHECK(hipStreamSynchronize(s));
+                if (found <= cap) {
+                    edges.resize(found);
+                    if (found) RPH_HIP_CHECK(hipMemcpy(edges.data(), d_e.data(), found * sizeof(rph_edge), hipMemcpyDeviceToHost));
+                    for (uint64_t e = 0; e < found; e++) {  // to the numbering of the concatenation
+                        if (e >= n_cross) edges[e].i += (uint32_t)n_old;
+                        edges[e].j += (uint32_t)n_old;
+                    }
+                    break;
+                }
+                if (attempt >= 2) {
+                    rph_set_error("rph_group_files_pdq_append: edge list kept growing (%llu)", found);
+                    return RPH_ERR_CAPACITY;
+                }
+                cap = found + found / 16 + 1024;
+            }
+        }
+        if (new_comparisons_out) *new_comparisons_out = edges.size();
+        return rph_host_union_find_append(old_members, old_offsets, n_old_groups, edges.data(), edges.size(), n_total, members, offsets,
+                                          n_groups_out);
     });
 }
 

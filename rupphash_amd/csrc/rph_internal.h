@@ -41,6 +41,7 @@ struct rph_ctx {
     } rz_last;
     // 2 = fp4 MFMA formulation of the sweep's fast path, popcount-sorted {0,1} operands for plain all-pairs sweeps (default),
     // 3 = fp4 MFMA with +-1 operands everywhere, 4 = sorted {0,1} at every size, 1 = int8 MFMA, 0 = VALU xor + popcount
+    // (cross sweeps: 2, 3 and 4 all mean fp4 MFMA with +-1 operands)
     int hamming_kernel = 2;
     // 512x512 RGB8: 0 = always generic; 1 / 2 = fused one-wave-per-image kernel (64- / 128-px strips); 3 = fused low-latency kernel (eight
     // waves per image); 4 = automatic: low-latency below 768 images per call, one-wave-per-image (64-px strips) from there
@@ -116,6 +117,13 @@ int rph_launch_featureless_variants(const uint8_t *d_hashes, const uint8_t *d_ha
 int rph_launch_hamming_sweep(rph_ctx *ctx, const uint8_t *d_rows, uint32_t n_variants, const uint8_t *d_cols, const uint8_t *d_low_conf,
                              const uint8_t *d_has_features, uint64_t n, uint32_t threshold, uint32_t part, uint32_t nparts, rph_edge *d_edges,
                              uint64_t cap, unsigned long long *d_count, hipStream_t stream, int use_mfma);
+// cross form: set A (n_a files x n_variants, its own flags) against set B (n_b hashes, its own flags), every pair; e.i indexes A, e.j B
+int rph_launch_hamming_cross_sweep(rph_ctx *ctx, const uint8_t *d_a, uint32_t n_variants, const uint8_t *d_low_conf_a, const uint8_t *d_has_features_a,
+                                   uint64_t n_a, const uint8_t *d_b, const uint8_t *d_low_conf_b, uint64_t n_b, uint32_t threshold, uint32_t part,
+                                   uint32_t nparts, rph_edge *d_edges, uint64_t cap, unsigned long long *d_count, hipStream_t stream, int use_mfma);
+// which set a cross sweep puts on the row side, its segment length and block count (exported for the tests, not in the header)
+extern "C" void rph_debug_hamming_cross_layout(uint64_t n_a, uint32_t n_variants, uint64_t n_b, uint32_t nparts, int kernel, uint32_t *swap_out,
+                                               uint32_t *seg_tiles_out, uint32_t *n_col_segs_out, uint64_t *n_blocks_out);
 int rph_launch_hamming64_sweep(const uint64_t *d_hashes, uint64_t n, uint32_t threshold, uint32_t part, uint32_t nparts,
                                rph_edge *d_edges, uint64_t cap, unsigned long long *d_count, hipStream_t stream, int use_mfma);
 int rph_launch_mih_build256(rph_ctx *ctx, const uint8_t *d_hashes, uint64_t n, uint32_t *d_offsets, uint32_t *d_values,
@@ -182,5 +190,8 @@ void rph_jpeg_forget_threads(rph_ctx *ctx);
 // host_grouping.cpp
 int rph_host_union_find(const rph_edge *edges, uint64_t n_edges, uint64_t n, uint32_t *members, uint32_t *offsets,
                         uint32_t *n_groups_out);
+// the same union-find started from the components of an earlier call (old_members / old_offsets as it returned them, validated here)
+int rph_host_union_find_append(const uint32_t *old_members, const uint32_t *old_offsets, uint32_t n_old_groups, const rph_edge *edges,
+                               uint64_t n_edges, uint64_t n, uint32_t *members, uint32_t *offsets, uint32_t *n_groups_out);
 int rph_host_find_groups(const rph_edge *edges, uint64_t n_edges, uint64_t n, uint32_t *members, uint32_t *offsets,
                          uint32_t *n_groups_out);

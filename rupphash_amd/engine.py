@@ -594,6 +594,51 @@ class Engine:
         check(self.L.rph_hamming_variant_pairs_dev(self.ctx, d_variants, n_variants, d_hashes, d_low_conf, n, similarity, part,
                                                    nparts, d_edges, cap, d_count, stream), "rph_hamming_variant_pairs_dev")
 
+    def hamming_cross_pairs(self, a, b, threshold, part=0, nparts=1, cap=None):
+        """Every pair (i in a, j in b) within `threshold`: edges with i indexing `a` and j indexing `b`."""
+        return self.hamming_variant_cross_pairs(np.ascontiguousarray(a, np.uint8).reshape(-1, 1, 32), b, threshold, part=part, nparts=nparts, cap=cap)
+
+    def hamming_cross_pairs_dev(self, d_a, n_a, d_b, n_b, threshold, d_edges, cap, d_count, part=0, nparts=1, stream=None):
+        check(self.L.rph_hamming_cross_pairs_dev(self.ctx, d_a, n_a, d_b, n_b, threshold, part, nparts, d_edges, cap, d_count, stream),
+              "rph_hamming_cross_pairs_dev")
+
+    def hamming_variant_cross_pairs(self, variants_a, hashes_b, similarity, low_conf_a=None, low_conf_b=None, part=0, nparts=1, cap=None):
+        """variants_a: (n_a, 1 or 8, 32) rows of set A; hashes_b: (n_b, 32).  With cap given, RPH_ERR_CAPACITY raises (RphError)."""
+        hashes_b = np.ascontiguousarray(hashes_b, np.uint8).reshape(-1, 32)
+        variants_a = np.ascontiguousarray(variants_a, np.uint8)
+        variants_a = variants_a.reshape(-1, 1, 32) if variants_a.ndim < 3 else variants_a
+        n_a, nv, n_b = variants_a.shape[0], variants_a.shape[1], len(hashes_b)
+        la = None if low_conf_a is None else np.ascontiguousarray(low_conf_a, np.uint8)
+        lb = None if low_conf_b is None else np.ascontiguousarray(low_conf_b, np.uint8)
+        grow = cap is None
+        cap = max(1 << 16, 8 * (n_a + n_b)) if cap is None else cap
+        plain = nv == 1 and la is None and lb is None
+        while True:
+            edges = np.zeros(cap, EDGE_DTYPE)
+            found = C.c_uint64()
+            if plain:
+                rc = self.L.rph_hamming_cross_pairs(self.ctx, _ptr(variants_a), n_a, _ptr(hashes_b), n_b, similarity, part, nparts, _ptr(edges), cap,
+                                                    C.byref(found))
+            else:
+                rc = self.L.rph_hamming_variant_cross_pairs(self.ctx, _ptr(variants_a), nv, _ptr(la), n_a, _ptr(hashes_b), _ptr(lb), n_b, similarity,
+                                                            part, nparts, _ptr(edges), cap, C.byref(found))
+            if rc == _lib.RPH_ERR_CAPACITY and grow:
+                cap = int(found.value) + 1024
+                continue
+            check(rc, "rph_hamming_cross_pairs" if plain else "rph_hamming_variant_cross_pairs")
+            return edges[: found.value]
+
+    def hamming_variant_cross_pairs_dev(self, d_variants_a, n_variants, n_a, d_hashes_b, n_b, similarity, d_edges, cap, d_count, d_low_conf_a=None,
+                                        d_low_conf_b=None, part=0, nparts=1, stream=None):
+        check(self.L.rph_hamming_variant_cross_pairs_dev(self.ctx, d_variants_a, n_variants, d_low_conf_a, n_a, d_hashes_b, d_low_conf_b, n_b,
+                                                         similarity, part, nparts, d_edges, cap, d_count, stream), "rph_hamming_variant_cross_pairs_dev")
+
+    def hamming_cross_layout(self, n_a, n_b, n_variants=1, nparts=1, kernel=2):
+        """(A rides on the column side?, column tiles per block, segments per row tile, blocks) of a cross sweep: the launcher's own rule."""
+        swap, seg, segs, blocks = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint64()
+        self.L.rph_debug_hamming_cross_layout(n_a, n_variants, n_b, nparts, kernel, C.byref(swap), C.byref(seg), C.byref(segs), C.byref(blocks))
+        return bool(swap.value), seg.value, segs.value, blocks.value
+
     @staticmethod
     def _groups(members, offsets, ng):
         return [members[offsets[g]:offsets[g + 1]].tolist() for g in range(ng)]
@@ -667,6 +712,52 @@ class Engine:
         cmp_count = C.c_uint64()
         check(self.L.rph_group_files_pdq(self.ctx, _ptr(hashes), _ptr(c), _ptr(hf), _ptr(q), n, similarity, _ptr(members),
                                          _ptr(offsets), C.byref(ng), C.byref(cmp_count)), "rph_group_files_pdq")
+        return self._groups(members, offsets, ng.value), cmp_count.value
+
+    @staticmethod
+    def _flatten_groups(groups):
+        members = np.array([m for g in groups for m in g], np.uint32)
+        offsets = np.zeros(len(groups) + 1, np.uint32)
+        if len(groups):
+            offsets[1:] = np.cumsum([len(g) for g in groups])
+        return members, offsets
+
+    def union_find_groups_append(self, old_groups, edges, n_total):
+        """Union-find over n_total files from the groups of an earlier call plus `edges`.  old_groups: a list of member lists, or the
+        raw (members, offsets) arrays."""
+        om, oo = old_groups if isinstance(old_groups, tuple) else self._flatten_groups(old_groups)
+        om, oo = np.ascontiguousarray(om, np.uint32), np.ascontiguousarray(oo, np.uint32)
+        edges = np.ascontiguousarray(edges, EDGE_DTYPE)
+        members = np.zeros(max(n_total, 1), np.uint32)
+        offsets = np.zeros(n_total // 2 + 2, np.uint32)
+        ng = C.c_uint32()
+        check(self.L.rph_union_find_groups_append(_ptr(om), _ptr(oo), max(len(oo) - 1, 0), _ptr(edges), len(edges), n_total, _ptr(members),
+                                                  _ptr(offsets), C.byref(ng)), "rph_union_find_groups_append")
+        return self._groups(members, offsets, ng.value)
+
+    def group_files_pdq_append(self, old_hashes, old_groups, new_hashes, similarity, old_coeffs=None, old_has_features=None, old_quality=None,
+                               new_coeffs=None, new_has_features=None, new_quality=None):
+        """Incremental group_files_pdq: the library (grouped before: old_groups as group_files_pdq returned them) plus new files, numbered
+        as the concatenation.  Returns (groups of the concatenation, comparisons the new files added)."""
+        oh = np.ascontiguousarray(old_hashes, np.uint8).reshape(-1, 32)
+        nh = np.ascontiguousarray(new_hashes, np.uint8).reshape(-1, 32)
+        n_old, n_new = len(oh), len(nh)
+
+        def side(coeffs, hf, q, n):
+            return (None if coeffs is None else np.ascontiguousarray(coeffs, np.float32).reshape(n, 256),
+                    None if hf is None else np.ascontiguousarray(hf, np.uint8), None if q is None else np.ascontiguousarray(q, np.int32))
+
+        oc, ohf, oq = side(old_coeffs, old_has_features, old_quality, n_old)
+        nc, nhf, nq = side(new_coeffs, new_has_features, new_quality, n_new)
+        om, oo = self._flatten_groups(old_groups)
+        n = n_old + n_new
+        members = np.zeros(max(n, 1), np.uint32)
+        offsets = np.zeros(n // 2 + 2, np.uint32)
+        ng = C.c_uint32()
+        cmp_count = C.c_uint64()
+        check(self.L.rph_group_files_pdq_append(self.ctx, _ptr(oh), _ptr(oc), _ptr(ohf), _ptr(oq), n_old, _ptr(om), _ptr(oo), len(old_groups),
+                                                _ptr(nh), _ptr(nc), _ptr(nhf), _ptr(nq), n_new, similarity, _ptr(members), _ptr(offsets),
+                                                C.byref(ng), C.byref(cmp_count)), "rph_group_files_pdq_append")
         return self._groups(members, offsets, ng.value), cmp_count.value
 
     def mih_build256(self, hashes):

@@ -106,6 +106,19 @@ def group_with_pdqhash(hashes, similarity, coefficients=None, has_features=None,
     return (engine or default_engine()).group_files_pdq(hashes, similarity, coefficients, has_features, q)
 
 
+def group_with_pdqhash_append(old_hashes, old_groups, new_hashes, similarity, old_coefficients=None, old_has_features=None, old_quality=None,
+                              new_coefficients=None, new_has_features=None, new_quality=None, engine=None):
+    """group_with_pdqhash for a library that was grouped before (`old_groups`: the groups that call returned) plus new files.
+    Files are numbered as the concatenation library ++ new.  Returns (groups, new_comparisons): the groups group_with_pdqhash
+    gives on the concatenation, and the comparisons the new files added to the library's own count."""
+    def q32(quality):
+        return None if quality is None else np.array([-1 if x is None else int(x) for x in quality], np.int32)
+
+    return (engine or default_engine()).group_files_pdq_append(
+        old_hashes, old_groups, new_hashes, similarity, old_coefficients, old_has_features, q32(old_quality), new_coefficients,
+        new_has_features, q32(new_quality))
+
+
 def group_max_dist(groups, hashes, pivots, coefficients=None, has_features=None, engine=None):
     """Per-group `max_dist` of process_raw_groups (scanner.rs:2214-2241).
 
