@@ -129,6 +129,53 @@ int rph_pdq_hash_ragged_dev(rph_ctx *ctx, const void *d_px, const uint64_t *offs
                             void *d_coeffs, void *d_dihedral, void *d_valid, void *stream);
 
 /*
+ * What the scan computes for one decoded image (scanner.rs:1386-1410), for n images of ANY mix of geometries and LAYOUTS in
+ * one call: the PDQ outputs and the pixel hash, both from one upload.  load_image_fast returns an image::DynamicImage of any
+ * variant; scanner.rs:1393-1404 takes blake3 of its to_rgba16(), scanner.rs:1410 hands it to generate_pdq_features, whose
+ * to_luma601 (pdqhash.rs:268-284) borrows Luma8, reads Rgb8 and Rgba8 directly and sends every other variant through to_rgb8().
+ *
+ * layout[i] = channels + (16-bit samples ? 16 : 0), one of the RPH_LAYOUT_* codes; 1, 3 and 4 mean what `channels` means in
+ * rph_pdq_hash_ragged.  Samples are interleaved; 16-bit samples are native little-endian uint16, as in the crate's buffer.
+ * Rgb32F / Rgba32F images are not taken.
+ *  - hash32_out and pixel_hash32_out are each nullable; both null is RPH_ERR_INVALID_ARG.  With hash32_out null no PDQ kernel
+ *    is launched and quality_out, coeffs_out, dihedral_out and valid_out must be null as well.  n = 0 is RPH_OK.
+ *  - PDQ: image i's outputs are bit for bit what rph_pdq_hash_ragged returns for the 8-bit hasher pixels of that image ("What
+ *    is hashed", PNG section): Luma8, Rgb8 and Rgba8 as they are; LumaA8: the L plane is the luma ((299 l + 587 l + 114 l + 500)
+ *    / 1000 = l); Luma16 / LumaA16: luma = (v + 128) / 257; Rgb16 / Rgba16: each sample through (v + 128) / 257, then the 601
+ *    luma.  Alpha is ignored.  w[i] or h[i] < 5: valid 0, outputs zeroed (pdqhash.rs:167-169).
+ *  - Pixel hash: blake3::hash of to_rgba16() as little-endian bytes for EVERY image, those below 5 px too (the reference hashes
+ *    before it looks at the size); w * h = 0 gives the hash of the empty string.  8-bit samples become v * 257, 16-bit samples
+ *    stay, gray is replicated into R, G and B, a missing alpha is 65535.  The RGBA16 stream is never written to memory.
+ *  - RPH_ERR_INVALID_ARG for the whole call, with nothing launched and no output touched: a layout outside the eight codes,
+ *    row_stride[i] < w[i] * bytes per pixel, a 16-bit image whose address (device form: d_px + offset[i]) or row_stride is odd,
+ *    w[i] * h[i] > 2^40, a null required pointer (ctx, px / d_px, px[i], offset, w, h, layout, row_stride).
+ *  - Images with both sides 128..512, and larger ones whose <= 512 px thumbnail has both sides >= 128, are hashed by the
+ *    descriptor-driven kernels of rph_pdq_hash_ragged; images of the five other layouts reach them as Luma8 planes a kernel
+ *    writes into scratch.  The rest go through rph_pdq_hash_batch_dev in runs of equal geometry, the five other layouts as
+ *    Luma8 read from their planes.  No pixel is converted on the host.
+ */
+#define RPH_LAYOUT_LUMA8 1
+#define RPH_LAYOUT_LUMAA8 2
+#define RPH_LAYOUT_RGB8 3
+#define RPH_LAYOUT_RGBA8 4
+#define RPH_LAYOUT_LUMA16 17
+#define RPH_LAYOUT_LUMAA16 18
+#define RPH_LAYOUT_RGB16 19
+#define RPH_LAYOUT_RGBA16 20
+int rph_image_hash_ragged(rph_ctx *ctx, const void *const *px, const uint32_t *w, const uint32_t *h, const uint32_t *layout,
+                          const size_t *row_stride, uint32_t n, uint8_t *hash32_out, float *quality_out, float *coeffs_out,
+                          uint8_t *dihedral_out, uint8_t *valid_out, uint8_t *pixel_hash32_out);
+/* Pixels already on the device: image i starts at (uint8_t *)d_px + offset[i]; the descriptor arrays are HOST arrays,
+ * reusable when the call returns.  Asynchronous on `stream`, exactly like rph_pdq_hash_ragged_dev. */
+int rph_image_hash_ragged_dev(rph_ctx *ctx, const void *d_px, const uint64_t *offset, const uint32_t *w, const uint32_t *h,
+                              const uint32_t *layout, const size_t *row_stride, uint32_t n, void *d_hash32, void *d_quality,
+                              void *d_coeffs, void *d_dihedral, void *d_valid, void *d_pixel_hash32, void *stream);
+/* Context-free host restatements of the two rules above, no GPU call (like rph_blake3_host, rph_png_decode_host): the Luma8
+ * plane the hasher sees (luma_out: w * h bytes, rows packed) and the pixel hash of one image.  RPH_ERR_INVALID_ARG as above. */
+int rph_image_luma601_host(const void *px, uint32_t w, uint32_t h, uint32_t layout, size_t row_stride, uint8_t *luma_out);
+int rph_image_pixel_hash_host(const void *px, uint32_t w, uint32_t h, uint32_t layout, size_t row_stride, uint8_t *digest32_out);
+
+/*
  * generate_pdq_features for ONE image, as scanner.rs:1410 calls it from many rayon workers at once: thread-safe and
  * blocking; concurrent callers are coalesced into GPU batches (images of any mix of sizes) whose transfers are pipelined
  * over three slots.  A batch goes as soon as nobody is still copying into it and a pipeline slot is free, so its size

@@ -48,10 +48,16 @@ private:
     rph_ctx *ctx_ = nullptr;
 };
 
-// Minimal stand-in for image::DynamicImage: interleaved u8 pixels, channels 1 (Luma8), 3 (Rgb8) or 4 (Rgba8).
+// Minimal stand-in for image::DynamicImage: interleaved pixels, channels 1 (Luma), 2 (LumaA), 3 (Rgb) or 4 (Rgba); bit_depth 8 (u8
+// samples) or 16 (native u16 samples at an even address).  Luma8, Rgb8 and Rgba8 are what the hasher reads directly; the other five
+// variants go through rph_image_hash_ragged, which hashes them as to_luma601's to_rgb8() arm does (pdqhash.rs:281-283).
 struct ImageView {
     const uint8_t *data;
     uint32_t width, height, channels;
+    uint32_t bit_depth = 8;
+    uint32_t layout() const { return channels + (bit_depth == 16 ? 16u : 0u); }  // RPH_LAYOUT_*
+    size_t row_bytes() const { return (size_t)width * channels * (bit_depth == 16 ? 2 : 1); }
+    bool direct() const { return bit_depth == 8 && channels != 2; }
 };
 
 namespace pdqhash {
@@ -83,6 +89,15 @@ inline std::optional<std::pair<PdqFeatures, float>> generate_pdq_features(const 
     Hash h{};
     float q = 0.f;
     uint8_t valid = 0;
+    if (!img.direct()) {  // LumaA8 and the 16-bit variants: one image through the call that takes every layout
+        const void *px = img.data;
+        const uint32_t layout = img.layout();
+        const size_t rs = img.row_bytes();
+        check(rph_image_hash_ragged(Context::get(), &px, &img.width, &img.height, &layout, &rs, 1, h.data(), &q, f.coefficients.data(), nullptr, &valid, nullptr),
+              "generate_pdq_features");
+        if (!valid) return std::nullopt;
+        return std::make_pair(f, q);
+    }
     check(rph_pdq_hash_one(Context::get(), img.data, img.width, img.height, img.channels, (size_t)img.width * img.channels, h.data(), &q,
                            f.coefficients.data(), &valid),
           "generate_pdq_features");
@@ -95,6 +110,14 @@ inline std::optional<std::pair<Hash, float>> generate_pdq(const ImageView &img)
     Hash h{};
     float q = 0.f;
     uint8_t valid = 0;
+    if (!img.direct()) {
+        const void *px = img.data;
+        const uint32_t layout = img.layout();
+        const size_t rs = img.row_bytes();
+        check(rph_image_hash_ragged(Context::get(), &px, &img.width, &img.height, &layout, &rs, 1, h.data(), &q, nullptr, nullptr, &valid, nullptr), "generate_pdq");
+        if (!valid) return std::nullopt;
+        return std::make_pair(h, q);
+    }
     check(rph_pdq_hash_one(Context::get(), img.data, img.width, img.height, img.channels, (size_t)img.width * img.channels, h.data(), &q,
                            nullptr, &valid),
           "generate_pdq");
@@ -109,17 +132,24 @@ inline std::vector<std::optional<std::pair<PdqFeatures, float>>> generate_pdq_fe
     std::vector<const uint8_t *> px(n);
     std::vector<uint32_t> w(n), h(n), ch(n);
     std::vector<size_t> rs(n);
+    bool direct = true;
     for (uint32_t i = 0; i < n; i++) {
         px[i] = imgs[i].data;
         w[i] = imgs[i].width;
         h[i] = imgs[i].height;
-        ch[i] = imgs[i].channels;
-        rs[i] = (size_t)imgs[i].width * imgs[i].channels;
+        ch[i] = imgs[i].layout();
+        rs[i] = imgs[i].row_bytes();
+        direct = direct && imgs[i].direct();
     }
     std::vector<uint8_t> hash((size_t)n * 32 + 1), valid(n + 1);
     std::vector<float> q(n + 1), c((size_t)n * 256 + 1);
-    check(rph_pdq_hash_ragged(Context::get(), px.data(), w.data(), h.data(), ch.data(), rs.data(), n, hash.data(), q.data(), c.data(), nullptr, valid.data()),
-          "generate_pdq_features_many");
+    if (direct)
+        check(rph_pdq_hash_ragged(Context::get(), px.data(), w.data(), h.data(), ch.data(), rs.data(), n, hash.data(), q.data(), c.data(), nullptr, valid.data()),
+              "generate_pdq_features_many");
+    else  // some LumaA8 or 16-bit image: the call that takes every layout
+        check(rph_image_hash_ragged(Context::get(), reinterpret_cast<const void *const *>(px.data()), w.data(), h.data(), ch.data(), rs.data(), n, hash.data(),
+                                    q.data(), c.data(), nullptr, valid.data(), nullptr),
+              "generate_pdq_features_many");
     std::vector<std::optional<std::pair<PdqFeatures, float>>> out(n);
     for (uint32_t i = 0; i < n; i++) {
         if (!valid[i]) continue;
@@ -298,6 +328,48 @@ inline std::optional<DecodedImage> load_image_fast(const uint8_t *bytes, size_t 
     img.pixels.resize((size_t)img.width * img.height * img.channels);
     if (rph_jpeg_decode(Context::get(), bytes, len, flavour, img.pixels.data()) != RPH_OK) return std::nullopt;
     return img;
+}
+// scanner.rs:1386-1410 for a list of decoded images of any mix of sizes and layouts, one call (rph_image_hash_ragged): the PDQ hash,
+// quality and features of each (features nullopt <=> generate_pdq_features gave None: a side below 5 px) and, with pixel_hash, the
+// --pixel-hash digest (blake3 of to_rgba16(), scanner.rs:1393-1404), which every image has.
+struct ImageHashes {
+    pdqhash::Hash hash{};
+    float quality = 0.f;
+    std::optional<pdqhash::PdqFeatures> features;
+    std::optional<std::array<uint8_t, 32>> pixel_hash;
+};
+inline std::vector<ImageHashes> hash_images(const std::vector<ImageView> &imgs, bool pixel_hash = true)
+{
+    const uint32_t n = (uint32_t)imgs.size();
+    std::vector<const void *> px(n);
+    std::vector<uint32_t> w(n), h(n), layout(n);
+    std::vector<size_t> rs(n);
+    for (uint32_t i = 0; i < n; i++) {
+        px[i] = imgs[i].data;
+        w[i] = imgs[i].width;
+        h[i] = imgs[i].height;
+        layout[i] = imgs[i].layout();
+        rs[i] = imgs[i].row_bytes();
+    }
+    std::vector<uint8_t> hash((size_t)n * 32 + 1), valid(n + 1), ph((size_t)n * 32 + 1);
+    std::vector<float> q(n + 1), c((size_t)n * 256 + 1);
+    check(rph_image_hash_ragged(Context::get(), px.data(), w.data(), h.data(), layout.data(), rs.data(), n, hash.data(), q.data(), c.data(), nullptr, valid.data(),
+                                pixel_hash ? ph.data() : nullptr),
+          "hash_images");
+    std::vector<ImageHashes> out(n);
+    for (uint32_t i = 0; i < n; i++) {
+        if (valid[i]) {
+            std::copy(hash.begin() + (size_t)i * 32, hash.begin() + (size_t)(i + 1) * 32, out[i].hash.begin());
+            out[i].quality = q[i];
+            out[i].features.emplace();
+            std::copy(c.begin() + (size_t)i * 256, c.begin() + (size_t)(i + 1) * 256, out[i].features->coefficients.begin());
+        }
+        if (pixel_hash) {
+            out[i].pixel_hash.emplace();
+            std::copy(ph.begin() + (size_t)i * 32, ph.begin() + (size_t)(i + 1) * 32, out[i].pixel_hash->begin());
+        }
+    }
+    return out;
 }
 // A batch of files -> hashes (scan loop of scanner.rs:1202-1418 for JPEG files): hash, quality and validity per file; a file that
 // cannot be decoded here comes back with valid = false and keeps the caller's own path.

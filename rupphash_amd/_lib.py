@@ -21,6 +21,10 @@ RPH_ERR_CAPACITY = -6
 RPH_JPEG_ZUNE = 0
 RPH_JPEG_LIBJPEG = 1
 
+# rph_image_hash_ragged: layout = channels + (16 for uint16 samples)
+RPH_LAYOUT_LUMA8, RPH_LAYOUT_LUMAA8, RPH_LAYOUT_RGB8, RPH_LAYOUT_RGBA8 = 1, 2, 3, 4
+RPH_LAYOUT_LUMA16, RPH_LAYOUT_LUMAA16, RPH_LAYOUT_RGB16, RPH_LAYOUT_RGBA16 = 17, 18, 19, 20
+
 RPH_PNG_INFLATE_HOST = 0
 RPH_PNG_INFLATE_DEVICE = 1
 RPH_PNG_INFLATE_AUTO = 2
@@ -68,6 +72,10 @@ SIGNATURES = {
                                          _vp, _vp, _vp]),
     "rph_pdq_hash_ragged": (C.c_int, [_vp, C.POINTER(C.c_void_p), _u32p, _u32p, _u32p, C.POINTER(C.c_size_t), C.c_uint32, _u8p, _f32p, _f32p, _u8p, _u8p]),
     "rph_pdq_hash_ragged_dev": (C.c_int, [_vp, _vp, _u64p, _u32p, _u32p, _u32p, C.POINTER(C.c_size_t), C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rph_image_hash_ragged": (C.c_int, [_vp, C.POINTER(C.c_void_p), _u32p, _u32p, _u32p, C.POINTER(C.c_size_t), C.c_uint32, _u8p, _f32p, _f32p, _u8p, _u8p, _u8p]),
+    "rph_image_hash_ragged_dev": (C.c_int, [_vp, _vp, _u64p, _u32p, _u32p, _u32p, C.POINTER(C.c_size_t), C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rph_image_luma601_host": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, _sz, _u8p]),
+    "rph_image_pixel_hash_host": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, _sz, _u8p]),
     "rph_pdq_hash_one": (C.c_int, [_vp, _u8p, C.c_uint32, C.c_uint32, C.c_uint32, _sz, _u8p, _f32p, _f32p, _u8p]),
     "rph_pdq_batcher_config": (C.c_int, [_vp, C.c_uint32, C.c_uint32]),
     "rph_pdq_batcher_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

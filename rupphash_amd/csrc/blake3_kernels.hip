@@ -13,6 +13,8 @@
 // a pixel are built in registers from the u8 samples; the RGBA16 stream is never written anywhere.  PARITY: the v * 257 widening
 // is the `image` crate's u8 -> u16 conversion as published (to_rgba16 of an 8-bit DynamicImage); the crate's source is not part of
 // the reference tree, so agreement with the Rust binary's digest rests on that mapping.
+// b3_pixels_ragged_kernel is the same for images of any mix of sizes and of the eight layouts of rph_image_hash_ragged (u8 or u16 samples,
+// 1 to 4 channels): a wave finds its image in a prefix table of groups and takes its geometry and layout from a descriptor.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -294,6 +296,133 @@ __global__ void __launch_bounds__(256) b3_pixels_kernel(const uint8_t *__restric
     }
 }
 
+// -------- pixel hash, a geometry and a layout per image --------
+
+// the two RGBA16 message words of one pixel of layout L (RPH_LAYOUT_*: channels + 16 for u16 samples) from its samples s[0 .. channels):
+// u8 samples widen as v * 257, u16 samples stay, gray goes into R, G and B, a missing alpha is 65535
+template <int L>
+__device__ __forceinline__ void layout_words(const uint32_t s[4], uint32_t &w0, uint32_t &w1)
+{
+    constexpr int CH = L & 15;
+    constexpr bool WIDE = L > 16;
+    const uint32_t r = s[0], g = CH >= 3 ? s[1] : r, b = CH >= 3 ? s[2] : r, a = CH == 2 ? s[1] : CH == 4 ? s[3] : (WIDE ? 0xFFFFu : 0xFFu);
+    w0 = (r | (g << 16)) * (WIDE ? 1u : 0x101u);
+    w1 = (b | (a << 16)) * (WIDE ? 1u : 0x101u);
+}
+
+// The chaining value of chunk c (128 pixels from pixel c * 128) of one image of layout L: the chunk loop of b3_pixels_kernel with the
+// sample width and count of the layout.  16-bit images lie at even addresses with even row strides (checked by the entry points).
+template <int L>
+__device__ __forceinline__ void layout_chunk(const uint8_t *__restrict__ img, uint32_t w, size_t row_stride, uint64_t npx, uint64_t nchunks, uint64_t c, uint32_t cv[8])
+{
+    constexpr int CH = L & 15, BPS = L > 16 ? 2 : 1, BPP = CH * BPS;
+    const uint64_t p0 = c * PX_PER_CHUNK;
+    const uint32_t cpx = (uint32_t)min<uint64_t>(PX_PER_CHUNK, npx - min(npx, p0));  // pixels of this chunk
+    const uint32_t nb = cpx ? (cpx + 7) / 8 : 1;
+    uint32_t y = w ? (uint32_t)(p0 / w) : 0, x = w ? (uint32_t)(p0 - (uint64_t)y * w) : 0;
+    const uint8_t *row = img + (size_t)y * row_stride;
+    for (uint32_t bk = 0; bk < nb; bk++) {
+        const uint32_t bpx = min(8u, cpx - min(cpx, bk * 8));
+        uint32_t m[16];
+        if (bpx == 8 && x + 8 <= w) {  // 8 pixels of one row: 8 * BPP bytes through aligned dwords, realigned in registers
+            const uint8_t *p = row + (size_t)x * BPP;
+            const uint32_t sh = (uint32_t)((uintptr_t)p & 3);
+            const uint32_t *q = reinterpret_cast<const uint32_t *>(p - sh);
+            constexpr int ND = 2 * BPP;  // dwords of the 8 pixels
+            uint32_t d[ND + 1], u[ND];
+#pragma unroll
+            for (int i = 0; i < ND; i++) d[i] = q[i];
+            d[ND] = sh ? q[ND] : 0u;  // only when the block's last byte lies in it
+#pragma unroll
+            for (int i = 0; i < ND; i++) u[i] = funnel(d[i], d[i + 1], sh);
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                uint32_t s[4] = {0, 0, 0, 0};
+#pragma unroll
+                for (int k = 0; k < CH; k++) {
+                    const int j = i * CH + k;  // sample j of the block (for Rgba16 the words below are u[2 i], u[2 i + 1]: the image's own bytes)
+                    s[k] = BPS == 2 ? (u[j >> 1] >> (16 * (j & 1))) & 0xFFFFu : (u[j >> 2] >> (8 * (j & 3))) & 0xFFu;
+                }
+                layout_words<L>(s, m[2 * i], m[2 * i + 1]);
+            }
+            x += 8;
+            if (x == w) x = 0, row += row_stride;
+        } else {  // a block that crosses a row end (or the image's last, partial block): pixel by pixel
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                m[2 * i] = m[2 * i + 1] = 0;
+                if ((uint32_t)i < bpx) {
+                    const uint8_t *p = row + (size_t)x * BPP;
+                    uint32_t s[4] = {0, 0, 0, 0};
+#pragma unroll
+                    for (int k = 0; k < CH; k++) s[k] = BPS == 2 ? (uint32_t) reinterpret_cast<const uint16_t *>(p)[k] : (uint32_t)p[k];
+                    layout_words<L>(s, m[2 * i], m[2 * i + 1]);
+                    if (++x == w) x = 0, row += row_stride;
+                }
+            }
+        }
+        const uint32_t fl = (bk == 0 ? B3_CHUNK_START : 0u) | (bk + 1 == nb ? B3_CHUNK_END : 0u) | ((bk + 1 == nb && nchunks == 1) ? B3_ROOT : 0u);
+        b3_compress(cv, m, c, bpx * 8, fl, cv);
+    }
+}
+
+// One wave per group (64 chunks, 8192 pixels) of one image; the wave finds its image in the prefix table of groups (group_first[i] =
+// first group of image i, group_first[n] = the grid's waves).  The search and the descriptor are uniform: scalar loads; the layout is
+// branched on once.  Images of one group write their digest, the others leave group values in cvs for b3_fold_kernel.
+__global__ void __launch_bounds__(256) b3_pixels_ragged_kernel(const uint8_t *__restrict__ px, const RphPixelImage *__restrict__ desc,
+                                                               const uint32_t *__restrict__ group_first, uint32_t n, uint32_t *__restrict__ cvs,
+                                                               uint8_t *__restrict__ digest)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t g = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64);
+    if (g >= group_first[n]) return;
+    uint32_t lo = 0, hi = n;  // the image with group_first[img] <= g < group_first[img + 1]
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) / 2;
+        if (group_first[mid] <= g) lo = mid;
+        else hi = mid;
+    }
+    const uint32_t img = lo, k = g - group_first[img];
+    const RphPixelImage &d = desc[img];
+    const uint32_t w = d.w, layout = d.layout;
+    const size_t row_stride = (size_t)d.row_stride;
+    const uint8_t *base = px + d.src_off;
+    const uint64_t npx = (uint64_t)w * d.h;
+    const uint64_t nchunks = npx ? (npx + PX_PER_CHUNK - 1) / PX_PER_CHUNK : 1;
+    const uint64_t c0 = (uint64_t)k * GROUP_CHUNKS, c = c0 + lane;
+    const uint32_t in_group = (uint32_t)min<uint64_t>(GROUP_CHUNKS, nchunks - c0);
+    Key iv;
+#pragma unroll
+    for (int i = 0; i < 8; i++) iv.w[i] = b3_iv(i);
+    uint32_t cv[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) cv[i] = iv.w[i];
+    if (lane < in_group) {
+        switch (layout) {  // (uniform)
+        case RPH_LAYOUT_LUMA8: layout_chunk<RPH_LAYOUT_LUMA8>(base, w, row_stride, npx, nchunks, c, cv); break;
+        case RPH_LAYOUT_LUMAA8: layout_chunk<RPH_LAYOUT_LUMAA8>(base, w, row_stride, npx, nchunks, c, cv); break;
+        case RPH_LAYOUT_RGB8: layout_chunk<RPH_LAYOUT_RGB8>(base, w, row_stride, npx, nchunks, c, cv); break;
+        case RPH_LAYOUT_RGBA8: layout_chunk<RPH_LAYOUT_RGBA8>(base, w, row_stride, npx, nchunks, c, cv); break;
+        case RPH_LAYOUT_LUMA16: layout_chunk<RPH_LAYOUT_LUMA16>(base, w, row_stride, npx, nchunks, c, cv); break;
+        case RPH_LAYOUT_LUMAA16: layout_chunk<RPH_LAYOUT_LUMAA16>(base, w, row_stride, npx, nchunks, c, cv); break;
+        case RPH_LAYOUT_RGB16: layout_chunk<RPH_LAYOUT_RGB16>(base, w, row_stride, npx, nchunks, c, cv); break;
+        default: layout_chunk<RPH_LAYOUT_RGBA16>(base, w, row_stride, npx, nchunks, c, cv); break;
+        }
+    }
+    const bool whole = nchunks <= GROUP_CHUNKS;
+    wave_fold(cv, in_group, whole, iv, 0);
+    uint32_t v = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const uint32_t x = __shfl(cv[i], 0);  // the folded value is lane 0's: word i goes out from lane i
+        v = lane == (uint32_t)i ? x : v;
+    }
+    if (lane < 8) {
+        if (whole) reinterpret_cast<uint32_t *>(digest + (size_t)img * 32)[lane] = v;
+        else cvs[(size_t)g * 8 + lane] = v;
+    }
+}
+
 Key key_of(const uint8_t *key32)
 {
     Key k;
@@ -341,6 +470,40 @@ int rph_launch_pixel_hash(const uint8_t *d_px, uint32_t n, uint32_t w, uint32_t 
     if (G > 1) {
         hipLaunchKernelGGL(b3_fold_kernel, dim3(n), dim3(64), 0, stream, (const uint32_t *)nullptr, G, (uint32_t)std::min<uint64_t>(waves, UINT32_MAX),
                            key_of(nullptr), 0u, cvs, d_hash32);
+        RPH_HIP_CHECK(hipGetLastError());
+    }
+    return RPH_OK;
+}
+
+// The plan of a ragged pixel-hash call (images already checked): one descriptor per image and the prefix table of groups, n + 1 entries.
+// false: more groups than the 32-bit tables hold.
+bool rph_pixel_hash_ragged_plan(const uint64_t *offset, const uint32_t *w, const uint32_t *h, const uint32_t *layout, const size_t *row_stride, uint32_t n,
+                                std::vector<RphPixelImage> &desc, std::vector<uint32_t> &group_first)
+{
+    desc.resize(n);
+    group_first.resize((size_t)n + 1);
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        desc[i] = RphPixelImage{offset[i], (uint64_t)row_stride[i], w[i], h[i], layout[i], 0};
+        group_first[i] = (uint32_t)total;
+        const uint64_t npx = (uint64_t)w[i] * h[i], nchunks = npx ? (npx + PX_PER_CHUNK - 1) / PX_PER_CHUNK : 1;
+        total += (nchunks + GROUP_CHUNKS - 1) / GROUP_CHUNKS;
+        if (total > UINT32_MAX / 2) return false;
+    }
+    group_first[n] = (uint32_t)total;
+    return true;
+}
+
+// pixel hashes of n images of any mix of geometries and layouts, asynchronous on `stream`.  d_desc, d_group_first: the plan on the device;
+// d_cvs: 32 bytes per group (group_first[n] of them) the launches may use in stream order; multi_group: some image has more than one group
+int rph_launch_pixel_hash_ragged(const uint8_t *d_px, const RphPixelImage *d_desc, const uint32_t *d_group_first, uint32_t n, uint32_t groups, bool multi_group,
+                                 uint32_t *d_cvs, uint8_t *d_hash32, hipStream_t stream)
+{
+    if (n == 0) return RPH_OK;
+    hipLaunchKernelGGL(b3_pixels_ragged_kernel, dim3((groups + 3) / 4), dim3(256), 0, stream, d_px, d_desc, d_group_first, n, d_cvs, d_hash32);
+    RPH_HIP_CHECK(hipGetLastError());
+    if (multi_group) {
+        hipLaunchKernelGGL(b3_fold_kernel, dim3(n), dim3(64), 0, stream, d_group_first, 0u, groups, key_of(nullptr), 0u, d_cvs, d_hash32);
         RPH_HIP_CHECK(hipGetLastError());
     }
     return RPH_OK;

@@ -432,4 +432,46 @@ __device__ __forceinline__ uint32_t st_luma_quad(const uint8_t *p, uint32_t q, u
     return o;
 }
 
+// The same dword of Luma8 for the layouts the hasher does not read directly (include/rupphash.h, rph_image_hash_ragged; the rules of
+// pixel_rules.h): LumaA8 (L = 2) -- the L samples; Luma16 / LumaA16 (17, 18) -- (v + 128) / 257 of the L samples; Rgb16 / Rgba16 (19, 20) --
+// each sample through (v + 128) / 257, then the 601 luma.  Alpha is not used.  The 8 .. 32 bytes of the quad come as aligned dwords +
+// v_alignbyte; 16-bit rows start at even addresses.
+template <int L>
+__device__ __forceinline__ uint32_t st_luma_quad_layout(const uint8_t *p, uint32_t q, uint32_t w)
+{
+    constexpr int CH = L & 15, BPS = L > 16 ? 2 : 1, ND = CH * BPS;  // ND: dwords of four pixels
+    uint32_t d[ND];
+    if (q * 4 + 4 <= w) {
+        const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 3u);
+        const uint32_t *p4 = reinterpret_cast<const uint32_t *>(p - sh);
+        uint32_t raw[ND + 1];
+#pragma unroll
+        for (int i = 0; i < ND; i++) raw[i] = p4[i];
+        raw[ND] = sh ? p4[ND] : 0u;  // (as in st_luma_quad: with sh != 0 that dword holds bytes of this quad)
+#pragma unroll
+        for (int i = 0; i < ND; i++) d[i] = __builtin_amdgcn_alignbyte(raw[i + 1], raw[i], sh);
+    } else {
+#pragma unroll
+        for (int i = 0; i < ND; i++) d[i] = 0;
+        for (uint32_t b = 0; b < (w - q * 4) * CH * BPS; b++) d[b >> 2] |= (uint32_t)p[b] << (8 * (b & 3));
+    }
+    auto sample8 = [&](int j) -> uint32_t {  // sample j of the quad as the hasher's u8
+        if (BPS == 1) return (d[j >> 2] >> (8 * (j & 3))) & 0xFFu;
+        return (((d[j >> 1] >> (16 * (j & 1))) & 0xFFFFu) + 128u) / 257u;
+    };
+    uint32_t o = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        uint32_t y;
+        if (CH <= 2) {
+            y = sample8(i * CH);
+        } else {
+            const uint32_t r = sample8(i * CH), g = sample8(i * CH + 1), b = sample8(i * CH + 2);
+            y = (299u * r + 587u * g + 114u * b + 500u) / 1000u;
+        }
+        o |= y << (8 * i);
+    }
+    return o;
+}
+
 }  // namespace

@@ -12,6 +12,7 @@
 #include <thread>
 #include <vector>
 
+#include "pixel_rules.h"
 #include "rph_internal.h"
 
 static thread_local char g_err[512] = "";
@@ -109,8 +110,8 @@ namespace {
 constexpr size_t kPipeChunkBytes = (size_t)64 << 20;
 struct PipeSet {  // one staging set: pinned host + device buffers of one chunk and the stream they are used on
     hipStream_t stream = nullptr;
-    PinnedBuf h_px, h_hash, h_q, h_c, h_d, h_v;
-    DevBuf d_px, d_hash, d_q, d_c, d_d, d_v;
+    PinnedBuf h_px, h_hash, h_q, h_c, h_d, h_v, h_ph;
+    DevBuf d_px, d_hash, d_q, d_c, d_d, d_v, d_ph;  // (ph: pixel hashes, rph_image_hash_ragged only)
 };
 struct HostPipe {
     PipeSet set[2];
@@ -124,7 +125,7 @@ struct HostPipe {
     }
 };
 
-int pipe_of(rph_ctx *ctx, size_t px_bytes, uint32_t images, HostPipe **out)
+int pipe_of(rph_ctx *ctx, size_t px_bytes, uint32_t images, HostPipe **out, bool pixel_hashes = false)
 {
     if (!ctx->pipe) ctx->pipe = new HostPipe();
     HostPipe &P = *static_cast<HostPipe *>(ctx->pipe);
@@ -140,6 +141,7 @@ int pipe_of(rph_ctx *ctx, size_t px_bytes, uint32_t images, HostPipe **out)
         RPH_TRY(twin(S.h_c, S.d_c, (size_t)images * 1024));
         RPH_TRY(twin(S.h_d, S.d_d, (size_t)images * 256));
         RPH_TRY(twin(S.h_v, S.d_v, images));
+        if (pixel_hashes) RPH_TRY(twin(S.h_ph, S.d_ph, (size_t)images * 32));
     }
     *out = &P;
     return RPH_OK;
@@ -432,9 +434,93 @@ int rph_pdq_hash_batch_keep(rph_ctx *ctx, const uint8_t *px, uint32_t n, uint32_
     });
 }
 
-// Host form of the ragged call: the images are packed into the pinned staging sets of rph_pdq_hash_batch -- each at a 16-byte aligned
-// offset, rows at a pitch that is a multiple of 4 (the streaming kernel reads Luma8 images of 128..512 px straight from there) -- in
-// chunks of ctx->ragged_chunk_bytes; chunk k is hashed while the host threads pack chunk k + 1 into the other set.
+// Host form of the ragged calls: the images are packed into the pinned staging sets of rph_pdq_hash_batch -- each at a 16-byte aligned
+// offset, rows at a pitch that is a multiple of 4 (the streaming kernel reads Luma8 images of 128..512 px straight from there; 16-bit
+// images lie at even addresses with even pitches) -- in chunks of ctx->ragged_chunk_bytes; chunk k is hashed while the host threads pack
+// chunk k + 1 into the other set.  layout: RPH_LAYOUT_* codes, checked by the caller; hash32_out or pixel_hash32_out may be null
+// (rph_image_hash_ragged): both hashes of a chunk come from its one upload.
+static int ragged_host(rph_ctx *ctx, const uint8_t *const *px, const uint32_t *w, const uint32_t *h, const uint32_t *layout, const size_t *row_stride, uint32_t n,
+                       uint8_t *hash32_out, float *quality_out, float *coeffs_out, uint8_t *dihedral_out, uint8_t *valid_out, uint8_t *pixel_hash32_out)
+{
+    RPH_HIP_CHECK(hipSetDevice(ctx->device));
+    // the packed form of every image, and the chunks
+    constexpr uint32_t kMaxChunkImages = 16384;
+    std::vector<size_t> pitch(n);
+    std::vector<uint64_t> offset(n);
+    std::vector<uint32_t> chunk_first;  // + the end
+    size_t max_bytes = 0, bytes = 0;
+    uint32_t max_images = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        pitch[i] = align_up((size_t)w[i] * rph_layout_bytes(layout[i]), 4);
+        const size_t size = pitch[i] * h[i];
+        // (an image larger than a chunk gets one of its own)
+        if (chunk_first.empty() || (i > chunk_first.back() && (align_up(bytes, 16) + size > ctx->ragged_chunk_bytes || i - chunk_first.back() >= kMaxChunkImages))) {
+            chunk_first.push_back(i);
+            bytes = 0;
+        }
+        offset[i] = align_up(bytes, 16);
+        bytes = offset[i] + size;
+        max_bytes = std::max(max_bytes, bytes);
+        max_images = std::max(max_images, i - chunk_first.back() + 1);
+    }
+    chunk_first.push_back(n);
+    std::lock_guard<std::mutex> pipe_lock(ctx->pipe_mu);
+    HostPipe *P = nullptr;
+    RPH_TRY(pipe_of(ctx, max_bytes + 16, max_images, &P, pixel_hash32_out != nullptr));
+    struct Pending {
+        uint32_t first = 0, m = 0;
+        bool active = false;
+    } pend[2];
+    auto finish = [&](int b) -> int {  // results of the chunk that used set b -> the caller's arrays
+        if (!pend[b].active) return RPH_OK;
+        const PipeSet &S = P->set[b];
+        RPH_HIP_CHECK(hipStreamSynchronize(S.stream));
+        const uint32_t first = pend[b].first, m = pend[b].m;
+        if (hash32_out) std::memcpy(hash32_out + (size_t)first * 32, S.h_hash.data(), (size_t)m * 32);
+        if (quality_out) std::memcpy(quality_out + first, S.h_q.data(), (size_t)m * 4);
+        if (coeffs_out) std::memcpy(coeffs_out + (size_t)first * 256, S.h_c.data(), (size_t)m * 1024);
+        if (dihedral_out) std::memcpy(dihedral_out + (size_t)first * 256, S.h_d.data(), (size_t)m * 256);
+        if (valid_out) std::memcpy(valid_out + first, S.h_v.data(), m);
+        if (pixel_hash32_out) std::memcpy(pixel_hash32_out + (size_t)first * 32, S.h_ph.data(), (size_t)m * 32);
+        pend[b].active = false;
+        return RPH_OK;
+    };
+    const unsigned nt = std::min(8u, rph_host_threads());
+    for (size_t k = 0; k + 1 < chunk_first.size(); k++) {
+        const int b = (int)(k & 1);
+        RPH_TRY(finish(b));
+        PipeSet &S = P->set[b];
+        const uint32_t first = chunk_first[k], m = chunk_first[k + 1] - first;
+        parallel_for(first, first + m, nt, [&](size_t i) {
+            uint8_t *to = S.h_px.data() + offset[i];
+            const size_t row = (size_t)w[i] * rph_layout_bytes(layout[i]);
+            if (row_stride[i] == pitch[i]) {
+                if (h[i]) std::memcpy(to, px[i], pitch[i] * (h[i] - 1) + row);
+            } else {
+                for (uint32_t y = 0; y < h[i]; y++) std::memcpy(to + y * pitch[i], px[i] + (size_t)y * row_stride[i], row);
+            }
+        });
+        const size_t used = (size_t)offset[first + m - 1] + pitch[first + m - 1] * h[first + m - 1];
+        hipStream_t s = S.stream;
+        if (used) RPH_HIP_CHECK(hipMemcpyAsync(S.d_px.data(), S.h_px.data(), used, hipMemcpyHostToDevice, s));
+        RPH_TRY(rph_image_ragged_run(ctx, S.d_px.data(), offset.data() + first, w + first, h + first, layout + first, pitch.data() + first, m,
+                                     hash32_out ? S.d_hash.data() : nullptr, quality_out ? S.d_q.as<float>() : nullptr, coeffs_out ? S.d_c.as<float>() : nullptr,
+                                     dihedral_out ? S.d_d.data() : nullptr, valid_out ? S.d_v.data() : nullptr, pixel_hash32_out ? S.d_ph.data() : nullptr, s));
+        if (hash32_out) RPH_HIP_CHECK(hipMemcpyAsync(S.h_hash.data(), S.d_hash.data(), (size_t)m * 32, hipMemcpyDeviceToHost, s));
+        if (quality_out) RPH_HIP_CHECK(hipMemcpyAsync(S.h_q.data(), S.d_q.data(), (size_t)m * 4, hipMemcpyDeviceToHost, s));
+        if (coeffs_out) RPH_HIP_CHECK(hipMemcpyAsync(S.h_c.data(), S.d_c.data(), (size_t)m * 1024, hipMemcpyDeviceToHost, s));
+        if (dihedral_out) RPH_HIP_CHECK(hipMemcpyAsync(S.h_d.data(), S.d_d.data(), (size_t)m * 256, hipMemcpyDeviceToHost, s));
+        if (valid_out) RPH_HIP_CHECK(hipMemcpyAsync(S.h_v.data(), S.d_v.data(), m, hipMemcpyDeviceToHost, s));
+        if (pixel_hash32_out) RPH_HIP_CHECK(hipMemcpyAsync(S.h_ph.data(), S.d_ph.data(), (size_t)m * 32, hipMemcpyDeviceToHost, s));
+        pend[b].first = first;
+        pend[b].m = m;
+        pend[b].active = true;
+    }
+    RPH_TRY(finish(0));
+    RPH_TRY(finish(1));
+    return RPH_OK;
+}
+
 extern "C" int rph_pdq_hash_ragged(rph_ctx *ctx, const uint8_t *const *px, const uint32_t *w, const uint32_t *h, const uint32_t *channels, const size_t *row_stride,
                                    uint32_t n, uint8_t *hash32_out, float *quality_out, float *coeffs_out, uint8_t *dihedral_out, uint8_t *valid_out)
 {
@@ -449,80 +535,105 @@ extern "C" int rph_pdq_hash_ragged(rph_ctx *ctx, const uint8_t *const *px, const
                 rph_set_error("rph_pdq_hash_ragged: invalid argument (image %u: %ux%ux%u row_stride=%zu)", i, w[i], h[i], channels[i], px[i] ? row_stride[i] : (size_t)0);
                 return RPH_ERR_INVALID_ARG;
             }
-        RPH_HIP_CHECK(hipSetDevice(ctx->device));
-        // the packed form of every image, and the chunks
-        constexpr uint32_t kMaxChunkImages = 16384;
-        std::vector<size_t> pitch(n);
-        std::vector<uint64_t> offset(n);
-        std::vector<uint32_t> chunk_first;  // + the end
-        size_t max_bytes = 0, bytes = 0;
-        uint32_t max_images = 0;
-        for (uint32_t i = 0; i < n; i++) {
-            pitch[i] = align_up((size_t)w[i] * channels[i], 4);
-            const size_t size = pitch[i] * h[i];
-            // (an image larger than a chunk gets one of its own)
-            if (chunk_first.empty() || (i > chunk_first.back() && (align_up(bytes, 16) + size > ctx->ragged_chunk_bytes || i - chunk_first.back() >= kMaxChunkImages))) {
-                chunk_first.push_back(i);
-                bytes = 0;
+        return ragged_host(ctx, px, w, h, channels, row_stride, n, hash32_out, quality_out, coeffs_out, dihedral_out, valid_out, nullptr);
+    });
+}
+
+// what is wrong with one image of an rph_image_* call (px: null only where the caller allows it), or nullptr
+static const char *image_fault(const void *px, uint32_t w, uint32_t h, uint32_t layout, size_t row_stride)
+{
+    const uint32_t bpp = rph_layout_bytes(layout);
+    if (!bpp) return "unknown layout";
+    if (row_stride < (size_t)w * bpp) return "row_stride below the row's bytes";
+    if (layout > 16 && (((uintptr_t)px | row_stride) & 1)) return "16-bit image at an odd address or with an odd row_stride";
+    if ((uint64_t)w * h > ((uint64_t)1 << 40)) return "more than 2^40 pixels";
+    return nullptr;
+}
+
+extern "C" int rph_image_hash_ragged(rph_ctx *ctx, const void *const *px, const uint32_t *w, const uint32_t *h, const uint32_t *layout, const size_t *row_stride,
+                                     uint32_t n, uint8_t *hash32_out, float *quality_out, float *coeffs_out, uint8_t *dihedral_out, uint8_t *valid_out,
+                                     uint8_t *pixel_hash32_out)
+{
+    return rph_guarded("rph_image_hash_ragged", [&]() -> int {
+        if (ctx && n == 0) return RPH_OK;
+        if (!ctx || !px || !w || !h || !layout || !row_stride || (!hash32_out && !pixel_hash32_out) ||
+            (!hash32_out && (quality_out || coeffs_out || dihedral_out || valid_out))) {
+            rph_set_error("rph_image_hash_ragged: null argument (or no output, or PDQ outputs without hash32_out)");
+            return RPH_ERR_INVALID_ARG;
+        }
+        for (uint32_t i = 0; i < n; i++)
+            if (const char *why = px[i] ? image_fault(px[i], w[i], h[i], layout[i], row_stride[i]) : "null pixels") {
+                rph_set_error("rph_image_hash_ragged: invalid argument (image %u: %ux%u layout %u: %s)", i, w[i], h[i], layout[i], why);
+                return RPH_ERR_INVALID_ARG;
             }
-            offset[i] = align_up(bytes, 16);
-            bytes = offset[i] + size;
-            max_bytes = std::max(max_bytes, bytes);
-            max_images = std::max(max_images, i - chunk_first.back() + 1);
+        return ragged_host(ctx, reinterpret_cast<const uint8_t *const *>(px), w, h, layout, row_stride, n, hash32_out, quality_out, coeffs_out, dihedral_out, valid_out,
+                           pixel_hash32_out);
+    });
+}
+
+// the native samples of pixel x of a row (pixel_rules.h takes them as u32)
+static inline void native_samples(const uint8_t *row, uint32_t x, uint32_t ch, bool wide, uint32_t v[4])
+{
+    for (uint32_t k = 0; k < ch; k++) {
+        if (wide) {
+            uint16_t s;
+            std::memcpy(&s, row + ((size_t)x * ch + k) * 2, 2);
+            v[k] = s;
+        } else {
+            v[k] = row[(size_t)x * ch + k];
         }
-        chunk_first.push_back(n);
-        std::lock_guard<std::mutex> pipe_lock(ctx->pipe_mu);
-        HostPipe *P = nullptr;
-        RPH_TRY(pipe_of(ctx, max_bytes + 16, max_images, &P));
-        struct Pending {
-            uint32_t first = 0, m = 0;
-            bool active = false;
-        } pend[2];
-        auto finish = [&](int b) -> int {  // results of the chunk that used set b -> the caller's arrays
-            if (!pend[b].active) return RPH_OK;
-            const PipeSet &S = P->set[b];
-            RPH_HIP_CHECK(hipStreamSynchronize(S.stream));
-            const uint32_t first = pend[b].first, m = pend[b].m;
-            std::memcpy(hash32_out + (size_t)first * 32, S.h_hash.data(), (size_t)m * 32);
-            if (quality_out) std::memcpy(quality_out + first, S.h_q.data(), (size_t)m * 4);
-            if (coeffs_out) std::memcpy(coeffs_out + (size_t)first * 256, S.h_c.data(), (size_t)m * 1024);
-            if (dihedral_out) std::memcpy(dihedral_out + (size_t)first * 256, S.h_d.data(), (size_t)m * 256);
-            if (valid_out) std::memcpy(valid_out + first, S.h_v.data(), m);
-            pend[b].active = false;
-            return RPH_OK;
-        };
-        const unsigned nt = std::min(8u, rph_host_threads());
-        for (size_t k = 0; k + 1 < chunk_first.size(); k++) {
-            const int b = (int)(k & 1);
-            RPH_TRY(finish(b));
-            PipeSet &S = P->set[b];
-            const uint32_t first = chunk_first[k], m = chunk_first[k + 1] - first;
-            parallel_for(first, first + m, nt, [&](size_t i) {
-                uint8_t *to = S.h_px.data() + offset[i];
-                const size_t row = (size_t)w[i] * channels[i];
-                if (row_stride[i] == pitch[i]) {
-                    if (h[i]) std::memcpy(to, px[i], pitch[i] * (h[i] - 1) + row);
-                } else {
-                    for (uint32_t y = 0; y < h[i]; y++) std::memcpy(to + y * pitch[i], px[i] + (size_t)y * row_stride[i], row);
-                }
-            });
-            const size_t used = (size_t)offset[first + m - 1] + pitch[first + m - 1] * h[first + m - 1];
-            hipStream_t s = S.stream;
-            if (used) RPH_HIP_CHECK(hipMemcpyAsync(S.d_px.data(), S.h_px.data(), used, hipMemcpyHostToDevice, s));
-            RPH_TRY(rph_pdq_ragged_run(ctx, S.d_px.data(), offset.data() + first, w + first, h + first, channels + first, pitch.data() + first, m, S.d_hash.data(),
-                                       quality_out ? S.d_q.as<float>() : nullptr, coeffs_out ? S.d_c.as<float>() : nullptr, dihedral_out ? S.d_d.data() : nullptr,
-                                       valid_out ? S.d_v.data() : nullptr, s));
-            RPH_HIP_CHECK(hipMemcpyAsync(S.h_hash.data(), S.d_hash.data(), (size_t)m * 32, hipMemcpyDeviceToHost, s));
-            if (quality_out) RPH_HIP_CHECK(hipMemcpyAsync(S.h_q.data(), S.d_q.data(), (size_t)m * 4, hipMemcpyDeviceToHost, s));
-            if (coeffs_out) RPH_HIP_CHECK(hipMemcpyAsync(S.h_c.data(), S.d_c.data(), (size_t)m * 1024, hipMemcpyDeviceToHost, s));
-            if (dihedral_out) RPH_HIP_CHECK(hipMemcpyAsync(S.h_d.data(), S.d_d.data(), (size_t)m * 256, hipMemcpyDeviceToHost, s));
-            if (valid_out) RPH_HIP_CHECK(hipMemcpyAsync(S.h_v.data(), S.d_v.data(), m, hipMemcpyDeviceToHost, s));
-            pend[b].first = first;
-            pend[b].m = m;
-            pend[b].active = true;
+    }
+}
+
+extern "C" int rph_image_luma601_host(const void *px, uint32_t w, uint32_t h, uint32_t layout, size_t row_stride, uint8_t *luma_out)
+{
+    return rph_guarded("rph_image_luma601_host", [&]() -> int {
+        const bool empty = (uint64_t)w * h == 0;
+        if (const char *why = !px && !empty ? "null pixels" : image_fault(px, w, h, layout, row_stride); why || (!luma_out && !empty)) {
+            rph_set_error("rph_image_luma601_host: invalid argument (%ux%u layout %u: %s)", w, h, layout, why ? why : "null output");
+            return RPH_ERR_INVALID_ARG;
         }
-        RPH_TRY(finish(0));
-        RPH_TRY(finish(1));
+        const uint32_t ch = layout & 15u, depth = layout > 16 ? 16 : 8;
+        for (uint32_t y = 0; y < h; y++) {
+            const uint8_t *row = (const uint8_t *)px + (size_t)y * row_stride;
+            for (uint32_t x = 0; x < w; x++) {
+                uint32_t v[4] = {0, 0, 0, 0};
+                uint8_t o[4] = {0, 0, 0, 0};
+                native_samples(row, x, ch, depth == 16, v);
+                rphx::hasher_pixel(ch, depth, v, o);
+                // to_luma601 (pdqhash.rs:268-284) of the hasher's pixel; Luma8 is borrowed
+                luma_out[(size_t)y * w + x] = (ch == 1 && depth == 8) ? o[0] : (uint8_t)((299u * o[0] + 587u * o[1] + 114u * o[2] + 500u) / 1000u);
+            }
+        }
+        return RPH_OK;
+    });
+}
+
+extern "C" int rph_image_pixel_hash_host(const void *px, uint32_t w, uint32_t h, uint32_t layout, size_t row_stride, uint8_t *digest32_out)
+{
+    return rph_guarded("rph_image_pixel_hash_host", [&]() -> int {
+        const bool empty = (uint64_t)w * h == 0;
+        if (const char *why = !px && !empty ? "null pixels" : image_fault(px, w, h, layout, row_stride); why || !digest32_out) {
+            rph_set_error("rph_image_pixel_hash_host: invalid argument (%ux%u layout %u: %s)", w, h, layout, why ? why : "null output");
+            return RPH_ERR_INVALID_ARG;
+        }
+        const uint32_t ch = layout & 15u;
+        const bool wide = layout > 16;
+        std::vector<uint8_t> stream((size_t)w * h * 8);  // to_rgba16() as little-endian bytes
+        size_t at = 0;
+        for (uint32_t y = 0; y < h; y++) {
+            const uint8_t *row = (const uint8_t *)px + (size_t)y * row_stride;
+            for (uint32_t x = 0; x < w; x++) {
+                uint32_t v[4] = {0, 0, 0, 0};
+                uint16_t o[4];
+                native_samples(row, x, ch, wide, v);
+                if (!wide)
+                    for (uint32_t k = 0; k < ch; k++) v[k] *= 257u;  // the crate's u8 -> u16
+                rphx::rgba16_pixel(ch, v, o);
+                for (int k = 0; k < 4; k++) stream[at++] = (uint8_t)(o[k] & 0xFF), stream[at++] = (uint8_t)(o[k] >> 8);
+            }
+        }
+        rph_blake3_host(stream.data(), stream.size(), nullptr, digest32_out);
         return RPH_OK;
     });
 }

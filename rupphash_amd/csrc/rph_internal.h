@@ -33,6 +33,10 @@ struct rph_ctx {
     // (RPH_RAGGED_CHUNK_BYTES, tests only: read once, by rph_init)
     void *ragged = nullptr;
     size_t ragged_chunk_bytes = (size_t)64 << 20;
+    // rph_image_hash_ragged (pdq_ragged.hip): Luma8 planes of the images of the other layouts that go through rph_pdq_hash_batch_dev;
+    // image_mu is held from the kernel that writes them to the last launch that reads them, and guards the scratch in place of mu
+    std::mutex image_mu;
+    SharedScratch image_planes;
     void *axis_cache = nullptr;  // per-geometry coefficient tables of the pre-downsample, kept across calls (resize_kernels.hip)
     // where the last pre-downsample call left its thumbnails in rz_scratch (rph_debug_copy_thumbnails; n = 0: the call took several chunks)
     struct {
@@ -106,9 +110,20 @@ int rph_launch_pdq_resized(rph_ctx *ctx, const uint8_t *d_px, uint32_t n, uint32
 // coefficient of every output); false: the taps of some output differ (the matrix-pipe form does not apply)
 bool rph_resize_axis_tables(uint32_t in_size, uint32_t out_size, std::vector<uint32_t> &start, std::vector<uint32_t> &size, std::vector<int32_t> &c1, int *precision);
 // pdq_ragged.hip: images of any mix of geometries, validated by the caller (rph_api.cpp); d_px + offset[i] = image i
+// (channels: 1, 3, 4 for rph_pdq_hash_ragged; any RPH_LAYOUT_* code for rph_image_hash_ragged)
 int rph_pdq_ragged_run(rph_ctx *ctx, const uint8_t *d_px, const uint64_t *offset, const uint32_t *w, const uint32_t *h, const uint32_t *channels,
                        const size_t *row_stride, uint32_t n, uint8_t *d_hash, float *d_quality, float *d_coeffs, uint8_t *d_dihedral, uint8_t *d_valid,
                        hipStream_t stream);
+// rph_image_hash_ragged_dev without its checks: PDQ outputs when d_hash is given, pixel hashes when d_pixel_hash is
+int rph_image_ragged_run(rph_ctx *ctx, const uint8_t *d_px, const uint64_t *offset, const uint32_t *w, const uint32_t *h, const uint32_t *layout,
+                         const size_t *row_stride, uint32_t n, uint8_t *d_hash, float *d_quality, float *d_coeffs, uint8_t *d_dihedral, uint8_t *d_valid,
+                         uint8_t *d_pixel_hash, hipStream_t stream);
+// bytes per pixel of a layout code, 0 for a code that is none
+static inline uint32_t rph_layout_bytes(uint32_t layout)
+{
+    const uint32_t ch = layout & 15u;
+    return ((layout & ~16u) == ch && ch >= 1 && ch <= 4) ? ch * (layout > 16 ? 2u : 1u) : 0u;
+}
 void rph_ragged_forget(rph_ctx *ctx);
 int rph_launch_pdq_from_coeffs(const float *d_coeffs, uint32_t n, uint8_t *d_hash, uint8_t *d_dihedral, hipStream_t stream);
 int rph_launch_lowconf_from_quality(const float *d_quality, const uint8_t *d_valid, uint64_t n, uint8_t *d_low, hipStream_t stream);
@@ -141,6 +156,16 @@ int rph_launch_synth_hashes(uint8_t *d_out, uint64_t first, uint64_t count, uint
 size_t rph_pixel_hash_scratch_bytes(uint32_t n, uint32_t w, uint32_t h);
 int rph_launch_pixel_hash(const uint8_t *d_px, uint32_t n, uint32_t w, uint32_t h, uint32_t channels, size_t row_stride, size_t image_stride,
                           uint8_t *d_hash32, hipStream_t stream, void *d_scratch);
+// the same for n images of any mix of geometries and layouts (RPH_LAYOUT_*), image i at d_px + src_off: the host plans the call into one
+// descriptor per image and the prefix table of 64-chunk groups, the caller uploads both and gives 32 bytes of scratch per group
+struct RphPixelImage {
+    uint64_t src_off, row_stride;
+    uint32_t w, h, layout, pad;
+};
+bool rph_pixel_hash_ragged_plan(const uint64_t *offset, const uint32_t *w, const uint32_t *h, const uint32_t *layout, const size_t *row_stride, uint32_t n,
+                                std::vector<RphPixelImage> &desc, std::vector<uint32_t> &group_first);
+int rph_launch_pixel_hash_ragged(const uint8_t *d_px, const RphPixelImage *d_desc, const uint32_t *d_group_first, uint32_t n, uint32_t groups, bool multi_group,
+                                 uint32_t *d_cvs, uint8_t *d_hash32, hipStream_t stream);
 
 // png_kernels.hip: one wave per zlib stream (rphp::StreamDesc: compressed bytes, destination, the image whose status a refused stream
 // sets); the TIFF path runs its Deflate strips and tiles through it too

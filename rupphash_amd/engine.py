@@ -53,6 +53,48 @@ def ragged_pack(images, align=16, pitch_align=4, fill=0):
     return buf, offset, ws, hs, chs, rs
 
 
+def _image_view(image):
+    """(h, w), (h, w, 2), (h, w, 3) or (h, w, 4), uint8 or uint16 -> (array, h, w, layout, row stride in bytes): _ragged_view for every
+    layout of rph_image_hash_ragged (layout = channels + 16 for uint16).  Other dtypes are taken as uint8, as np.asarray(image, np.uint8)."""
+    a = np.asarray(image)
+    if a.dtype.kind == "u" and a.dtype.itemsize == 2:
+        a = a if a.dtype.isnative else a.astype(np.uint16)
+    else:
+        a = np.asarray(a, np.uint8)
+    if a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] not in (2, 3, 4)):
+        raise ValueError(f"image of shape {a.shape}: (h, w), (h, w, 2), (h, w, 3) or (h, w, 4) wanted")
+    h, w = a.shape[:2]
+    ch, bps = (1 if a.ndim == 2 else a.shape[2]), a.dtype.itemsize
+    inner = (bps,) if a.ndim == 2 else (ch * bps, bps)
+    if h and w and (a.strides[1:] != inner or (h > 1 and a.strides[0] < w * ch * bps) or (a.ctypes.data | a.strides[0]) % bps):
+        a = np.ascontiguousarray(a)
+    return a, h, w, ch + (16 if bps == 2 else 0), (a.strides[0] if h > 1 and w else w * ch * bps)
+
+
+def image_pack(images, align=16, pitch_align=4, fill=0):
+    """ragged_pack for Engine.image_hash_ragged_dev: one uint8 buffer with image i (uint8 or uint16, 1 to 4 channels) at offset[i] (a
+    multiple of `align`; rounded up to an even number for a 16-bit image), its rows row_stride[i] = the row's bytes rounded up to
+    `pitch_align` (and to 2 for a 16-bit image) apart; 16-bit samples in native byte order; gaps and row padding hold `fill`.
+    Returns (buffer, offset uint64, w uint32, h uint32, layout uint32, row_stride uintp)."""
+    views = [_image_view(im) for im in images]
+    n = len(views)
+    offset, ws, hs, ls, rs = np.zeros(n, np.uint64), np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uintp)
+    end = 0
+    for i, (a, h, w, layout, _) in enumerate(views):
+        row, even = w * (layout & 15) * a.dtype.itemsize, a.dtype.itemsize
+        pitch = -(-(-(-row // pitch_align) * pitch_align) // even) * even
+        at = -(-(-(-end // align) * align) // even) * even
+        offset[i], ws[i], hs[i], ls[i], rs[i] = at, w, h, layout, pitch
+        end = at + pitch * h
+    buf = np.full(max(end, 1), fill, np.uint8)
+    for i, (a, h, w, layout, _) in enumerate(views):
+        if h and w:
+            row = w * (layout & 15) * a.dtype.itemsize
+            rows = np.lib.stride_tricks.as_strided(buf[int(offset[i]):], (h, row), (int(rs[i]), 1), writeable=True)
+            rows[...] = np.ascontiguousarray(a).view(np.uint8).reshape(h, row)
+    return buf, offset, ws, hs, ls, rs
+
+
 class Engine:
     def __init__(self, device=0):
         self.L = _lib.load()
@@ -148,6 +190,61 @@ class Engine:
             raise ValueError("descriptor arrays of different lengths")
         check(self.L.rph_pdq_hash_ragged_dev(self.ctx, d_px, _ptr(offset), _ptr(w), _ptr(h), _ptr(channels), row_stride.ctypes.data_as(C.POINTER(C.c_size_t)), n,
                                              d_hash, d_quality, d_coeffs, d_dihedral, d_valid, stream), "rph_pdq_hash_ragged_dev")
+
+    def image_hash_ragged(self, images, want_pdq=True, want_pixel_hash=True, want_quality=True, want_coeffs=False, want_dihedral=False):
+        """What the scan computes per decoded image (scanner.rs:1386-1410), one call for a list of images of ANY mix of sizes and layouts:
+        uint8 or uint16 arrays (h, w), (h, w, 2) [gray + alpha], (h, w, 3) or (h, w, 4), slices of larger arrays read where they lie.
+        Returns dict(hash, quality, coeffs, dihedral, valid, pixel_hash); the PDQ entries are None without want_pdq, pixel_hash (n x 32)
+        without want_pixel_hash.  valid 0 and zeros for an image with a side < 5; its pixel hash is still there."""
+        if not (want_pdq or want_pixel_hash):
+            raise ValueError("image_hash_ragged: neither hash wanted")
+        views = [_image_view(im) for im in images]
+        n = len(views)
+        px = (C.c_void_p * max(n, 1))(*[v[0].ctypes.data for v in views])
+        h = np.array([v[1] for v in views], np.uint32)
+        w = np.array([v[2] for v in views], np.uint32)
+        layout = np.array([v[3] for v in views], np.uint32)
+        rs = (C.c_size_t * max(n, 1))(*[v[4] for v in views])
+        out = {
+            "hash": np.zeros((n, 32), np.uint8) if want_pdq else None,
+            "quality": np.zeros(n, np.float32) if want_pdq and want_quality else None,
+            "coeffs": np.zeros((n, 256), np.float32) if want_pdq and want_coeffs else None,
+            "dihedral": np.zeros((n, 8, 32), np.uint8) if want_pdq and want_dihedral else None,
+            "valid": np.zeros(n, np.uint8) if want_pdq else None,
+            "pixel_hash": np.zeros((n, 32), np.uint8) if want_pixel_hash else None,
+        }
+        check(self.L.rph_image_hash_ragged(self.ctx, px, _ptr(w), _ptr(h), _ptr(layout), rs, n, _ptr(out["hash"]), _ptr(out["quality"]), _ptr(out["coeffs"]),
+                                           _ptr(out["dihedral"]), _ptr(out["valid"]), _ptr(out["pixel_hash"])), "rph_image_hash_ragged")
+        return out
+
+    def image_hash_ragged_dev(self, d_px, offset, w, h, layout, row_stride, d_hash=None, d_quality=None, d_coeffs=None, d_dihedral=None, d_valid=None,
+                              d_pixel_hash=None, stream=None):
+        """Images on the device: image i at d_px + offset[i]; the descriptor arrays are host arrays (image_pack() makes them).
+        Asynchronous on `stream`; results in slot i of the device output arrays that are given (d_hash, d_pixel_hash or both)."""
+        offset = np.ascontiguousarray(offset, np.uint64)
+        w, h, layout = (np.ascontiguousarray(a, np.uint32) for a in (w, h, layout))
+        row_stride = np.ascontiguousarray(row_stride, np.uintp)
+        n = len(offset)
+        if not (len(w) == len(h) == len(layout) == len(row_stride) == n):
+            raise ValueError("descriptor arrays of different lengths")
+        check(self.L.rph_image_hash_ragged_dev(self.ctx, d_px, _ptr(offset), _ptr(w), _ptr(h), _ptr(layout), row_stride.ctypes.data_as(C.POINTER(C.c_size_t)), n,
+                                               d_hash, d_quality, d_coeffs, d_dihedral, d_valid, d_pixel_hash, stream), "rph_image_hash_ragged_dev")
+
+    @staticmethod
+    def image_luma601_host(image):
+        """Host restatement (no GPU call): the Luma8 plane (h, w) the PDQ hasher sees for an image of any layout."""
+        a, h, w, layout, rs = _image_view(image)
+        out = np.zeros((h, w), np.uint8)
+        check(_lib.load().rph_image_luma601_host(C.c_void_p(a.ctypes.data), w, h, layout, rs, _ptr(out)), "rph_image_luma601_host")
+        return out
+
+    @staticmethod
+    def image_pixel_hash_host(image):
+        """Host restatement (no GPU call): the pixel hash (32 bytes) of an image of any layout."""
+        a, h, w, layout, rs = _image_view(image)
+        out = np.zeros(32, np.uint8)
+        check(_lib.load().rph_image_pixel_hash_host(C.c_void_p(a.ctypes.data), w, h, layout, rs, _ptr(out)), "rph_image_pixel_hash_host")
+        return out.tobytes()
 
     def pdq_hash_one(self, image, want_coeffs=True):
         """One image through the batching queue (thread-safe; concurrent callers share a GPU batch).

@@ -6,7 +6,8 @@
     generate_pdq_features(image) -> Option<(PdqFeatures, f32)>   :166-196
     generate_pdq(image) -> Option<([u8; 32], f32)>               :199-201
 plus the batch forms the GPU wants.  `image` is a numpy uint8 array: (h, w) = Luma8 (borrowed as
-is, :173), (h, w, 3) = Rgb8, (h, w, 4) = Rgba8 (alpha ignored, :279).  None is returned for
+is, :173), (h, w, 3) = Rgb8, (h, w, 4) = Rgba8 (alpha ignored, :279); uint16 arrays and (h, w, 2) gray + alpha are the other
+DynamicImage variants, hashed through to_rgb8 as :281-283 does (Engine.image_hash_ragged).  None is returned for
 w or h < 5 exactly like the reference.  Image hashing runs on the GPU; to_hash / generate_dihedral_hashes of ONE
 feature vector are the library's host-scalar functions (compare + bit operations, what the reference's per-file
 call sites scanner.rs:1412, :1622 bind); the batch forms go to the GPU.
@@ -39,7 +40,16 @@ class PdqFeatures:
         return out
 
 
+def _other_layout(image):
+    """True for the decoded images the uniform path does not take: uint16 samples, or (h, w, 2) gray + alpha (what scanner.load_png and
+    load_tiff return for such files).  They go through Engine.image_hash_ragged, which hashes them as the reference's to_luma601 does."""
+    a = np.asarray(image)
+    return (a.dtype.kind == "u" and a.dtype.itemsize == 2) or (a.ndim == 3 and a.shape[2] == 2)
+
+
 def generate_pdq_features(image, engine=None):
+    if _other_layout(image):
+        return generate_pdq_features_many([image], engine)[0]
     image = np.asarray(image, np.uint8)
     out = (engine or default_engine()).pdq_hash_batch(image[None], want_quality=True, want_coeffs=True)
     if not out["valid"][0]:
@@ -48,6 +58,9 @@ def generate_pdq_features(image, engine=None):
 
 
 def generate_pdq(image, engine=None):
+    if _other_layout(image):
+        out = (engine or default_engine()).image_hash_ragged([image], want_pixel_hash=False)
+        return (out["hash"][0], float(out["quality"][0])) if out["valid"][0] else None
     image = np.asarray(image, np.uint8)
     out = (engine or default_engine()).pdq_hash_batch(image[None], want_quality=True)
     if not out["valid"][0]:
@@ -63,7 +76,11 @@ def generate_pdq_features_batch(images, engine=None, want_dihedral=False):
 def generate_pdq_features_many(images, engine=None):
     """generate_pdq_features of a list of images of any mix of sizes and channel counts in one GPU call (rph_pdq_hash_ragged):
     [(PdqFeatures, quality) or None], None for an image that is too small, like the single form."""
-    out = (engine or default_engine()).pdq_hash_ragged(list(images), want_quality=True, want_coeffs=True)
+    images = list(images)
+    if any(_other_layout(im) for im in images):
+        out = (engine or default_engine()).image_hash_ragged(images, want_pixel_hash=False, want_coeffs=True)
+    else:
+        out = (engine or default_engine()).pdq_hash_ragged(images, want_quality=True, want_coeffs=True)
     return [(PdqFeatures(out["coeffs"][i]), float(out["quality"][i])) if out["valid"][i] else None for i in range(len(out["valid"]))]
 
 

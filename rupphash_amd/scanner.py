@@ -8,6 +8,7 @@
     load_tiff (the TiffDecoder arm)                scanner.rs:628-708
     load_gif (the image-crate arm for .gif)        scanner.rs:713-734
     pixel_hash (--pixel-hash)                      scanner.rs:1393-1404
+    hash_images (both hashes of decoded images)    scanner.rs:1386-1410
     identical_duplicates                           scanner.rs:1843-1864 (analyze_group steps 1-3)
 File-name logic after the union-find (merge_groups_by_stem, the sorting inside process_raw_groups) stays with the caller.
 """
@@ -72,9 +73,30 @@ def load_gif(path, data, engine=None):
 
 def pixel_hash(image, engine=None):
     """The pixel hash of one decoded image (scanner.rs:1393-1404): blake3::hash of to_rgba16() as little-endian bytes, on the
-    device.  image: (h, w) Luma8, (h, w, 3) Rgb8 or (h, w, 4) Rgba8 uint8.  Returns 32 bytes."""
+    device.  image: (h, w) Luma8, (h, w, 3) Rgb8 or (h, w, 4) Rgba8 uint8; a uint16 array or (h, w, 2) gray + alpha (what load_png and
+    load_tiff return for such files) goes through Engine.image_hash_ragged.  Returns 32 bytes."""
+    a = np.asarray(image)
+    if (a.dtype.kind == "u" and a.dtype.itemsize == 2) or (a.ndim == 3 and a.shape[2] == 2):
+        return (engine or default_engine()).image_hash_ragged([a], want_pdq=False)["pixel_hash"][0].tobytes()
     a = np.asarray(image, np.uint8)
     return (engine or default_engine()).pixel_hash_batch(a[None])[0].tobytes()
+
+
+def hash_images(images, pixel_hash=True, engine=None):
+    """scanner.rs:1386-1410 for a list of decoded images of any mix of sizes and layouts (uint8 or uint16; (h, w), (h, w, 2), (h, w, 3),
+    (h, w, 4)) in one GPU call: [(pdq hash, quality, PdqFeatures or None, pixel hash)] -- 32-byte hash and float quality, or
+    (None, None, None, pixel hash) for an image below 5 px; pixel hash: 32 bytes, None without pixel_hash."""
+    from .pdqhash import PdqFeatures
+
+    out = (engine or default_engine()).image_hash_ragged(list(images), want_pixel_hash=pixel_hash, want_coeffs=True)
+    res = []
+    for i in range(len(out["valid"])):
+        ph = out["pixel_hash"][i].tobytes() if pixel_hash else None
+        if out["valid"][i]:
+            res.append((out["hash"][i].tobytes(), float(out["quality"][i]), PdqFeatures(out["coeffs"][i]), ph))
+        else:
+            res.append((None, None, None, ph))
+    return res
 
 
 def identical_duplicates(content_hashes, pixel_hashes=None):

@@ -41,30 +41,51 @@ impl PdqFeatures {
     }
 }
 
-/// Pixels of the image in a layout the library takes as it is: Luma8 is borrowed (pdqhash.rs:173-176), Rgb8 / Rgba8 go down unchanged
-/// (to_luma601 ignores alpha, pdqhash.rs:276-279), every other format through to_rgb8() as in the reference (pdqhash.rs:281).
+/// The bytes of a buffer of u16 samples, as they lie in memory (native byte order, what RPH_LAYOUT_*16 wants).
+fn sample_bytes(raw: &[u16]) -> &[u8] {
+    unsafe { std::slice::from_raw_parts(raw.as_ptr() as *const u8, raw.len() * 2) }
+}
+
+/// Pixels of the image and their layout code (channels + 16 for u16 samples): Luma8 is borrowed (pdqhash.rs:173-176), Rgb8 / Rgba8 go
+/// down unchanged (to_luma601 ignores alpha, pdqhash.rs:276-279), LumaA8 and the 16-bit variants go down as they are too -- the library
+/// does what to_rgb8() does to them (pdqhash.rs:281) on the device.  Only the float variants are converted here.
 fn packed_pixels(image: &image::DynamicImage) -> (Cow<'_, [u8]>, u32) {
     match image {
-        image::DynamicImage::ImageLuma8(buf) => (Cow::Borrowed(buf.as_raw().as_slice()), 1),
-        image::DynamicImage::ImageRgb8(buf) => (Cow::Borrowed(buf.as_raw().as_slice()), 3),
-        image::DynamicImage::ImageRgba8(buf) => (Cow::Borrowed(buf.as_raw().as_slice()), 4),
-        other => (Cow::Owned(other.to_rgb8().into_raw()), 3),
+        image::DynamicImage::ImageLuma8(buf) => (Cow::Borrowed(buf.as_raw().as_slice()), ffi::RPH_LAYOUT_LUMA8 as u32),
+        image::DynamicImage::ImageLumaA8(buf) => (Cow::Borrowed(buf.as_raw().as_slice()), ffi::RPH_LAYOUT_LUMAA8 as u32),
+        image::DynamicImage::ImageRgb8(buf) => (Cow::Borrowed(buf.as_raw().as_slice()), ffi::RPH_LAYOUT_RGB8 as u32),
+        image::DynamicImage::ImageRgba8(buf) => (Cow::Borrowed(buf.as_raw().as_slice()), ffi::RPH_LAYOUT_RGBA8 as u32),
+        image::DynamicImage::ImageLuma16(buf) => (Cow::Borrowed(sample_bytes(buf.as_raw())), ffi::RPH_LAYOUT_LUMA16 as u32),
+        image::DynamicImage::ImageLumaA16(buf) => (Cow::Borrowed(sample_bytes(buf.as_raw())), ffi::RPH_LAYOUT_LUMAA16 as u32),
+        image::DynamicImage::ImageRgb16(buf) => (Cow::Borrowed(sample_bytes(buf.as_raw())), ffi::RPH_LAYOUT_RGB16 as u32),
+        image::DynamicImage::ImageRgba16(buf) => (Cow::Borrowed(sample_bytes(buf.as_raw())), ffi::RPH_LAYOUT_RGBA16 as u32),
+        other => (Cow::Owned(other.to_rgb8().into_raw()), ffi::RPH_LAYOUT_RGB8 as u32),
     }
 }
 
 /// One image through rph_pdq_hash_one: blocking, callable from every rayon worker at once (the library coalesces concurrent callers into
-/// GPU batches, csrc/batcher.cpp).  Sides > 512 px are pre-downsampled on the GPU (resize_luma_fast, pdqhash.rs:181-220).
+/// GPU batches, csrc/batcher.cpp).  Sides > 512 px are pre-downsampled on the GPU (resize_luma_fast, pdqhash.rs:181-220).  LumaA8 and
+/// 16-bit images, which that queue does not take, go through rph_image_hash_ragged with n = 1.
 /// None: a side below 5 px (pdqhash.rs:167-169), or a library error (logged by the caller's policy; the reference has no error path here).
 fn hash_one(image: &image::DynamicImage, want_coefficients: bool) -> Option<([u8; HASH_LENGTH], Option<PdqFeatures>, f32)> {
-    let (pixels, channels) = packed_pixels(image);
+    let (pixels, layout) = packed_pixels(image);
     let (w, h) = (image.width(), image.height());
+    let bytes_per_pixel = ((layout & 15) as usize) * if layout > 16 { 2 } else { 1 };
+    let row_stride = (w as usize) * bytes_per_pixel;
     let mut hash = [0u8; HASH_LENGTH];
     let mut quality = 0f32;
     let mut valid = 0u8;
     let mut features = PdqFeatures { coefficients: [0.0; NUM_COEFFICIENTS] };
     let coeffs_ptr = if want_coefficients { features.coefficients.as_mut_ptr() } else { std::ptr::null_mut() };
+    let direct = layout == ffi::RPH_LAYOUT_LUMA8 as u32 || layout == ffi::RPH_LAYOUT_RGB8 as u32 || layout == ffi::RPH_LAYOUT_RGBA8 as u32;
     let rc = unsafe {
-        ffi::rph_pdq_hash_one(ffi::ctx(), pixels.as_ptr(), w, h, channels, (w as usize) * (channels as usize), hash.as_mut_ptr(), &mut quality, coeffs_ptr, &mut valid)
+        if direct {
+            ffi::rph_pdq_hash_one(ffi::ctx(), pixels.as_ptr(), w, h, layout, row_stride, hash.as_mut_ptr(), &mut quality, coeffs_ptr, &mut valid)
+        } else {
+            let px = pixels.as_ptr() as *const std::ffi::c_void;
+            ffi::rph_image_hash_ragged(ffi::ctx(), &px, &w, &h, &layout, &row_stride, 1, hash.as_mut_ptr(), &mut quality, coeffs_ptr, std::ptr::null_mut(), &mut valid,
+                                       std::ptr::null_mut())
+        }
     };
     if rc != ffi::RPH_OK || valid == 0 {
         return None;
