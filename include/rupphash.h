@@ -852,6 +852,81 @@ int rph_gif_set_decompress(rph_ctx *ctx, int where);
 int rph_gif_release(rph_ctx *ctx);
 
 /* =====================================================================
+ * BMP decode feeding the hasher: "bmp" is in the reference's is_image_ext list (scanner.rs:2271-2289) and goes through the image-crate arm
+ * of load_image_fast (scanner.rs:713-734: image 0.25's BmpDecoder), followed by the pixel hash and generate_pdq_features.  Unless a file
+ * is RLE-compressed its bytes already are the pixels: the host parses the headers and copies the pixel array into pinned staging as it
+ * lies in the file, one descriptor-driven kernel turns the arrays of a whole chunk into native pixels (rows flipped, B G R reordered,
+ * bit fields scaled, palettes looked up), and rph_image_hash_ragged_dev hashes them where they lie, whatever mix of sizes the call holds;
+ * only hashes come back.  RLE8 / RLE4 streams are decoded by the host threads into 8-bit index planes, and there is no mode to choose.
+ * What is decoded:
+ *   headers      "BM" + the 14-byte file header; DIB headers of 12 (BITMAPCOREHEADER: 16-bit sizes, 3-byte palette entries), 40, 52,
+ *                56, 108 and 124 bytes.  Width > 0; a negative height means top-down rows; planes = 1; a side of at most 65 535.
+ *   depths       BI_RGB (0): 1, 2, 4, 8 with a palette, 16 as X1R5G5B5, 24, 32 (the fourth byte ignored); BI_RLE8 (1): 8; BI_RLE4 (2):
+ *                4; BI_BITFIELDS (3) and BI_ALPHABITFIELDS (6): 16 or 32.
+ *   masks        read under compressions 3 and 6 only.  Behind a 40-byte header: three dwords (3) or four (6); inside a 52-byte header:
+ *                R G B; inside a 56-, 108- or 124-byte header: R G B A.  A mask is one contiguous run of bits (16-bit files: within the
+ *                low 16).  A channel of len bits has max = 2^len - 1 and a sample v becomes (v * 255 + max / 2) / max, round to nearest
+ *                (max is odd: no ties); a channel wider than 8 bits keeps its top 8; a zero colour mask gives 0.
+ *   palette      biClrUsed entries, 1 << bits when that is 0, B G R x each; an index past the palette is black (0, 0, 0).
+ *   rows         padded to 4 bytes, bottom-up unless the height is negative; depths below 8 most significant bits first.
+ *   RLE          encoded runs, absolute runs (padded to 16 bits), end-of-line, end-of-bitmap, delta; always bottom-up.  Pixels the
+ *                stream skips are (0, 0, 0), not palette entry 0.
+ * Native pixels (rph_bmp_decode, rph_bmp_decode_host): top-down, rows packed, Rgba8 when the file declares a non-zero alpha mask
+ *   (compression 3 or 6), else Rgb8: palette files, 24-bit files, BI_RGB at 16 and 32 bits and files whose alpha mask is zero or absent.
+ *   These rules follow the image crate as recollected: its source is not in the reference tree, so parity with it is UNPINNED.  Where the
+ *   rules and Pillow must agree -- BI_RGB at 1, 4, 8, 24, 32 bits, both row orders, 32-bit BITFIELDS without alpha, RLE streams that
+ *   cover every pixel -- the arithmetic is pinned against Pillow in the tests byte for byte; Pillow floors where the rule rounds, so
+ *   16-bit files agree within 1 per sample, and Pillow shows palette entry 0 for skipped RLE pixels.
+ * What is hashed follows the PNG section word for word: PDQ through to_luma601 (alpha ignored), pixel hash = blake3 of to_rgba16()
+ * little-endian (v -> v * 257, a missing alpha 65535).  A 24-bit BMP of the pixels of an Rgb8 PNG has that PNG's PDQ hash and pixel hash.
+ * ONE RULE for damaged or hostile files, all of it in the host parser (bmp_host.cpp; the one RLE decoder lives there too and the device
+ * never sees a stream): a file's status does not depend on the other files of its call, and a file rph_bmp_info accepts decodes.  Parity
+ * with the image crate on damaged input is UNPINNED.
+ *   REFUSED (RPH_ERR_INVALID_ARG)
+ *     - fewer than 18 bytes, a signature other than "BM", a DIB header that reaches outside the file;
+ *     - planes other than 1; a width <= 0; a height of 0;
+ *     - a top-down RLE file;
+ *     - a palette of more than 1 << bits entries, or one that reaches outside the file; masks that reach outside the file;
+ *     - a mask whose bits are not one contiguous run, or (16-bit files) lie above bit 15;
+ *     - a pixel-array offset that points into the headers (file header, DIB header, masks, palette) or at or past the end of the file;
+ *     - a pixel array shorter than row_stride * |height| (the crate and Pillow fail on it too);
+ *     - an RLE encoded or absolute run that passes the end of its row or lies above the top row, a delta that moves past the row's end
+ *       (x > width) or above the row over the top (y > height), an end-of-line there; an absolute run cut off by the end of the file;
+ *     - an RLE stream that ends without end-of-bitmap, whether or not every pixel has been set.
+ *   ACCEPTED
+ *     - anything behind end-of-bitmap, and behind the last row of an uncompressed array; a gap between the headers and the array;
+ *     - biSizeImage, the resolution, biClrImportant, the colour space and profile fields of the long headers, bfSize: not read;
+ *     - biClrUsed of a file deeper than 8 bits: not read (no palette is looked for);
+ *     - masks in a long header under BI_RGB: not read; masks that overlap each other.
+ *   RPH_ERR_UNSUPPORTED, before any pixel memory is allocated
+ *     - a DIB header size other than 12, 40, 52, 56, 108, 124 (OS/2 2.x's 64 among them);
+ *     - a side above 65 535 (the crate's bound); more than 2^28 pixels (the PNG bound);
+ *     - BI_JPEG, BI_PNG and every other compression; a depth the table above does not list for its compression.
+ *   The checks run in this order and the first that fails decides: length and signature; header size known; header inside the file;
+ *   planes; width and height non-zero and positive width; the side and pixel limits; compression and depth; top-down RLE; palette count,
+ *   palette inside the file (depth <= 8) or masks inside the file, their shape (depth 16, 32); the array's offset; its length; the RLE
+ *   stream, start to end-of-bitmap.  rph_bmp_info runs all of them.
+ *   VALID BUT SMALL: an image below 5 px gets valid = 0 with status RPH_OK, and still its pixel hash.
+ * ===================================================================== */
+/* Host code, no context: the native layout rph_bmp_decode will produce (channels 3 or 4, bit_depth 8); returns the file's status by the
+ * rule above. */
+int rph_bmp_info(const uint8_t *data, size_t len, uint32_t *w, uint32_t *h, uint32_t *channels, uint32_t *bit_depth);
+/* The whole decoder on the CPU, no context (tests, tools): native pixels, packed rows, w * h * channels bytes into pixels_out
+ * (cap_bytes; RPH_ERR_CAPACITY if too small). */
+int rph_bmp_decode_host(const uint8_t *data, size_t len, void *pixels_out, size_t cap_bytes);
+/* One BMP decoded on the device: the same native pixels as rph_bmp_decode_host. */
+int rph_bmp_decode(rph_ctx *ctx, const uint8_t *data, size_t len, void *pixels_out, size_t cap_bytes);
+/* n BMP files -> n PDQ hashes (+ optional quality, 256 coefficients, 8 dihedral hashes, as rph_pdq_hash_batch) and optional pixel
+ * hashes (32 bytes each); the arguments mean what they mean in rph_png_pdq_hash_batch.  status_out[i] by the rule above (the call itself
+ * returns RPH_OK); a file that cannot be decoded has zero outputs and valid 0.  Each file's outputs are bit for bit those of
+ * rph_image_hash_ragged on its native pixels. */
+int rph_bmp_pdq_hash_batch(rph_ctx *ctx, const uint8_t *const *data, const size_t *len, uint32_t n, uint32_t n_threads, uint8_t *hash32_out,
+                           float *quality_out, float *coeffs_out, uint8_t *dihedral_out, uint8_t *valid_out, int32_t *status_out,
+                           uint8_t *pixel_hash32_out);
+/* The BMP path keeps its staging and device buffers in the context between calls; this returns them. */
+int rph_bmp_release(rph_ctx *ctx);
+
+/* =====================================================================
  * BLAKE3 identity hashes (blake3 crate 1.x, 32-byte output): the two exact hashes the reference computes next to the PDQ hash.
  *   content hash  blake3::keyed_hash(content_key, file_bytes)                     scanner.rs:1343-1347 (the cache key)
  *                 -> rph_blake3_host per file in the scan loop, or rph_blake3_batch(_dev) for a batch of files

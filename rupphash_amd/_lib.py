@@ -177,6 +177,12 @@ SIGNATURES = {
                                          _i32p, _u8p]),
     "rph_gif_set_decompress": (C.c_int, [_vp, C.c_int]),
     "rph_gif_release": (C.c_int, [_vp]),
+    "rph_bmp_info": (C.c_int, [C.c_char_p, _sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "rph_bmp_decode_host": (C.c_int, [C.c_char_p, _sz, _vp, _sz]),
+    "rph_bmp_decode": (C.c_int, [_vp, C.c_char_p, _sz, _vp, _sz]),
+    "rph_bmp_pdq_hash_batch": (C.c_int, [_vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_uint32, C.c_uint32, _u8p, _f32p, _f32p, _u8p, _u8p,
+                                         _i32p, _u8p]),
+    "rph_bmp_release": (C.c_int, [_vp]),
     "rph_blake3_batch": (C.c_int, [_vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_uint32, _u8p, _u8p]),
     "rph_blake3_batch_dev": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _u8p, _vp, _vp]),
     "rph_blake3_host": (None, [_u8p, _sz, _u8p, _u8p]),

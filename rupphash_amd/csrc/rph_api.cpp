@@ -259,6 +259,7 @@ int rph_shutdown(rph_ctx *ctx)
     rph_tiff_forget(ctx);
     rph_webp_forget(ctx);
     rph_gif_forget(ctx);
+    rph_bmp_forget(ctx);
     rph_jpeg_forget_threads(ctx);
     if (ctx->sink) (void)hipFree(ctx->sink);
     (void)hipStreamDestroy(ctx->stream);

@@ -84,6 +84,9 @@ struct rph_ctx {
     std::mutex gif_mu;
     void *gif = nullptr;
     int gif_decompress = RPH_GIF_DECOMPRESS_AUTO;
+    // BMP path (bmp_pipeline.cpp): the same arrangement; no mode: the pixel arrays cross PCIe as they are, RLE streams are the host's
+    std::mutex bmp_mu;
+    void *bmp = nullptr;
 };
 
 // ---- launchers implemented in the .hip files (all asynchronous on `stream`) ----
@@ -210,6 +213,8 @@ void rph_tiff_forget(rph_ctx *ctx);
 void rph_webp_forget(rph_ctx *ctx);
 // gif_pipeline.cpp
 void rph_gif_forget(rph_ctx *ctx);
+// bmp_pipeline.cpp
+void rph_bmp_forget(rph_ctx *ctx);
 void rph_jpeg_forget_threads(rph_ctx *ctx);
 
 // host_grouping.cpp

@@ -566,6 +566,56 @@ class Engine:
               "rph_gif_pdq_hash_batch")
         return out
 
+    # ---- BMP (include/rupphash.h, BMP section) ----
+    @staticmethod
+    def bmp_info(data):
+        """(w, h, channels, bit_depth) of the native pixels (host code), or raises RphError by the damaged-file rule."""
+        w, h, c, d = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        check(_lib.load().rph_bmp_info(data, len(data), C.byref(w), C.byref(h), C.byref(c), C.byref(d)), "rph_bmp_info")
+        return w.value, h.value, c.value, d.value
+
+    @staticmethod
+    def _bmp_array(data):
+        w, h, c, _ = Engine.bmp_info(data)
+        return np.zeros((h, w, c), np.uint8)
+
+    @staticmethod
+    def bmp_decode_host(data):
+        """The whole decoder on the CPU: (h, w, 3) Rgb8, or (h, w, 4) Rgba8 for a file with an alpha mask; uint8, top-down."""
+        out = Engine._bmp_array(data)
+        check(_lib.load().rph_bmp_decode_host(data, len(data), _ptr(out), out.nbytes), "rph_bmp_decode_host")
+        return out
+
+    def bmp_decode(self, data):
+        """One BMP byte string decoded on the device: the same array as bmp_decode_host."""
+        out = self._bmp_array(data)
+        check(self.L.rph_bmp_decode(self.ctx, data, len(data), _ptr(out), out.nbytes), "rph_bmp_decode")
+        return out
+
+    def bmp_release(self):
+        """give the BMP path's cached staging / device buffers back"""
+        check(self.L.rph_bmp_release(self.ctx), "rph_bmp_release")
+
+    def bmp_pdq_hash_batch(self, files, threads=0, want_quality=True, want_coeffs=False, want_dihedral=False, want_pixel_hash=False):
+        """files: list of BMP byte strings (any mix of sizes and depths), or the tuple jpeg_file_list() made of one.  Returns dict(hash,
+        quality, coeffs, dihedral, valid, status[, pixel_hash]) as jpeg_pdq_hash_batch: status[i] != 0 for a file the rule refuses (zero
+        outputs), valid[i] = 0 with status 0 for an image below 5 px (which still has its pixel hash)."""
+        arr, lens, n = files if isinstance(files, tuple) else self.jpeg_file_list(files)
+        out = {
+            "hash": np.zeros((n, 32), np.uint8),
+            "quality": np.zeros(n, np.float32) if want_quality else None,
+            "coeffs": np.zeros((n, 256), np.float32) if want_coeffs else None,
+            "dihedral": np.zeros((n, 8, 32), np.uint8) if want_dihedral else None,
+            "valid": np.zeros(n, np.uint8),
+            "status": np.zeros(n, np.int32),
+        }
+        if want_pixel_hash:
+            out["pixel_hash"] = np.zeros((n, 32), np.uint8)
+        check(self.L.rph_bmp_pdq_hash_batch(self.ctx, arr, lens, n, int(threads), _ptr(out["hash"]), _ptr(out["quality"]), _ptr(out["coeffs"]),
+                                            _ptr(out["dihedral"]), _ptr(out["valid"]), _ptr(out["status"]), _ptr(out.get("pixel_hash"))),
+              "rph_bmp_pdq_hash_batch")
+        return out
+
     # ---- BLAKE3 identity hashes ----
     @staticmethod
     def blake3_host(data, key=None):

@@ -7,6 +7,7 @@
     load_png (the "png" arm, image + png crates)    scanner.rs:461-736 (load_image_fast's generic path for .png)
     load_tiff (the TiffDecoder arm)                scanner.rs:628-708
     load_gif (the image-crate arm for .gif)        scanner.rs:713-734
+    load_bmp (the image-crate arm for .bmp)        scanner.rs:713-734
     pixel_hash (--pixel-hash)                      scanner.rs:1393-1404
     hash_images (both hashes of decoded images)    scanner.rs:1386-1410
     identical_duplicates                           scanner.rs:1843-1864 (analyze_group steps 1-3)
@@ -69,6 +70,18 @@ def load_gif(path, data, engine=None):
     if ext != "gif":
         raise ValueError(f"load_gif: '{ext}' is not a GIF file name")
     return (engine or default_engine()).gif_decode(data)
+
+
+def load_bmp(path, data, engine=None):
+    """The image-crate arm of load_image_fast for a .bmp (scanner.rs:713-734): decoded on the device and returned as (h, w, 3) uint8
+    Rgb8, or (h, w, 4) Rgba8 for a file with an alpha mask, the native layout of the header's BMP section.  A file the rule refuses raises
+    RphError; extensions other than bmp raise ValueError.  load_image_fast itself stays JPEG-only."""
+    import os
+
+    ext = os.path.splitext(str(path))[1].lstrip(".").lower()
+    if ext != "bmp":
+        raise ValueError(f"load_bmp: '{ext}' is not a BMP file name")
+    return (engine or default_engine()).bmp_decode(data)
 
 
 def pixel_hash(image, engine=None):
