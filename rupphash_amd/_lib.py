@@ -217,6 +217,7 @@ DEBUG_SIGNATURES = {
     "rph_debug_copy_thumbnails": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32]),
     "rph_debug_hamming_cross_layout": (None, [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                               C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "rph_debug_file_chunks": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
 }
 
 _lib = None

@@ -13,7 +13,7 @@
 #include <vector>
 
 #include "bmp_host.h"
-#include "decoded_hash.h"  // (FileOutputs, reserve_slack and the chunk limits only: the hash stage here is the ragged one)
+#include "decoded_hash.h"  // (FileOutputs and reserve_slack only: the hash stage here is the ragged one)
 #include "rph_internal.h"
 
 int rph_bmp_launch_expand(const uint8_t *d_src, const void *d_images, const uint32_t *d_pals, const void *d_work, uint32_t n_work, uint8_t *d_out, hipStream_t s);
@@ -25,9 +25,6 @@ struct BmpPipe {
     DevBuf src, px, meta, res;
     PinnedBuf h_src, h_meta, h_res;
 };
-
-// Per chunk at most this many bytes of staged source and of native pixels (one image larger than a limit forms a chunk of its own)
-constexpr uint64_t CHUNK_SRC = (uint64_t)256 << 20, CHUNK_OUT = (uint64_t)384 << 20;
 
 // one chunk: files[idx[k]] for k in [0, m), all parsed RPH_OK
 int run_chunk(rph_ctx *ctx, BmpPipe &P, const uint8_t *const *data, std::vector<rphb::Parsed> &parsed, const uint32_t *idx, size_t m, unsigned threads,
@@ -134,17 +131,21 @@ int run(rph_ctx *ctx, const uint8_t *const *data, const size_t *len, uint32_t n,
     std::vector<uint32_t> ok;
     for (uint32_t i = 0; i < n; i++)
         if (out.status[i] == RPH_OK) ok.push_back(i);
+    const rph_file_limits &lim = ctx->file_limits;
+    rph_file_chunk_log &log = ctx->file_chunks[RPH_FILE_BMP];
+    log = rph_file_chunk_log();
     for (size_t a = 0; a < ok.size();) {
         size_t b = a;
         uint64_t src = 0, px = 0;
-        while (b < ok.size() && b - a < CHUNK_FILES) {
+        while (b < ok.size() && b - a < lim.files) {
             const rphb::Image &im = parsed[ok[b]].im;
             const uint64_t sb = (uint64_t)im.src_stride * im.h, ob = (uint64_t)im.out_stride * im.h;
-            if (b > a && (src + sb > CHUNK_SRC || px + ob > CHUNK_OUT)) break;
+            if (b > a && (src + sb > lim.bmp_src || px + ob > lim.bmp_out)) break;
             src += sb;
             px += ob;
             b++;
         }
+        log.sizes.push_back((uint32_t)(b - a));
         RPH_TRY(run_chunk(ctx, *P, data, parsed, ok.data() + a, b - a, threads, out));
         a = b;
     }

@@ -10,10 +10,8 @@
 
 #include "rph_internal.h"
 
-// Per chunk of a call at most this much: files, compressed bytes, decompressed bytes, pixels (one image larger than a limit forms a chunk
-// of its own)
-constexpr size_t CHUNK_FILES = 8192;
-constexpr uint64_t CHUNK_COMP = (uint64_t)256 << 20, CHUNK_RAW = (uint64_t)768 << 20, CHUNK_PIXELS = (uint64_t)192 << 20;
+// Per chunk of a call at most ctx->file_limits (rph_internal.h): files, compressed bytes, decompressed bytes, pixels (one image larger
+// than a limit forms a chunk of its own)
 
 // what a batch call hands out (any of them may be absent); native: the native pixels of the call's one image (rph_*_decode)
 struct FileOutputs {

@@ -129,19 +129,23 @@ int run(rph_ctx *ctx, const uint8_t *const *data, const size_t *len, uint32_t n,
     std::vector<uint32_t> ok;
     for (uint32_t i = 0; i < n; i++)
         if (out.status[i] == RPH_OK) ok.push_back(i);
+    const rph_file_limits &lim = ctx->file_limits;
+    rph_file_chunk_log &log = ctx->file_chunks[RPH_FILE_GIF];
+    log = rph_file_chunk_log();
     for (size_t a = 0; a < ok.size();) {
         size_t b = a;
         uint64_t comp = 0, dec = 0, px = 0;
-        while (b < ok.size() && b - a < CHUNK_FILES) {
+        while (b < ok.size() && b - a < lim.files) {
             const rphg::Parsed &p = parsed[ok[b]];
             const uint64_t pix = (uint64_t)p.im.w * p.im.h;
             const uint64_t ind = (uint64_t)p.im.fw * p.im.fh;
-            if (b > a && (comp + p.stream_len > CHUNK_COMP || dec + ind > CHUNK_RAW || px + pix > CHUNK_PIXELS / 2)) break;  // (4 bytes per pixel)
+            if (b > a && (comp + p.stream_len > lim.comp || dec + ind > lim.raw || px + pix > lim.pixels / 2)) break;  // (4 bytes per pixel)
             comp += p.stream_len;
             dec += ind;
             px += pix;
             b++;
         }
+        log.sizes.push_back((uint32_t)(b - a));
         RPH_TRY(run_chunk(ctx, *P, data, parsed, ok.data() + a, b - a, threads, out));
         a = b;
     }

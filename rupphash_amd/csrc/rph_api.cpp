@@ -234,6 +234,22 @@ int rph_init(int device, rph_ctx **out)
         ctx->compute_units = prop.multiProcessorCount;
         if (const char *e = getenv("RPH_RAGGED_CHUNK_BYTES"))  // tests: several staging chunks from a few small images
             if (const long long v = atoll(e); v > 0) ctx->ragged_chunk_bytes = (size_t)v;
+        // tests: several chunks (and WebP parse windows) from a hundred small files
+        rph_file_limits &fl = ctx->file_limits;
+        const struct {
+            const char *name;
+            uint64_t *value;
+        } knobs[] = {{"RPH_FILE_CHUNK_FILES", &fl.files},
+                     {"RPH_FILE_CHUNK_COMP_BYTES", &fl.comp},
+                     {"RPH_FILE_CHUNK_RAW_BYTES", &fl.raw},
+                     {"RPH_FILE_CHUNK_PIXELS", &fl.pixels},
+                     {"RPH_WEBP_CHUNK_TABLE_BYTES", &fl.webp_chunk_tables},
+                     {"RPH_WEBP_WINDOW_TABLE_BYTES", &fl.webp_window_tables},
+                     {"RPH_BMP_CHUNK_SRC_BYTES", &fl.bmp_src},
+                     {"RPH_BMP_CHUNK_OUT_BYTES", &fl.bmp_out}};
+        for (const auto &k : knobs)
+            if (const char *e = getenv(k.name))
+                if (const long long v = atoll(e); v > 0) *k.value = (uint64_t)v;
         hipError_t e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
         if (e != hipSuccess) {
             rph_set_error("hipStreamCreate failed: %s", hipGetErrorString(e));
@@ -264,6 +280,19 @@ int rph_shutdown(rph_ctx *ctx)
     if (ctx->sink) (void)hipFree(ctx->sink);
     (void)hipStreamDestroy(ctx->stream);
     delete ctx;  // the shared and per-stream scratch free themselves
+    return RPH_OK;
+}
+
+int rph_debug_file_chunks(rph_ctx *ctx, int format, uint32_t *sizes_out, uint32_t cap, uint32_t *n_chunks_out, uint32_t *n_windows_out)
+{
+    if (!ctx || format < 0 || format >= RPH_FILE_FORMATS) return RPH_ERR_INVALID_ARG;
+    std::mutex *const mu[RPH_FILE_FORMATS] = {&ctx->png_mu, &ctx->tiff_mu, &ctx->webp_mu, &ctx->gif_mu, &ctx->bmp_mu};
+    std::lock_guard<std::mutex> lock(*mu[format]);
+    const rph_file_chunk_log &log = ctx->file_chunks[format];
+    if (sizes_out)
+        for (size_t k = 0; k < std::min<size_t>(cap, log.sizes.size()); k++) sizes_out[k] = log.sizes[k];
+    if (n_chunks_out) *n_chunks_out = (uint32_t)log.sizes.size();
+    if (n_windows_out) *n_windows_out = log.n_windows;
     return RPH_OK;
 }
 

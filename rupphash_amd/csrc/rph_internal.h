@@ -12,6 +12,31 @@
 #include "../../include/rupphash.h"
 #include "rph_buffers.h"
 
+// What one chunk of a file pipeline's call (PNG, TIFF, WebP, GIF, BMP) may hold at most; one image larger than a limit forms a chunk of
+// its own.  files, comp, raw and pixels are shared by the five formats (GIF and WebP allow pixels / 2: their pixels take 4 bytes);
+// webp_*_tables: tables and sub-images of the parsed files of one chunk, and of one parse window; bmp_*: staged source bytes and native
+// pixel bytes.  The defaults are what the library runs with; the variables named behind them override them
+// (tests only: read once, by rph_init; absent, zero or unparsable: the default)
+struct rph_file_limits {
+    uint64_t files = 8192;                                 // RPH_FILE_CHUNK_FILES
+    uint64_t comp = (uint64_t)256 << 20;                   // RPH_FILE_CHUNK_COMP_BYTES
+    uint64_t raw = (uint64_t)768 << 20;                    // RPH_FILE_CHUNK_RAW_BYTES
+    uint64_t pixels = (uint64_t)192 << 20;                 // RPH_FILE_CHUNK_PIXELS
+    uint64_t webp_chunk_tables = (uint64_t)256 << 20;      // RPH_WEBP_CHUNK_TABLE_BYTES
+    uint64_t webp_window_tables = (uint64_t)1 << 30;       // RPH_WEBP_WINDOW_TABLE_BYTES
+    uint64_t bmp_src = (uint64_t)256 << 20;                // RPH_BMP_CHUNK_SRC_BYTES
+    uint64_t bmp_out = (uint64_t)384 << 20;                // RPH_BMP_CHUNK_OUT_BYTES
+};
+
+// the formats of rph_debug_file_chunks
+enum { RPH_FILE_PNG = 0, RPH_FILE_TIFF = 1, RPH_FILE_WEBP = 2, RPH_FILE_GIF = 3, RPH_FILE_BMP = 4, RPH_FILE_FORMATS = 5 };
+
+// what the last call of one file pipeline did (rph_debug_file_chunks): files per run_chunk call, in order; WebP's parse windows
+struct rph_file_chunk_log {
+    std::vector<uint32_t> sizes;
+    uint32_t n_windows = 0;
+};
+
 struct rph_ctx {
     int device = 0;
     int compute_units = 0;
@@ -87,6 +112,10 @@ struct rph_ctx {
     // BMP path (bmp_pipeline.cpp): the same arrangement; no mode: the pixel arrays cross PCIe as they are, RLE streams are the host's
     std::mutex bmp_mu;
     void *bmp = nullptr;
+    // the five file pipelines' chunk limits (tests only: read once, by rph_init) and what each one's last call did with them, written
+    // under that pipeline's mutex (rph_debug_file_chunks)
+    rph_file_limits file_limits;
+    rph_file_chunk_log file_chunks[RPH_FILE_FORMATS];
 };
 
 // ---- launchers implemented in the .hip files (all asynchronous on `stream`) ----
@@ -142,6 +171,10 @@ int rph_launch_hamming_cross_sweep(rph_ctx *ctx, const uint8_t *d_a, uint32_t n_
 // which set a cross sweep puts on the row side, its segment length and block count (exported for the tests, not in the header)
 extern "C" void rph_debug_hamming_cross_layout(uint64_t n_a, uint32_t n_variants, uint64_t n_b, uint32_t nparts, int kernel, uint32_t *swap_out,
                                                uint32_t *seg_tiles_out, uint32_t *n_col_segs_out, uint64_t *n_blocks_out);
+// how the last call of one file pipeline (RPH_FILE_*: a batch call or rph_*_decode) on this context was cut: the number of run_chunk
+// calls, the files of each (the first `cap` of them into sizes_out) and, for WebP, the number of parse windows (exported for the tests,
+// not in the header; any of the three outputs may be null)
+extern "C" int rph_debug_file_chunks(rph_ctx *ctx, int format, uint32_t *sizes_out, uint32_t cap, uint32_t *n_chunks_out, uint32_t *n_windows_out);
 int rph_launch_hamming64_sweep(const uint64_t *d_hashes, uint64_t n, uint32_t threshold, uint32_t part, uint32_t nparts,
                                rph_edge *d_edges, uint64_t cap, unsigned long long *d_count, hipStream_t stream, int use_mfma);
 int rph_launch_mih_build256(rph_ctx *ctx, const uint8_t *d_hashes, uint64_t n, uint32_t *d_offsets, uint32_t *d_values,

@@ -37,8 +37,7 @@ struct WebpPipe {
 // the device loses to 16 host threads at every ratio tried: photographs at 2:1 (1.23 vs 2.99 GB/s of pixels), palette images at 11:1
 // (1.21 vs 1.55), screenshots at 2700:1 (14.9 vs 22.6).  So there is no threshold, and AUTO is HOST
 constexpr uint64_t AUTO_DEVICE_MIN_RATIO = 0;  // 0: AUTO never chooses the device
-// tables (and sub-images) the parsed files of one window, and of one chunk, may hold
-constexpr uint64_t WINDOW_TABLE_BYTES = (uint64_t)1 << 30, CHUNK_TABLE_BYTES = (uint64_t)256 << 20;
+// tables (and sub-images) a parsed file holds: bounded per window and per chunk (ctx->file_limits.webp_window_tables, webp_chunk_tables)
 inline uint64_t table_bytes(const rphw::Parsed &p) { return p.codes.size() * 2 + p.words.size() * 4; }
 
 // a stream's bytes in staging: zero bytes behind them for the dwords the bit reader loads past the end before the count of consumed
@@ -165,12 +164,16 @@ int run(rph_ctx *ctx, const uint8_t *const *data, const size_t *len, uint32_t n,
     // The fronts of a window of files at a time: their tables are the bulk of what a parsed file holds.  A window ends early at the first
     // file that finds the window's tables above their bound (files behind it that were parsed meanwhile are parsed again in the next one)
     std::vector<rphw::Parsed> parsed(n);
+    const rph_file_limits &lim = ctx->file_limits;
+    rph_file_chunk_log &log = ctx->file_chunks[RPH_FILE_WEBP];
+    log = rph_file_chunk_log();
     for (uint32_t a = 0; a < n;) {
-        uint32_t b = (uint32_t)std::min<uint64_t>(n, (uint64_t)a + CHUNK_FILES);
+        uint32_t b = (uint32_t)std::min<uint64_t>(n, (uint64_t)a + lim.files);
         std::atomic<uint64_t> held{0};
         std::atomic<uint32_t> deferred{b};
+        log.n_windows++;
         parallel_for(a, b, threads, [&](size_t i) {
-            if (i > a && (held.load() > WINDOW_TABLE_BYTES || i > deferred.load())) {
+            if (i > a && (held.load() > lim.webp_window_tables || i > deferred.load())) {
                 uint32_t d = deferred.load();
                 while ((uint32_t)i < d && !deferred.compare_exchange_weak(d, (uint32_t)i)) {}
                 return;
@@ -189,12 +192,13 @@ int run(rph_ctx *ctx, const uint8_t *const *data, const size_t *len, uint32_t n,
             while (e < ok.size()) {
                 const rphw::Parsed &p = parsed[ok[e]];
                 const uint64_t pix = (uint64_t)p.im.w * p.im.h;
-                if (e > c && (comp + p.chunk_len > CHUNK_COMP || px + pix > CHUNK_PIXELS / 2 || tab + table_bytes(p) > CHUNK_TABLE_BYTES)) break;
+                if (e > c && (comp + p.chunk_len > lim.comp || px + pix > lim.pixels / 2 || tab + table_bytes(p) > lim.webp_chunk_tables)) break;
                 tab += table_bytes(p);
                 comp += p.chunk_len;
                 px += pix;
                 e++;
             }
+            log.sizes.push_back((uint32_t)(e - c));
             RPH_TRY(run_chunk(ctx, *P, parsed, ok.data() + c, e - c, threads, out));
             c = e;
         }

@@ -687,6 +687,18 @@ class Engine:
         check(self.L.rph_debug_copy_thumbnails(self.ctx, _ptr(out), n, nw, nh), "rph_debug_copy_thumbnails")
         return out
 
+    FILE_FORMATS = ("png", "tiff", "webp", "gif", "bmp")
+
+    def debug_file_chunks(self, fmt):
+        """How the last call of one file pipeline ("png", "tiff", "webp", "gif", "bmp": a batch call or a *_decode) on this context was
+        cut: (files of every run_chunk call in order, number of parse windows -- counted by WebP only, 0 elsewhere).  Debug / tests only."""
+        which = self.FILE_FORMATS.index(fmt)
+        n, nw = C.c_uint32(), C.c_uint32()
+        check(self.L.rph_debug_file_chunks(self.ctx, which, None, 0, C.byref(n), C.byref(nw)), "rph_debug_file_chunks")
+        sizes = (C.c_uint32 * max(1, n.value))()
+        check(self.L.rph_debug_file_chunks(self.ctx, which, sizes, n.value, C.byref(n), C.byref(nw)), "rph_debug_file_chunks")
+        return list(sizes[:n.value]), nw.value
+
     def pdq_hashes_from_coeffs(self, coeffs, want_hash=True, want_dihedral=True):
         coeffs = np.ascontiguousarray(coeffs, np.float32).reshape(-1, 256)
         n = len(coeffs)

@@ -161,10 +161,11 @@ def test_call_larger_than_one_chunk(eng):
     rng = np.random.default_rng(23)
     small = [tu.make_file(rng, 6 + k % 5, 7, compression=(1, 5, 8, 32773)[k % 4]) for k in range(40)]
     files = [small[k % 40] for k in range(8192 + 300)]
-    out = eng.tiff_pdq_hash_batch(files)
-    ref = eng.tiff_pdq_hash_batch(small)
-    for k in range(len(files)):
-        assert np.array_equal(out["hash"][k], ref["hash"][k % 40])
+    out = eng.tiff_pdq_hash_batch(files, want_pixel_hash=True)
+    assert eng.debug_file_chunks("tiff")[0] == [8192, 300]
+    ref = eng.tiff_pdq_hash_batch(small, want_pixel_hash=True)
+    for key in ("hash", "quality", "valid", "status", "pixel_hash"):
+        assert out[key].tobytes() == ref[key][np.arange(len(files)) % 40].tobytes(), key
     assert out["valid"].all() and not out["status"].any()
 
 
