@@ -310,19 +310,49 @@ def test_sorted_zero_one_sweep_on_adversarial_popcounts(eng, oracle, thr):
     assert res[4] == res[3] == res[0]  # flags (find_groups reachability / probe slot) too
 
 
+@pytest.mark.parametrize("kernel", [2, 4, 3, 1, 0])
 @pytest.mark.parametrize("thr", [0, 40, 70])
-def test_all_pairs_heavily_duplicated_data(eng, thr):
-    """thousands of identical hashes: every pair of a chunk is a candidate, the MFMA kernel's candidate queue overflows
-    and its exhaustive fallback must still report every pair exactly once"""
+def test_all_pairs_heavily_duplicated_data(eng, thr, kernel):
+    """thousands of identical hashes: every pair of a chunk is a candidate, so every lane queues an entry with every bitmap bit set
+    and the MFMA kernels drain a FULL candidate queue (64 .. 127 entries: a chunk adds at most one per lane to the fewer than 64 a
+    queue keeps undrained) after every chunk; every pair must still be reported exactly once.  The exhaustive completion the kernel
+    keeps for a queue beyond QCAP entries is unreachable at QCAP = 128 (63 + 64 = 127), so this is NOT what runs here.  Setting 4
+    sends every edge back through the sort's permutation and re-establishes i < j afterwards."""
     n = 2100
     h = np.tile(np.arange(32, dtype=np.uint8) * 7, (n, 1))
     h[n - 100:, 0] ^= 0xFF          # a second cluster at distance 8 from the first
-    e = eng.hamming_all_pairs(h, thr, cap=n * n // 2)
+    eng.set_hamming_kernel(kernel)
+    try:
+        e = eng.hamming_all_pairs(h, thr, cap=n * n // 2)
+    finally:
+        eng.set_hamming_kernel(2)
     a, b = n - 100, 100
     want = a * (a - 1) // 2 + b * (b - 1) // 2 + (a * b if thr >= 8 else 0)
-    assert len(e) == want and (e["i"] < e["j"]).all()
-    assert len({(int(x["i"]), int(x["j"])) for x in e}) == want
+    assert len(e) == want and (e["i"] < e["j"]).all() and (e["j"] < n).all()
+    assert len(np.unique(e["i"].astype(np.int64) * n + e["j"])) == want  # every pair once
     assert set(np.unique(e["d"]).tolist()) == ({0, 8} if thr >= 8 else {0})
+    assert ((e["d"] == 8) == ((e["i"] < a) & (e["j"] >= a))).all()
+
+
+@pytest.mark.parametrize("kernel", [2, 0])
+@pytest.mark.parametrize("thr", [0, 7, 8, 40])
+def test_all_pairs_u64_heavily_duplicated_data(eng, thr, kernel):
+    """the same for 64-bit hashes, whose drain completes every queued pair one by one (no batched first-half loads)"""
+    n = 2100
+    h = np.full(n, 0x0123_4567_89AB_CDEF, np.uint64)
+    h[n - 100:] ^= np.uint64(0xFF << 24)  # a second cluster at distance 8 from the first
+    eng.set_hamming_kernel(kernel)
+    try:
+        e = eng.hamming_all_pairs64(h, thr, cap=n * n // 2)
+    finally:
+        eng.set_hamming_kernel(2)
+    a, b = n - 100, 100
+    want = a * (a - 1) // 2 + b * (b - 1) // 2 + (a * b if thr >= 8 else 0)
+    assert len(e) == want and (e["i"] < e["j"]).all() and (e["j"] < n).all()
+    assert len(np.unique(e["i"].astype(np.int64) * n + e["j"])) == want
+    assert ((e["d"] == 8) == ((e["i"] < a) & (e["j"] >= a))).all() and (e["d"][e["d"] != 8] == 0).all()
+    # probe key: chunk 0 is equal for every pair (the clusters differ in byte 3)
+    assert (e["flags"] == 0x8000).all()
 
 
 def test_all_pairs_edge_cases(eng):
@@ -372,6 +402,20 @@ def test_find_groups_reference_tests_on_gpu(eng):
 @pytest.mark.parametrize("sim", [0, 16, 31, 40, 63])
 def test_group_files_pdq_matches_oracle(eng, oracle, sim):
     """scanner.rs:1640-1823: 8 dihedral variants of file i against hash j > i, low-confidence rule, union-find."""
+    _group_files_case(eng, oracle, sim)
+
+
+@pytest.mark.parametrize("kernel", [1, 0])
+def test_group_files_pdq_matches_oracle_under_other_kernels(eng, oracle, kernel):
+    """the same under the int8 MFMA and the VALU sweeps (group_files is the only route to the in-kernel has_features rule)"""
+    eng.set_hamming_kernel(kernel)
+    try:
+        _group_files_case(eng, oracle, 40)
+    finally:
+        eng.set_hamming_kernel(2)
+
+
+def _group_files_case(eng, oracle, sim):
     rng = np.random.default_rng(500 + sim)
     n = 1500
     coeffs = rng.normal(0, 20, (n, 256)).astype(np.float32)
