@@ -149,40 +149,10 @@ SIGNATURES = {
                                           _u8p, _u8p, _i32p]),
     "rph_jpeg_pdq_pixel_hash_batch": (C.c_int, [_vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_uint32, C.c_int, C.c_uint32, _u8p, _f32p,
                                                 _f32p, _u8p, _u8p, _i32p, _u8p]),
-    "rph_png_info": (C.c_int, [C.c_char_p, _sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
-    "rph_png_decode_host": (C.c_int, [C.c_char_p, _sz, _vp, _sz]),
-    "rph_png_decode": (C.c_int, [_vp, C.c_char_p, _sz, _vp, _sz]),
-    "rph_png_pdq_hash_batch": (C.c_int, [_vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_uint32, C.c_uint32, _u8p, _f32p, _f32p, _u8p, _u8p,
-                                         _i32p, _u8p]),
     "rph_png_set_inflate": (C.c_int, [_vp, C.c_int]),
-    "rph_png_release": (C.c_int, [_vp]),
-    "rph_tiff_info": (C.c_int, [C.c_char_p, _sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
-    "rph_tiff_decode_host": (C.c_int, [C.c_char_p, _sz, _vp, _sz]),
-    "rph_tiff_decode": (C.c_int, [_vp, C.c_char_p, _sz, _vp, _sz]),
-    "rph_tiff_pdq_hash_batch": (C.c_int, [_vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_uint32, C.c_uint32, _u8p, _f32p, _f32p, _u8p, _u8p,
-                                         _i32p, _u8p]),
     "rph_tiff_set_decompress": (C.c_int, [_vp, C.c_int]),
-    "rph_tiff_release": (C.c_int, [_vp]),
-    "rph_webp_info": (C.c_int, [C.c_char_p, _sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
-    "rph_webp_decode_host": (C.c_int, [C.c_char_p, _sz, _vp, _sz]),
-    "rph_webp_decode": (C.c_int, [_vp, C.c_char_p, _sz, _vp, _sz]),
-    "rph_webp_pdq_hash_batch": (C.c_int, [_vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_uint32, C.c_uint32, _u8p, _f32p, _f32p, _u8p, _u8p,
-                                         _i32p, _u8p]),
     "rph_webp_set_entropy": (C.c_int, [_vp, C.c_int]),
-    "rph_webp_release": (C.c_int, [_vp]),
-    "rph_gif_info": (C.c_int, [C.c_char_p, _sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
-    "rph_gif_decode_host": (C.c_int, [C.c_char_p, _sz, _vp, _sz]),
-    "rph_gif_decode": (C.c_int, [_vp, C.c_char_p, _sz, _vp, _sz]),
-    "rph_gif_pdq_hash_batch": (C.c_int, [_vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_uint32, C.c_uint32, _u8p, _f32p, _f32p, _u8p, _u8p,
-                                         _i32p, _u8p]),
     "rph_gif_set_decompress": (C.c_int, [_vp, C.c_int]),
-    "rph_gif_release": (C.c_int, [_vp]),
-    "rph_bmp_info": (C.c_int, [C.c_char_p, _sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
-    "rph_bmp_decode_host": (C.c_int, [C.c_char_p, _sz, _vp, _sz]),
-    "rph_bmp_decode": (C.c_int, [_vp, C.c_char_p, _sz, _vp, _sz]),
-    "rph_bmp_pdq_hash_batch": (C.c_int, [_vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_uint32, C.c_uint32, _u8p, _f32p, _f32p, _u8p, _u8p,
-                                         _i32p, _u8p]),
-    "rph_bmp_release": (C.c_int, [_vp]),
     "rph_blake3_batch": (C.c_int, [_vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_uint32, _u8p, _u8p]),
     "rph_blake3_batch_dev": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _u8p, _vp, _vp]),
     "rph_blake3_host": (None, [_u8p, _sz, _u8p, _u8p]),
@@ -211,6 +181,16 @@ SIGNATURES = {
     "rph_event_destroy": (C.c_int, [_vp, _vp]),
     "rph_stream": (C.c_void_p, [_vp]),
 }
+
+# the entry points every file format has (include/rupphash.h, PNG / TIFF / WebP / GIF / BMP sections): rph_<format>_<name>
+FILE_SIGNATURES = {
+    "info": (C.c_int, [C.c_char_p, _sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "decode_host": (C.c_int, [C.c_char_p, _sz, _vp, _sz]),
+    "decode": (C.c_int, [_vp, C.c_char_p, _sz, _vp, _sz]),
+    "pdq_hash_batch": (C.c_int, [_vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_uint32, C.c_uint32, _u8p, _f32p, _f32p, _u8p, _u8p, _i32p, _u8p]),
+    "release": (C.c_int, [_vp]),
+}
+SIGNATURES.update({f"rph_{fmt}_{name}": sig for fmt in ("png", "tiff", "webp", "gif", "bmp") for name, sig in FILE_SIGNATURES.items()})
 
 # exports that are NOT in include/rupphash.h (debug / tests only), bound the same way
 DEBUG_SIGNATURES = {

@@ -21,6 +21,45 @@ struct FileOutputs {
     bool want_pdq = true;
 };
 
+// The result sections of a chunk of n images, each 256-byte aligned: where they lie in the device buffer and in its pinned copy
+// (hash 32 B, quality 4 B, coefficients 1024 B, dihedral hashes 256 B, valid 1 B and pixel hash 32 B per image)
+struct ResultSections {
+    size_t hash, quality, coeffs, dihedral, valid, pixel, end;
+    explicit ResultSections(size_t n)
+    {
+        Layout L;
+        hash = L.add(n * 32), quality = L.add(n * 4, 256), coeffs = L.add(n * 1024, 256), dihedral = L.add(n * 256, 256), valid = L.add(n, 256);
+        pixel = L.add(n * 32, 256), end = L.end();
+    }
+    size_t bytes() const { return end; }
+    // slot k of every section in the device buffer R; nullptr for what `out` does not ask for
+    struct Slots {
+        uint8_t *hash, *quality, *coeffs, *dihedral, *valid, *pixel;
+    };
+    Slots device(uint8_t *R, size_t k, const FileOutputs &out) const
+    {
+        const bool pdq = out.want_pdq;
+        return {pdq ? R + hash + k * 32 : nullptr,
+                pdq && out.quality ? R + quality + k * 4 : nullptr,
+                pdq && out.coeffs ? R + coeffs + k * 1024 : nullptr,
+                pdq && out.dihedral ? R + dihedral + k * 256 : nullptr,
+                pdq ? R + valid + k : nullptr,
+                out.pixel ? R + pixel + k * 32 : nullptr};
+    }
+    // slot k of the pinned copy H -> file f of the caller's arrays
+    void scatter(const uint8_t *H, size_t k, uint32_t f, const FileOutputs &out) const
+    {
+        if (out.want_pdq) {
+            memcpy(out.hash + (size_t)f * 32, H + hash + k * 32, 32);
+            if (out.quality) memcpy(out.quality + f, H + quality + k * 4, 4);
+            if (out.coeffs) memcpy(out.coeffs + (size_t)f * 256, H + coeffs + k * 1024, 1024);
+            if (out.dihedral) memcpy(out.dihedral + (size_t)f * 256, H + dihedral + k * 256, 256);
+            if (out.valid) out.valid[f] = H[valid + k];
+        }
+        if (out.pixel) memcpy(out.pixel + (size_t)f * 32, H + pixel + k * 32, 32);
+    }
+};
+
 // buffers of this stage, kept by the pipeline between calls
 struct HashStageBufs {
     DevBuf hp, x16, nat, res, b3, dig;
@@ -79,12 +118,12 @@ int hash_decoded_images(rph_ctx *ctx, hipStream_t s, HashStageBufs &P, Image *im
     }
     b3off[n16] = x16_bytes;
     // buffers of this stage
-    const size_t res_bytes = g * (32 + 4 + 1024 + 256 + 1 + 32) + 4 * 256;
+    const ResultSections RS(g);
     RPH_TRY(reserve(P.hp, hp_bytes));
     if (x16_bytes) RPH_TRY(reserve(P.x16, x16_bytes));
     if (nat_bytes) RPH_TRY(reserve(P.nat, nat_bytes));
-    RPH_TRY(reserve(P.res, res_bytes));
-    RPH_TRY(reserve(P.h_res, res_bytes));
+    RPH_TRY(reserve(P.res, RS.bytes()));
+    RPH_TRY(reserve(P.h_res, RS.bytes()));
     size_t b3_scratch = 0;
     for (size_t q = 0; q < g;) {  // runs of equal geometry
         const Image &a = imgs[good[q]];
@@ -96,49 +135,35 @@ int hash_decoded_images(rph_ctx *ctx, hipStream_t s, HashStageBufs &P, Image *im
     if (b3_scratch) RPH_TRY(reserve(P.b3, b3_scratch));
     if (n16) RPH_TRY(reserve(P.dig, n16 * 32));
     RPH_TRY(expand((uint32_t)g, max_px, want_hp, x16_bytes, nat_bytes));
-    // result sections, each 256-byte aligned
-    Layout RL;
-    const size_t o_hash = RL.add(g * 32), o_q = RL.add(g * 4, 256), o_c = RL.add(g * 1024, 256), o_d = RL.add(g * 256, 256), o_v = RL.add(g, 256), o_px = RL.add(g * 32, 256);
-    uint8_t *R = P.res.data(), *r_hash = R + o_hash, *r_q = R + o_q, *r_c = R + o_c, *r_d = R + o_d, *r_v = R + o_v, *r_px = R + o_px;
+    uint8_t *R = P.res.data();
     for (size_t q = 0; q < g;) {
         const Image &a = imgs[good[q]];
         size_t e = q + 1;
         while (e < g && imgs[good[e]].w == a.w && imgs[good[e]].h == a.h && imgs[good[e]].hc == a.hc && imgs[good[e]].out_depth == a.out_depth) e++;
         const uint32_t cnt = (uint32_t)(e - q);
         const size_t istride = align_up((uint64_t)a.hstride * a.h, 64);
+        const ResultSections::Slots r = RS.device(R, q, out);
         // pixel hashes first: the reference hashes to_rgba16() before generate_pdq_features (scanner.rs:1393-1410).  (A run of 16-bit
         // images is consecutive in the RGBA16 buffer: hashed below, all 16-bit images of the chunk at once.)
         if (out.pixel && a.out_depth != 16)
-            RPH_TRY(rph_launch_pixel_hash(P.hp.data() + a.hp_off, cnt, a.w, a.h, a.hc, a.hstride, istride, r_px + q * 32, s, b3_scratch ? P.b3.data() : nullptr));
+            RPH_TRY(rph_launch_pixel_hash(P.hp.data() + a.hp_off, cnt, a.w, a.h, a.hc, a.hstride, istride, r.pixel, s, b3_scratch ? P.b3.data() : nullptr));
         if (out.want_pdq)
-            RPH_TRY(rph_pdq_hash_batch_dev(ctx, P.hp.data() + a.hp_off, cnt, a.w, a.h, a.hc, a.hstride, istride, r_hash + q * 32, out.quality ? r_q + q * 4 : nullptr,
-                                           out.coeffs ? r_c + q * 1024 : nullptr, out.dihedral ? r_d + q * 256 : nullptr, r_v + q, s));
+            RPH_TRY(rph_pdq_hash_batch_dev(ctx, P.hp.data() + a.hp_off, cnt, a.w, a.h, a.hc, a.hstride, istride, r.hash, r.quality, r.coeffs, r.dihedral,
+                                           r.valid, s));
         q = e;
     }
     // 16-bit pixel hashes: BLAKE3 of the RGBA16 strings, digests into the result slots of those images (in the same order)
     std::vector<uint8_t> dig16(n16 * 32);
     if (n16) RPH_TRY(rph_blake3_batch_dev(ctx, P.x16.data(), d_b3off, (uint32_t)n16, nullptr, P.dig.data(), s));
     if (n16) RPH_HIP_CHECK(hipMemcpyAsync(dig16.data(), P.dig.data(), n16 * 32, hipMemcpyDeviceToHost, s));
-    RPH_HIP_CHECK(hipMemcpyAsync(P.h_res.data(), R, res_bytes, hipMemcpyDeviceToHost, s));
+    RPH_HIP_CHECK(hipMemcpyAsync(P.h_res.data(), R, RS.bytes(), hipMemcpyDeviceToHost, s));
     if (out.native) RPH_HIP_CHECK(hipMemcpyAsync(out.native, P.nat.data(), nat_bytes, hipMemcpyDeviceToHost, s));
     RPH_HIP_CHECK(hipStreamSynchronize(s));
-    const uint8_t *H = P.h_res.data(), *h_hash = H + o_hash, *h_q = H + o_q, *h_c = H + o_c, *h_d = H + o_d, *h_v = H + o_v, *h_px = H + o_px;
     size_t i16 = 0;
     for (size_t q = 0; q < g; q++) {
         const uint32_t f = idx[good[q]];
-        if (out.want_pdq) {
-            memcpy(out.hash + (size_t)f * 32, h_hash + q * 32, 32);
-            if (out.quality) memcpy(out.quality + f, h_q + q * 4, 4);
-            if (out.coeffs) memcpy(out.coeffs + (size_t)f * 256, h_c + q * 1024, 1024);
-            if (out.dihedral) memcpy(out.dihedral + (size_t)f * 256, h_d + q * 256, 256);
-            if (out.valid) out.valid[f] = h_v[q];
-        }
-        if (out.pixel) {
-            if (imgs[good[q]].out_depth == 16)
-                memcpy(out.pixel + (size_t)f * 32, dig16.data() + 32 * i16++, 32);
-            else
-                memcpy(out.pixel + (size_t)f * 32, h_px + q * 32, 32);
-        }
+        RS.scatter(P.h_res.data(), q, f, out);
+        if (out.pixel && imgs[good[q]].out_depth == 16) memcpy(out.pixel + (size_t)f * 32, dig16.data() + 32 * i16++, 32);  // (no kernel wrote its slot)
     }
     return RPH_OK;
 }

@@ -11,7 +11,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "decoded_hash.h"
+#include "file_pipeline.h"
 #include "gif_host.h"
 #include "rph_internal.h"
 
@@ -21,8 +21,7 @@ int rph_gif_launch_expand(const uint8_t *d_dec, const void *d_images, const uint
 
 namespace {
 
-struct GifPipe {
-    hipStream_t s = nullptr;  // (rph_gif_forget: synchronised before the buffers are freed)
+struct GifPipe : FilePipeBase {
     DevBuf comp, dec, meta, status;
     PinnedBuf h_comp, h_dec, h_meta, h_status;
     HashStageBufs hash;
@@ -57,7 +56,7 @@ int run_chunk(rph_ctx *ctx, GifPipe &P, const uint8_t *const *data, std::vector<
         stream_bytes += pp.stream_len;
         max_rows = std::max(max_rows, pp.im.h);
     }
-    int mode = ctx->gif_decompress;
+    int mode = ctx->file[RPH_FILE_GIF].mode;
     if (mode == RPH_GIF_DECOMPRESS_AUTO)
         mode = AUTO_DEVICE_MIN_RATIO && index_bytes >= AUTO_DEVICE_MIN_RATIO * stream_bytes ? RPH_GIF_DECOMPRESS_DEVICE : RPH_GIF_DECOMPRESS_HOST;
     const bool device = mode == RPH_GIF_DECOMPRESS_DEVICE;
@@ -110,164 +109,61 @@ int run_chunk(rph_ctx *ctx, GifPipe &P, const uint8_t *const *data, std::vector<
 
 int run(rph_ctx *ctx, const uint8_t *const *data, const size_t *len, uint32_t n, unsigned threads, const FileOutputs &out)
 {
-    std::lock_guard<std::mutex> lock(ctx->gif_mu);
-    RPH_HIP_CHECK(hipSetDevice(ctx->device));
-    GifPipe *P = static_cast<GifPipe *>(ctx->gif);
-    if (!P) {
-        P = new GifPipe();
-        hipError_t e = hipStreamCreateWithFlags(&P->s, hipStreamNonBlocking);
-        if (e != hipSuccess) {
-            delete P;
-            rph_set_error("hipStreamCreate failed: %s", hipGetErrorString(e));
-            return RPH_ERR_HIP;
+    return with_file_pipe<GifPipe>(ctx, RPH_FILE_GIF, threads, [&](GifPipe &P, rph_file_slot &slot, unsigned threads) -> int {
+        std::vector<rphg::Parsed> parsed(n);
+        const std::vector<uint32_t> ok = parse_files(data, len, n, threads, out.status, slot.log, [&](size_t i) { return rphg::parse(data[i], len[i], parsed[i]); });
+        const rph_file_limits &lim = ctx->file_limits;
+        for (size_t a = 0; a < ok.size();) {
+            const size_t b = chunk_end<3>(ok, a, lim.files, {lim.comp, lim.raw, lim.pixels / 2}, [&](uint32_t i) -> std::array<uint64_t, 3> {
+                const rphg::Parsed &p = parsed[i];
+                return {p.stream_len, (uint64_t)p.im.fw * p.im.fh, (uint64_t)p.im.w * p.im.h};  // (pixels / 2: 4 bytes per pixel)
+            });
+            slot.log.sizes.push_back((uint32_t)(b - a));
+            RPH_TRY(run_chunk(ctx, P, data, parsed, ok.data() + a, b - a, threads, out));
+            a = b;
         }
-        ctx->gif = P;
-    }
-    if (!threads) threads = rph_host_threads();
-    std::vector<rphg::Parsed> parsed(n);
-    parallel_for(0, n, threads, [&](size_t i) { out.status[i] = (data[i] && len[i]) ? rphg::parse(data[i], len[i], parsed[i]) : RPH_ERR_INVALID_ARG; });
-    std::vector<uint32_t> ok;
-    for (uint32_t i = 0; i < n; i++)
-        if (out.status[i] == RPH_OK) ok.push_back(i);
-    const rph_file_limits &lim = ctx->file_limits;
-    rph_file_chunk_log &log = ctx->file_chunks[RPH_FILE_GIF];
-    log = rph_file_chunk_log();
-    for (size_t a = 0; a < ok.size();) {
-        size_t b = a;
-        uint64_t comp = 0, dec = 0, px = 0;
-        while (b < ok.size() && b - a < lim.files) {
-            const rphg::Parsed &p = parsed[ok[b]];
-            const uint64_t pix = (uint64_t)p.im.w * p.im.h;
-            const uint64_t ind = (uint64_t)p.im.fw * p.im.fh;
-            if (b > a && (comp + p.stream_len > lim.comp || dec + ind > lim.raw || px + pix > lim.pixels / 2)) break;  // (4 bytes per pixel)
-            comp += p.stream_len;
-            dec += ind;
-            px += pix;
-            b++;
-        }
-        log.sizes.push_back((uint32_t)(b - a));
-        RPH_TRY(run_chunk(ctx, *P, data, parsed, ok.data() + a, b - a, threads, out));
-        a = b;
-    }
-    return RPH_OK;
+        return RPH_OK;
+    });
 }
 
 }  // namespace
 
-void rph_gif_forget(rph_ctx *ctx)
-{
-    GifPipe *P = static_cast<GifPipe *>(ctx->gif);
-    if (!P) return;
-    (void)hipStreamSynchronize(P->s);
-    (void)hipStreamDestroy(P->s);
-    delete P;
-    ctx->gif = nullptr;
-}
+void rph_gif_forget(rph_ctx *ctx) { forget_file_pipe<GifPipe>(ctx, RPH_FILE_GIF); }
 
 extern "C" {
 
 int rph_gif_info(const uint8_t *data, size_t len, uint32_t *w, uint32_t *h, uint32_t *channels, uint32_t *bit_depth)
 {
-    return rph_guarded("rph_gif_info", [&]() -> int {
-        if (!data) return RPH_ERR_INVALID_ARG;
-        rphg::Parsed p;
-        const int rc = rphg::parse(data, len, p);
-        if (rc) return rc;
-        if (w) *w = p.im.w;
-        if (h) *h = p.im.h;
-        if (channels) *channels = p.im.out_ch;
-        if (bit_depth) *bit_depth = p.im.out_depth;
-        return RPH_OK;
-    });
+    return rph_guarded("rph_gif_info", [&] { return file_info<rphg::Parsed>(data, len, w, h, channels, bit_depth, rphg::parse, image_out_depth); });
 }
 
 int rph_gif_decode_host(const uint8_t *data, size_t len, void *pixels_out, size_t cap_bytes)
 {
-    return rph_guarded("rph_gif_decode_host", [&]() -> int {
-        if (!data || !pixels_out) return RPH_ERR_INVALID_ARG;
-        rphg::Parsed p;
-        std::vector<uint8_t> px;
-        const int rc = rphg::decode_host(data, len, p, px);
-        if (rc) return rc;
-        if (px.size() > cap_bytes) {
-            rph_set_error("rph_gif_decode_host: %zu bytes needed", px.size());
-            return RPH_ERR_CAPACITY;
-        }
-        memcpy(pixels_out, px.data(), px.size());
-        return RPH_OK;
-    });
+    return rph_guarded("rph_gif_decode_host",
+                       [&] { return file_decode_host<rphg::Parsed>("rph_gif_decode_host", data, len, pixels_out, cap_bytes, rphg::decode_host); });
 }
 
 int rph_gif_decode(rph_ctx *ctx, const uint8_t *data, size_t len, void *pixels_out, size_t cap_bytes)
 {
-    return rph_guarded("rph_gif_decode", [&]() -> int {
-        if (!ctx || !data || !pixels_out) return RPH_ERR_INVALID_ARG;
-        rphg::Parsed p;
-        int rc = rphg::parse(data, len, p);
-        if (rc) return rc;
-        const size_t need = (size_t)p.im.w * p.im.h * 4;
-        if (need > cap_bytes) {
-            rph_set_error("rph_gif_decode: %zu bytes needed", need);
-            return RPH_ERR_CAPACITY;
-        }
-        int32_t status = RPH_OK;
-        FileOutputs o;
-        o.want_pdq = false;
-        o.status = &status;
-        std::vector<uint8_t> staging(align_up(need, 64) + 64);
-        o.native = staging.data();
-        RPH_TRY(run(ctx, &data, &len, 1, 0, o));
-        if (status != RPH_OK) return status;
-        memcpy(pixels_out, staging.data(), need);
-        return RPH_OK;
+    return rph_guarded("rph_gif_decode", [&] {
+        return file_decode<rphg::Parsed>(
+            "rph_gif_decode", ctx, data, len, pixels_out, cap_bytes, rphg::parse,
+            [](const rphg::Image &im) { return (size_t)im.w * im.h * 4; }, [&](const FileOutputs &o) { return run(ctx, &data, &len, 1, 0, o); });
     });
 }
 
 int rph_gif_pdq_hash_batch(rph_ctx *ctx, const uint8_t *const *data, const size_t *len, uint32_t n, uint32_t n_threads, uint8_t *hash32_out,
-                            float *quality_out, float *coeffs_out, uint8_t *dihedral_out, uint8_t *valid_out, int32_t *status_out,
-                            uint8_t *pixel_hash32_out)
+                           float *quality_out, float *coeffs_out, uint8_t *dihedral_out, uint8_t *valid_out, int32_t *status_out,
+                           uint8_t *pixel_hash32_out)
 {
-    return rph_guarded("rph_gif_pdq_hash_batch", [&]() -> int {
-        if (!ctx || (n && (!data || !len || !hash32_out))) {
-            rph_set_error("rph_gif_pdq_hash_batch: null argument");
-            return RPH_ERR_INVALID_ARG;
-        }
-        if (n == 0) return RPH_OK;
-        std::vector<int32_t> st_local(status_out ? 0 : n);
-        std::vector<uint8_t> v_local(valid_out ? 0 : n);
-        FileOutputs o;
-        o.hash = hash32_out;
-        o.quality = quality_out;
-        o.coeffs = coeffs_out;
-        o.dihedral = dihedral_out;
-        o.valid = valid_out ? valid_out : v_local.data();
-        o.status = status_out ? status_out : st_local.data();
-        o.pixel = pixel_hash32_out;
-        memset(hash32_out, 0, (size_t)n * 32);
-        if (quality_out) memset(quality_out, 0, (size_t)n * 4);
-        if (coeffs_out) memset(coeffs_out, 0, (size_t)n * 1024);
-        if (dihedral_out) memset(dihedral_out, 0, (size_t)n * 256);
-        memset(o.valid, 0, n);
-        if (pixel_hash32_out) memset(pixel_hash32_out, 0, (size_t)n * 32);
-        return run(ctx, data, len, n, n_threads, o);
+    return rph_guarded("rph_gif_pdq_hash_batch", [&] {
+        return file_hash_batch("rph_gif_pdq_hash_batch", ctx, data, len, n, hash32_out, quality_out, coeffs_out, dihedral_out, valid_out, status_out, pixel_hash32_out,
+                               [&](const FileOutputs &o) { return run(ctx, data, len, n, n_threads, o); });
     });
 }
 
-int rph_gif_set_decompress(rph_ctx *ctx, int where)
-{
-    if (!ctx || where < RPH_GIF_DECOMPRESS_HOST || where > RPH_GIF_DECOMPRESS_AUTO) return RPH_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(ctx->gif_mu);
-    ctx->gif_decompress = where;
-    return RPH_OK;
-}
+int rph_gif_set_decompress(rph_ctx *ctx, int where) { return file_set_mode(ctx, RPH_FILE_GIF, where, RPH_GIF_DECOMPRESS_HOST, RPH_GIF_DECOMPRESS_AUTO); }
 
-int rph_gif_release(rph_ctx *ctx)
-{
-    if (!ctx) return RPH_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(ctx->gif_mu);
-    (void)hipSetDevice(ctx->device);
-    rph_gif_forget(ctx);
-    return RPH_OK;
-}
+int rph_gif_release(rph_ctx *ctx) { return file_release(ctx, RPH_FILE_GIF, rph_gif_forget); }
 
 }  // extern "C"

@@ -10,7 +10,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "decoded_hash.h"
+#include "file_pipeline.h"
 #include "png_host.h"
 #include "rph_internal.h"
 
@@ -20,8 +20,7 @@ int rph_png_launch_expand(const uint8_t *d_raw, const void *d_images, const uint
 
 namespace {
 
-struct PngPipe {
-    hipStream_t s = nullptr;  // (rph_png_forget: synchronised before the buffers are freed)
+struct PngPipe : FilePipeBase {
     DevBuf comp, raw, meta, status;
     PinnedBuf h_comp, h_raw, h_meta, h_status;
     HashStageBufs hash;
@@ -41,7 +40,7 @@ int run_chunk(rph_ctx *ctx, PngPipe &P, const uint8_t *const *data, std::vector<
 {
     hipStream_t s = P.s;
     auto reserve = [s](auto &buf, size_t bytes) { return reserve_slack(buf, bytes, s); };
-    int mode = ctx->png_inflate;
+    int mode = ctx->file[RPH_FILE_PNG].mode;
     // raw / compressed placement
     uint64_t raw_bytes = 0, comp_bytes = 0;
     std::vector<uint64_t> comp_off(m);
@@ -114,116 +113,46 @@ int run_chunk(rph_ctx *ctx, PngPipe &P, const uint8_t *const *data, std::vector<
 
 int run(rph_ctx *ctx, const uint8_t *const *data, const size_t *len, uint32_t n, unsigned threads, const Outputs &out)
 {
-    std::lock_guard<std::mutex> lock(ctx->png_mu);
-    RPH_HIP_CHECK(hipSetDevice(ctx->device));
-    PngPipe *P = static_cast<PngPipe *>(ctx->png);
-    if (!P) {
-        P = new PngPipe();
-        hipError_t e = hipStreamCreateWithFlags(&P->s, hipStreamNonBlocking);
-        if (e != hipSuccess) {
-            delete P;
-            rph_set_error("hipStreamCreate failed: %s", hipGetErrorString(e));
-            return RPH_ERR_HIP;
+    return with_file_pipe<PngPipe>(ctx, RPH_FILE_PNG, threads, [&](PngPipe &P, rph_file_slot &slot, unsigned threads) -> int {
+        std::vector<rphp::Parsed> parsed(n);
+        const std::vector<uint32_t> ok = parse_files(data, len, n, threads, out.status, slot.log, [&](size_t i) { return rphp::parse(data[i], len[i], parsed[i]); });
+        const rph_file_limits &lim = ctx->file_limits;
+        for (size_t a = 0; a < ok.size();) {
+            const size_t b = chunk_end<3>(ok, a, lim.files, {lim.comp, lim.raw, lim.pixels}, [&](uint32_t i) -> std::array<uint64_t, 3> {
+                const rphp::Parsed &p = parsed[i];
+                return {p.idat_bytes, p.im.raw_bytes, (uint64_t)p.im.w * p.im.h};
+            });
+            slot.log.sizes.push_back((uint32_t)(b - a));
+            RPH_TRY(run_chunk(ctx, P, data, parsed, ok.data() + a, b - a, threads, out));
+            a = b;
         }
-        ctx->png = P;
-    }
-    if (!threads) threads = rph_host_threads();
-    std::vector<rphp::Parsed> parsed(n);
-    parallel_for(0, n, threads, [&](size_t i) { out.status[i] = (data[i] && len[i]) ? rphp::parse(data[i], len[i], parsed[i]) : RPH_ERR_INVALID_ARG; });
-    std::vector<uint32_t> ok;
-    for (uint32_t i = 0; i < n; i++)
-        if (out.status[i] == RPH_OK) ok.push_back(i);
-    const rph_file_limits &lim = ctx->file_limits;
-    rph_file_chunk_log &log = ctx->file_chunks[RPH_FILE_PNG];
-    log = rph_file_chunk_log();
-    for (size_t a = 0; a < ok.size();) {
-        size_t b = a;
-        uint64_t comp = 0, raw = 0, px = 0;
-        while (b < ok.size() && b - a < lim.files) {
-            const rphp::Parsed &p = parsed[ok[b]];
-            const uint64_t pix = (uint64_t)p.im.w * p.im.h;
-            if (b > a && (comp + p.idat_bytes > lim.comp || raw + p.im.raw_bytes > lim.raw || px + pix > lim.pixels)) break;
-            comp += p.idat_bytes;
-            raw += p.im.raw_bytes;
-            px += pix;
-            b++;
-        }
-        log.sizes.push_back((uint32_t)(b - a));
-        RPH_TRY(run_chunk(ctx, *P, data, parsed, ok.data() + a, b - a, threads, out));
-        a = b;
-    }
-    return RPH_OK;
+        return RPH_OK;
+    });
 }
 
 }  // namespace
 
-void rph_png_forget(rph_ctx *ctx)
-{
-    PngPipe *P = static_cast<PngPipe *>(ctx->png);
-    if (!P) return;
-    (void)hipStreamSynchronize(P->s);
-    (void)hipStreamDestroy(P->s);
-    delete P;
-    ctx->png = nullptr;
-}
+void rph_png_forget(rph_ctx *ctx) { forget_file_pipe<PngPipe>(ctx, RPH_FILE_PNG); }
 
 extern "C" {
 
 int rph_png_info(const uint8_t *data, size_t len, uint32_t *w, uint32_t *h, uint32_t *channels, uint32_t *bit_depth)
 {
-    return rph_guarded("rph_png_info", [&]() -> int {
-        if (!data) return RPH_ERR_INVALID_ARG;
-        rphp::Parsed p;
-        const int rc = rphp::parse(data, len, p);
-        if (rc) return rc;
-        if (w) *w = p.im.w;
-        if (h) *h = p.im.h;
-        if (channels) *channels = p.im.out_ch;
-        if (bit_depth) *bit_depth = p.im.out_depth;
-        return RPH_OK;
-    });
+    return rph_guarded("rph_png_info", [&] { return file_info<rphp::Parsed>(data, len, w, h, channels, bit_depth, rphp::parse, image_out_depth); });
 }
 
 int rph_png_decode_host(const uint8_t *data, size_t len, void *pixels_out, size_t cap_bytes)
 {
-    return rph_guarded("rph_png_decode_host", [&]() -> int {
-        if (!data || !pixels_out) return RPH_ERR_INVALID_ARG;
-        rphp::Parsed p;
-        std::vector<uint8_t> px;
-        const int rc = rphp::decode_host(data, len, p, px);
-        if (rc) return rc;
-        if (px.size() > cap_bytes) {
-            rph_set_error("rph_png_decode_host: %zu bytes needed", px.size());
-            return RPH_ERR_CAPACITY;
-        }
-        memcpy(pixels_out, px.data(), px.size());
-        return RPH_OK;
-    });
+    return rph_guarded("rph_png_decode_host",
+                       [&] { return file_decode_host<rphp::Parsed>("rph_png_decode_host", data, len, pixels_out, cap_bytes, rphp::decode_host); });
 }
 
 int rph_png_decode(rph_ctx *ctx, const uint8_t *data, size_t len, void *pixels_out, size_t cap_bytes)
 {
-    return rph_guarded("rph_png_decode", [&]() -> int {
-        if (!ctx || !data || !pixels_out) return RPH_ERR_INVALID_ARG;
-        rphp::Parsed p;
-        int rc = rphp::parse(data, len, p);
-        if (rc) return rc;
-        const size_t need = (size_t)p.im.w * p.im.h * p.im.out_ch * (p.im.out_depth / 8);
-        if (need > cap_bytes) {
-            rph_set_error("rph_png_decode: %zu bytes needed", need);
-            return RPH_ERR_CAPACITY;
-        }
-        int32_t status = RPH_OK;
-        Outputs o;
-        o.want_pdq = false;
-        o.status = &status;
-        // (the pinned result copy is skipped: the native pixels land in a device buffer and are copied to the caller's memory)
-        std::vector<uint8_t> staging(align_up(need, 64) + 64);
-        o.native = staging.data();
-        RPH_TRY(run(ctx, &data, &len, 1, 1, o));
-        if (status != RPH_OK) return status;
-        memcpy(pixels_out, staging.data(), need);
-        return RPH_OK;
+    return rph_guarded("rph_png_decode", [&] {
+        return file_decode<rphp::Parsed>(
+            "rph_png_decode", ctx, data, len, pixels_out, cap_bytes, rphp::parse,
+            [](const rphp::Image &im) { return (size_t)im.w * im.h * im.out_ch * (im.out_depth / 8); }, [&](const Outputs &o) { return run(ctx, &data, &len, 1, 1, o); });
     });
 }
 
@@ -231,47 +160,14 @@ int rph_png_pdq_hash_batch(rph_ctx *ctx, const uint8_t *const *data, const size_
                            float *quality_out, float *coeffs_out, uint8_t *dihedral_out, uint8_t *valid_out, int32_t *status_out,
                            uint8_t *pixel_hash32_out)
 {
-    return rph_guarded("rph_png_pdq_hash_batch", [&]() -> int {
-        if (!ctx || (n && (!data || !len || !hash32_out))) {
-            rph_set_error("rph_png_pdq_hash_batch: null argument");
-            return RPH_ERR_INVALID_ARG;
-        }
-        if (n == 0) return RPH_OK;
-        std::vector<int32_t> st_local(status_out ? 0 : n);
-        std::vector<uint8_t> v_local(valid_out ? 0 : n);
-        Outputs o;
-        o.hash = hash32_out;
-        o.quality = quality_out;
-        o.coeffs = coeffs_out;
-        o.dihedral = dihedral_out;
-        o.valid = valid_out ? valid_out : v_local.data();
-        o.status = status_out ? status_out : st_local.data();
-        o.pixel = pixel_hash32_out;
-        memset(hash32_out, 0, (size_t)n * 32);
-        if (quality_out) memset(quality_out, 0, (size_t)n * 4);
-        if (coeffs_out) memset(coeffs_out, 0, (size_t)n * 1024);
-        if (dihedral_out) memset(dihedral_out, 0, (size_t)n * 256);
-        memset(o.valid, 0, n);
-        if (pixel_hash32_out) memset(pixel_hash32_out, 0, (size_t)n * 32);
-        return run(ctx, data, len, n, n_threads, o);
+    return rph_guarded("rph_png_pdq_hash_batch", [&] {
+        return file_hash_batch("rph_png_pdq_hash_batch", ctx, data, len, n, hash32_out, quality_out, coeffs_out, dihedral_out, valid_out, status_out, pixel_hash32_out,
+                               [&](const Outputs &o) { return run(ctx, data, len, n, n_threads, o); });
     });
 }
 
-int rph_png_set_inflate(rph_ctx *ctx, int where)
-{
-    if (!ctx || where < RPH_PNG_INFLATE_HOST || where > RPH_PNG_INFLATE_AUTO) return RPH_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(ctx->png_mu);
-    ctx->png_inflate = where;
-    return RPH_OK;
-}
+int rph_png_set_inflate(rph_ctx *ctx, int where) { return file_set_mode(ctx, RPH_FILE_PNG, where, RPH_PNG_INFLATE_HOST, RPH_PNG_INFLATE_AUTO); }
 
-int rph_png_release(rph_ctx *ctx)
-{
-    if (!ctx) return RPH_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(ctx->png_mu);
-    (void)hipSetDevice(ctx->device);
-    rph_png_forget(ctx);
-    return RPH_OK;
-}
+int rph_png_release(rph_ctx *ctx) { return file_release(ctx, RPH_FILE_PNG, rph_png_forget); }
 
 }  // extern "C"

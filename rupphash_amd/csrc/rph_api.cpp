@@ -286,9 +286,8 @@ int rph_shutdown(rph_ctx *ctx)
 int rph_debug_file_chunks(rph_ctx *ctx, int format, uint32_t *sizes_out, uint32_t cap, uint32_t *n_chunks_out, uint32_t *n_windows_out)
 {
     if (!ctx || format < 0 || format >= RPH_FILE_FORMATS) return RPH_ERR_INVALID_ARG;
-    std::mutex *const mu[RPH_FILE_FORMATS] = {&ctx->png_mu, &ctx->tiff_mu, &ctx->webp_mu, &ctx->gif_mu, &ctx->bmp_mu};
-    std::lock_guard<std::mutex> lock(*mu[format]);
-    const rph_file_chunk_log &log = ctx->file_chunks[format];
+    std::lock_guard<std::mutex> lock(ctx->file[format].mu);
+    const rph_file_chunk_log &log = ctx->file[format].log;
     if (sizes_out)
         for (size_t k = 0; k < std::min<size_t>(cap, log.sizes.size()); k++) sizes_out[k] = log.sizes[k];
     if (n_chunks_out) *n_chunks_out = (uint32_t)log.sizes.size();

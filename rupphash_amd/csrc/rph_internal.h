@@ -37,6 +37,18 @@ struct rph_file_chunk_log {
     uint32_t n_windows = 0;
 };
 
+// One file pipeline's place in the context (file_pipeline.h): its staging and device buffers and its stream, kept across calls behind
+// `pipe`; one batch call at a time (mu); where the format's streams are decoded, 0 = host threads, 1 = device, 2 = automatic (the
+// default: RPH_PNG_INFLATE_AUTO, RPH_TIFF_DECOMPRESS_AUTO, RPH_WEBP_ENTROPY_AUTO, RPH_GIF_DECOMPRESS_AUTO); what the last call did with
+// the chunk limits, written under mu (rph_debug_file_chunks)
+struct rph_file_slot {
+    std::mutex mu;
+    void *pipe = nullptr;
+    int mode = 2;
+    rph_file_chunk_log log;
+};
+static_assert(RPH_PNG_INFLATE_AUTO == 2 && RPH_TIFF_DECOMPRESS_AUTO == 2 && RPH_WEBP_ENTROPY_AUTO == 2 && RPH_GIF_DECOMPRESS_AUTO == 2, "rph_file_slot::mode");
+
 struct rph_ctx {
     int device = 0;
     int compute_units = 0;
@@ -92,30 +104,12 @@ struct rph_ctx {
     bool jpeg_leader = false;
     std::vector<void *> jpeg_thread_buffers;  // the callers' pinned coefficient buffers (one per calling thread), freed with the context
     uint64_t serial = 0;                      // distinguishes this context from an earlier one at the same address
-    // PNG path (png_pipeline.cpp): staging and device buffers kept across calls, one batch call at a time; where the zlib streams are
-    // inflated (RPH_PNG_INFLATE_*)
-    std::mutex png_mu;
-    void *png = nullptr;
-    int png_inflate = RPH_PNG_INFLATE_AUTO;
-    // TIFF path (tiff_pipeline.cpp): the same arrangement; where the strips and tiles are decompressed (RPH_TIFF_DECOMPRESS_*)
-    std::mutex tiff_mu;
-    void *tiff = nullptr;
-    int tiff_decompress = RPH_TIFF_DECOMPRESS_AUTO;
-    // WebP path (webp_pipeline.cpp): the same arrangement; where the main ARGB streams are entropy-decoded (RPH_WEBP_ENTROPY_*)
-    std::mutex webp_mu;
-    void *webp = nullptr;
-    int webp_entropy = RPH_WEBP_ENTROPY_AUTO;
-    // GIF path (gif_pipeline.cpp): the same arrangement; where the frames' LZW streams are decoded (RPH_GIF_DECOMPRESS_*)
-    std::mutex gif_mu;
-    void *gif = nullptr;
-    int gif_decompress = RPH_GIF_DECOMPRESS_AUTO;
-    // BMP path (bmp_pipeline.cpp): the same arrangement; no mode: the pixel arrays cross PCIe as they are, RLE streams are the host's
-    std::mutex bmp_mu;
-    void *bmp = nullptr;
-    // the five file pipelines' chunk limits (tests only: read once, by rph_init) and what each one's last call did with them, written
-    // under that pipeline's mutex (rph_debug_file_chunks)
+    // The five file pipelines, by RPH_FILE_*.  The mode says where the PNG path's zlib streams are inflated (RPH_PNG_INFLATE_*), the TIFF
+    // path's strips and tiles decompressed (RPH_TIFF_DECOMPRESS_*), the WebP path's main ARGB streams entropy-decoded
+    // (RPH_WEBP_ENTROPY_*) and the GIF path's LZW streams decoded (RPH_GIF_DECOMPRESS_*); the BMP path has no mode: the pixel arrays cross
+    // PCIe as they are, RLE streams are the host's.  Their chunk limits (tests only: read once, by rph_init)
+    rph_file_slot file[RPH_FILE_FORMATS];
     rph_file_limits file_limits;
-    rph_file_chunk_log file_chunks[RPH_FILE_FORMATS];
 };
 
 // ---- launchers implemented in the .hip files (all asynchronous on `stream`) ----

@@ -14,7 +14,7 @@
 #include <atomic>
 #include <vector>
 
-#include "decoded_hash.h"
+#include "file_pipeline.h"
 #include "rph_internal.h"
 #include "webp_host.h"
 
@@ -24,8 +24,7 @@ int rph_webp_launch_finish(const void *d_images, const uint32_t *d_list, uint32_
 
 namespace {
 
-struct WebpPipe {
-    hipStream_t s = nullptr;  // (rph_webp_forget: synchronised before the buffers are freed)
+struct WebpPipe : FilePipeBase {
     DevBuf comp, argb, words, codes, meta, status;
     PinnedBuf h_comp, h_argb, h_words, h_codes, h_meta, h_status;
     HashStageBufs hash;
@@ -79,7 +78,7 @@ int run_chunk(rph_ctx *ctx, WebpPipe &P, std::vector<rphw::Parsed> &parsed, cons
         pp.im.b_off = a_words + b_words;
         b_words += align_up((uint64_t)pp.im.w * pp.im.h, 16);
     }
-    int mode = ctx->webp_entropy;
+    int mode = ctx->file[RPH_FILE_WEBP].mode;
     if (mode == RPH_WEBP_ENTROPY_AUTO) mode = AUTO_DEVICE_MIN_RATIO && argb_bytes >= AUTO_DEVICE_MIN_RATIO * chunk_bytes ? RPH_WEBP_ENTROPY_DEVICE : RPH_WEBP_ENTROPY_HOST;
     const bool device = mode == RPH_WEBP_ENTROPY_DEVICE;
     Layout L;
@@ -147,135 +146,70 @@ int run_chunk(rph_ctx *ctx, WebpPipe &P, std::vector<rphw::Parsed> &parsed, cons
 
 int run(rph_ctx *ctx, const uint8_t *const *data, const size_t *len, uint32_t n, unsigned threads, const FileOutputs &out)
 {
-    std::lock_guard<std::mutex> lock(ctx->webp_mu);
-    RPH_HIP_CHECK(hipSetDevice(ctx->device));
-    WebpPipe *P = static_cast<WebpPipe *>(ctx->webp);
-    if (!P) {
-        P = new WebpPipe();
-        hipError_t e = hipStreamCreateWithFlags(&P->s, hipStreamNonBlocking);
-        if (e != hipSuccess) {
-            delete P;
-            rph_set_error("hipStreamCreate failed: %s", hipGetErrorString(e));
-            return RPH_ERR_HIP;
-        }
-        ctx->webp = P;
-    }
-    if (!threads) threads = rph_host_threads();
-    // The fronts of a window of files at a time: their tables are the bulk of what a parsed file holds.  A window ends early at the first
-    // file that finds the window's tables above their bound (files behind it that were parsed meanwhile are parsed again in the next one)
-    std::vector<rphw::Parsed> parsed(n);
-    const rph_file_limits &lim = ctx->file_limits;
-    rph_file_chunk_log &log = ctx->file_chunks[RPH_FILE_WEBP];
-    log = rph_file_chunk_log();
-    for (uint32_t a = 0; a < n;) {
-        uint32_t b = (uint32_t)std::min<uint64_t>(n, (uint64_t)a + lim.files);
-        std::atomic<uint64_t> held{0};
-        std::atomic<uint32_t> deferred{b};
-        log.n_windows++;
-        parallel_for(a, b, threads, [&](size_t i) {
-            if (i > a && (held.load() > lim.webp_window_tables || i > deferred.load())) {
-                uint32_t d = deferred.load();
-                while ((uint32_t)i < d && !deferred.compare_exchange_weak(d, (uint32_t)i)) {}
-                return;
+    return with_file_pipe<WebpPipe>(ctx, RPH_FILE_WEBP, threads, [&](WebpPipe &P, rph_file_slot &slot, unsigned threads) -> int {
+        // The fronts of a window of files at a time: their tables are the bulk of what a parsed file holds.  A window ends early at the
+        // first file that finds the window's tables above their bound (files behind it that were parsed meanwhile are parsed again in the
+        // next one)
+        std::vector<rphw::Parsed> parsed(n);
+        const rph_file_limits &lim = ctx->file_limits;
+        rph_file_chunk_log &log = slot.log;
+        log = rph_file_chunk_log();
+        for (uint32_t a = 0; a < n;) {
+            uint32_t b = (uint32_t)std::min<uint64_t>(n, (uint64_t)a + lim.files);
+            std::atomic<uint64_t> held{0};
+            std::atomic<uint32_t> deferred{b};
+            log.n_windows++;
+            parallel_for(a, b, threads, [&](size_t i) {
+                if (i > a && (held.load() > lim.webp_window_tables || i > deferred.load())) {
+                    uint32_t d = deferred.load();
+                    while ((uint32_t)i < d && !deferred.compare_exchange_weak(d, (uint32_t)i)) {}
+                    return;
+                }
+                out.status[i] = (data[i] && len[i]) ? rphw::front(data[i], len[i], parsed[i]) : RPH_ERR_INVALID_ARG;
+                held += table_bytes(parsed[i]);
+            });
+            for (uint32_t i = deferred.load(); i < b; i++) parsed[i] = rphw::Parsed();
+            b = deferred.load();
+            const std::vector<uint32_t> ok = ok_files(out.status, a, b);
+            for (size_t c = 0; c < ok.size();) {  // (no file bound: the window is one)
+                const size_t e = chunk_end<3>(ok, c, UINT64_MAX, {lim.comp, lim.pixels / 2, lim.webp_chunk_tables}, [&](uint32_t i) -> std::array<uint64_t, 3> {
+                    const rphw::Parsed &p = parsed[i];
+                    return {p.chunk_len, (uint64_t)p.im.w * p.im.h, table_bytes(p)};
+                });
+                log.sizes.push_back((uint32_t)(e - c));
+                RPH_TRY(run_chunk(ctx, P, parsed, ok.data() + c, e - c, threads, out));
+                c = e;
             }
-            out.status[i] = (data[i] && len[i]) ? rphw::front(data[i], len[i], parsed[i]) : RPH_ERR_INVALID_ARG;
-            held += table_bytes(parsed[i]);
-        });
-        for (uint32_t i = deferred.load(); i < b; i++) parsed[i] = rphw::Parsed();
-        b = deferred.load();
-        std::vector<uint32_t> ok;
-        for (uint32_t i = a; i < b; i++)
-            if (out.status[i] == RPH_OK) ok.push_back(i);
-        for (size_t c = 0; c < ok.size();) {
-            size_t e = c;
-            uint64_t comp = 0, px = 0, tab = 0;
-            while (e < ok.size()) {
-                const rphw::Parsed &p = parsed[ok[e]];
-                const uint64_t pix = (uint64_t)p.im.w * p.im.h;
-                if (e > c && (comp + p.chunk_len > lim.comp || px + pix > lim.pixels / 2 || tab + table_bytes(p) > lim.webp_chunk_tables)) break;
-                tab += table_bytes(p);
-                comp += p.chunk_len;
-                px += pix;
-                e++;
-            }
-            log.sizes.push_back((uint32_t)(e - c));
-            RPH_TRY(run_chunk(ctx, *P, parsed, ok.data() + c, e - c, threads, out));
-            c = e;
+            for (uint32_t i = a; i < b; i++) parsed[i] = rphw::Parsed();
+            a = b;
         }
-        for (uint32_t i = a; i < b; i++) parsed[i] = rphw::Parsed();
-        a = b;
-    }
-    return RPH_OK;
+        return RPH_OK;
+    });
 }
 
 }  // namespace
 
-void rph_webp_forget(rph_ctx *ctx)
-{
-    WebpPipe *P = static_cast<WebpPipe *>(ctx->webp);
-    if (!P) return;
-    (void)hipStreamSynchronize(P->s);
-    (void)hipStreamDestroy(P->s);
-    delete P;
-    ctx->webp = nullptr;
-}
+void rph_webp_forget(rph_ctx *ctx) { forget_file_pipe<WebpPipe>(ctx, RPH_FILE_WEBP); }
 
 extern "C" {
 
 int rph_webp_info(const uint8_t *data, size_t len, uint32_t *w, uint32_t *h, uint32_t *channels, uint32_t *bit_depth)
 {
-    return rph_guarded("rph_webp_info", [&]() -> int {
-        if (!data) return RPH_ERR_INVALID_ARG;
-        rphw::Parsed p;
-        const int rc = rphw::parse(data, len, p);
-        if (rc) return rc;
-        if (w) *w = p.im.w;
-        if (h) *h = p.im.h;
-        if (channels) *channels = p.im.out_ch;
-        if (bit_depth) *bit_depth = p.im.out_depth;
-        return RPH_OK;
-    });
+    return rph_guarded("rph_webp_info", [&] { return file_info<rphw::Parsed>(data, len, w, h, channels, bit_depth, rphw::parse, image_out_depth); });
 }
 
 int rph_webp_decode_host(const uint8_t *data, size_t len, void *pixels_out, size_t cap_bytes)
 {
-    return rph_guarded("rph_webp_decode_host", [&]() -> int {
-        if (!data || !pixels_out) return RPH_ERR_INVALID_ARG;
-        rphw::Parsed p;
-        std::vector<uint8_t> px;
-        const int rc = rphw::decode_host(data, len, p, px);
-        if (rc) return rc;
-        if (px.size() > cap_bytes) {
-            rph_set_error("rph_webp_decode_host: %zu bytes needed", px.size());
-            return RPH_ERR_CAPACITY;
-        }
-        memcpy(pixels_out, px.data(), px.size());
-        return RPH_OK;
-    });
+    return rph_guarded("rph_webp_decode_host",
+                       [&] { return file_decode_host<rphw::Parsed>("rph_webp_decode_host", data, len, pixels_out, cap_bytes, rphw::decode_host); });
 }
 
 int rph_webp_decode(rph_ctx *ctx, const uint8_t *data, size_t len, void *pixels_out, size_t cap_bytes)
 {
-    return rph_guarded("rph_webp_decode", [&]() -> int {
-        if (!ctx || !data || !pixels_out) return RPH_ERR_INVALID_ARG;
-        rphw::Parsed p;
-        int rc = rphw::parse(data, len, p);
-        if (rc) return rc;
-        const size_t need = (size_t)p.im.w * p.im.h * p.im.out_ch;
-        if (need > cap_bytes) {
-            rph_set_error("rph_webp_decode: %zu bytes needed", need);
-            return RPH_ERR_CAPACITY;
-        }
-        int32_t status = RPH_OK;
-        FileOutputs o;
-        o.want_pdq = false;
-        o.status = &status;
-        std::vector<uint8_t> staging(align_up(need, 64) + 64);
-        o.native = staging.data();
-        RPH_TRY(run(ctx, &data, &len, 1, 0, o));
-        if (status != RPH_OK) return status;
-        memcpy(pixels_out, staging.data(), need);
-        return RPH_OK;
+    return rph_guarded("rph_webp_decode", [&] {
+        return file_decode<rphw::Parsed>(
+            "rph_webp_decode", ctx, data, len, pixels_out, cap_bytes, rphw::parse,
+            [](const rphw::Image &im) { return (size_t)im.w * im.h * im.out_ch; }, [&](const FileOutputs &o) { return run(ctx, &data, &len, 1, 0, o); });
     });
 }
 
@@ -283,47 +217,14 @@ int rph_webp_pdq_hash_batch(rph_ctx *ctx, const uint8_t *const *data, const size
                             float *quality_out, float *coeffs_out, uint8_t *dihedral_out, uint8_t *valid_out, int32_t *status_out,
                             uint8_t *pixel_hash32_out)
 {
-    return rph_guarded("rph_webp_pdq_hash_batch", [&]() -> int {
-        if (!ctx || (n && (!data || !len || !hash32_out))) {
-            rph_set_error("rph_webp_pdq_hash_batch: null argument");
-            return RPH_ERR_INVALID_ARG;
-        }
-        if (n == 0) return RPH_OK;
-        std::vector<int32_t> st_local(status_out ? 0 : n);
-        std::vector<uint8_t> v_local(valid_out ? 0 : n);
-        FileOutputs o;
-        o.hash = hash32_out;
-        o.quality = quality_out;
-        o.coeffs = coeffs_out;
-        o.dihedral = dihedral_out;
-        o.valid = valid_out ? valid_out : v_local.data();
-        o.status = status_out ? status_out : st_local.data();
-        o.pixel = pixel_hash32_out;
-        memset(hash32_out, 0, (size_t)n * 32);
-        if (quality_out) memset(quality_out, 0, (size_t)n * 4);
-        if (coeffs_out) memset(coeffs_out, 0, (size_t)n * 1024);
-        if (dihedral_out) memset(dihedral_out, 0, (size_t)n * 256);
-        memset(o.valid, 0, n);
-        if (pixel_hash32_out) memset(pixel_hash32_out, 0, (size_t)n * 32);
-        return run(ctx, data, len, n, n_threads, o);
+    return rph_guarded("rph_webp_pdq_hash_batch", [&] {
+        return file_hash_batch("rph_webp_pdq_hash_batch", ctx, data, len, n, hash32_out, quality_out, coeffs_out, dihedral_out, valid_out, status_out, pixel_hash32_out,
+                               [&](const FileOutputs &o) { return run(ctx, data, len, n, n_threads, o); });
     });
 }
 
-int rph_webp_set_entropy(rph_ctx *ctx, int where)
-{
-    if (!ctx || where < RPH_WEBP_ENTROPY_HOST || where > RPH_WEBP_ENTROPY_AUTO) return RPH_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(ctx->webp_mu);
-    ctx->webp_entropy = where;
-    return RPH_OK;
-}
+int rph_webp_set_entropy(rph_ctx *ctx, int where) { return file_set_mode(ctx, RPH_FILE_WEBP, where, RPH_WEBP_ENTROPY_HOST, RPH_WEBP_ENTROPY_AUTO); }
 
-int rph_webp_release(rph_ctx *ctx)
-{
-    if (!ctx) return RPH_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(ctx->webp_mu);
-    (void)hipSetDevice(ctx->device);
-    rph_webp_forget(ctx);
-    return RPH_OK;
-}
+int rph_webp_release(rph_ctx *ctx) { return file_release(ctx, RPH_FILE_WEBP, rph_webp_forget); }
 
 }  // extern "C"

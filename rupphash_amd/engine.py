@@ -348,32 +348,67 @@ class Engine:
               "rph_jpeg_pdq_hash_batch")
         return out
 
+    # ---- the five file formats (include/rupphash.h, PNG / TIFF / WebP / GIF / BMP sections): one body behind every format's methods ----
+    @staticmethod
+    def _file_info(fmt, data):
+        w, h, c, d = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        check(getattr(_lib.load(), f"rph_{fmt}_info")(data, len(data), C.byref(w), C.byref(h), C.byref(c), C.byref(d)), f"rph_{fmt}_info")
+        return w.value, h.value, c.value, d.value
+
+    @staticmethod
+    def _file_array(fmt, data):
+        """the zeroed array of a file's native pixels: PNG and TIFF give (h, w) for one channel and uint16 at 16 bits, the others
+        always (h, w, channels) uint8 (GIF: always 4 channels)"""
+        w, h, c, d = Engine._file_info(fmt, data)
+        if fmt in ("png", "tiff"):
+            return np.zeros((h, w) if c == 1 else (h, w, c), np.uint16 if d == 16 else np.uint8)
+        return np.zeros((h, w, c), np.uint8)
+
+    @staticmethod
+    def _file_decode_host(fmt, data):
+        out = Engine._file_array(fmt, data)
+        check(getattr(_lib.load(), f"rph_{fmt}_decode_host")(data, len(data), _ptr(out), out.nbytes), f"rph_{fmt}_decode_host")
+        return out
+
+    def _file_decode(self, fmt, data):
+        out = self._file_array(fmt, data)
+        check(getattr(self.L, f"rph_{fmt}_decode")(self.ctx, data, len(data), _ptr(out), out.nbytes), f"rph_{fmt}_decode")
+        return out
+
+    def _file_release(self, fmt):
+        check(getattr(self.L, f"rph_{fmt}_release")(self.ctx), f"rph_{fmt}_release")
+
+    def _file_hash_batch(self, fmt, files, threads, want_quality, want_coeffs, want_dihedral, want_pixel_hash):
+        arr, lens, n = files if isinstance(files, tuple) else self.jpeg_file_list(files)
+        out = {
+            "hash": np.zeros((n, 32), np.uint8),
+            "quality": np.zeros(n, np.float32) if want_quality else None,
+            "coeffs": np.zeros((n, 256), np.float32) if want_coeffs else None,
+            "dihedral": np.zeros((n, 8, 32), np.uint8) if want_dihedral else None,
+            "valid": np.zeros(n, np.uint8),
+            "status": np.zeros(n, np.int32),
+        }
+        if want_pixel_hash:
+            out["pixel_hash"] = np.zeros((n, 32), np.uint8)
+        check(getattr(self.L, f"rph_{fmt}_pdq_hash_batch")(self.ctx, arr, lens, n, int(threads), _ptr(out["hash"]), _ptr(out["quality"]), _ptr(out["coeffs"]),
+                                                           _ptr(out["dihedral"]), _ptr(out["valid"]), _ptr(out["status"]), _ptr(out.get("pixel_hash"))),
+              f"rph_{fmt}_pdq_hash_batch")
+        return out
+
     # ---- PNG (include/rupphash.h, PNG section) ----
     @staticmethod
     def png_info(data):
         """(w, h, channels, bit_depth) of the native pixels (host code), or raises RphError by the damaged-file rule."""
-        w, h, c, d = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
-        check(_lib.load().rph_png_info(data, len(data), C.byref(w), C.byref(h), C.byref(c), C.byref(d)), "rph_png_info")
-        return w.value, h.value, c.value, d.value
-
-    @staticmethod
-    def _png_array(data):
-        w, h, c, d = Engine.png_info(data)
-        dt = np.uint16 if d == 16 else np.uint8
-        return np.zeros((h, w) if c == 1 else (h, w, c), dt)
+        return Engine._file_info("png", data)
 
     @staticmethod
     def png_decode_host(data):
         """The whole decoder on the CPU: (h, w) for Luma, else (h, w, channels); uint8, or uint16 for 16-bit files."""
-        out = Engine._png_array(data)
-        check(_lib.load().rph_png_decode_host(data, len(data), _ptr(out), out.nbytes), "rph_png_decode_host")
-        return out
+        return Engine._file_decode_host("png", data)
 
     def png_decode(self, data):
         """load_image_fast for one PNG byte string, decoded on the device: the same array as png_decode_host."""
-        out = self._png_array(data)
-        check(self.L.rph_png_decode(self.ctx, data, len(data), _ptr(out), out.nbytes), "rph_png_decode")
-        return out
+        return self._file_decode("png", data)
 
     def png_set_inflate(self, where):
         """0 = host threads inflate, 1 = the device (one wave per stream), 2 = automatic (default)"""
@@ -381,54 +416,28 @@ class Engine:
 
     def png_release(self):
         """give the PNG path's cached staging / device buffers back"""
-        check(self.L.rph_png_release(self.ctx), "rph_png_release")
+        self._file_release("png")
 
     def png_pdq_hash_batch(self, files, threads=0, want_quality=True, want_coeffs=False, want_dihedral=False, want_pixel_hash=False):
         """files: list of PNG byte strings (any mix), or the tuple jpeg_file_list() made of one.  Returns dict(hash, quality, coeffs,
         dihedral, valid, status[, pixel_hash]) as jpeg_pdq_hash_batch: status[i] != 0 for a file the rule refuses (zero outputs),
         valid[i] = 0 with status 0 for an image below 5 px (which still has its pixel hash)."""
-        arr, lens, n = files if isinstance(files, tuple) else self.jpeg_file_list(files)
-        out = {
-            "hash": np.zeros((n, 32), np.uint8),
-            "quality": np.zeros(n, np.float32) if want_quality else None,
-            "coeffs": np.zeros((n, 256), np.float32) if want_coeffs else None,
-            "dihedral": np.zeros((n, 8, 32), np.uint8) if want_dihedral else None,
-            "valid": np.zeros(n, np.uint8),
-            "status": np.zeros(n, np.int32),
-        }
-        if want_pixel_hash:
-            out["pixel_hash"] = np.zeros((n, 32), np.uint8)
-        check(self.L.rph_png_pdq_hash_batch(self.ctx, arr, lens, n, int(threads), _ptr(out["hash"]), _ptr(out["quality"]), _ptr(out["coeffs"]),
-                                            _ptr(out["dihedral"]), _ptr(out["valid"]), _ptr(out["status"]), _ptr(out.get("pixel_hash"))),
-              "rph_png_pdq_hash_batch")
-        return out
+        return self._file_hash_batch("png", files, threads, want_quality, want_coeffs, want_dihedral, want_pixel_hash)
 
     # ---- TIFF (include/rupphash.h, TIFF section) ----
     @staticmethod
     def tiff_info(data):
         """(w, h, channels, bit_depth) of the native pixels (host code), or raises RphError by the damaged-file rule."""
-        w, h, c, d = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
-        check(_lib.load().rph_tiff_info(data, len(data), C.byref(w), C.byref(h), C.byref(c), C.byref(d)), "rph_tiff_info")
-        return w.value, h.value, c.value, d.value
-
-    @staticmethod
-    def _tiff_array(data):
-        w, h, c, d = Engine.tiff_info(data)
-        dt = np.uint16 if d == 16 else np.uint8
-        return np.zeros((h, w) if c == 1 else (h, w, c), dt)
+        return Engine._file_info("tiff", data)
 
     @staticmethod
     def tiff_decode_host(data):
         """The whole decoder on the CPU: (h, w) for Luma, else (h, w, channels); uint8, or uint16 for 16-bit files."""
-        out = Engine._tiff_array(data)
-        check(_lib.load().rph_tiff_decode_host(data, len(data), _ptr(out), out.nbytes), "rph_tiff_decode_host")
-        return out
+        return Engine._file_decode_host("tiff", data)
 
     def tiff_decode(self, data):
         """load_image_fast for one TIFF byte string, decoded on the device: the same array as tiff_decode_host."""
-        out = self._tiff_array(data)
-        check(self.L.rph_tiff_decode(self.ctx, data, len(data), _ptr(out), out.nbytes), "rph_tiff_decode")
-        return out
+        return self._file_decode("tiff", data)
 
     def tiff_set_decompress(self, where):
         """0 = host threads decompress, 1 = the device (one wave per strip or tile), 2 = automatic (default)"""
@@ -436,53 +445,28 @@ class Engine:
 
     def tiff_release(self):
         """give the TIFF path's cached staging / device buffers back"""
-        check(self.L.rph_tiff_release(self.ctx), "rph_tiff_release")
+        self._file_release("tiff")
 
     def tiff_pdq_hash_batch(self, files, threads=0, want_quality=True, want_coeffs=False, want_dihedral=False, want_pixel_hash=False):
         """files: list of TIFF byte strings (any mix), or the tuple jpeg_file_list() made of one.  Returns dict(hash, quality, coeffs,
         dihedral, valid, status[, pixel_hash]) as jpeg_pdq_hash_batch: status[i] != 0 for a file the rule refuses (zero outputs),
         valid[i] = 0 with status 0 for an image below 5 px (which still has its pixel hash)."""
-        arr, lens, n = files if isinstance(files, tuple) else self.jpeg_file_list(files)
-        out = {
-            "hash": np.zeros((n, 32), np.uint8),
-            "quality": np.zeros(n, np.float32) if want_quality else None,
-            "coeffs": np.zeros((n, 256), np.float32) if want_coeffs else None,
-            "dihedral": np.zeros((n, 8, 32), np.uint8) if want_dihedral else None,
-            "valid": np.zeros(n, np.uint8),
-            "status": np.zeros(n, np.int32),
-        }
-        if want_pixel_hash:
-            out["pixel_hash"] = np.zeros((n, 32), np.uint8)
-        check(self.L.rph_tiff_pdq_hash_batch(self.ctx, arr, lens, n, int(threads), _ptr(out["hash"]), _ptr(out["quality"]), _ptr(out["coeffs"]),
-                                            _ptr(out["dihedral"]), _ptr(out["valid"]), _ptr(out["status"]), _ptr(out.get("pixel_hash"))),
-              "rph_tiff_pdq_hash_batch")
-        return out
+        return self._file_hash_batch("tiff", files, threads, want_quality, want_coeffs, want_dihedral, want_pixel_hash)
 
     # ---- WebP (include/rupphash.h, WebP section) ----
     @staticmethod
     def webp_info(data):
         """(w, h, channels, bit_depth) of the native pixels (host code), or raises RphError by the damaged-file rule."""
-        w, h, c, d = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
-        check(_lib.load().rph_webp_info(data, len(data), C.byref(w), C.byref(h), C.byref(c), C.byref(d)), "rph_webp_info")
-        return w.value, h.value, c.value, d.value
-
-    @staticmethod
-    def _webp_array(data):
-        w, h, c, _ = Engine.webp_info(data)
-        return np.zeros((h, w, c), np.uint8)
+        return Engine._file_info("webp", data)
 
     @staticmethod
     def webp_decode_host(data):
         """The whole decoder on the CPU: (h, w, 3) Rgb8 or (h, w, 4) Rgba8, uint8."""
-        out = Engine._webp_array(data)
-        check(_lib.load().rph_webp_decode_host(data, len(data), _ptr(out), out.nbytes), "rph_webp_decode_host")
-        return out
+        return Engine._file_decode_host("webp", data)
 
     def webp_decode(self, data):
         """load_image_fast for one WebP byte string, decoded on the device: the same array as webp_decode_host."""
-        out = self._webp_array(data)
-        check(self.L.rph_webp_decode(self.ctx, data, len(data), _ptr(out), out.nbytes), "rph_webp_decode")
-        return out
+        return self._file_decode("webp", data)
 
     def webp_set_entropy(self, where):
         """0 = host threads decode the main ARGB stream, 1 = the device (one wave per stream), 2 = automatic (default)"""
@@ -490,53 +474,28 @@ class Engine:
 
     def webp_release(self):
         """give the WebP path's cached staging / device buffers back"""
-        check(self.L.rph_webp_release(self.ctx), "rph_webp_release")
+        self._file_release("webp")
 
     def webp_pdq_hash_batch(self, files, threads=0, want_quality=True, want_coeffs=False, want_dihedral=False, want_pixel_hash=False):
         """files: list of lossless WebP byte strings (any mix), or the tuple jpeg_file_list() made of one.  Returns dict(hash, quality, coeffs,
         dihedral, valid, status[, pixel_hash]) as jpeg_pdq_hash_batch: status[i] != 0 for a file the rule refuses (zero outputs),
         valid[i] = 0 with status 0 for an image below 5 px (which still has its pixel hash)."""
-        arr, lens, n = files if isinstance(files, tuple) else self.jpeg_file_list(files)
-        out = {
-            "hash": np.zeros((n, 32), np.uint8),
-            "quality": np.zeros(n, np.float32) if want_quality else None,
-            "coeffs": np.zeros((n, 256), np.float32) if want_coeffs else None,
-            "dihedral": np.zeros((n, 8, 32), np.uint8) if want_dihedral else None,
-            "valid": np.zeros(n, np.uint8),
-            "status": np.zeros(n, np.int32),
-        }
-        if want_pixel_hash:
-            out["pixel_hash"] = np.zeros((n, 32), np.uint8)
-        check(self.L.rph_webp_pdq_hash_batch(self.ctx, arr, lens, n, int(threads), _ptr(out["hash"]), _ptr(out["quality"]), _ptr(out["coeffs"]),
-                                            _ptr(out["dihedral"]), _ptr(out["valid"]), _ptr(out["status"]), _ptr(out.get("pixel_hash"))),
-              "rph_webp_pdq_hash_batch")
-        return out
+        return self._file_hash_batch("webp", files, threads, want_quality, want_coeffs, want_dihedral, want_pixel_hash)
 
     # ---- GIF (include/rupphash.h, GIF section) ----
     @staticmethod
     def gif_info(data):
         """(w, h, channels, bit_depth) of the native pixels (host code), or raises RphError by the damaged-file rule."""
-        w, h, c, d = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
-        check(_lib.load().rph_gif_info(data, len(data), C.byref(w), C.byref(h), C.byref(c), C.byref(d)), "rph_gif_info")
-        return w.value, h.value, c.value, d.value
-
-    @staticmethod
-    def _gif_array(data):
-        w, h, c, _ = Engine.gif_info(data)
-        return np.zeros((h, w, c), np.uint8)  # (always 4 channels)
+        return Engine._file_info("gif", data)
 
     @staticmethod
     def gif_decode_host(data):
         """The whole decoder on the CPU: (h, w, 4) Rgba8 at the logical screen's size, uint8."""
-        out = Engine._gif_array(data)
-        check(_lib.load().rph_gif_decode_host(data, len(data), _ptr(out), out.nbytes), "rph_gif_decode_host")
-        return out
+        return Engine._file_decode_host("gif", data)
 
     def gif_decode(self, data):
         """The first frame of one GIF byte string on its screen, decoded on the device: the same array as gif_decode_host."""
-        out = self._gif_array(data)
-        check(self.L.rph_gif_decode(self.ctx, data, len(data), _ptr(out), out.nbytes), "rph_gif_decode")
-        return out
+        return self._file_decode("gif", data)
 
     def gif_set_decompress(self, where):
         """0 = host threads decode the LZW streams, 1 = the device (one wave per file), 2 = automatic (default)"""
@@ -544,77 +503,38 @@ class Engine:
 
     def gif_release(self):
         """give the GIF path's cached staging / device buffers back"""
-        check(self.L.rph_gif_release(self.ctx), "rph_gif_release")
+        self._file_release("gif")
 
     def gif_pdq_hash_batch(self, files, threads=0, want_quality=True, want_coeffs=False, want_dihedral=False, want_pixel_hash=False):
         """files: list of GIF byte strings (any mix), or the tuple jpeg_file_list() made of one.  Returns dict(hash, quality, coeffs,
         dihedral, valid, status[, pixel_hash]) as jpeg_pdq_hash_batch: status[i] != 0 for a file the rule refuses (zero outputs),
         valid[i] = 0 with status 0 for an image below 5 px (which still has its pixel hash)."""
-        arr, lens, n = files if isinstance(files, tuple) else self.jpeg_file_list(files)
-        out = {
-            "hash": np.zeros((n, 32), np.uint8),
-            "quality": np.zeros(n, np.float32) if want_quality else None,
-            "coeffs": np.zeros((n, 256), np.float32) if want_coeffs else None,
-            "dihedral": np.zeros((n, 8, 32), np.uint8) if want_dihedral else None,
-            "valid": np.zeros(n, np.uint8),
-            "status": np.zeros(n, np.int32),
-        }
-        if want_pixel_hash:
-            out["pixel_hash"] = np.zeros((n, 32), np.uint8)
-        check(self.L.rph_gif_pdq_hash_batch(self.ctx, arr, lens, n, int(threads), _ptr(out["hash"]), _ptr(out["quality"]), _ptr(out["coeffs"]),
-                                            _ptr(out["dihedral"]), _ptr(out["valid"]), _ptr(out["status"]), _ptr(out.get("pixel_hash"))),
-              "rph_gif_pdq_hash_batch")
-        return out
+        return self._file_hash_batch("gif", files, threads, want_quality, want_coeffs, want_dihedral, want_pixel_hash)
 
     # ---- BMP (include/rupphash.h, BMP section) ----
     @staticmethod
     def bmp_info(data):
         """(w, h, channels, bit_depth) of the native pixels (host code), or raises RphError by the damaged-file rule."""
-        w, h, c, d = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
-        check(_lib.load().rph_bmp_info(data, len(data), C.byref(w), C.byref(h), C.byref(c), C.byref(d)), "rph_bmp_info")
-        return w.value, h.value, c.value, d.value
-
-    @staticmethod
-    def _bmp_array(data):
-        w, h, c, _ = Engine.bmp_info(data)
-        return np.zeros((h, w, c), np.uint8)
+        return Engine._file_info("bmp", data)
 
     @staticmethod
     def bmp_decode_host(data):
         """The whole decoder on the CPU: (h, w, 3) Rgb8, or (h, w, 4) Rgba8 for a file with an alpha mask; uint8, top-down."""
-        out = Engine._bmp_array(data)
-        check(_lib.load().rph_bmp_decode_host(data, len(data), _ptr(out), out.nbytes), "rph_bmp_decode_host")
-        return out
+        return Engine._file_decode_host("bmp", data)
 
     def bmp_decode(self, data):
         """One BMP byte string decoded on the device: the same array as bmp_decode_host."""
-        out = self._bmp_array(data)
-        check(self.L.rph_bmp_decode(self.ctx, data, len(data), _ptr(out), out.nbytes), "rph_bmp_decode")
-        return out
+        return self._file_decode("bmp", data)
 
     def bmp_release(self):
         """give the BMP path's cached staging / device buffers back"""
-        check(self.L.rph_bmp_release(self.ctx), "rph_bmp_release")
+        self._file_release("bmp")
 
     def bmp_pdq_hash_batch(self, files, threads=0, want_quality=True, want_coeffs=False, want_dihedral=False, want_pixel_hash=False):
         """files: list of BMP byte strings (any mix of sizes and depths), or the tuple jpeg_file_list() made of one.  Returns dict(hash,
         quality, coeffs, dihedral, valid, status[, pixel_hash]) as jpeg_pdq_hash_batch: status[i] != 0 for a file the rule refuses (zero
         outputs), valid[i] = 0 with status 0 for an image below 5 px (which still has its pixel hash)."""
-        arr, lens, n = files if isinstance(files, tuple) else self.jpeg_file_list(files)
-        out = {
-            "hash": np.zeros((n, 32), np.uint8),
-            "quality": np.zeros(n, np.float32) if want_quality else None,
-            "coeffs": np.zeros((n, 256), np.float32) if want_coeffs else None,
-            "dihedral": np.zeros((n, 8, 32), np.uint8) if want_dihedral else None,
-            "valid": np.zeros(n, np.uint8),
-            "status": np.zeros(n, np.int32),
-        }
-        if want_pixel_hash:
-            out["pixel_hash"] = np.zeros((n, 32), np.uint8)
-        check(self.L.rph_bmp_pdq_hash_batch(self.ctx, arr, lens, n, int(threads), _ptr(out["hash"]), _ptr(out["quality"]), _ptr(out["coeffs"]),
-                                            _ptr(out["dihedral"]), _ptr(out["valid"]), _ptr(out["status"]), _ptr(out.get("pixel_hash"))),
-              "rph_bmp_pdq_hash_batch")
-        return out
+        return self._file_hash_batch("bmp", files, threads, want_quality, want_coeffs, want_dihedral, want_pixel_hash)
 
     # ---- BLAKE3 identity hashes ----
     @staticmethod
