@@ -157,7 +157,8 @@ def edge_indices(n):
 def planted():
     """Uniform random hashes with planted pairs at distances 0 .. 46.  No unplanted pair of uniform 256-bit hashes lies within 46 bits
     (46 is more than 10 sigma below the mean of 128: over 8.6e9 pairs the expected count is far below 1e-10), so the edge set at
-    threshold 40 is exactly the planted pairs of distance <= 40.  Every column is derived from one row; rows are unrelated."""
+    threshold 40 is exactly the planted pairs of distance <= 40.  Every column is derived from one row; rows are unrelated.
+    Returns (a, b, the planted pairs within 40, those at 41 .. 46)."""
     n_a, n_b = 65_536 + 5, 131_072 + 37
     rng = np.random.default_rng(4040)
     a = rng.integers(0, 256, (n_a, 32), dtype=np.uint8)
@@ -172,20 +173,25 @@ def planted():
         (want if d <= 40 else absent).append((r, c, d))
     assert len(cols) >= 2 * 47 and len(cols) >= len(rows)  # every distance twice, every planted row used
     assert {d for _, _, d in want} == set(range(41)) and {d for _, _, d in absent} == set(range(41, 47))
-    return a, b, sorted(want)
+    return a, b, sorted(want), sorted(absent)
 
 
 def test_planted_pairs_across_tiles_chunks_and_segments(eng, planted):
-    a, b, want = planted
+    """At thresholds 50 and 60 the edge set is every planted pair: the binomial tail puts the expected number of unplanted pairs among
+    the 8.6e9 at 4.9e-14 (threshold 50) and 2.2e-8 (threshold 60); at 75 it would be 0.12.  The prefix widths are 4 at threshold 40,
+    5 (int8 MFMA, VALU) and 6 (fp4 MFMA) at 50, 6 at 60: the wider prefixes under segments of two column tiles and more."""
+    a, b, want, absent = planted
     # the launcher's own rule: this rectangle is swept in segments of at least two column tiles by the MFMA kernels
     for k in (2, 1):
         assert eng.hamming_cross_layout(len(a), len(b), kernel=k)[1] >= 2
-    got = under_every_kernel(eng, lambda: eng.hamming_cross_pairs(a, b, 40))
-    assert ijd(got) == want
+    assert [[eng.L.rph_hamming_prefix_dwords(thr, k) for k in KERNELS] for thr in (40, 50, 60)] == [[4, 4, 4], [6, 5, 5], [6, 6, 6]]
+    for thr in (40, 50, 60):
+        got = under_every_kernel(eng, lambda: eng.hamming_cross_pairs(a, b, thr))
+        assert ijd(got) == (want if thr == 40 else sorted(want + absent)), thr
 
 
 def test_planted_pairs_in_three_parts(eng, planted):
-    a, b, want = planted
+    a, b, want, _ = planted
     parts = [under_every_kernel(eng, lambda p=p: eng.hamming_cross_pairs(a, b, 40, part=p, nparts=3)) for p in range(3)]
     assert all(len(p) > 0 for p in parts)
     union = sorted(x for p in parts for x in ijd(p))
