@@ -875,117 +875,92 @@ static int prepare_sorted(rph_ctx *ctx, const uint8_t *d_hashes, uint64_t n, int
     return RPH_OK;
 }
 
-int rph_launch_hamming_sweep(rph_ctx *ctx, const uint8_t *d_rows, uint32_t n_variants, const uint8_t *d_cols, const uint8_t *d_low_conf,
-                             const uint8_t *d_has_features, uint64_t n, uint32_t threshold, uint32_t part, uint32_t nparts, rph_edge *d_edges,
-                             uint64_t cap, unsigned long long *d_count, hipStream_t stream, int use_mfma)
+namespace {
+// ---- what every form of a sweep shares on the host ----
+// The fields of SweepArgs / Sweep64Args that do not depend on the form.  The threshold is clamped to the width of the hash; mih_tol is
+// find_groups' chunk_tolerance = max_dist / NUM_CHUNKS (hamminghash.rs:193), NUM_CHUNKS = 16 for 256-bit hashes and 8 for u64: 1 or 0.
+template <class Args>
+void fill_shared(Args &a, const rph_sweep &q, uint64_t n_rows)
 {
-    if (nparts == 0 || part >= nparts || (n_variants != 1 && n_variants != 8) || n > 0xFFFFFFFFull) {
-        rph_set_error("hamming sweep: bad arguments (n=%llu variants=%u part=%u/%u)", (unsigned long long)n, n_variants,
-                      part, nparts);
-        return RPH_ERR_INVALID_ARG;
-    }
-    if (n < 2) return RPH_OK;
-    SweepArgs a;
-    a.rows = reinterpret_cast<const uint32_t *>(d_rows);
-    a.cols = reinterpret_cast<const uint32_t *>(d_cols);
-    a.low_conf = d_low_conf;
-    a.has_features = d_has_features;
-    a.n = n;
-    a.n_variants = n_variants;
-    a.threshold = threshold > 256 ? 256 : threshold;
-    a.mih_tol = (threshold / 16u) >= 1 ? 1 : 0;
-    a.part = part;
-    a.nparts = nparts;
-    a.n_tiles = (uint32_t)((n + T_FILES - 1) / T_FILES);
-    a.n_tile_pairs = (unsigned long long)a.n_tiles * (a.n_tiles + 1ull) / 2ull;
-    a.seg_tiles = 1;
-    if (use_mfma >= 1) {
-        // MFMA kernels: a block sweeps a row tile against a segment of up to 8 column tiles; shorter segments while that
-        // would leave this rank fewer than ~8 blocks per resident block slot (2 per CU)
-        const unsigned long long want_blocks = 8ull * 512ull * nparts;
-        unsigned long long S = a.n_tile_pairs / want_blocks;
-        a.seg_tiles = (uint32_t)(S < 1 ? 1 : (S > 8 ? 8 : S));
-        a.n_tile_pairs = seg_G(a.n_tiles, a.seg_tiles);  // number of segment blocks
-    }
-    a.edges = d_edges;
-    a.cap = cap;
-    a.count = d_count;
-    a.perm = nullptr;
-    a.pcs = nullptr;
-    const unsigned long long mine = (a.n_tile_pairs > part) ? (a.n_tile_pairs - part + nparts - 1) / nparts : 0;
-    if (mine == 0) return RPH_OK;
-    const int pw = rph_hamming_prefix_dwords(a.threshold, use_mfma);
-    // plain all-pairs sweeps (rows are the columns, no per-file rules) run on popcount-sorted {0,1} operands
-    const bool zero_one = (use_mfma == 4 || (use_mfma == 2 && n >= ZO_MIN_N)) && ctx && n_variants == 1 && d_rows == d_cols && !d_low_conf && !d_has_features;
-    std::unique_lock<std::mutex> scratch_lock;
-    if (zero_one) {
-        scratch_lock = std::unique_lock<std::mutex>(ctx->mu);
-        int rc = prepare_sorted(ctx, d_cols, n, pw, stream, a);
-        if (rc != RPH_OK) return rc;
-    }
-    for (unsigned long long b0 = 0; b0 < mine; b0 += MAX_GRID) {  // one launch carries at most MAX_GRID tile pairs
+    const uint32_t bits = q.bits64 ? 64 : 256, chunks = q.bits64 ? 8 : 16;
+    a.n = n_rows;
+    a.threshold = q.threshold > bits ? bits : q.threshold;
+    a.mih_tol = (q.threshold / chunks) >= 1 ? 1 : 0;
+    a.part = q.part;
+    a.nparts = q.nparts;
+    a.n_tiles = (uint32_t)((n_rows + T_FILES - 1) / T_FILES);
+    a.edges = q.edges;
+    a.cap = q.cap;
+    a.count = q.count;
+}
+
+// Segment length of the MFMA kernels: a block sweeps a row tile against a segment of up to 8 column tiles; shorter segments while that
+// would leave a part fewer than ~8 blocks per resident block slot.  Slots: 2 blocks per CU for the 256-bit kernels, 3 per CU for the
+// 64-bit one.  `tile_pairs`: the triangle's tile pairs for a square sweep, the rectangle's for a cross sweep.
+constexpr unsigned long long SEG_WANT_BLOCKS_256 = 8ull * 512ull, SEG_WANT_BLOCKS_64 = 8ull * 768ull;
+uint32_t seg_length(unsigned long long tile_pairs, unsigned long long want_blocks, uint32_t nparts)
+{
+    const unsigned long long S = tile_pairs / (want_blocks * nparts);
+    return (uint32_t)(S < 1 ? 1 : (S > 8 ? 8 : S));
+}
+
+// This part's share of the a.n_tile_pairs blocks: every nparts-th from `part` on (none is no error)
+template <class Args>
+unsigned long long part_share(const Args &a)
+{
+    return (a.n_tile_pairs > a.part) ? (a.n_tile_pairs - a.part + a.nparts - 1) / a.nparts : 0;
+}
+// ... in launches of at most MAX_GRID blocks: launch(grid) runs with a.block0 set to the first block slot of the launch
+template <class Args, class F>
+int launch_share(Args &a, F &&launch)
+{
+    const unsigned long long mine = part_share(a);
+    for (unsigned long long b0 = 0; b0 < mine; b0 += MAX_GRID) {
         a.block0 = b0;
-        const dim3 grid((unsigned)((mine - b0) < MAX_GRID ? (mine - b0) : MAX_GRID)), block(BLOCK), mblock(MF_BLOCK);
-        if (zero_one) {
-            if (pw == 4)
-                hipLaunchKernelGGL((hamming_mfma_kernel<FmtFp4ZO, 4>), grid, mblock, 0, stream, a);
-            else if (pw == 6)
-                hipLaunchKernelGGL((hamming_mfma_kernel<FmtFp4ZO, 6>), grid, mblock, 0, stream, a);
-            else
-                hipLaunchKernelGGL((hamming_mfma_kernel<FmtFp4ZO, 8>), grid, mblock, 0, stream, a);
-        } else if (use_mfma >= 2) {
-            if (pw == 4)
-                hipLaunchKernelGGL((hamming_mfma_kernel<FmtFp4, 4>), grid, mblock, 0, stream, a);
-            else if (pw == 6)
-                hipLaunchKernelGGL((hamming_mfma_kernel<FmtFp4, 6>), grid, mblock, 0, stream, a);
-            else
-                hipLaunchKernelGGL((hamming_mfma_kernel<FmtFp4, 8>), grid, mblock, 0, stream, a);
-        } else if (use_mfma) {
-            if (pw == 4)
-                hipLaunchKernelGGL((hamming_mfma_kernel<FmtI8, 4>), grid, mblock, 0, stream, a);
-            else if (pw == 5)
-                hipLaunchKernelGGL((hamming_mfma_kernel<FmtI8, 5>), grid, mblock, 0, stream, a);
-            else if (pw == 6)
-                hipLaunchKernelGGL((hamming_mfma_kernel<FmtI8, 6>), grid, mblock, 0, stream, a);
-            else if (pw == 7)
-                hipLaunchKernelGGL((hamming_mfma_kernel<FmtI8, 7>), grid, mblock, 0, stream, a);
-            else
-                hipLaunchKernelGGL((hamming_mfma_kernel<FmtI8, 8>), grid, mblock, 0, stream, a);
-        } else {
-            if (pw == 4)
-                hipLaunchKernelGGL(hamming_sweep_kernel<4>, grid, block, 0, stream, a);
-            else if (pw == 5)
-                hipLaunchKernelGGL(hamming_sweep_kernel<5>, grid, block, 0, stream, a);
-            else if (pw == 6)
-                hipLaunchKernelGGL(hamming_sweep_kernel<6>, grid, block, 0, stream, a);
-            else if (pw == 7)
-                hipLaunchKernelGGL(hamming_sweep_kernel<7>, grid, block, 0, stream, a);
-            else
-                hipLaunchKernelGGL(hamming_sweep_kernel<8>, grid, block, 0, stream, a);
-        }
+        RPH_TRY(launch(dim3((unsigned)((mine - b0) < MAX_GRID ? (mine - b0) : MAX_GRID))));
         RPH_HIP_CHECK(hipGetLastError());
     }
-    if (zero_one) RPH_TRY(ctx->sweep_scratch.publish(stream));
     return RPH_OK;
 }
+
+// f(std::integral_constant<int, W>) for the W of the list that equals pw (the last one for a pw that is none of them)
+template <int W, int... Rest, class F>
+void with_width(int pw, F &&f)
+{
+    if constexpr (sizeof...(Rest) == 0)
+        f(std::integral_constant<int, W>{});
+    else if (pw == W)
+        f(std::integral_constant<int, W>{});
+    else
+        with_width<Rest...>(pw, f);
+}
+
+// the prefix widths a family of kernels is built for: every one for the VALU kernel and the int8 format, the even ones for fp4
+template <class F, bool CROSS, int... W>
+void launch_mfma(int pw, dim3 grid, hipStream_t stream, const SweepArgs &a)
+{
+    with_width<W...>(pw, [&](auto w) { hipLaunchKernelGGL((hamming_mfma_kernel<F, decltype(w)::value, false, CROSS>), grid, dim3(MF_BLOCK), 0, stream, a); });
+}
+template <bool CROSS>
+void launch_valu(int pw, dim3 grid, hipStream_t stream, const SweepArgs &a)
+{
+    with_width<4, 5, 6, 7, 8>(pw, [&](auto w) { hipLaunchKernelGGL((hamming_sweep_kernel<decltype(w)::value, CROSS>), grid, dim3(BLOCK), 0, stream, a); });
+}
+}  // namespace
 
 // Block layout of a cross sweep (exported for the tests: Engine.hamming_cross_layout).  Set A becomes the row side unless it has one
 // variant per file and is the smaller set: rows are what a block holds in registers, a full tile of 1024 of them shared by its four
 // waves, while columns stream through LDS in chunks of 128 or 256 and a block stops after the last live chunk.  A small set therefore
 // costs little as columns (one chunk, all four waves busy on it) and much as rows (a pass over every column of the segment for a few
 // live rows, three of the four waves idle), so the larger set goes to the rows.  Variants are laid out per row and always stay there.
-// Segments: as many column tiles per block (up to 8) as leave ~8 blocks per resident block slot, from the rectangle's tile count.
+// Segments: seg_length of the rectangle's tile count.
 extern "C" void rph_debug_hamming_cross_layout(uint64_t n_a, uint32_t n_variants, uint64_t n_b, uint32_t nparts, int kernel, uint32_t *swap_out,
                                          uint32_t *seg_tiles_out, uint32_t *n_col_segs_out, uint64_t *n_blocks_out)
 {
     const bool swap = n_variants == 1 && n_a < n_b;
     const uint64_t n_rows = swap ? n_b : n_a, n_cols = swap ? n_a : n_b;
     const uint64_t rt = (n_rows + T_FILES - 1) / T_FILES, ct = (n_cols + T_FILES - 1) / T_FILES;
-    uint64_t S = 1;
-    if (kernel >= 1) {
-        S = rt * ct / (8ull * 512ull * (nparts ? nparts : 1));
-        S = S < 1 ? 1 : (S > 8 ? 8 : S);
-    }
+    const uint64_t S = kernel >= 1 ? seg_length(rt * ct, SEG_WANT_BLOCKS_256, nparts ? nparts : 1) : 1;
     const uint64_t segs = (ct + S - 1) / S;
     if (swap_out) *swap_out = swap ? 1u : 0u;
     if (seg_tiles_out) *seg_tiles_out = (uint32_t)S;
@@ -993,143 +968,90 @@ extern "C" void rph_debug_hamming_cross_layout(uint64_t n_a, uint32_t n_variants
     if (n_blocks_out) *n_blocks_out = rt * segs;
 }
 
-template <class F>
-static void launch_cross_mfma(int pw, dim3 grid, hipStream_t stream, const SweepArgs &a)
+int rph_hamming_sweep_check(const rph_sweep &q)
 {
-    const dim3 mblock(MF_BLOCK);
-    if (pw == 4)
-        hipLaunchKernelGGL((hamming_mfma_kernel<F, 4, false, true>), grid, mblock, 0, stream, a);
-    else if (pw == 6)
-        hipLaunchKernelGGL((hamming_mfma_kernel<F, 6, false, true>), grid, mblock, 0, stream, a);
-    else if (pw == 8)
-        hipLaunchKernelGGL((hamming_mfma_kernel<F, 8, false, true>), grid, mblock, 0, stream, a);
-    else if constexpr (F::nfrag(5) == 5) {  // odd widths: the int8 format only
-        if (pw == 5)
-            hipLaunchKernelGGL((hamming_mfma_kernel<F, 5, false, true>), grid, mblock, 0, stream, a);
-        else
-            hipLaunchKernelGGL((hamming_mfma_kernel<F, 7, false, true>), grid, mblock, 0, stream, a);
-    }
-}
-
-// Cross form of rph_launch_hamming_sweep: every pair (a, b) of two different sets, a's variants against b's hash; e.i indexes A and
-// e.j indexes B.  Kernel settings 2, 3 and 4 all run the +-1 fp4 form here (the popcount-sorted {0,1} form sorts ONE array and
-// needs rows == columns).
-int rph_launch_hamming_cross_sweep(rph_ctx *ctx, const uint8_t *d_a, uint32_t n_variants, const uint8_t *d_low_conf_a, const uint8_t *d_has_features_a,
-                                   uint64_t n_a, const uint8_t *d_b, const uint8_t *d_low_conf_b, uint64_t n_b, uint32_t threshold, uint32_t part,
-                                   uint32_t nparts, rph_edge *d_edges, uint64_t cap, unsigned long long *d_count, hipStream_t stream, int use_mfma)
-{
-    (void)ctx;
-    if (nparts == 0 || part >= nparts || (n_variants != 1 && n_variants != 8) || n_a > 0xFFFFFFFFull || n_b > 0xFFFFFFFFull) {
-        rph_set_error("hamming cross sweep: bad arguments (n_a=%llu n_b=%llu variants=%u part=%u/%u)", (unsigned long long)n_a,
-                      (unsigned long long)n_b, n_variants, part, nparts);
+    const uint64_t n_cols = q.cross ? q.n_cols : q.n;
+    if (q.nparts == 0 || q.part >= q.nparts || (q.n_variants != 1 && q.n_variants != 8) || q.n > 0xFFFFFFFFull || n_cols > 0xFFFFFFFFull) {
+        rph_set_error("hamming sweep: bad arguments (n=%llu columns=%llu variants=%u part=%u/%u)", (unsigned long long)q.n, (unsigned long long)n_cols,
+                      q.n_variants, q.part, q.nparts);
         return RPH_ERR_INVALID_ARG;
-    }
-    if (n_a == 0 || n_b == 0) return RPH_OK;
-    uint32_t swap = 0;
-    uint64_t n_blocks = 0;
-    SweepArgs a;
-    rph_debug_hamming_cross_layout(n_a, n_variants, n_b, nparts, use_mfma, &swap, &a.seg_tiles, &a.n_col_segs, &n_blocks);
-    a.rows = reinterpret_cast<const uint32_t *>(swap ? d_b : d_a);
-    a.cols = reinterpret_cast<const uint32_t *>(swap ? d_a : d_b);
-    a.low_conf = swap ? d_low_conf_b : d_low_conf_a;
-    a.low_conf_cols = swap ? d_low_conf_a : d_low_conf_b;
-    a.has_features = n_variants > 1 ? d_has_features_a : nullptr;
-    a.n = swap ? n_b : n_a;
-    a.n_cols = swap ? n_a : n_b;
-    a.swap_ij = swap;
-    a.n_variants = n_variants;
-    a.threshold = threshold > 256 ? 256 : threshold;
-    a.mih_tol = (threshold / 16u) >= 1 ? 1 : 0;
-    a.part = part;
-    a.nparts = nparts;
-    a.n_tiles = (uint32_t)((a.n + T_FILES - 1) / T_FILES);
-    a.n_tile_pairs = n_blocks;
-    a.edges = d_edges;
-    a.cap = cap;
-    a.count = d_count;
-    a.perm = nullptr;
-    a.pcs = nullptr;
-    const unsigned long long mine = (a.n_tile_pairs > part) ? (a.n_tile_pairs - part + nparts - 1) / nparts : 0;
-    const int pw = rph_hamming_prefix_dwords(a.threshold, use_mfma);
-    for (unsigned long long b0 = 0; b0 < mine; b0 += MAX_GRID) {  // one launch carries at most MAX_GRID blocks
-        a.block0 = b0;
-        const dim3 grid((unsigned)((mine - b0) < MAX_GRID ? (mine - b0) : MAX_GRID)), block(BLOCK);
-        if (use_mfma >= 2) {
-            launch_cross_mfma<FmtFp4>(pw, grid, stream, a);
-        } else if (use_mfma) {
-            launch_cross_mfma<FmtI8>(pw, grid, stream, a);
-        } else {
-            if (pw == 4)
-                hipLaunchKernelGGL((hamming_sweep_kernel<4, true>), grid, block, 0, stream, a);
-            else if (pw == 5)
-                hipLaunchKernelGGL((hamming_sweep_kernel<5, true>), grid, block, 0, stream, a);
-            else if (pw == 6)
-                hipLaunchKernelGGL((hamming_sweep_kernel<6, true>), grid, block, 0, stream, a);
-            else if (pw == 7)
-                hipLaunchKernelGGL((hamming_sweep_kernel<7, true>), grid, block, 0, stream, a);
-            else
-                hipLaunchKernelGGL((hamming_sweep_kernel<8, true>), grid, block, 0, stream, a);
-        }
-        RPH_HIP_CHECK(hipGetLastError());
     }
     return RPH_OK;
 }
 
-int rph_launch_hamming64_sweep(const uint64_t *d_hashes, uint64_t n, uint32_t threshold, uint32_t part, uint32_t nparts,
-                               rph_edge *d_edges, uint64_t cap, unsigned long long *d_count, hipStream_t stream, int use_mfma)
+// Every form of the sweep (rph_internal.h: rph_sweep).  Square: the upper-triangular tile pairs of one set.  Cross: every pair of two
+// sets, e.i indexing the request's rows and e.j its columns whichever side rph_debug_hamming_cross_layout puts on the kernel's rows;
+// kernel settings 2, 3 and 4 all run the +-1 fp4 form there (the popcount-sorted {0,1} form sorts ONE array and needs rows == columns).
+// 64-bit hashes: the fp4 MFMA kernel with the whole hash as one slice, or the VALU kernel of their own.
+int rph_launch_hamming_sweep(rph_ctx *ctx, const rph_sweep &q, hipStream_t stream, int use_mfma)
 {
-    if (nparts == 0 || part >= nparts || n > 0xFFFFFFFFull) {
-        rph_set_error("hamming64 sweep: bad arguments");
-        return RPH_ERR_INVALID_ARG;
+    RPH_TRY(rph_hamming_sweep_check(q));
+    if (q.cross ? (q.n == 0 || q.n_cols == 0) : q.n < 2) return RPH_OK;  // no pair
+    if (q.bits64 && !use_mfma) {
+        Sweep64Args a;
+        a.hashes = reinterpret_cast<const uint2 *>(q.rows);
+        fill_shared(a, q, q.n);
+        a.n_tile_pairs = seg_G(a.n_tiles, 1);
+        return launch_share(a, [&](dim3 grid) -> int {
+            hipLaunchKernelGGL(hamming64_sweep_kernel, grid, dim3(256), 0, stream, a);
+            return RPH_OK;
+        });
     }
-    if (n < 2) return RPH_OK;
-    if (use_mfma) {
-        // fp4 MFMA formulation (the whole 64-bit hash is one slice): same kernel as the 256-bit sweep
-        SweepArgs m;
-        m.rows = m.cols = reinterpret_cast<const uint32_t *>(d_hashes);
-        m.low_conf = nullptr;
-        m.has_features = nullptr;
-        m.n = n;
-        m.n_variants = 1;
-        m.threshold = threshold > 64 ? 64 : threshold;
-        m.mih_tol = (threshold / 8u) >= 1 ? 1 : 0;  // chunk_tolerance = max_dist / NUM_CHUNKS (hamminghash.rs:193), NUM_CHUNKS = 8
-        m.part = part;
-        m.nparts = nparts;
-        m.n_tiles = (uint32_t)((n + T_FILES - 1) / T_FILES);
-        const unsigned long long pairs = (unsigned long long)m.n_tiles * (m.n_tiles + 1ull) / 2ull;
-        const unsigned long long S = pairs / (8ull * 768ull * nparts);  // 3 blocks per CU
-        m.seg_tiles = (uint32_t)(S < 1 ? 1 : (S > 8 ? 8 : S));
-        m.n_tile_pairs = seg_G(m.n_tiles, m.seg_tiles);
-        m.edges = d_edges;
-        m.cap = cap;
-        m.count = d_count;
-        const unsigned long long mine = (m.n_tile_pairs > part) ? (m.n_tile_pairs - part + nparts - 1) / nparts : 0;
-        for (unsigned long long b0 = 0; b0 < mine; b0 += MAX_GRID) {
-            m.block0 = b0;
-            hipLaunchKernelGGL((hamming_mfma_kernel<FmtFp4, 2, true>), dim3((unsigned)((mine - b0) < MAX_GRID ? (mine - b0) : MAX_GRID)), dim3(MF_BLOCK), 0,
-                               stream, m);
-            RPH_HIP_CHECK(hipGetLastError());
+    SweepArgs a{};
+    uint32_t swap = 0;
+    if (q.cross) {
+        uint64_t n_blocks = 0;
+        rph_debug_hamming_cross_layout(q.n, q.n_variants, q.n_cols, q.nparts, use_mfma, &swap, &a.seg_tiles, &a.n_col_segs, &n_blocks);
+        a.n_tile_pairs = n_blocks;
+        a.n_cols = swap ? q.n : q.n_cols;
+        a.swap_ij = swap;
+    }
+    a.rows = reinterpret_cast<const uint32_t *>(swap ? q.cols : q.rows);
+    a.cols = reinterpret_cast<const uint32_t *>(swap ? q.rows : q.cols);
+    a.low_conf = swap ? q.low_conf_cols : q.low_conf;
+    a.low_conf_cols = swap ? q.low_conf : q.low_conf_cols;
+    a.has_features = q.cross && q.n_variants == 1 ? nullptr : q.has_features;
+    a.n_variants = q.n_variants;
+    fill_shared(a, q, swap ? q.n_cols : q.n);
+    if (!q.cross) {  // segments of the triangle (the VALU kernel: one tile pair per block)
+        a.seg_tiles = use_mfma ? seg_length(seg_G(a.n_tiles, 1), q.bits64 ? SEG_WANT_BLOCKS_64 : SEG_WANT_BLOCKS_256, q.nparts) : 1;
+        a.n_tile_pairs = seg_G(a.n_tiles, a.seg_tiles);
+    }
+    const int pw = rph_hamming_prefix_dwords(a.threshold, use_mfma);
+    // plain all-pairs sweeps (rows are the columns, no per-file rules) run on popcount-sorted {0,1} operands, unless this part's share
+    // is empty: prepare_sorted points a.rows / a.cols / a.perm / a.pcs at the context's sweep scratch, and ctx->mu is held from there
+    // through the launches to the scratch's publish
+    const bool zero_one = part_share(a) > 0 && (use_mfma == 4 || (use_mfma == 2 && q.n >= ZO_MIN_N)) && ctx && !q.cross && !q.bits64 &&
+                          q.n_variants == 1 && q.rows == q.cols && !q.low_conf && !q.has_features;
+    std::unique_lock<std::mutex> scratch_lock;
+    if (zero_one) {
+        scratch_lock = std::unique_lock<std::mutex>(ctx->mu);
+        RPH_TRY(prepare_sorted(ctx, (const uint8_t *)q.cols, q.n, pw, stream, a));
+    }
+    RPH_TRY(launch_share(a, [&](dim3 grid) -> int {
+        // (the kernels stand in the code object in the order in which this text names them, width lists included: both are kept as
+        // they have always been, so that the device assembly of two revisions can be compared line by line)
+        if (zero_one) {
+            launch_mfma<FmtFp4ZO, false, 4, 6, 8>(pw, grid, stream, a);
+        } else if (!q.cross && !q.bits64) {
+            if (use_mfma >= 2)
+                launch_mfma<FmtFp4, false, 4, 6, 8>(pw, grid, stream, a);
+            else if (use_mfma)
+                launch_mfma<FmtI8, false, 4, 5, 6, 7, 8>(pw, grid, stream, a);
+            else
+                launch_valu<false>(pw, grid, stream, a);
+        } else if (q.cross) {
+            if (use_mfma >= 2)
+                launch_mfma<FmtFp4, true, 4, 6, 8>(pw, grid, stream, a);
+            else if (use_mfma)
+                launch_mfma<FmtI8, true, 4, 6, 8, 5, 7>(pw, grid, stream, a);
+            else
+                launch_valu<true>(pw, grid, stream, a);
+        } else {  // 64-bit hashes: the whole hash is one slice
+            hipLaunchKernelGGL((hamming_mfma_kernel<FmtFp4, 2, true>), grid, dim3(MF_BLOCK), 0, stream, a);
         }
         return RPH_OK;
-    }
-    Sweep64Args a;
-    a.hashes = reinterpret_cast<const uint2 *>(d_hashes);
-    a.n = n;
-    a.threshold = threshold > 64 ? 64 : threshold;
-    a.mih_tol = (threshold / 8u) >= 1 ? 1 : 0;  // chunk_tolerance = max_dist / NUM_CHUNKS (hamminghash.rs:193), NUM_CHUNKS = 8
-    a.part = part;
-    a.nparts = nparts;
-    a.n_tiles = (uint32_t)((n + T_FILES - 1) / T_FILES);
-    a.n_tile_pairs = (unsigned long long)a.n_tiles * (a.n_tiles + 1ull) / 2ull;
-    a.edges = d_edges;
-    a.cap = cap;
-    a.count = d_count;
-    const unsigned long long mine = (a.n_tile_pairs > part) ? (a.n_tile_pairs - part + nparts - 1) / nparts : 0;
-    if (mine == 0) return RPH_OK;
-    for (unsigned long long b0 = 0; b0 < mine; b0 += MAX_GRID) {
-        a.block0 = b0;
-        hipLaunchKernelGGL(hamming64_sweep_kernel, dim3((unsigned)((mine - b0) < MAX_GRID ? (mine - b0) : MAX_GRID)), dim3(256), 0, stream, a);
-        RPH_HIP_CHECK(hipGetLastError());
-    }
+    }));
+    if (zero_one) RPH_TRY(ctx->sweep_scratch.publish(stream));
     return RPH_OK;
 }

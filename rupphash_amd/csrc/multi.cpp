@@ -188,16 +188,19 @@ int sweep_all(rph_multi *m, const std::vector<const uint8_t *> &d_rows, uint32_t
     std::vector<DevMem> d_e(world), d_c(world);
     std::vector<unsigned long long> found(world, 0);
     std::vector<bool> done(world, false);
-    for (int attempt = 0; attempt < 3; attempt++) {
+    for (int attempt = 0; attempt < RPH_GROW_GROUP_FILES.attempts; attempt++) {
         for (int i = 0; i < world; i++) {
             if (done[i]) continue;
             rph_ctx *c = m->ctx[i];
             RPH_TRY(d_e[i].alloc(m->devices[i], cap[i] * sizeof(rph_edge)));
             RPH_TRY(d_c[i].alloc(m->devices[i], 8));
             RPH_HIP_CHECK(hipMemsetAsync(d_c[i].p, 0, 8, c->stream));
-            RPH_TRY(rph_launch_hamming_sweep(c, d_rows[i], n_variants, d_hashes[i], d_low.empty() ? nullptr : d_low[i], d_hf.empty() ? nullptr : d_hf[i], n,
-                                             threshold, (uint32_t)i, (uint32_t)world, d_e[i].as<rph_edge>(), cap[i], d_c[i].as<unsigned long long>(), c->stream,
-                                             c->hamming_kernel));
+            rph_sweep q;
+            q.rows = d_rows[i], q.n_variants = n_variants, q.cols = d_hashes[i], q.n = n;
+            q.low_conf = d_low.empty() ? nullptr : d_low[i], q.has_features = d_hf.empty() ? nullptr : d_hf[i];
+            q.threshold = threshold, q.part = (uint32_t)i, q.nparts = (uint32_t)world;
+            q.edges = d_e[i].as<rph_edge>(), q.cap = cap[i], q.count = d_c[i].as<unsigned long long>();
+            RPH_TRY(rph_launch_hamming_sweep(c, q, c->stream, c->hamming_kernel));
             RPH_HIP_CHECK(hipMemcpyAsync(&found[i], d_c[i].p, 8, hipMemcpyDeviceToHost, c->stream));
         }
         bool again = false;
@@ -211,7 +214,7 @@ int sweep_all(rph_multi *m, const std::vector<const uint8_t *> &d_rows, uint32_t
                 if (found[i]) RPH_HIP_CHECK(hipMemcpy(edges.data() + at, d_e[i].p, found[i] * sizeof(rph_edge), hipMemcpyDeviceToHost));
                 done[i] = true;
             } else {
-                cap[i] = found[i] + found[i] / 16 + 1024;  // rare: this device's share again, into a buffer of the size it reported
+                cap[i] = RPH_GROW_GROUP_FILES.next_cap(found[i]);  // rare: this device's share again, into a buffer of the size it reported
                 again = true;
             }
         }

@@ -29,73 +29,213 @@ namespace {
 hipStream_t pick(rph_ctx *ctx, void *stream) { return stream ? (hipStream_t)stream : ctx->stream; }
 }  // namespace
 
-static int sweep_host(rph_ctx *ctx, const uint8_t *variants, uint32_t n_variants, const uint8_t *hashes32,
-                      const uint8_t *low_conf, const uint8_t *has_features, uint64_t n, uint32_t thr, uint32_t part,
-                      uint32_t nparts, rph_edge *edges, uint64_t cap, uint64_t *n_edges_out)
+// ---- what the Hamming and grouping entry points share (rph_sweep: rph_internal.h) ----
+namespace {
+// the two forms of a request over 256-bit hashes; where its edges go is set with `into`
+rph_sweep square_sweep(const void *rows, uint32_t n_variants, const void *hashes, const void *low_conf, const void *has_features, uint64_t n,
+                       uint32_t threshold, uint32_t part, uint32_t nparts)
 {
-    if (!ctx || (!hashes32 && n) || !n_edges_out || (!edges && cap)) {
-        rph_set_error("hamming sweep: null argument");
+    rph_sweep q;
+    q.rows = rows, q.n_variants = n_variants, q.cols = hashes, q.n = n;
+    q.low_conf = (const uint8_t *)low_conf, q.has_features = (const uint8_t *)has_features;
+    q.threshold = threshold, q.part = part, q.nparts = nparts;
+    return q;
+}
+rph_sweep cross_sweep(const void *rows, uint32_t n_variants, const void *low_conf, const void *has_features, uint64_t n, const void *hashes_b,
+                      const void *low_conf_b, uint64_t n_b, uint32_t threshold, uint32_t part, uint32_t nparts)
+{
+    rph_sweep q = square_sweep(rows, n_variants, hashes_b, low_conf, has_features, n, threshold, part, nparts);
+    q.cross = true, q.low_conf_cols = (const uint8_t *)low_conf_b, q.n_cols = n_b;
+    return q;
+}
+rph_sweep into(rph_sweep q, void *edges, uint64_t cap, void *count = nullptr)
+{
+    q.edges = (rph_edge *)edges, q.cap = cap, q.count = (unsigned long long *)count;
+    return q;
+}
+
+// a _dev entry point: the request as it is, on the caller's stream
+int sweep_dev(const char *who, rph_ctx *ctx, const rph_sweep &q, void *stream)
+{
+    const uint64_t n_cols = q.cross ? q.n_cols : q.n;
+    if (!ctx || (!q.rows && q.n) || (!q.cols && n_cols) || !q.count || (!q.edges && q.cap)) {
+        rph_set_error("%s: null argument", who);
+        return RPH_ERR_INVALID_ARG;
+    }
+    RPH_HIP_CHECK(hipSetDevice(ctx->device));
+    return rph_launch_hamming_sweep(ctx, q, pick(ctx, stream), ctx->hamming_kernel);
+}
+
+// The edge list of a sweep on the device: the buffer and the 8-byte cursor that the kernels append through.  A sweep that finds more
+// than `cap` edges writes the first `cap` and counts them all.
+struct EdgeSink {
+    DevBuf d_e, d_cnt;
+    uint64_t cap = 0;
+    // a buffer of `capacity` edges and the cursor zeroed on `s`; `q` reports there
+    int open(uint64_t capacity, hipStream_t s, rph_sweep &q)
+    {
+        cap = capacity;
+        RPH_TRY(d_e.alloc(cap * sizeof(rph_edge)));
+        if (!d_cnt.data()) RPH_TRY(d_cnt.alloc(8));
+        RPH_HIP_CHECK(hipMemsetAsync(d_cnt.data(), 0, 8, s));
+        q = into(q, d_e.data(), cap, d_cnt.data());
+        return RPH_OK;
+    }
+    // the cursor as it stands behind the work queued on `s` so far (asynchronous: *found is valid once `s` has been synchronised)
+    int read(unsigned long long *found, hipStream_t s) const
+    {
+        RPH_HIP_CHECK(hipMemcpyAsync(found, d_cnt.data(), 8, hipMemcpyDeviceToHost, s));
+        return RPH_OK;
+    }
+    // behind that synchronisation: the first min(found, cap) edges to `out`; more found than fit is RPH_ERR_CAPACITY, with the count
+    int take(const char *who, unsigned long long found, rph_edge *out) const
+    {
+        const uint64_t n_take = std::min<uint64_t>(found, cap);
+        if (n_take) RPH_HIP_CHECK(hipMemcpy(out, d_e.data(), n_take * sizeof(rph_edge), hipMemcpyDeviceToHost));
+        if (found > cap) {
+            rph_set_error("%s: %llu edges found, capacity %llu", who, found, (unsigned long long)cap);
+            return RPH_ERR_CAPACITY;
+        }
+        return RPH_OK;
+    }
+};
+
+// The arrays of a request given in host pointers, on the device.  Rows that the request names are an array of their own there, whatever
+// they alias on the host; a square request without rows (rph_hamming_all_pairs, the 64-bit form, rph_find_groups*) sweeps its hashes
+// against themselves, and only then rows and columns are one device array, as a caller of rph_hamming_all_pairs_dev passes them.
+struct SweepOperands {
+    DevBuf rows, cols, low_conf, has_features, low_conf_cols;
+    int upload(const rph_sweep &host, hipStream_t s, rph_sweep &dev)
+    {
+        auto up = [s](DevBuf &b, const void *src, size_t bytes) -> int {
+            RPH_TRY(b.alloc(bytes));
+            RPH_HIP_CHECK(hipMemcpyAsync(b.data(), src, bytes, hipMemcpyHostToDevice, s));
+            return RPH_OK;
+        };
+        const size_t width = host.bits64 ? 8 : 32;
+        dev = host;
+        RPH_TRY(up(cols, host.cols, (host.cross ? host.n_cols : host.n) * width));
+        dev.rows = dev.cols = cols.data();
+        if (host.rows) {
+            RPH_TRY(up(rows, host.rows, host.n * width * host.n_variants));
+            dev.rows = rows.data();
+        }
+        if (host.low_conf) {
+            RPH_TRY(up(low_conf, host.low_conf, host.n));
+            dev.low_conf = low_conf.data();
+        }
+        if (host.has_features) {
+            RPH_TRY(up(has_features, host.has_features, host.n));
+            dev.has_features = has_features.data();
+        }
+        if (host.low_conf_cols) {
+            RPH_TRY(up(low_conf_cols, host.low_conf_cols, host.n_cols));
+            dev.low_conf_cols = low_conf_cols.data();
+        }
+        return RPH_OK;
+    }
+};
+
+// A host entry point: the request in host pointers (a square one may leave `rows` null: SweepOperands), `q.edges` the caller's array of
+// `q.cap` edges.  The square forms answer a set of
+// fewer than two files before they look at part / nparts / n_variants; the cross forms check those before they look at the sizes.
+int sweep_host(const char *who, rph_ctx *ctx, const rph_sweep &q, uint64_t *n_edges_out)
+{
+    const uint64_t n_cols = q.cross ? q.n_cols : q.n;
+    if (!ctx || (q.cross && !q.rows && q.n) || (!q.cols && n_cols) || !n_edges_out || (!q.edges && q.cap)) {
+        rph_set_error("%s: null argument", who);
         return RPH_ERR_INVALID_ARG;
     }
     *n_edges_out = 0;
-    if (n < 2) return RPH_OK;
+    if (!q.cross && q.n < 2) return RPH_OK;
+    RPH_TRY(rph_hamming_sweep_check(q));
+    if (q.n == 0 || n_cols == 0) return RPH_OK;
     RPH_HIP_CHECK(hipSetDevice(ctx->device));
-    DevBuf d_h, d_v, d_lc, d_hf, d_e, d_cnt;
-    RPH_TRY(d_h.alloc(n * 32));
-    RPH_HIP_CHECK(hipMemcpyAsync(d_h.data(), hashes32, n * 32, hipMemcpyHostToDevice, ctx->stream));
-    const uint8_t *rows = (const uint8_t *)d_h.data();
-    if (variants) {
-        RPH_TRY(d_v.alloc(n * 32 * n_variants));
-        RPH_HIP_CHECK(hipMemcpyAsync(d_v.data(), variants, n * 32 * n_variants, hipMemcpyHostToDevice, ctx->stream));
-        rows = (const uint8_t *)d_v.data();
-    } else {
-        n_variants = 1;
-    }
-    if (low_conf) {
-        RPH_TRY(d_lc.alloc(n));
-        RPH_HIP_CHECK(hipMemcpyAsync(d_lc.data(), low_conf, n, hipMemcpyHostToDevice, ctx->stream));
-    }
-    if (has_features) {
-        RPH_TRY(d_hf.alloc(n));
-        RPH_HIP_CHECK(hipMemcpyAsync(d_hf.data(), has_features, n, hipMemcpyHostToDevice, ctx->stream));
-    }
-    RPH_TRY(d_e.alloc(cap * sizeof(rph_edge)));
-    RPH_TRY(d_cnt.alloc(8));
-    RPH_HIP_CHECK(hipMemsetAsync(d_cnt.data(), 0, 8, ctx->stream));
-    RPH_TRY(rph_launch_hamming_sweep(ctx, rows, n_variants, (const uint8_t *)d_h.data(), (const uint8_t *)d_lc.data(),
-                                     (const uint8_t *)d_hf.data(), n, thr, part, nparts, (rph_edge *)d_e.data(), cap,
-                                     (unsigned long long *)d_cnt.data(), ctx->stream, ctx->hamming_kernel));
-    unsigned long long cnt = 0;
-    RPH_HIP_CHECK(hipMemcpyAsync(&cnt, d_cnt.data(), 8, hipMemcpyDeviceToHost, ctx->stream));
-    RPH_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    *n_edges_out = cnt;
-    const uint64_t take = std::min<uint64_t>(cnt, cap);
-    if (take) RPH_HIP_CHECK(hipMemcpy(edges, d_e.data(), take * sizeof(rph_edge), hipMemcpyDeviceToHost));
-    if (cnt > cap) {
-        rph_set_error("hamming sweep: %llu edges found, capacity %llu", cnt, (unsigned long long)cap);
-        return RPH_ERR_CAPACITY;
-    }
-    return RPH_OK;
+    hipStream_t s = ctx->stream;
+    SweepOperands ops;
+    EdgeSink sink;
+    rph_sweep d;
+    RPH_TRY(ops.upload(q, s, d));
+    RPH_TRY(sink.open(q.cap, s, d));
+    RPH_TRY(rph_launch_hamming_sweep(ctx, d, s, ctx->hamming_kernel));
+    unsigned long long found = 0;
+    RPH_TRY(sink.read(&found, s));
+    RPH_HIP_CHECK(hipStreamSynchronize(s));
+    *n_edges_out = found;
+    return sink.take(who, found, q.edges);
 }
 
-// Run a sweep whose edge count is not known in advance: grow the edge buffer until it fits.
+// A sweep whose edge count is not known in advance: into a buffer of `cap` edges, and while it finds more than fit, again into one
+// that `growth` sizes from what it counted.  launch(sink, cap) opens the sink for its request and queues its sweeps on `s`, all of
+// them appending through the one cursor.
 template <class F>
-static int sweep_growing(uint64_t n, std::vector<rph_edge> &edges, F &&run)
+int sweep_growing(const char *who, uint64_t cap, const rph_edge_growth &growth, hipStream_t s, std::vector<rph_edge> &edges, F &&launch)
 {
-    uint64_t cap = std::max<uint64_t>(1u << 20, 4 * n);
-    for (int attempt = 0; attempt < 8; attempt++) {
-        edges.resize(cap);
-        uint64_t found = 0;
-        int rc = run(edges.data(), cap, &found);
-        if (rc == RPH_OK) {
+    EdgeSink sink;
+    unsigned long long found = 0;
+    for (int attempt = 0; attempt < growth.attempts; attempt++) {
+        RPH_TRY(launch(sink, cap));
+        RPH_TRY(sink.read(&found, s));
+        RPH_HIP_CHECK(hipStreamSynchronize(s));
+        if (found <= cap) {
             edges.resize(found);
-            return RPH_OK;
+            return sink.take(who, found, edges.data());
         }
-        if (rc != RPH_ERR_CAPACITY) return rc;
-        cap = found + found / 8 + 1024;
+        cap = growth.next_cap(found);
     }
+    rph_set_error("%s: edge list kept growing (%llu)", who, found);
     return RPH_ERR_CAPACITY;
 }
+
+// One set of files of the grouping calls on the device: hashes, the variants its files own as rows (8 per file from the coefficients,
+// which cross PCIe in 256 MiB pieces through a fixed staging buffer: scanner.rs:1621-1623; else the hash itself), has_features and
+// low-confidence flags.  Everything between the caller's arrays and the edge list stays on the device.
+struct GroupSide {
+    DevBuf d_h, d_var, d_lc, d_hf, d_stage;
+    std::vector<uint8_t> low_conf_host;
+    uint64_t n = 0;
+    uint32_t n_variants = 1;
+    bool use_hf = false;
+    const uint8_t *rows() const { return n_variants == 8 ? d_var.data() : d_h.data(); }
+    const uint8_t *has_features() const { return use_hf ? d_hf.data() : nullptr; }
+    // this side's rows against its own hashes (pairs i < j), or against the hashes of `other` (every pair)
+    rph_sweep sweep(uint32_t similarity, const GroupSide *other = nullptr) const
+    {
+        return other ? cross_sweep(rows(), n_variants, d_lc.data(), has_features(), n, other->d_h.data(), other->d_lc.data(), other->n, similarity, 0, 1)
+                     : square_sweep(rows(), n_variants, d_h.data(), d_lc.data(), has_features(), n, similarity, 0, 1);
+    }
+    int upload(const uint8_t *hashes32, const float *coeffs, const uint8_t *hf, const int32_t *quality, uint64_t count, bool want_rows, hipStream_t s)
+    {
+        n = count;
+        if (n == 0) return RPH_OK;
+        RPH_TRY(d_h.alloc(n * 32));
+        RPH_HIP_CHECK(hipMemcpyAsync(d_h.data(), hashes32, n * 32, hipMemcpyHostToDevice, s));
+        if (quality) {
+            low_conf_host.resize(n);
+            for (uint64_t i = 0; i < n; i++) low_conf_host[i] = (uint8_t)rph_is_low_pdq_quality(quality[i]);
+            RPH_TRY(d_lc.alloc(n));
+            RPH_HIP_CHECK(hipMemcpyAsync(d_lc.data(), low_conf_host.data(), n, hipMemcpyHostToDevice, s));
+        }
+        if (!coeffs || !want_rows) return RPH_OK;
+        n_variants = 8;
+        use_hf = hf != nullptr;
+        if (use_hf) {
+            RPH_TRY(d_hf.alloc(n));
+            RPH_HIP_CHECK(hipMemcpyAsync(d_hf.data(), hf, n, hipMemcpyHostToDevice, s));
+        }
+        RPH_TRY(d_var.alloc(n * 256));
+        const uint64_t step = 1u << 18;  // 256 MiB of coefficients per piece
+        RPH_TRY(d_stage.alloc(std::min<uint64_t>(step, n) * 1024));
+        for (uint64_t first = 0; first < n; first += step) {
+            const uint32_t m = (uint32_t)std::min<uint64_t>(step, n - first);
+            RPH_HIP_CHECK(hipMemcpyAsync(d_stage.data(), coeffs + first * 256, (size_t)m * 1024, hipMemcpyHostToDevice, s));
+            RPH_TRY(rph_launch_pdq_from_coeffs((const float *)d_stage.data(), m, nullptr, d_var.as<uint8_t>() + first * 256, s));
+        }
+        if (use_hf) RPH_TRY(rph_launch_featureless_variants(d_h.as<uint8_t>(), d_hf.as<uint8_t>(), n, d_var.as<uint8_t>(), s));
+        return RPH_OK;
+    }
+};
+}  // namespace
 
 // 1/3/4 channels, rows do not overlap, images do not overlap (a single image needs no image_stride)
 static bool pdq_geometry_ok(uint32_t n, uint32_t w, uint32_t h, uint32_t channels, size_t row_stride, size_t image_stride)
@@ -708,35 +848,25 @@ int rph_pdq_hashes_from_coeffs(rph_ctx *ctx, const float *coeffs, uint32_t n, ui
 int rph_hamming_all_pairs_dev(rph_ctx *ctx, const void *d_hashes32, uint64_t n, uint32_t threshold, uint32_t part,
                               uint32_t nparts, void *d_edges, uint64_t cap, void *d_count, void *stream)
 {
-    if (!ctx || (!d_hashes32 && n) || !d_count || (!d_edges && cap)) {
-        rph_set_error("rph_hamming_all_pairs: null argument");
-        return RPH_ERR_INVALID_ARG;
-    }
-    RPH_HIP_CHECK(hipSetDevice(ctx->device));
-    return rph_launch_hamming_sweep(ctx, (const uint8_t *)d_hashes32, 1, (const uint8_t *)d_hashes32, nullptr, nullptr, n, threshold,
-                                    part, nparts, (rph_edge *)d_edges, cap, (unsigned long long *)d_count, pick(ctx, stream),
-                                    ctx->hamming_kernel);
+    return sweep_dev("rph_hamming_all_pairs", ctx,
+                     into(square_sweep(d_hashes32, 1, d_hashes32, nullptr, nullptr, n, threshold, part, nparts), d_edges, cap, d_count), stream);
 }
 
 int rph_hamming_variant_pairs_dev(rph_ctx *ctx, const void *d_variants, uint32_t n_variants, const void *d_hashes32,
                                   const void *d_low_conf, uint64_t n, uint32_t similarity, uint32_t part, uint32_t nparts,
                                   void *d_edges, uint64_t cap, void *d_count, void *stream)
 {
-    if (!ctx || ((!d_variants || !d_hashes32) && n) || !d_count || (!d_edges && cap)) {
-        rph_set_error("rph_hamming_variant_pairs: null argument");
-        return RPH_ERR_INVALID_ARG;
-    }
-    RPH_HIP_CHECK(hipSetDevice(ctx->device));
-    return rph_launch_hamming_sweep(ctx, (const uint8_t *)d_variants, n_variants, (const uint8_t *)d_hashes32,
-                                    (const uint8_t *)d_low_conf, nullptr, n, similarity, part, nparts, (rph_edge *)d_edges, cap,
-                                    (unsigned long long *)d_count, pick(ctx, stream), ctx->hamming_kernel);
+    return sweep_dev("rph_hamming_variant_pairs", ctx,
+                     into(square_sweep(d_variants, n_variants, d_hashes32, d_low_conf, nullptr, n, similarity, part, nparts), d_edges, cap, d_count),
+                     stream);
 }
 
 int rph_hamming_all_pairs(rph_ctx *ctx, const uint8_t *hashes32, uint64_t n, uint32_t threshold, uint32_t part,
                           uint32_t nparts, rph_edge *edges, uint64_t cap, uint64_t *n_edges_out)
 {
     return rph_guarded("rph_hamming_all_pairs", [&]() -> int {
-        return sweep_host(ctx, nullptr, 1, hashes32, nullptr, nullptr, n, threshold, part, nparts, edges, cap, n_edges_out);
+        return sweep_host("rph_hamming_all_pairs", ctx, into(square_sweep(nullptr, 1, hashes32, nullptr, nullptr, n, threshold, part, nparts), edges, cap),
+                          n_edges_out);
     });
 }
 
@@ -749,8 +879,8 @@ int rph_hamming_variant_pairs(rph_ctx *ctx, const uint8_t *variants, uint32_t n_
             rph_set_error("rph_hamming_variant_pairs: variants is null");
             return RPH_ERR_INVALID_ARG;
         }
-        return sweep_host(ctx, variants, n_variants, hashes32, low_conf, nullptr, n, similarity, part, nparts, edges, cap,
-                          n_edges_out);
+        return sweep_host("rph_hamming_variant_pairs", ctx,
+                          into(square_sweep(variants, n_variants, hashes32, low_conf, nullptr, n, similarity, part, nparts), edges, cap), n_edges_out);
     });
 }
 
@@ -759,14 +889,10 @@ int rph_hamming_variant_cross_pairs_dev(rph_ctx *ctx, const void *d_variants_a, 
                                         const void *d_hashes_b, const void *d_low_conf_b, uint64_t n_b, uint32_t similarity, uint32_t part,
                                         uint32_t nparts, void *d_edges, uint64_t cap, void *d_count, void *stream)
 {
-    if (!ctx || (!d_variants_a && n_a) || (!d_hashes_b && n_b) || !d_count || (!d_edges && cap)) {
-        rph_set_error("rph_hamming_variant_cross_pairs: null argument");
-        return RPH_ERR_INVALID_ARG;
-    }
-    RPH_HIP_CHECK(hipSetDevice(ctx->device));
-    return rph_launch_hamming_cross_sweep(ctx, (const uint8_t *)d_variants_a, n_variants, (const uint8_t *)d_low_conf_a, nullptr, n_a,
-                                          (const uint8_t *)d_hashes_b, (const uint8_t *)d_low_conf_b, n_b, similarity, part, nparts,
-                                          (rph_edge *)d_edges, cap, (unsigned long long *)d_count, pick(ctx, stream), ctx->hamming_kernel);
+    return sweep_dev("rph_hamming_variant_cross_pairs", ctx,
+                     into(cross_sweep(d_variants_a, n_variants, d_low_conf_a, nullptr, n_a, d_hashes_b, d_low_conf_b, n_b, similarity, part, nparts), d_edges,
+                          cap, d_count),
+                     stream);
 }
 
 int rph_hamming_cross_pairs_dev(rph_ctx *ctx, const void *d_a32, uint64_t n_a, const void *d_b32, uint64_t n_b, uint32_t threshold, uint32_t part,
@@ -776,133 +902,76 @@ int rph_hamming_cross_pairs_dev(rph_ctx *ctx, const void *d_a32, uint64_t n_a, c
                                                stream);
 }
 
-static int cross_host(rph_ctx *ctx, const uint8_t *variants_a, uint32_t n_variants, const uint8_t *low_conf_a, uint64_t n_a, const uint8_t *hashes_b,
-                      const uint8_t *low_conf_b, uint64_t n_b, uint32_t thr, uint32_t part, uint32_t nparts, rph_edge *edges, uint64_t cap,
-                      uint64_t *n_edges_out)
+int rph_hamming_variant_cross_pairs(rph_ctx *ctx, const uint8_t *variants_a, uint32_t n_variants, const uint8_t *low_conf_a, uint64_t n_a,
+                                    const uint8_t *hashes_b, const uint8_t *low_conf_b, uint64_t n_b, uint32_t similarity, uint32_t part,
+                                    uint32_t nparts, rph_edge *edges, uint64_t cap, uint64_t *n_edges_out)
 {
-    if (!ctx || (!variants_a && n_a) || (!hashes_b && n_b) || !n_edges_out || (!edges && cap)) {
-        rph_set_error("hamming cross sweep: null argument");
-        return RPH_ERR_INVALID_ARG;
-    }
-    *n_edges_out = 0;
-    if (nparts == 0 || part >= nparts || (n_variants != 1 && n_variants != 8) || n_a > 0xFFFFFFFFull || n_b > 0xFFFFFFFFull) {
-        rph_set_error("hamming cross sweep: bad arguments (n_a=%llu n_b=%llu variants=%u part=%u/%u)", (unsigned long long)n_a,
-                      (unsigned long long)n_b, n_variants, part, nparts);
-        return RPH_ERR_INVALID_ARG;
-    }
-    if (n_a == 0 || n_b == 0) return RPH_OK;
-    RPH_HIP_CHECK(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    DevBuf d_a, d_b, d_la, d_lb, d_e, d_cnt;
-    RPH_TRY(d_a.alloc(n_a * 32 * n_variants));
-    RPH_HIP_CHECK(hipMemcpyAsync(d_a.data(), variants_a, n_a * 32 * n_variants, hipMemcpyHostToDevice, s));
-    RPH_TRY(d_b.alloc(n_b * 32));
-    RPH_HIP_CHECK(hipMemcpyAsync(d_b.data(), hashes_b, n_b * 32, hipMemcpyHostToDevice, s));
-    if (low_conf_a) {
-        RPH_TRY(d_la.alloc(n_a));
-        RPH_HIP_CHECK(hipMemcpyAsync(d_la.data(), low_conf_a, n_a, hipMemcpyHostToDevice, s));
-    }
-    if (low_conf_b) {
-        RPH_TRY(d_lb.alloc(n_b));
-        RPH_HIP_CHECK(hipMemcpyAsync(d_lb.data(), low_conf_b, n_b, hipMemcpyHostToDevice, s));
-    }
-    RPH_TRY(d_e.alloc(cap * sizeof(rph_edge)));
-    RPH_TRY(d_cnt.alloc(8));
-    RPH_HIP_CHECK(hipMemsetAsync(d_cnt.data(), 0, 8, s));
-    RPH_TRY(rph_launch_hamming_cross_sweep(ctx, d_a.data(), n_variants, d_la.data(), nullptr, n_a, d_b.data(), d_lb.data(), n_b, thr, part, nparts,
-                                           d_e.as<rph_edge>(), cap, d_cnt.as<unsigned long long>(), s, ctx->hamming_kernel));
-    unsigned long long cnt = 0;
-    RPH_HIP_CHECK(hipMemcpyAsync(&cnt, d_cnt.data(), 8, hipMemcpyDeviceToHost, s));
-    RPH_HIP_CHECK(hipStreamSynchronize(s));
-    *n_edges_out = cnt;
-    const uint64_t take = std::min<uint64_t>(cnt, cap);
-    if (take) RPH_HIP_CHECK(hipMemcpy(edges, d_e.data(), take * sizeof(rph_edge), hipMemcpyDeviceToHost));
-    if (cnt > cap) {
-        rph_set_error("hamming cross sweep: %llu edges found, capacity %llu", cnt, (unsigned long long)cap);
-        return RPH_ERR_CAPACITY;
-    }
-    return RPH_OK;
+    return rph_guarded("rph_hamming_variant_cross_pairs", [&]() -> int {
+        return sweep_host("rph_hamming_variant_cross_pairs", ctx,
+                          into(cross_sweep(variants_a, n_variants, low_conf_a, nullptr, n_a, hashes_b, low_conf_b, n_b, similarity, part, nparts), edges, cap),
+                          n_edges_out);
+    });
 }
 
 int rph_hamming_cross_pairs(rph_ctx *ctx, const uint8_t *a32, uint64_t n_a, const uint8_t *b32, uint64_t n_b, uint32_t threshold, uint32_t part,
                             uint32_t nparts, rph_edge *edges, uint64_t cap, uint64_t *n_edges_out)
 {
     return rph_guarded("rph_hamming_cross_pairs", [&]() -> int {
-        return cross_host(ctx, a32, 1, nullptr, n_a, b32, nullptr, n_b, threshold, part, nparts, edges, cap, n_edges_out);
+        return sweep_host("rph_hamming_cross_pairs", ctx,
+                          into(cross_sweep(a32, 1, nullptr, nullptr, n_a, b32, nullptr, n_b, threshold, part, nparts), edges, cap), n_edges_out);
     });
 }
 
-int rph_hamming_variant_cross_pairs(rph_ctx *ctx, const uint8_t *variants_a, uint32_t n_variants, const uint8_t *low_conf_a, uint64_t n_a,
-                                    const uint8_t *hashes_b, const uint8_t *low_conf_b, uint64_t n_b, uint32_t similarity, uint32_t part,
-                                    uint32_t nparts, rph_edge *edges, uint64_t cap, uint64_t *n_edges_out)
+// ---- 64-bit hashes ----
+static rph_sweep square_sweep64(const void *rows, const void *hashes64, uint64_t n, uint32_t threshold, uint32_t part, uint32_t nparts)
 {
-    return rph_guarded("rph_hamming_variant_cross_pairs", [&]() -> int {
-        return cross_host(ctx, variants_a, n_variants, low_conf_a, n_a, hashes_b, low_conf_b, n_b, similarity, part, nparts, edges, cap,
-                          n_edges_out);
-    });
+    rph_sweep q = square_sweep(rows, 1, hashes64, nullptr, nullptr, n, threshold, part, nparts);
+    q.bits64 = true;
+    return q;
 }
 
 int rph_hamming_all_pairs64_dev(rph_ctx *ctx, const void *d_hashes64, uint64_t n, uint32_t threshold, uint32_t part,
                                 uint32_t nparts, void *d_edges, uint64_t cap, void *d_count, void *stream)
 {
-    if (!ctx || (!d_hashes64 && n) || !d_count || (!d_edges && cap)) {
-        rph_set_error("rph_hamming_all_pairs64: null argument");
-        return RPH_ERR_INVALID_ARG;
-    }
-    RPH_HIP_CHECK(hipSetDevice(ctx->device));
-    return rph_launch_hamming64_sweep((const uint64_t *)d_hashes64, n, threshold, part, nparts, (rph_edge *)d_edges, cap,
-                                      (unsigned long long *)d_count, pick(ctx, stream), ctx->hamming_kernel);
+    return sweep_dev("rph_hamming_all_pairs64", ctx, into(square_sweep64(d_hashes64, d_hashes64, n, threshold, part, nparts), d_edges, cap, d_count), stream);
 }
 
 int rph_hamming_all_pairs64(rph_ctx *ctx, const uint64_t *hashes64, uint64_t n, uint32_t threshold, uint32_t part,
                             uint32_t nparts, rph_edge *edges, uint64_t cap, uint64_t *n_edges_out)
 {
     return rph_guarded("rph_hamming_all_pairs64", [&]() -> int {
-        if (!ctx || (!hashes64 && n) || !n_edges_out || (!edges && cap)) {
-            rph_set_error("rph_hamming_all_pairs64: null argument");
-            return RPH_ERR_INVALID_ARG;
-        }
-        *n_edges_out = 0;
-        if (n < 2) return RPH_OK;
-        RPH_HIP_CHECK(hipSetDevice(ctx->device));
-        DevBuf d_h, d_e, d_cnt;
-        RPH_TRY(d_h.alloc(n * 8));
-        RPH_TRY(d_e.alloc(cap * sizeof(rph_edge)));
-        RPH_TRY(d_cnt.alloc(8));
-        RPH_HIP_CHECK(hipMemcpyAsync(d_h.data(), hashes64, n * 8, hipMemcpyHostToDevice, ctx->stream));
-        RPH_HIP_CHECK(hipMemsetAsync(d_cnt.data(), 0, 8, ctx->stream));
-        RPH_TRY(rph_launch_hamming64_sweep((const uint64_t *)d_h.data(), n, threshold, part, nparts, (rph_edge *)d_e.data(), cap,
-                                           (unsigned long long *)d_cnt.data(), ctx->stream, ctx->hamming_kernel));
-        unsigned long long cnt = 0;
-        RPH_HIP_CHECK(hipMemcpyAsync(&cnt, d_cnt.data(), 8, hipMemcpyDeviceToHost, ctx->stream));
-        RPH_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        *n_edges_out = cnt;
-        const uint64_t take = std::min<uint64_t>(cnt, cap);
-        if (take) RPH_HIP_CHECK(hipMemcpy(edges, d_e.data(), take * sizeof(rph_edge), hipMemcpyDeviceToHost));
-        if (cnt > cap) {
-            rph_set_error("hamming64 sweep: %llu edges found, capacity %llu", cnt, (unsigned long long)cap);
-            return RPH_ERR_CAPACITY;
-        }
-        return RPH_OK;
+        return sweep_host("rph_hamming_all_pairs64", ctx, into(square_sweep64(nullptr, hashes64, n, threshold, part, nparts), edges, cap), n_edges_out);
     });
+}
+
+// rph_find_groups256 / rph_find_groups64: all pairs of one set, the operands uploaded once, then find_groups over the edges on the host
+static int find_groups(const char *who, rph_ctx *ctx, const rph_sweep &q, uint32_t *members, uint32_t *offsets, uint32_t *n_groups_out)
+{
+    if (!ctx || (!q.cols && q.n) || !members || !offsets || !n_groups_out) {
+        rph_set_error("%s: null argument", who);
+        return RPH_ERR_INVALID_ARG;
+    }
+    *n_groups_out = 0;
+    offsets[0] = 0;
+    if (q.n < 2) return RPH_OK;
+    RPH_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    SweepOperands ops;
+    rph_sweep d;
+    RPH_TRY(ops.upload(q, s, d));
+    std::vector<rph_edge> edges;
+    RPH_TRY(sweep_growing(who, std::max<uint64_t>(1u << 20, 4 * q.n), RPH_GROW_FIND_GROUPS, s, edges, [&](EdgeSink &sink, uint64_t cap) -> int {
+        RPH_TRY(sink.open(cap, s, d));
+        return rph_launch_hamming_sweep(ctx, d, s, ctx->hamming_kernel);
+    }));
+    return rph_host_find_groups(edges.data(), edges.size(), q.n, members, offsets, n_groups_out);
 }
 
 int rph_find_groups64(rph_ctx *ctx, const uint64_t *hashes64, uint64_t n, uint32_t max_dist, uint32_t *members,
                       uint32_t *offsets, uint32_t *n_groups_out)
 {
     return rph_guarded("rph_find_groups64", [&]() -> int {
-        if (!ctx || (!hashes64 && n) || !members || !offsets || !n_groups_out) {
-            rph_set_error("rph_find_groups64: null argument");
-            return RPH_ERR_INVALID_ARG;
-        }
-        *n_groups_out = 0;
-        offsets[0] = 0;
-        if (n < 2) return RPH_OK;
-        std::vector<rph_edge> edges;
-        RPH_TRY(sweep_growing(n, edges, [&](rph_edge *e, uint64_t cap, uint64_t *found) {
-            return rph_hamming_all_pairs64(ctx, hashes64, n, max_dist, 0, 1, e, cap, found);
-        }));
-        return rph_host_find_groups(edges.data(), edges.size(), n, members, offsets, n_groups_out);
+        return find_groups("rph_find_groups64", ctx, square_sweep64(nullptr, hashes64, n, max_dist, 0, 1), members, offsets, n_groups_out);
     });
 }
 
@@ -928,19 +997,17 @@ int rph_find_groups256(rph_ctx *ctx, const uint8_t *hashes32, uint64_t n, uint32
                        uint32_t *offsets, uint32_t *n_groups_out)
 {
     return rph_guarded("rph_find_groups256", [&]() -> int {
-        if (!ctx || (!hashes32 && n) || !members || !offsets || !n_groups_out) {
-            rph_set_error("rph_find_groups256: null argument");
-            return RPH_ERR_INVALID_ARG;
-        }
-        *n_groups_out = 0;
-        offsets[0] = 0;
-        if (n < 2) return RPH_OK;
-        std::vector<rph_edge> edges;
-        RPH_TRY(sweep_growing(n, edges, [&](rph_edge *e, uint64_t cap, uint64_t *found) {
-            return sweep_host(ctx, nullptr, 1, hashes32, nullptr, nullptr, n, max_dist, 0, 1, e, cap, found);
-        }));
-        return rph_host_find_groups(edges.data(), edges.size(), n, members, offsets, n_groups_out);
+        return find_groups("rph_find_groups256", ctx, square_sweep(nullptr, 1, hashes32, nullptr, nullptr, n, max_dist, 0, 1), members, offsets,
+                           n_groups_out);
     });
+}
+
+// scanner.rs:1650-1655 asserts this
+static int check_similarity(uint32_t similarity)
+{
+    if (similarity <= RPH_MAX_SIMILARITY_256) return RPH_OK;
+    rph_set_error("Similarity distances above %u require R=4 bit-flip checks, which are not implemented.", RPH_MAX_SIMILARITY_256);
+    return RPH_ERR_INVALID_ARG;
 }
 
 int rph_group_files_pdq(rph_ctx *ctx, const uint8_t *hashes32, const float *coeffs, const uint8_t *has_features,
@@ -952,75 +1019,23 @@ int rph_group_files_pdq(rph_ctx *ctx, const uint8_t *hashes32, const float *coef
             rph_set_error("rph_group_files_pdq: null argument");
             return RPH_ERR_INVALID_ARG;
         }
-        if (similarity > RPH_MAX_SIMILARITY_256) {
-            // scanner.rs:1650-1655 asserts this
-            rph_set_error("Similarity distances above %u require R=4 bit-flip checks, which are not implemented.",
-                          RPH_MAX_SIMILARITY_256);
-            return RPH_ERR_INVALID_ARG;
-        }
+        RPH_TRY(check_similarity(similarity));
         *n_groups_out = 0;
         offsets[0] = 0;
         if (comparison_count_out) *comparison_count_out = 0;
         if (n < 2) return RPH_OK;
         RPH_HIP_CHECK(hipSetDevice(ctx->device));
-
-        // Everything between the caller's arrays and the edge list stays on the device: the hashes go up once, the 8 dihedral
-        // variants of every file are produced there from its coefficients (scanner.rs:1621-1623; the coefficients cross PCIe in
-        // 256 MiB pieces through a fixed staging buffer) and feed the variant sweep directly.
-        std::vector<uint8_t> low_conf;
-        if (quality) {
-            low_conf.resize(n);
-            for (uint64_t i = 0; i < n; i++) low_conf[i] = (uint8_t)rph_is_low_pdq_quality(quality[i]);
-        }
         hipStream_t s = ctx->stream;
-        DevBuf d_h, d_var, d_lc, d_hf, d_stage, d_e, d_cnt;
-        RPH_TRY(d_h.alloc(n * 32));
-        RPH_HIP_CHECK(hipMemcpyAsync(d_h.data(), hashes32, n * 32, hipMemcpyHostToDevice, s));
-        if (quality) {
-            RPH_TRY(d_lc.alloc(n));
-            RPH_HIP_CHECK(hipMemcpyAsync(d_lc.data(), low_conf.data(), n, hipMemcpyHostToDevice, s));
-        }
-        const bool use_hf = coeffs && has_features;
-        if (use_hf) {
-            RPH_TRY(d_hf.alloc(n));
-            RPH_HIP_CHECK(hipMemcpyAsync(d_hf.data(), has_features, n, hipMemcpyHostToDevice, s));
-        }
-        if (coeffs) {
-            RPH_TRY(d_var.alloc(n * 256));
-            const uint64_t step = 1u << 18;  // 256 MiB of coefficients per piece
-            RPH_TRY(d_stage.alloc(std::min<uint64_t>(step, n) * 1024));
-            for (uint64_t first = 0; first < n; first += step) {
-                const uint32_t m = (uint32_t)std::min<uint64_t>(step, n - first);
-                RPH_HIP_CHECK(hipMemcpyAsync(d_stage.data(), coeffs + first * 256, (size_t)m * 1024, hipMemcpyHostToDevice, s));
-                RPH_TRY(rph_launch_pdq_from_coeffs((const float *)d_stage.data(), m, nullptr, d_var.as<uint8_t>() + first * 256, s));
-            }
-            if (use_hf) RPH_TRY(rph_launch_featureless_variants(d_h.as<uint8_t>(), d_hf.as<uint8_t>(), n, d_var.as<uint8_t>(), s));
-        }
-        // Edge capacity: 32 per file to begin with (device memory is plentiful, 12 B each); a sweep that finds more is repeated
-        // once into a buffer of the size it reported.
+        GroupSide set;
+        RPH_TRY(set.upload(hashes32, coeffs, has_features, quality, n, true, s));
+        // Edge capacity: 32 per file to begin with (device memory is plentiful, 12 B each)
         std::vector<rph_edge> edges;
-        uint64_t cap = std::max<uint64_t>(1u << 20, 32 * n);
-        RPH_TRY(d_cnt.alloc(8));
-        for (int attempt = 0;; attempt++) {
-            RPH_TRY(d_e.alloc(cap * sizeof(rph_edge)));
-            RPH_HIP_CHECK(hipMemsetAsync(d_cnt.data(), 0, 8, s));
-            RPH_TRY(rph_launch_hamming_sweep(ctx, coeffs ? d_var.as<uint8_t>() : d_h.as<uint8_t>(), coeffs ? 8 : 1, d_h.as<uint8_t>(), d_lc.as<uint8_t>(),
-                                             use_hf ? d_hf.as<uint8_t>() : nullptr, n, similarity, 0, 1, d_e.as<rph_edge>(), cap,
-                                             d_cnt.as<unsigned long long>(), s, ctx->hamming_kernel));
-            unsigned long long found = 0;
-            RPH_HIP_CHECK(hipMemcpyAsync(&found, d_cnt.data(), 8, hipMemcpyDeviceToHost, s));
-            RPH_HIP_CHECK(hipStreamSynchronize(s));
-            if (found <= cap) {
-                edges.resize(found);
-                if (found) RPH_HIP_CHECK(hipMemcpy(edges.data(), d_e.data(), found * sizeof(rph_edge), hipMemcpyDeviceToHost));
-                break;
-            }
-            if (attempt >= 2) {
-                rph_set_error("rph_group_files_pdq: edge list kept growing (%llu)", found);
-                return RPH_ERR_CAPACITY;
-            }
-            cap = found + found / 16 + 1024;
-        }
+        rph_sweep q = set.sweep(similarity);
+        RPH_TRY(sweep_growing("rph_group_files_pdq", std::max<uint64_t>(1u << 20, 32 * n), RPH_GROW_GROUP_FILES, s, edges,
+                              [&](EdgeSink &sink, uint64_t cap) -> int {
+                                  RPH_TRY(sink.open(cap, s, q));
+                                  return rph_launch_hamming_sweep(ctx, q, s, ctx->hamming_kernel);
+                              }));
         if (comparison_count_out) *comparison_count_out = edges.size();
         return rph_host_union_find(edges.data(), edges.size(), n, members, offsets, n_groups_out);
     });
@@ -1038,51 +1053,6 @@ int rph_union_find_groups_append(const uint32_t *old_members, const uint32_t *ol
     });
 }
 
-namespace {
-// One side (library or new files) of rph_group_files_pdq_append on the device: hashes, the variants its files own as rows (8 per file
-// from the coefficients, else the hash itself), has_features and low-confidence flags -- what rph_group_files_pdq builds for its one set.
-struct GroupSide {
-    DevBuf d_h, d_var, d_lc, d_hf, d_stage;
-    uint64_t n = 0;
-    uint32_t n_variants = 1;
-    bool use_hf = false;
-    const uint8_t *rows() const { return n_variants == 8 ? d_var.data() : d_h.data(); }
-    const uint8_t *low_conf() const { return d_lc.data(); }
-    const uint8_t *has_features() const { return use_hf ? d_hf.data() : nullptr; }
-    int upload(const uint8_t *hashes32, const float *coeffs, const uint8_t *hf, const int32_t *quality, uint64_t count, bool want_rows,
-               std::vector<uint8_t> &low_conf_host, hipStream_t s)
-    {
-        n = count;
-        if (n == 0) return RPH_OK;
-        RPH_TRY(d_h.alloc(n * 32));
-        RPH_HIP_CHECK(hipMemcpyAsync(d_h.data(), hashes32, n * 32, hipMemcpyHostToDevice, s));
-        if (quality) {
-            low_conf_host.resize(n);
-            for (uint64_t i = 0; i < n; i++) low_conf_host[i] = (uint8_t)rph_is_low_pdq_quality(quality[i]);
-            RPH_TRY(d_lc.alloc(n));
-            RPH_HIP_CHECK(hipMemcpyAsync(d_lc.data(), low_conf_host.data(), n, hipMemcpyHostToDevice, s));
-        }
-        if (!coeffs || !want_rows) return RPH_OK;
-        n_variants = 8;
-        use_hf = hf != nullptr;
-        if (use_hf) {
-            RPH_TRY(d_hf.alloc(n));
-            RPH_HIP_CHECK(hipMemcpyAsync(d_hf.data(), hf, n, hipMemcpyHostToDevice, s));
-        }
-        RPH_TRY(d_var.alloc(n * 256));
-        const uint64_t step = 1u << 18;  // 256 MiB of coefficients per piece
-        RPH_TRY(d_stage.alloc(std::min<uint64_t>(step, n) * 1024));
-        for (uint64_t first = 0; first < n; first += step) {
-            const uint32_t m = (uint32_t)std::min<uint64_t>(step, n - first);
-            RPH_HIP_CHECK(hipMemcpyAsync(d_stage.data(), coeffs + first * 256, (size_t)m * 1024, hipMemcpyHostToDevice, s));
-            RPH_TRY(rph_launch_pdq_from_coeffs((const float *)d_stage.data(), m, nullptr, d_var.as<uint8_t>() + first * 256, s));
-        }
-        if (use_hf) RPH_TRY(rph_launch_featureless_variants(d_h.as<uint8_t>(), d_hf.as<uint8_t>(), n, d_var.as<uint8_t>(), s));
-        return RPH_OK;
-    }
-};
-}  // namespace
-
 int rph_group_files_pdq_append(rph_ctx *ctx, const uint8_t *old_hashes32, const float *old_coeffs, const uint8_t *old_has_features,
                                const int32_t *old_quality, uint64_t n_old, const uint32_t *old_members, const uint32_t *old_offsets,
                                uint32_t n_old_groups, const uint8_t *new_hashes32, const float *new_coeffs, const uint8_t *new_has_features,
@@ -1095,12 +1065,7 @@ int rph_group_files_pdq_append(rph_ctx *ctx, const uint8_t *old_hashes32, const 
             rph_set_error("rph_group_files_pdq_append: null argument");
             return RPH_ERR_INVALID_ARG;
         }
-        if (similarity > RPH_MAX_SIMILARITY_256) {
-            // scanner.rs:1650-1655 asserts this
-            rph_set_error("Similarity distances above %u require R=4 bit-flip checks, which are not implemented.",
-                          RPH_MAX_SIMILARITY_256);
-            return RPH_ERR_INVALID_ARG;
-        }
+        RPH_TRY(check_similarity(similarity));
         const uint64_t n_total = n_old + n_new;
         if (n_total > 0xFFFFFFFFull) {
             rph_set_error("rph_group_files_pdq_append: %llu files, at most 2^32 - 1", (unsigned long long)n_total);
@@ -1117,40 +1082,23 @@ int rph_group_files_pdq_append(rph_ctx *ctx, const uint8_t *old_hashes32, const 
             // the library comes first: the pairs the new files add are (library variants x new hashes), all of them, and
             // (new variants x new hashes, i < j).  The library's variants are only needed as rows; the new files are rows and columns.
             GroupSide lib, add;
-            std::vector<uint8_t> lc_old, lc_new;
-            RPH_TRY(lib.upload(old_hashes32, old_coeffs, old_has_features, old_quality, n_old, true, lc_old, s));
-            RPH_TRY(add.upload(new_hashes32, new_coeffs, new_has_features, new_quality, n_new, n_new > 1, lc_new, s));
-            DevBuf d_e, d_cnt;
-            uint64_t cap = std::max<uint64_t>(1u << 20, 32 * n_new);
-            RPH_TRY(d_cnt.alloc(8));
-            for (int attempt = 0;; attempt++) {
-                RPH_TRY(d_e.alloc(cap * sizeof(rph_edge)));
-                RPH_HIP_CHECK(hipMemsetAsync(d_cnt.data(), 0, 8, s));
-                unsigned long long n_cross = 0, found = 0;
-                if (n_old)
-                    RPH_TRY(rph_launch_hamming_cross_sweep(ctx, lib.rows(), lib.n_variants, lib.low_conf(), lib.has_features(), n_old, add.d_h.data(),
-                                                           add.low_conf(), n_new, similarity, 0, 1, d_e.as<rph_edge>(), cap,
-                                                           d_cnt.as<unsigned long long>(), s, ctx->hamming_kernel));
-                RPH_HIP_CHECK(hipMemcpyAsync(&n_cross, d_cnt.data(), 8, hipMemcpyDeviceToHost, s));
-                // the triangular sweep of the new files appends behind the cross edges (one cursor); its indices are local to the new set
-                RPH_TRY(rph_launch_hamming_sweep(ctx, add.rows(), add.n_variants, add.d_h.data(), add.low_conf(), add.has_features(), n_new, similarity,
-                                                 0, 1, d_e.as<rph_edge>(), cap, d_cnt.as<unsigned long long>(), s, ctx->hamming_kernel));
-                RPH_HIP_CHECK(hipMemcpyAsync(&found, d_cnt.data(), 8, hipMemcpyDeviceToHost, s));
-                RPH_HIP_CHECK(hipStreamSynchronize(s));
-                if (found <= cap) {
-                    edges.resize(found);
-                    if (found) RPH_HIP_CHECK(hipMemcpy(edges.data(), d_e.data(), found * sizeof(rph_edge), hipMemcpyDeviceToHost));
-                    for (uint64_t e = 0; e < found; e++) {  // to the numbering of the concatenation
-                        if (e >= n_cross) edges[e].i += (uint32_t)n_old;
-                        edges[e].j += (uint32_t)n_old;
-                    }
-                    break;
-                }
-                if (attempt >= 2) {
-                    rph_set_error("rph_group_files_pdq_append: edge list kept growing (%llu)", found);
-                    return RPH_ERR_CAPACITY;
-                }
-                cap = found + found / 16 + 1024;
+            RPH_TRY(lib.upload(old_hashes32, old_coeffs, old_has_features, old_quality, n_old, true, s));
+            RPH_TRY(add.upload(new_hashes32, new_coeffs, new_has_features, new_quality, n_new, n_new > 1, s));
+            rph_sweep cross = lib.sweep(similarity, &add), within = add.sweep(similarity);
+            unsigned long long n_cross = 0;
+            RPH_TRY(sweep_growing("rph_group_files_pdq_append", std::max<uint64_t>(1u << 20, 32 * n_new), RPH_GROW_GROUP_FILES, s, edges,
+                                  [&](EdgeSink &sink, uint64_t cap) -> int {
+                                      RPH_TRY(sink.open(cap, s, cross));
+                                      if (n_old) RPH_TRY(rph_launch_hamming_sweep(ctx, cross, s, ctx->hamming_kernel));
+                                      RPH_TRY(sink.read(&n_cross, s));
+                                      // the triangular sweep of the new files appends behind the cross edges (one cursor); its indices
+                                      // are local to the new set
+                                      within = into(within, cross.edges, cross.cap, cross.count);
+                                      return rph_launch_hamming_sweep(ctx, within, s, ctx->hamming_kernel);
+                                  }));
+            for (uint64_t e = 0; e < edges.size(); e++) {  // to the numbering of the concatenation
+                if (e >= n_cross) edges[e].i += (uint32_t)n_old;
+                edges[e].j += (uint32_t)n_old;
             }
         }
         if (new_comparisons_out) *new_comparisons_out = edges.size();

@@ -154,14 +154,38 @@ void rph_ragged_forget(rph_ctx *ctx);
 int rph_launch_pdq_from_coeffs(const float *d_coeffs, uint32_t n, uint8_t *d_hash, uint8_t *d_dihedral, hipStream_t stream);
 int rph_launch_lowconf_from_quality(const float *d_quality, const uint8_t *d_valid, uint64_t n, uint8_t *d_low, hipStream_t stream);
 int rph_launch_featureless_variants(const uint8_t *d_hashes, const uint8_t *d_has_features, uint64_t n, uint8_t *d_variants, hipStream_t stream);
-// hamming_kernels.hip
-int rph_launch_hamming_sweep(rph_ctx *ctx, const uint8_t *d_rows, uint32_t n_variants, const uint8_t *d_cols, const uint8_t *d_low_conf,
-                             const uint8_t *d_has_features, uint64_t n, uint32_t threshold, uint32_t part, uint32_t nparts, rph_edge *d_edges,
-                             uint64_t cap, unsigned long long *d_count, hipStream_t stream, int use_mfma);
-// cross form: set A (n_a files x n_variants, its own flags) against set B (n_b hashes, its own flags), every pair; e.i indexes A, e.j B
-int rph_launch_hamming_cross_sweep(rph_ctx *ctx, const uint8_t *d_a, uint32_t n_variants, const uint8_t *d_low_conf_a, const uint8_t *d_has_features_a,
-                                   uint64_t n_a, const uint8_t *d_b, const uint8_t *d_low_conf_b, uint64_t n_b, uint32_t threshold, uint32_t part,
-                                   uint32_t nparts, rph_edge *d_edges, uint64_t cap, unsigned long long *d_count, hipStream_t stream, int use_mfma);
+// hamming_kernels.hip: one request of a Hamming sweep, in device pointers (rph_api.cpp also fills one with a host form's arrays before it
+// uploads them; there a square request may leave `rows` null: its hashes are its rows).  Rows: n files of n_variants (1 or 8) 32-byte
+// hashes each, [n][n_variants][32], with the files' flags (either may be null; has_features: files with 0 only own variant 0).  Columns:
+// the hashes [n][32] of the SAME files -- the square form, which reports i < j; with one variant `cols` may be `rows` itself -- or, with
+// `cross`, another set of n_cols hashes with flags of its own, every pair reported, e.i indexing the rows and e.j the columns.  bits64:
+// rows == cols are n little-endian u64 hashes (square, no flags).  Edges are appended at edges[*count], the first `cap` of them written, all
+// of them counted.
+struct rph_sweep {
+    const void *rows = nullptr;
+    uint32_t n_variants = 1;
+    const uint8_t *low_conf = nullptr, *has_features = nullptr;
+    uint64_t n = 0;
+    const void *cols = nullptr;
+    bool cross = false, bits64 = false;
+    const uint8_t *low_conf_cols = nullptr;
+    uint64_t n_cols = 0;
+    uint32_t threshold = 0, part = 0, nparts = 1;
+    rph_edge *edges = nullptr;
+    uint64_t cap = 0;
+    unsigned long long *count = nullptr;
+};
+// RPH_ERR_INVALID_ARG for a part that is none, a number of variants other than 1 or 8, or a set of 2^32 files; the launcher's first step
+int rph_hamming_sweep_check(const rph_sweep &q);
+int rph_launch_hamming_sweep(rph_ctx *ctx, const rph_sweep &q, hipStream_t stream, int use_mfma);
+// How an edge buffer that proved too small grows (rph_api.cpp: sweep_growing; multi.cpp: sweep_all): to what the sweep counted plus a
+// margin, for a bounded number of attempts.  The find_groups calls and the grouping calls have always differed in both numbers.
+struct rph_edge_growth {
+    int attempts;
+    uint64_t margin_div;
+    uint64_t next_cap(uint64_t found) const { return found + found / margin_div + 1024; }
+};
+constexpr rph_edge_growth RPH_GROW_FIND_GROUPS{8, 8}, RPH_GROW_GROUP_FILES{3, 16};
 // which set a cross sweep puts on the row side, its segment length and block count (exported for the tests, not in the header)
 extern "C" void rph_debug_hamming_cross_layout(uint64_t n_a, uint32_t n_variants, uint64_t n_b, uint32_t nparts, int kernel, uint32_t *swap_out,
                                                uint32_t *seg_tiles_out, uint32_t *n_col_segs_out, uint64_t *n_blocks_out);
@@ -169,8 +193,6 @@ extern "C" void rph_debug_hamming_cross_layout(uint64_t n_a, uint32_t n_variants
 // calls, the files of each (the first `cap` of them into sizes_out) and, for WebP, the number of parse windows (exported for the tests,
 // not in the header; any of the three outputs may be null)
 extern "C" int rph_debug_file_chunks(rph_ctx *ctx, int format, uint32_t *sizes_out, uint32_t cap, uint32_t *n_chunks_out, uint32_t *n_windows_out);
-int rph_launch_hamming64_sweep(const uint64_t *d_hashes, uint64_t n, uint32_t threshold, uint32_t part, uint32_t nparts,
-                               rph_edge *d_edges, uint64_t cap, unsigned long long *d_count, hipStream_t stream, int use_mfma);
 int rph_launch_mih_build256(rph_ctx *ctx, const uint8_t *d_hashes, uint64_t n, uint32_t *d_offsets, uint32_t *d_values,
                             hipStream_t stream);
 int rph_launch_mih_build64(rph_ctx *ctx, const uint64_t *d_hashes, uint64_t n, uint32_t *d_offsets, uint32_t *d_values,

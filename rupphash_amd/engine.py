@@ -632,19 +632,25 @@ class Engine:
               "rph_pdq_hashes_from_coeffs_dev")
 
     # ---- Hamming ----
-    def hamming_all_pairs(self, hashes, threshold, part=0, nparts=1, cap=None):
-        hashes = np.ascontiguousarray(hashes, np.uint8).reshape(-1, 32)
-        n = len(hashes)
-        cap = max(1 << 16, 4 * n) if cap is None else cap
+    @staticmethod
+    def _sweep_growing(call, cap, grow, where):
+        """The edges of call(edges, cap, found) -> status, a host sweep into a buffer of `cap` edges.  While it answers RPH_ERR_CAPACITY and
+        `grow` is set, again into a buffer with room for what it found."""
         while True:
             edges = np.zeros(cap, EDGE_DTYPE)
             found = C.c_uint64()
-            rc = self.L.rph_hamming_all_pairs(self.ctx, _ptr(hashes), n, threshold, part, nparts, _ptr(edges), cap, C.byref(found))
-            if rc == _lib.RPH_ERR_CAPACITY:
+            rc = call(_ptr(edges), cap, C.byref(found))
+            if rc == _lib.RPH_ERR_CAPACITY and grow:
                 cap = int(found.value) + 1024
                 continue
-            check(rc, "rph_hamming_all_pairs")
+            check(rc, where)
             return edges[: found.value]
+
+    def hamming_all_pairs(self, hashes, threshold, part=0, nparts=1, cap=None):
+        hashes = np.ascontiguousarray(hashes, np.uint8).reshape(-1, 32)
+        n = len(hashes)
+        return self._sweep_growing(lambda e, c, f: self.L.rph_hamming_all_pairs(self.ctx, _ptr(hashes), n, threshold, part, nparts, e, c, f),
+                                   max(1 << 16, 4 * n) if cap is None else cap, True, "rph_hamming_all_pairs")
 
     def hamming_all_pairs_dev(self, d_hashes, n, threshold, d_edges, cap, d_count, part=0, nparts=1, stream=None):
         check(self.L.rph_hamming_all_pairs_dev(self.ctx, d_hashes, n, threshold, part, nparts, d_edges, cap, d_count, stream),
@@ -656,17 +662,9 @@ class Engine:
         variants = np.ascontiguousarray(variants, np.uint8).reshape(n, -1, 32)
         nv = variants.shape[1]
         lc = None if low_conf is None else np.ascontiguousarray(low_conf, np.uint8)
-        cap = max(1 << 16, 8 * n) if cap is None else cap
-        while True:
-            edges = np.zeros(cap, EDGE_DTYPE)
-            found = C.c_uint64()
-            rc = self.L.rph_hamming_variant_pairs(self.ctx, _ptr(variants), nv, _ptr(hashes), _ptr(lc), n, similarity, part,
-                                                  nparts, _ptr(edges), cap, C.byref(found))
-            if rc == _lib.RPH_ERR_CAPACITY:
-                cap = int(found.value) + 1024
-                continue
-            check(rc, "rph_hamming_variant_pairs")
-            return edges[: found.value]
+        return self._sweep_growing(lambda e, c, f: self.L.rph_hamming_variant_pairs(self.ctx, _ptr(variants), nv, _ptr(hashes), _ptr(lc), n, similarity,
+                                                                                    part, nparts, e, c, f),
+                                   max(1 << 16, 8 * n) if cap is None else cap, True, "rph_hamming_variant_pairs")
 
     def hamming_variant_pairs_dev(self, d_variants, n_variants, d_hashes, n, similarity, d_edges, cap, d_count, d_low_conf=None,
                                   part=0, nparts=1, stream=None):
@@ -689,23 +687,13 @@ class Engine:
         n_a, nv, n_b = variants_a.shape[0], variants_a.shape[1], len(hashes_b)
         la = None if low_conf_a is None else np.ascontiguousarray(low_conf_a, np.uint8)
         lb = None if low_conf_b is None else np.ascontiguousarray(low_conf_b, np.uint8)
-        grow = cap is None
-        cap = max(1 << 16, 8 * (n_a + n_b)) if cap is None else cap
-        plain = nv == 1 and la is None and lb is None
-        while True:
-            edges = np.zeros(cap, EDGE_DTYPE)
-            found = C.c_uint64()
-            if plain:
-                rc = self.L.rph_hamming_cross_pairs(self.ctx, _ptr(variants_a), n_a, _ptr(hashes_b), n_b, similarity, part, nparts, _ptr(edges), cap,
-                                                    C.byref(found))
-            else:
-                rc = self.L.rph_hamming_variant_cross_pairs(self.ctx, _ptr(variants_a), nv, _ptr(la), n_a, _ptr(hashes_b), _ptr(lb), n_b, similarity,
-                                                            part, nparts, _ptr(edges), cap, C.byref(found))
-            if rc == _lib.RPH_ERR_CAPACITY and grow:
-                cap = int(found.value) + 1024
-                continue
-            check(rc, "rph_hamming_cross_pairs" if plain else "rph_hamming_variant_cross_pairs")
-            return edges[: found.value]
+        start = max(1 << 16, 8 * (n_a + n_b)) if cap is None else cap
+        if nv == 1 and la is None and lb is None:
+            return self._sweep_growing(lambda e, c, f: self.L.rph_hamming_cross_pairs(self.ctx, _ptr(variants_a), n_a, _ptr(hashes_b), n_b, similarity, part,
+                                                                                      nparts, e, c, f), start, cap is None, "rph_hamming_cross_pairs")
+        return self._sweep_growing(lambda e, c, f: self.L.rph_hamming_variant_cross_pairs(self.ctx, _ptr(variants_a), nv, _ptr(la), n_a, _ptr(hashes_b),
+                                                                                          _ptr(lb), n_b, similarity, part, nparts, e, c, f),
+                                   start, cap is None, "rph_hamming_variant_cross_pairs")
 
     def hamming_variant_cross_pairs_dev(self, d_variants_a, n_variants, n_a, d_hashes_b, n_b, similarity, d_edges, cap, d_count, d_low_conf_a=None,
                                         d_low_conf_b=None, part=0, nparts=1, stream=None):
@@ -735,16 +723,8 @@ class Engine:
     def hamming_all_pairs64(self, hashes, threshold, part=0, nparts=1, cap=None):
         hashes = np.ascontiguousarray(hashes, np.uint64)
         n = len(hashes)
-        cap = max(1 << 16, 4 * n) if cap is None else cap
-        while True:
-            edges = np.zeros(cap, EDGE_DTYPE)
-            found = C.c_uint64()
-            rc = self.L.rph_hamming_all_pairs64(self.ctx, _ptr(hashes), n, threshold, part, nparts, _ptr(edges), cap, C.byref(found))
-            if rc == _lib.RPH_ERR_CAPACITY:
-                cap = int(found.value) + 1024
-                continue
-            check(rc, "rph_hamming_all_pairs64")
-            return edges[: found.value]
+        return self._sweep_growing(lambda e, c, f: self.L.rph_hamming_all_pairs64(self.ctx, _ptr(hashes), n, threshold, part, nparts, e, c, f),
+                                   max(1 << 16, 4 * n) if cap is None else cap, True, "rph_hamming_all_pairs64")
 
     def hamming_all_pairs64_dev(self, d_hashes, n, threshold, d_edges, cap, d_count, part=0, nparts=1, stream=None):
         check(self.L.rph_hamming_all_pairs64_dev(self.ctx, d_hashes, n, threshold, part, nparts, d_edges, cap, d_count, stream),
@@ -990,16 +970,8 @@ class MultiEngine:
     def hamming_all_pairs(self, hashes, threshold, cap=None):
         hashes = np.ascontiguousarray(hashes, np.uint8).reshape(-1, 32)
         n = len(hashes)
-        cap = max(1 << 16, 4 * n) if cap is None else cap
-        while True:
-            edges = np.zeros(cap, EDGE_DTYPE)
-            found = C.c_uint64()
-            rc = self.L.rph_multi_hamming_all_pairs(self.m, _ptr(hashes), n, threshold, _ptr(edges), cap, C.byref(found))
-            if rc == _lib.RPH_ERR_CAPACITY:
-                cap = int(found.value) + 1024
-                continue
-            check(rc, "rph_multi_hamming_all_pairs")
-            return edges[: found.value]
+        return Engine._sweep_growing(lambda e, c, f: self.L.rph_multi_hamming_all_pairs(self.m, _ptr(hashes), n, threshold, e, c, f),
+                                     max(1 << 16, 4 * n) if cap is None else cap, True, "rph_multi_hamming_all_pairs")
 
     def hash_and_group(self, images, similarity, want_coeffs=False):
         """images: uint8 (n,h,w,3|4) or (n,h,w).  Returns dict(hash, quality, coeffs, valid, groups, comparison_count)."""
