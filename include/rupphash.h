@@ -375,6 +375,56 @@ int rph_union_find_groups_append(const uint32_t *old_members, const uint32_t *ol
                                  const rph_edge *edges, uint64_t n_edges, uint64_t n_total, uint32_t *members,
                                  uint32_t *offsets, uint32_t *n_groups_out);
 
+/*
+ * The union-find on the device (scanner.rs:1781-1817), over an edge list that a sweep left there.
+ * d_labels: n uint32, in/out.  On entry a forest with d_labels[x] <= x (identity for a fresh set; the labels an earlier call left).
+ * Every edge e of d_edges[0 .. n_edges) unites e.i + i_base and e.j + j_base.  On exit d_labels[x] is the SMALLEST index of x's
+ * component, for every x (flattened); the result does not depend on the order of the edges.  An edge that names a file >= n, or a
+ * label above its file: RPH_ERR_INVALID_ARG, labels untouched.  n at most 2^31 - 1.  The call waits for its range check (it
+ * synchronises `stream` once); the unions and the flattening are asynchronous on `stream`.
+ */
+int rph_union_find_labels_dev(rph_ctx *ctx, const void *d_edges, uint64_t n_edges, uint32_t i_base, uint32_t j_base,
+                              void *d_labels, uint64_t n, void *stream);
+/* Flattened labels -> the groups of rph_union_find_groups: components with > 1 member, members ascending inside a group, groups
+ * ordered by first member.  members / offsets are host arrays of capacity n and n / 2 + 2.  Labels that are not flattened
+ * min-labels (label[x] > x, or label[label[x]] != label[x]) and n above 2^31 - 1: RPH_ERR_INVALID_ARG. */
+int rph_groups_from_labels_dev(rph_ctx *ctx, const void *d_labels, uint64_t n, uint32_t *members, uint32_t *offsets,
+                               uint32_t *n_groups_out, void *stream);
+
+/*
+ * A grouped library that stays on the device: hashes, the 8 variant rows of every file, flags and component labels live in HBM
+ * between calls (294 bytes per file), so that an append moves and sweeps the new files only and a query moves the queries only.
+ * The result is rph_group_files_pdq on everything appended so far, in order.  One similarity per library; at most 2^31 - 1 files;
+ * files cannot be removed (a union-find does not split).  One library serves one call at a time (calls from several threads
+ * queue); several libraries on one context are independent.  Destroy every library before rph_shutdown of its context.
+ */
+typedef struct rph_library rph_library;
+int rph_library_create(rph_ctx *ctx, uint32_t similarity, rph_library **lib_out);   /* similarity > RPH_MAX_SIMILARITY_256: RPH_ERR_INVALID_ARG */
+int rph_library_destroy(rph_library *lib);
+int rph_library_reserve(rph_library *lib, uint64_t n_files);                        /* room for n_files without another growth */
+int rph_library_size(rph_library *lib, uint64_t *n_files_out, uint64_t *comparisons_out);
+/* The new files become n .. n + n_new - 1.  Arguments per file as rph_group_files_pdq: coeffs NULL = these files have no features
+ * (has_features 0, one variant: scanner.rs:1624-1627); has_features only counts next to coeffs; quality NULL = none low-confidence.
+ * labels_out (nullable, n_new): for each new file the smallest index of the component it is in now (its own index if it is alone).
+ * All or nothing: an error (a null argument, the 2^31 - 1 limit, an edge list that kept growing, an allocation that failed) leaves
+ * size, labels and comparison count as they were.  Excepted: a HIP call that fails once the unions have been launched (RPH_ERR_HIP, a
+ * device lost to the context) leaves size and count, but resident labels may already be merged.  n_new == 0: RPH_OK, nothing changes. */
+int rph_library_append(rph_library *lib, const uint8_t *hashes32, const float *coeffs, const uint8_t *has_features,
+                       const int32_t *quality, uint64_t n_new, uint32_t *labels_out, uint64_t *new_comparisons_out);
+/* Start from what an earlier run kept: files plus their groups as rph_group_files_pdq / _append / rph_library_groups returned them, for the
+ * SAME similarity; no sweep.  Only on an empty library.  The groups are checked as rph_union_find_groups_append checks them. */
+int rph_library_restore(rph_library *lib, const uint8_t *hashes32, const float *coeffs, const uint8_t *has_features,
+                        const int32_t *quality, uint64_t n, const uint32_t *members, const uint32_t *offsets, uint32_t n_groups,
+                        uint64_t comparisons);
+/* members capacity size, offsets capacity size / 2 + 2: identical to rph_group_files_pdq on everything appended so far, in order. */
+int rph_library_groups(rph_library *lib, uint32_t *members, uint32_t *offsets, uint32_t *n_groups_out);
+/* first + count <= size */
+int rph_library_labels(rph_library *lib, uint64_t first, uint64_t count, uint32_t *labels_out);
+/* The library is not changed: every (library file i, variant v, query j) with d(variant_v(i), hash_q(j)) <= limit, the edge convention and
+ * capacity protocol of rph_hamming_variant_cross_pairs (e.i library, e.j query); quality_q nullable. */
+int rph_library_query(rph_library *lib, const uint8_t *hashes32_q, const int32_t *quality_q, uint64_t n_q, rph_edge *edges,
+                      uint64_t cap, uint64_t *n_edges_out);
+
 /* is_low_pdq_quality (scanner.rs:1592-1594); quality < 0 encodes None. */
 int rph_is_low_pdq_quality(int32_t quality);
 

@@ -117,6 +117,17 @@ SIGNATURES = {
     "rph_group_files_pdq_append": (C.c_int, [_vp, _u8p, _f32p, _u8p, _i32p, C.c_uint64, _u32p, _u32p, C.c_uint32, _u8p, _f32p, _u8p, _i32p,
                                              C.c_uint64, C.c_uint32, _u32p, _u32p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "rph_union_find_groups_append": (C.c_int, [_u32p, _u32p, C.c_uint32, _vp, C.c_uint64, C.c_uint64, _u32p, _u32p, C.POINTER(C.c_uint32)]),
+    "rph_union_find_labels_dev": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _vp]),
+    "rph_groups_from_labels_dev": (C.c_int, [_vp, _vp, C.c_uint64, _u32p, _u32p, C.POINTER(C.c_uint32), _vp]),
+    "rph_library_create": (C.c_int, [_vp, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "rph_library_destroy": (C.c_int, [_vp]),
+    "rph_library_reserve": (C.c_int, [_vp, C.c_uint64]),
+    "rph_library_size": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "rph_library_append": (C.c_int, [_vp, _u8p, _f32p, _u8p, _i32p, C.c_uint64, _u32p, C.POINTER(C.c_uint64)]),
+    "rph_library_restore": (C.c_int, [_vp, _u8p, _f32p, _u8p, _i32p, C.c_uint64, _u32p, _u32p, C.c_uint32, C.c_uint64]),
+    "rph_library_groups": (C.c_int, [_vp, _u32p, _u32p, C.POINTER(C.c_uint32)]),
+    "rph_library_labels": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _u32p]),
+    "rph_library_query": (C.c_int, [_vp, _u8p, _i32p, C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "rph_is_low_pdq_quality": (C.c_int, [C.c_int32]),
     "rph_mih_build256": (C.c_int, [_vp, _u8p, C.c_uint64, _u32p, _u32p]),
     "rph_mih_build64": (C.c_int, [_vp, _u64p, C.c_uint64, _u32p, _u32p]),
@@ -198,6 +209,7 @@ DEBUG_SIGNATURES = {
     "rph_debug_hamming_cross_layout": (None, [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                               C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "rph_debug_file_chunks": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "rph_debug_library_stages": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_float)]),
 }
 
 _lib = None

@@ -1,0 +1,346 @@
+// library.cpp -- rph_library: a grouped set of files that stays on the device (include/rupphash.h).  What rph_group_files_pdq_append
+// moves, expands and re-unions on every call -- the library's hashes, its variants, its flags and its components -- is kept in HBM
+// between calls: an append uploads the new files only, sweeps the pairs they add and unites the edges where the sweep left them
+// (components.hip); a query sweeps without changing anything.
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "rph_internal.h"
+
+struct rph_library {
+    rph_ctx *ctx = nullptr;
+    uint32_t similarity = 0;
+    std::mutex mu;  // one call at a time
+    // resident, `cap` files of room each: hashes [32], variants [8][32] (always 8 rows; files without features repeat their hash and
+    // carry has_features 0, which keeps them to variant 0 on the row side), low-confidence and has_features flags, min-labels
+    DevBuf d_h, d_var, d_lc, d_hf, d_lab;
+    uint64_t n = 0, cap = 0, want_cap = 1024, comparisons = 0;
+    // per call, kept: coefficient staging (GroupSide::upload's pieces), the edge list and its cursor, a query's hashes and flags
+    DevBuf d_stage, d_edges, d_cnt, d_qh, d_qlc;
+    std::vector<uint8_t> low_host;
+    // rph_debug_library_stages: events around the stages of the last append (created on the first request)
+    bool profile = false, staged = false;  // armed; an append has recorded all six since
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+};
+
+namespace {
+constexpr uint64_t MAX_FILES = 0x7FFFFFFFull;  // the export's hipCUB calls count in int
+constexpr uint64_t COEFF_STEP = 1u << 18;      // 256 MiB of coefficients per piece
+
+int fail(const char *who, const char *what)
+{
+    rph_set_error("%s: %s", who, what);
+    return RPH_ERR_INVALID_ARG;
+}
+
+// room for `need` files: geometric growth, device-to-device copy of the resident part, old buffers freed once the stream is through
+// with them.  The new buffers are all allocated before anything is replaced: a failure leaves the library as it was.
+int grow(rph_library *lib, uint64_t need, hipStream_t s)
+{
+    if (need <= lib->cap) return RPH_OK;
+    uint64_t cap = std::max<uint64_t>(lib->want_cap, 1024);
+    while (cap < need) cap *= 2;
+    cap = std::min(cap, MAX_FILES);
+    DevBuf *cur[5] = {&lib->d_h, &lib->d_var, &lib->d_lc, &lib->d_hf, &lib->d_lab};
+    const size_t width[5] = {32, 256, 1, 1, 4};
+    DevBuf next[5];
+    for (int k = 0; k < 5; k++) RPH_TRY(next[k].alloc(cap * width[k]));
+    for (int k = 0; k < 5 && lib->n; k++) RPH_HIP_CHECK(hipMemcpyAsync(next[k].data(), cur[k]->data(), lib->n * width[k], hipMemcpyDeviceToDevice, s));
+    RPH_HIP_CHECK(hipStreamSynchronize(s));
+    for (int k = 0; k < 5; k++) *cur[k] = std::move(next[k]);
+    lib->cap = cap;
+    return RPH_OK;
+}
+
+// `count` files behind the resident ones (which are not touched and whose number does not change): hashes, flags and variants
+int upload_behind(rph_library *lib, const uint8_t *hashes32, const float *coeffs, const uint8_t *hf, const int32_t *quality, uint64_t count, hipStream_t s)
+{
+    const uint64_t at = lib->n;
+    RPH_HIP_CHECK(hipMemcpyAsync(lib->d_h.data() + at * 32, hashes32, count * 32, hipMemcpyHostToDevice, s));
+    if (quality) {
+        lib->low_host.resize(count);
+        for (uint64_t i = 0; i < count; i++) lib->low_host[i] = (uint8_t)rph_is_low_pdq_quality(quality[i]);
+        RPH_HIP_CHECK(hipMemcpyAsync(lib->d_lc.data() + at, lib->low_host.data(), count, hipMemcpyHostToDevice, s));
+    } else {
+        RPH_HIP_CHECK(hipMemsetAsync(lib->d_lc.data() + at, 0, count, s));
+    }
+    if (coeffs && hf)
+        RPH_HIP_CHECK(hipMemcpyAsync(lib->d_hf.data() + at, hf, count, hipMemcpyHostToDevice, s));
+    else
+        RPH_HIP_CHECK(hipMemsetAsync(lib->d_hf.data() + at, coeffs ? 1 : 0, count, s));
+    if (coeffs) {
+        RPH_TRY(lib->d_stage.reserve(std::min(COEFF_STEP, count) * 1024, s));
+        for (uint64_t first = 0; first < count; first += COEFF_STEP) {
+            const uint32_t m = (uint32_t)std::min(COEFF_STEP, count - first);
+            RPH_HIP_CHECK(hipMemcpyAsync(lib->d_stage.data(), coeffs + first * 256, (size_t)m * 1024, hipMemcpyHostToDevice, s));
+            RPH_TRY(rph_launch_pdq_from_coeffs((const float *)lib->d_stage.data(), m, nullptr, lib->d_var.data() + (at + first) * 256, s));
+        }
+    }
+    // files without features (all of them when there are no coefficients): every row is the hash
+    if (!coeffs || hf) RPH_TRY(rph_launch_featureless_variants(lib->d_h.data() + at * 32, lib->d_hf.data() + at, count, lib->d_var.data() + at * 256, s));
+    return RPH_OK;
+}
+
+int mark(rph_library *lib, int k, hipStream_t s)
+{
+    if (lib->profile) RPH_HIP_CHECK(hipEventRecord(lib->ev[k], s));
+    return RPH_OK;
+}
+
+// the two requests of rph_group_files_pdq_append: the resident files' variants against the new hashes (every pair), and the new files'
+// variants against their own hashes (i < j, indices local to the new set)
+rph_sweep sweep_of(const rph_library *lib, uint64_t row_first, uint64_t n_rows, uint64_t col_first, uint64_t n_cols, bool cross)
+{
+    rph_sweep q;
+    q.rows = lib->d_var.data() + row_first * 256, q.n_variants = 8, q.n = n_rows;
+    q.low_conf = lib->d_lc.data() + row_first, q.has_features = lib->d_hf.data() + row_first;
+    q.cols = lib->d_h.data() + col_first * 32;
+    q.threshold = lib->similarity;
+    if (cross) q.cross = true, q.low_conf_cols = lib->d_lc.data() + col_first, q.n_cols = n_cols;
+    return q;
+}
+
+int append(rph_library *lib, const uint8_t *hashes32, const float *coeffs, const uint8_t *hf, const int32_t *quality, uint64_t n_new, uint32_t *labels_out,
+           uint64_t *new_comparisons_out)
+{
+    rph_ctx *ctx = lib->ctx;
+    hipStream_t s = ctx->stream;
+    const uint64_t n = lib->n;
+    RPH_TRY(mark(lib, 0, s));
+    RPH_TRY(grow(lib, n + n_new, s));
+    RPH_TRY(upload_behind(lib, hashes32, coeffs, hf, quality, n_new, s));
+    RPH_TRY(mark(lib, 1, s));
+    rph_sweep cross = sweep_of(lib, 0, n, n, n_new, true), within = sweep_of(lib, n, n_new, n, n_new, false);
+    if (!lib->d_cnt.data()) RPH_TRY(lib->d_cnt.alloc(8));
+    uint64_t cap = std::max<uint64_t>(1u << 20, 32 * n_new);
+    unsigned long long found[2] = {0, 0};  // behind the cross sweep, behind both
+    for (int attempt = 0;; attempt++) {
+        if (attempt == RPH_GROW_GROUP_FILES.attempts) {
+            rph_set_error("rph_library_append: edge list kept growing (%llu)", found[1]);
+            return RPH_ERR_CAPACITY;
+        }
+        RPH_TRY(lib->d_edges.reserve(cap * sizeof(rph_edge), s));
+        cap = lib->d_edges.capacity() / sizeof(rph_edge);
+        RPH_HIP_CHECK(hipMemsetAsync(lib->d_cnt.data(), 0, 8, s));
+        cross.edges = within.edges = lib->d_edges.as<rph_edge>();
+        cross.cap = within.cap = cap;
+        cross.count = within.count = lib->d_cnt.as<unsigned long long>();
+        RPH_TRY(rph_launch_hamming_sweep(ctx, cross, s, ctx->hamming_kernel));
+        RPH_HIP_CHECK(hipMemcpyAsync(&found[0], lib->d_cnt.data(), 8, hipMemcpyDeviceToHost, s));
+        RPH_TRY(mark(lib, 2, s));
+        RPH_TRY(rph_launch_hamming_sweep(ctx, within, s, ctx->hamming_kernel));  // appends behind the cross edges: one cursor
+        RPH_TRY(mark(lib, 3, s));
+        RPH_HIP_CHECK(hipMemcpyAsync(&found[1], lib->d_cnt.data(), 8, hipMemcpyDeviceToHost, s));  // only the cursor comes back
+        RPH_HIP_CHECK(hipStreamSynchronize(s));
+        if (found[1] <= cap) break;
+        cap = RPH_GROW_GROUP_FILES.next_cap(found[1]);
+    }
+    // The new files start as components of their own (behind the size: not part of the library yet).  Then the edges where the sweeps
+    // left them, the cross edges (library index, new-local index) and the inner ones (both new-local): one range check, which is the last
+    // thing that can refuse, two union launches, one flatten.  From the first union launch the resident labels change; what can still
+    // fail after it is a HIP call, that is a device that is lost to this context anyway.
+    const rph_edge *e = lib->d_edges.as<rph_edge>();
+    uint32_t *lab = lib->d_lab.as<uint32_t>();
+    std::vector<uint32_t> own(n_new);
+    for (uint64_t i = 0; i < n_new; i++) own[i] = (uint32_t)(n + i);
+    RPH_HIP_CHECK(hipMemcpyAsync(lab + n, own.data(), n_new * 4, hipMemcpyHostToDevice, s));
+    RPH_HIP_CHECK(hipStreamSynchronize(s));
+    const rph_union_edges sets[2] = {{e, found[0], 0, (uint32_t)n}, {e + found[0], found[1] - found[0], (uint32_t)n, (uint32_t)n}};
+    RPH_TRY(rph_union_find_labels(ctx, sets, 2, lab, n + n_new, s));
+    RPH_TRY(mark(lib, 4, s));
+    if (labels_out) RPH_HIP_CHECK(hipMemcpyAsync(labels_out, lab + n, n_new * 4, hipMemcpyDeviceToHost, s));
+    RPH_TRY(mark(lib, 5, s));
+    RPH_HIP_CHECK(hipStreamSynchronize(s));
+    lib->staged = lib->profile;
+    lib->n = n + n_new;
+    lib->comparisons += found[1];
+    if (new_comparisons_out) *new_comparisons_out = found[1];
+    return RPH_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int rph_library_create(rph_ctx *ctx, uint32_t similarity, rph_library **lib_out)
+{
+    return rph_guarded("rph_library_create", [&]() -> int {
+        if (!ctx || !lib_out) return fail("rph_library_create", "null argument");
+        *lib_out = nullptr;
+        if (similarity > RPH_MAX_SIMILARITY_256) return fail("rph_library_create", "Similarity distances above 63 require R=4 bit-flip checks, which are not implemented.");
+        rph_library *lib = new rph_library;
+        lib->ctx = ctx;
+        lib->similarity = similarity;
+        *lib_out = lib;
+        return RPH_OK;
+    });
+}
+
+int rph_library_destroy(rph_library *lib)
+{
+    if (!lib) return RPH_ERR_INVALID_ARG;
+    {
+        std::lock_guard<std::mutex> lock(lib->mu);
+        (void)hipSetDevice(lib->ctx->device);
+        (void)hipStreamSynchronize(lib->ctx->stream);
+        for (hipEvent_t e : lib->ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    delete lib;
+    return RPH_OK;
+}
+
+int rph_library_reserve(rph_library *lib, uint64_t n_files)
+{
+    return rph_guarded("rph_library_reserve", [&]() -> int {
+        if (!lib) return fail("rph_library_reserve", "null argument");
+        if (n_files > MAX_FILES) return fail("rph_library_reserve", "at most 2^31 - 1 files");
+        std::lock_guard<std::mutex> lock(lib->mu);
+        RPH_HIP_CHECK(hipSetDevice(lib->ctx->device));
+        const uint64_t before = lib->want_cap;
+        lib->want_cap = std::max(before, n_files);  // grow() sizes the first allocation by it
+        const int rc = grow(lib, n_files, lib->ctx->stream);
+        if (rc != RPH_OK) lib->want_cap = before;
+        return rc;
+    });
+}
+
+int rph_library_size(rph_library *lib, uint64_t *n_files_out, uint64_t *comparisons_out)
+{
+    if (!lib) return fail("rph_library_size", "null argument");
+    std::lock_guard<std::mutex> lock(lib->mu);
+    if (n_files_out) *n_files_out = lib->n;
+    if (comparisons_out) *comparisons_out = lib->comparisons;
+    return RPH_OK;
+}
+
+int rph_library_append(rph_library *lib, const uint8_t *hashes32, const float *coeffs, const uint8_t *has_features, const int32_t *quality, uint64_t n_new,
+                       uint32_t *labels_out, uint64_t *new_comparisons_out)
+{
+    return rph_guarded("rph_library_append", [&]() -> int {
+        if (!lib || (!hashes32 && n_new)) return fail("rph_library_append", "null argument");
+        if (new_comparisons_out) *new_comparisons_out = 0;
+        if (n_new == 0) return RPH_OK;
+        std::lock_guard<std::mutex> lock(lib->mu);
+        if (n_new > MAX_FILES || lib->n + n_new > MAX_FILES) return fail("rph_library_append", "at most 2^31 - 1 files");
+        RPH_HIP_CHECK(hipSetDevice(lib->ctx->device));
+        return append(lib, hashes32, coeffs, has_features, quality, n_new, labels_out, new_comparisons_out);
+    });
+}
+
+int rph_library_restore(rph_library *lib, const uint8_t *hashes32, const float *coeffs, const uint8_t *has_features, const int32_t *quality, uint64_t n,
+                        const uint32_t *members, const uint32_t *offsets, uint32_t n_groups, uint64_t comparisons)
+{
+    return rph_guarded("rph_library_restore", [&]() -> int {
+        if (!lib || (!hashes32 && n) || ((!members || !offsets) && n_groups)) return fail("rph_library_restore", "null argument");
+        std::lock_guard<std::mutex> lock(lib->mu);
+        if (lib->n) return fail("rph_library_restore", "the library is not empty");
+        if (n > MAX_FILES) return fail("rph_library_restore", "at most 2^31 - 1 files");
+        // the groups through the checks of rph_union_find_groups_append (no edges); what it lists has its smallest member first
+        std::vector<uint32_t> m(std::max<uint64_t>(n, 1)), o(n / 2 + 2), labels(n);
+        uint32_t ng = 0;
+        RPH_TRY(rph_host_union_find_append(members, offsets, n_groups, nullptr, 0, n, m.data(), o.data(), &ng));
+        for (uint64_t i = 0; i < n; i++) labels[i] = (uint32_t)i;
+        for (uint32_t g = 0; g < ng; g++)
+            for (uint32_t t = o[g]; t < o[g + 1]; t++) labels[m[t]] = m[o[g]];
+        if (n) {
+            RPH_HIP_CHECK(hipSetDevice(lib->ctx->device));
+            hipStream_t s = lib->ctx->stream;
+            RPH_TRY(grow(lib, n, s));
+            RPH_TRY(upload_behind(lib, hashes32, coeffs, has_features, quality, n, s));
+            RPH_HIP_CHECK(hipMemcpyAsync(lib->d_lab.data(), labels.data(), n * 4, hipMemcpyHostToDevice, s));
+            RPH_HIP_CHECK(hipStreamSynchronize(s));
+        }
+        lib->n = n;
+        lib->comparisons = comparisons;
+        return RPH_OK;
+    });
+}
+
+int rph_library_groups(rph_library *lib, uint32_t *members, uint32_t *offsets, uint32_t *n_groups_out)
+{
+    return rph_guarded("rph_library_groups", [&]() -> int {
+        if (!lib || !members || !offsets || !n_groups_out) return fail("rph_library_groups", "null argument");
+        std::lock_guard<std::mutex> lock(lib->mu);
+        return rph_groups_from_labels_dev(lib->ctx, lib->d_lab.data(), lib->n, members, offsets, n_groups_out, lib->ctx->stream);
+    });
+}
+
+int rph_library_labels(rph_library *lib, uint64_t first, uint64_t count, uint32_t *labels_out)
+{
+    return rph_guarded("rph_library_labels", [&]() -> int {
+        if (!lib || (!labels_out && count)) return fail("rph_library_labels", "null argument");
+        std::lock_guard<std::mutex> lock(lib->mu);
+        if (first > lib->n || count > lib->n - first) return fail("rph_library_labels", "first + count exceeds the size");
+        if (count == 0) return RPH_OK;
+        RPH_HIP_CHECK(hipSetDevice(lib->ctx->device));
+        RPH_HIP_CHECK(hipMemcpyAsync(labels_out, lib->d_lab.as<uint32_t>() + first, count * 4, hipMemcpyDeviceToHost, lib->ctx->stream));
+        RPH_HIP_CHECK(hipStreamSynchronize(lib->ctx->stream));
+        return RPH_OK;
+    });
+}
+
+int rph_library_query(rph_library *lib, const uint8_t *hashes32_q, const int32_t *quality_q, uint64_t n_q, rph_edge *edges, uint64_t cap,
+                      uint64_t *n_edges_out)
+{
+    return rph_guarded("rph_library_query", [&]() -> int {
+        if (!lib || (!hashes32_q && n_q) || !n_edges_out || (!edges && cap)) return fail("rph_library_query", "null argument");
+        *n_edges_out = 0;
+        if (n_q > 0xFFFFFFFFull) return fail("rph_library_query", "at most 2^32 - 1 queries");
+        std::lock_guard<std::mutex> lock(lib->mu);
+        if (n_q == 0 || lib->n == 0) return RPH_OK;
+        rph_ctx *ctx = lib->ctx;
+        RPH_HIP_CHECK(hipSetDevice(ctx->device));
+        hipStream_t s = ctx->stream;
+        RPH_TRY(lib->d_qh.reserve(n_q * 32, s));
+        RPH_HIP_CHECK(hipMemcpyAsync(lib->d_qh.data(), hashes32_q, n_q * 32, hipMemcpyHostToDevice, s));
+        rph_sweep q = sweep_of(lib, 0, lib->n, 0, n_q, true);
+        q.cols = lib->d_qh.data();
+        q.low_conf_cols = nullptr;
+        if (quality_q) {
+            lib->low_host.resize(n_q);
+            for (uint64_t i = 0; i < n_q; i++) lib->low_host[i] = (uint8_t)rph_is_low_pdq_quality(quality_q[i]);
+            RPH_TRY(lib->d_qlc.reserve(n_q, s));
+            RPH_HIP_CHECK(hipMemcpyAsync(lib->d_qlc.data(), lib->low_host.data(), n_q, hipMemcpyHostToDevice, s));
+            q.low_conf_cols = lib->d_qlc.data();
+        }
+        if (!lib->d_cnt.data()) RPH_TRY(lib->d_cnt.alloc(8));
+        RPH_TRY(lib->d_edges.reserve(cap * sizeof(rph_edge), s));
+        RPH_HIP_CHECK(hipMemsetAsync(lib->d_cnt.data(), 0, 8, s));
+        q.edges = lib->d_edges.as<rph_edge>(), q.cap = cap, q.count = lib->d_cnt.as<unsigned long long>();
+        RPH_TRY(rph_launch_hamming_sweep(ctx, q, s, ctx->hamming_kernel));
+        unsigned long long found = 0;
+        RPH_HIP_CHECK(hipMemcpyAsync(&found, lib->d_cnt.data(), 8, hipMemcpyDeviceToHost, s));
+        RPH_HIP_CHECK(hipStreamSynchronize(s));
+        *n_edges_out = found;
+        const uint64_t n_take = std::min<uint64_t>(found, cap);
+        if (n_take) RPH_HIP_CHECK(hipMemcpy(edges, lib->d_edges.data(), n_take * sizeof(rph_edge), hipMemcpyDeviceToHost));
+        if (found > cap) {
+            rph_set_error("rph_library_query: %llu edges found, capacity %llu", found, (unsigned long long)cap);
+            return RPH_ERR_CAPACITY;
+        }
+        return RPH_OK;
+    });
+}
+
+// The stages of the last append in device time (exported for tools/library_rate.py, not in the header): on != 0 arms the events for the
+// appends that follow; ms_out (nullable, 5 floats): upload and variants of the new files, cross sweep, triangular sweep, cursor read plus
+// union and flatten kernels, labels back.
+int rph_debug_library_stages(rph_library *lib, int on, float *ms_out)
+{
+    return rph_guarded("rph_debug_library_stages", [&]() -> int {
+        if (!lib) return fail("rph_debug_library_stages", "null argument");
+        std::lock_guard<std::mutex> lock(lib->mu);
+        RPH_HIP_CHECK(hipSetDevice(lib->ctx->device));
+        if (ms_out) {
+            if (!lib->staged) return fail("rph_debug_library_stages", "no append has run with the events armed");
+            for (int k = 0; k < 5; k++) RPH_HIP_CHECK(hipEventElapsedTime(&ms_out[k], lib->ev[k], lib->ev[k + 1]));
+        }
+        for (int k = 0; k < 6 && on && !lib->ev[k]; k++) RPH_HIP_CHECK(hipEventCreate(&lib->ev[k]));
+        lib->profile = on != 0;
+        lib->staged = false;
+        return RPH_OK;
+    });
+}
+
+}  // extern "C"

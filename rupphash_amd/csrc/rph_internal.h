@@ -57,7 +57,8 @@ struct rph_ctx {
     uint32_t *sink = nullptr;  // 4-byte result slot of the read-stream probe
     // device scratch shared by every caller stream (rph_buffers.h): the generic (multi-pass) PDQ kernel's two f32 planes per in-flight
     // image; the pre-downsample's u8 planes for > 512 px inputs (full-resolution luma, horizontal pass, thumbnail); the popcount-sorted
-    // sweep's sorted hashes, permutation, popcounts and radix-sort workspace; BLAKE3's plan and group values
+    // sweep's sorted hashes, permutation, popcounts and radix-sort workspace, and the component export's counts, sorted labels and
+    // hipCUB workspace (components.hip); BLAKE3's plan and group values
     SharedScratch scratch, rz_scratch, sweep_scratch, b3_scratch;
     // sample scratch of the low-latency PDQ kernel, one per caller stream (133 KB per image of a launch chunk): launches on different
     // streams -- the one-image queue's pipeline slots -- share nothing and need no ordering between them
@@ -193,6 +194,18 @@ extern "C" void rph_debug_hamming_cross_layout(uint64_t n_a, uint32_t n_variants
 // calls, the files of each (the first `cap` of them into sizes_out) and, for WebP, the number of parse windows (exported for the tests,
 // not in the header; any of the three outputs may be null)
 extern "C" int rph_debug_file_chunks(rph_ctx *ctx, int format, uint32_t *sizes_out, uint32_t cap, uint32_t *n_chunks_out, uint32_t *n_windows_out);
+// components.hip: one edge list of a union-find over a label array, e.i + i_base and e.j + j_base being the files an edge unites
+struct rph_union_edges {
+    const rph_edge *edges = nullptr;
+    uint64_t n_edges = 0;
+    uint32_t i_base = 0, j_base = 0;
+};
+// What rph_union_find_labels_dev does, for several lists at once: one range check of all of them and of the entry forest (it waits for
+// that: RPH_ERR_INVALID_ARG with nothing written), then one union launch per list and ONE flatten, asynchronous on `stream`
+int rph_union_find_labels(rph_ctx *ctx, const rph_union_edges *sets, uint32_t n_sets, uint32_t *d_labels, uint64_t n, hipStream_t stream);
+// library.cpp: the stages of a library's last append in device time (exported for tools/library_rate.py, not in the header)
+struct rph_library;
+extern "C" int rph_debug_library_stages(rph_library *lib, int on, float *ms_out);
 int rph_launch_mih_build256(rph_ctx *ctx, const uint8_t *d_hashes, uint64_t n, uint32_t *d_offsets, uint32_t *d_values,
                             hipStream_t stream);
 int rph_launch_mih_build64(rph_ctx *ctx, const uint64_t *d_hashes, uint64_t n, uint32_t *d_offsets, uint32_t *d_values,

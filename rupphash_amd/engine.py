@@ -819,6 +819,23 @@ class Engine:
                                                 C.byref(ng), C.byref(cmp_count)), "rph_group_files_pdq_append")
         return self._groups(members, offsets, ng.value), cmp_count.value
 
+    def union_find_labels_dev(self, d_edges, n_edges, d_labels, n, i_base=0, j_base=0, stream=None):
+        """Union-find on the device: d_labels (n uint32, a forest with label[x] <= x) becomes the min-label of every file's component."""
+        check(self.L.rph_union_find_labels_dev(self.ctx, d_edges, n_edges, i_base, j_base, d_labels, n, stream), "rph_union_find_labels_dev")
+
+    def groups_from_labels_dev(self, d_labels, n, stream=None):
+        """Flattened min-labels on the device -> the groups union_find_groups lists."""
+        members = np.zeros(max(n, 1), np.uint32)
+        offsets = np.zeros(n // 2 + 2, np.uint32)
+        ng = C.c_uint32()
+        check(self.L.rph_groups_from_labels_dev(self.ctx, d_labels, n, _ptr(members), _ptr(offsets), C.byref(ng), stream),
+              "rph_groups_from_labels_dev")
+        return self._groups(members, offsets, ng.value)
+
+    def library(self, similarity):
+        """A grouped library that stays on this engine's device (rph_library): see Library."""
+        return Library(self, similarity)
+
     def mih_build256(self, hashes):
         hashes = np.ascontiguousarray(hashes, np.uint8).reshape(-1, 32)
         n = len(hashes)
@@ -912,6 +929,97 @@ class Engine:
 
     def event_destroy(self, e):
         check(self.L.rph_event_destroy(self.ctx, e), "rph_event_destroy")
+
+
+class Library:
+    """rph_library: files appended so far stay on the device with their variants, flags and component labels.  groups() equals
+    Engine.group_files_pdq on everything appended, in order.  One similarity, at most 2^31 - 1 files, no removal.  Close it before its engine."""
+
+    def __init__(self, engine, similarity):
+        self.engine, self.L, self.similarity = engine, engine.L, similarity
+        h = C.c_void_p()
+        check(self.L.rph_library_create(engine.ctx, similarity, C.byref(h)), "rph_library_create")
+        self.handle = h
+
+    def close(self):
+        if getattr(self, "handle", None):
+            if getattr(self.engine, "ctx", None):  # the handle of a library that outlived its engine points into a context that is gone
+                self.L.rph_library_destroy(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _size(self):
+        n, c = C.c_uint64(), C.c_uint64()
+        check(self.L.rph_library_size(self.handle, C.byref(n), C.byref(c)), "rph_library_size")
+        return n.value, c.value
+
+    def __len__(self):
+        return self._size()[0]
+
+    @property
+    def comparisons(self):
+        return self._size()[1]
+
+    def reserve(self, n):
+        check(self.L.rph_library_reserve(self.handle, n), "rph_library_reserve")
+
+    @staticmethod
+    def _files(hashes, coeffs, has_features, quality):
+        hashes = np.ascontiguousarray(hashes, np.uint8).reshape(-1, 32)
+        n = len(hashes)
+        return (hashes, None if coeffs is None else np.ascontiguousarray(coeffs, np.float32).reshape(n, 256),
+                None if has_features is None else np.ascontiguousarray(has_features, np.uint8),
+                None if quality is None else np.ascontiguousarray(quality, np.int32))
+
+    def append(self, hashes, coeffs=None, has_features=None, quality=None):
+        """The files become len(self) .. len(self) + n - 1.  Returns (labels, new_comparisons): per new file the smallest index of the
+        component it is in now, and the comparisons these files added."""
+        h, c, hf, q = self._files(hashes, coeffs, has_features, quality)
+        labels = np.zeros(len(h), np.uint32)
+        cmp_count = C.c_uint64()
+        check(self.L.rph_library_append(self.handle, _ptr(h), _ptr(c), _ptr(hf), _ptr(q), len(h), _ptr(labels), C.byref(cmp_count)),
+              "rph_library_append")
+        return labels, cmp_count.value
+
+    def restore(self, hashes, groups, comparisons=0, coeffs=None, has_features=None, quality=None):
+        """Start an empty library from files an earlier run grouped at the same similarity (`groups` as it returned them): no sweep."""
+        h, c, hf, q = self._files(hashes, coeffs, has_features, quality)
+        om, oo = groups if isinstance(groups, tuple) else Engine._flatten_groups(groups)
+        om, oo = np.ascontiguousarray(om, np.uint32), np.ascontiguousarray(oo, np.uint32)
+        check(self.L.rph_library_restore(self.handle, _ptr(h), _ptr(c), _ptr(hf), _ptr(q), len(h), _ptr(om), _ptr(oo), max(len(oo) - 1, 0),
+                                         comparisons), "rph_library_restore")
+
+    def groups(self):
+        n = len(self)
+        members = np.zeros(max(n, 1), np.uint32)
+        offsets = np.zeros(n // 2 + 2, np.uint32)
+        ng = C.c_uint32()
+        check(self.L.rph_library_groups(self.handle, _ptr(members), _ptr(offsets), C.byref(ng)), "rph_library_groups")
+        return Engine._groups(members, offsets, ng.value)
+
+    def labels(self, first=0, count=None):
+        count = len(self) - first if count is None else count
+        out = np.zeros(max(count, 0), np.uint32)
+        check(self.L.rph_library_labels(self.handle, first, count, _ptr(out)), "rph_library_labels")
+        return out
+
+    def query(self, hashes, quality=None, cap=None):
+        """Edges (library file i, query j, d, variant in flags) of the queries against the resident files; the library is not changed.
+        With cap given, RPH_ERR_CAPACITY raises (RphError)."""
+        h, _, _, q = self._files(hashes, None, None, quality)
+        return Engine._sweep_growing(lambda e, c, f: self.L.rph_library_query(self.handle, _ptr(h), _ptr(q), len(h), e, c, f),
+                                     max(1 << 16, 8 * len(h)) if cap is None else cap, cap is None, "rph_library_query")
 
 
 _default = None

@@ -16,7 +16,7 @@ File-name logic after the union-find (merge_groups_by_stem, the sorting inside p
 import numpy as np
 
 from . import _lib
-from .engine import default_engine
+from .engine import Library, default_engine
 
 PDQ_MIN_QUALITY = 50
 
@@ -152,6 +152,29 @@ def group_with_pdqhash_append(old_hashes, old_groups, new_hashes, similarity, ol
     return (engine or default_engine()).group_files_pdq_append(
         old_hashes, old_groups, new_hashes, similarity, old_coefficients, old_has_features, q32(old_quality), new_coefficients,
         new_has_features, q32(new_quality))
+
+
+def _quality32(quality):
+    return None if quality is None else np.array([-1 if x is None else int(x) for x in quality], np.int32)
+
+
+class ScannerLibrary(Library):
+    """Engine.library with the helpers' argument names and quality as a list of None / int, like group_with_pdqhash."""
+
+    def append(self, hashes, coefficients=None, has_features=None, quality=None):
+        return super().append(hashes, coefficients, has_features, _quality32(quality))
+
+    def restore(self, hashes, groups, comparisons=0, coefficients=None, has_features=None, quality=None):
+        return super().restore(hashes, groups, comparisons, coefficients, has_features, _quality32(quality))
+
+    def query(self, hashes, quality=None, cap=None):
+        return super().query(hashes, _quality32(quality), cap)
+
+
+def open_library(similarity, engine=None):
+    """A grouped library that stays on the device between scans (ScannerLibrary): append(...) -> (labels, new_comparisons), restore(...),
+    groups(), labels(), query(...).  groups() is group_with_pdqhash on everything appended so far, in order."""
+    return ScannerLibrary(engine or default_engine(), similarity)
 
 
 def group_max_dist(groups, hashes, pivots, coefficients=None, has_features=None, engine=None):
