@@ -83,16 +83,127 @@ def groups_of(labels):
     return [m for _, m in sorted(by.items()) if len(m) > 1]
 
 
+def label_families(n):
+    ids = np.arange(n, dtype=np.uint32)
+    yield f"singletons-{n}", ids.copy()
+    yield f"one-component-{n}", np.zeros(n, np.uint32)
+    pairs = ids & ~np.uint32(1)
+    yield f"pairs-{n}", pairs
+    half = ids.copy()
+    half[n // 2: 2 * (n // 2)] = ids[: n // 2]  # (k, k + n / 2): members interleave in index order
+    yield f"interleaved-{n}", half
+
+
 def label_cases():
     for n in (1, 2, 255, 256, 257, 4099):
-        ids = np.arange(n, dtype=np.uint32)
-        yield f"singletons-{n}", ids.copy()
-        yield f"one-component-{n}", np.zeros(n, np.uint32)
-        pairs = ids & ~np.uint32(1)
-        yield f"pairs-{n}", pairs
-        half = ids.copy()
-        half[n // 2: 2 * (n // 2)] = ids[: n // 2]  # (k, k + n / 2): members interleave in index order
-        yield f"interleaved-{n}", half
+        yield from label_families(n)
+
+
+# ---------------------------------------------------------------- beyond one grid
+# A union-find or export launch has at most 8 * compute_units blocks of 256 lanes: G = 8 * cus * 256 items are one pass of the grid-stride
+# loops.  These cases are there for the second pass and the 64-bit indexing, not for depth: shallow components whose labels have a closed
+# form (`want`), edges shuffled.  test_library_cpu.py pins want == min_labels at G = 1024.
+LargeCase = namedtuple("LargeCase", "name n labels calls want")
+
+
+def grid_sizes(G):
+    return (G + 77, 2 * G + 1)  # one full pass and a ragged second; two full passes and one item
+
+
+def blocks_of_four(n):
+    """(x, x ^ 1) and (x, x ^ 2) for every x whose partner is inside n: label x & ~3, also in a ragged last block (its first member has an
+    edge to each of the others that exist)"""
+    x = np.arange(n, dtype=np.uint32)
+    edges = np.concatenate([np.stack([x, x ^ k], axis=1)[(x ^ k) < n] for k in (1, 2)])
+    want = x & ~np.uint32(3)
+    first = n & ~3
+    want[first:] = first + min_labels(n - first, edges[(edges >= first).all(axis=1)] - first)  # the ragged block, derived the same way
+    return edges, want
+
+
+def star_forest(n):
+    """hub 1000 k to each of its followers, the hub as j in half of the edges: hub contention in every block at once"""
+    x = np.arange(n, dtype=np.uint32)
+    hub = x - x % 1000
+    f = x[x != hub]
+    edges = np.where((f % 2 == 1)[:, None], np.stack([hub[f], f], axis=1), np.stack([f, hub[f]], axis=1)).astype(np.uint32)
+    return edges, hub
+
+
+def split_with_bases(edges, n):
+    """two calls: the edges inside the upper half local to it, with i_base = j_base = n / 2; the rest as they are"""
+    h = n // 2
+    upper = (edges >= h).all(axis=1)
+    return [(edges[~upper], 0, 0), (edges[upper] - np.uint32(h), h, h)]
+
+
+LARGE_CASES = [f"{family}-{size}{calls}" for family in ("blocks-of-four", "star-forest") for size in ("G+77", "2G+1") for calls in ("", "-two-calls")] + [
+    "star-forest-G+77-every-edge-8-times", "clique-1500-in-2000", "chain-4097-as-entry-forest"]
+
+
+def large_case(G, name):
+    """one of LARGE_CASES at a grid of G lanes (built on request: the large ones hold millions of edges)"""
+    rng = np.random.default_rng([4242, LARGE_CASES.index(name)])
+    if name == "clique-1500-in-2000":  # 1 124 250 edges, all aimed at one root
+        a, b = np.triu_indices(1500, 1)
+        edges = (np.stack([a, b], axis=1) + 250).astype(np.uint32)
+        want = np.arange(2000, dtype=np.uint32)
+        want[250:1750] = 250
+        return LargeCase(name, 2000, None, [(edges[rng.permutation(len(edges))], 0, 0)], want)
+    if name == "chain-4097-as-entry-forest":  # legal (labels[x] <= x) but not flattened: one chain, no edges
+        chain = np.maximum(np.arange(4097, dtype=np.int64) - 1, 0).astype(np.uint32)
+        return LargeCase(name, 4097, chain, [(_e([]), 0, 0)], np.zeros(4097, np.uint32))
+    n = grid_sizes(G)["2G+1" in name]
+    edges, want = (blocks_of_four if name.startswith("blocks") else star_forest)(n)
+    edges = edges[rng.permutation(len(edges))]
+    if name.endswith("two-calls"):
+        return LargeCase(name, n, None, split_with_bases(edges, n), want)
+    if name.endswith("8-times"):
+        edges = np.repeat(edges, 8, axis=0)  # as the variant sweeps report them
+    return LargeCase(name, n, None, [(edges, 0, 0)], want)
+
+
+def large_edge_lists(G):
+    for name in LARGE_CASES:
+        yield large_case(G, name)
+
+
+# ---------------------------------------------------------------- dense sets
+def library_first_cap(n_new):
+    """the edge capacity rph_library_append starts its retry loop with, read from library.cpp (the dense cases assert that they overflow
+    THIS number: when it changes they fail their premise, not their purpose)"""
+    import os
+    import re
+
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "rupphash_amd", "csrc", "library.cpp")).read()
+    found = re.findall(r"uint64_t cap = std::max<uint64_t>\((\d+)u << (\d+), (\d+) \* n_new\);", src)
+    assert len(found) == 1, "the initial capacity of append() is no longer written as max(a << b, c * n_new)"
+    a, b, c = map(int, found[0])
+    return max(a << b, c * n_new)
+
+
+def dense_hashes(m, seed=99, common=None):
+    """m files that share one hash, and one unrelated random hash behind every 40 of them (so that labels are not all zero):
+    (hashes, is_common)"""
+    rng = np.random.default_rng(seed)
+    common = rng.integers(0, 256, 32, dtype=np.uint8) if common is None else common
+    rows, flag = [], []
+    for k in range(m):
+        rows.append(common)
+        flag.append(True)
+        if k % 40 == 39:
+            rows.append(rng.integers(0, 256, 32, dtype=np.uint8))
+            flag.append(False)
+    return np.stack(rows), np.array(flag)
+
+
+def dense_expectation(is_common, rows_per_file=1):
+    """closed form of a dense set at a similarity under the unrelated hashes' distances: (labels, groups, comparisons)"""
+    ids = np.nonzero(is_common)[0]
+    labels = np.arange(len(is_common), dtype=np.uint32)
+    labels[ids] = ids[0] if len(ids) else 0
+    m = len(ids)
+    return labels, ([ids.tolist()] if m > 1 else []), rows_per_file * m * (m - 1) // 2
 
 
 # ---------------------------------------------------------------- files

@@ -73,6 +73,66 @@ def test_labels_and_groups_match_numpy_and_the_host_union_find(eng, caller_strea
     assert groups == eng.union_find_groups(as_edges(g), case.n) == lc.groups_of(want)
 
 
+@pytest.fixture(scope="module")
+def grid(eng):
+    """G: the lanes of the largest launch grid_for() makes, one pass of every grid-stride loop"""
+    return 8 * eng.device_info()[1] * 256
+
+
+@pytest.mark.parametrize("name", lc.LARGE_CASES)
+def test_labels_beyond_one_grid_match_the_closed_form(eng, grid, name):
+    case = lc.large_case(grid, name)
+    assert case.n > grid or case.n in (2000, 4097)
+    if name.startswith("clique"):
+        assert len(case.calls[0][0]) == 1124250 > 8 * 256 * 256  # more than one pass on a part of 256 CUs
+    start = np.arange(case.n, dtype=np.uint32) if case.labels is None else case.labels
+    with DeviceArray(eng, start) as d_labels:
+        for pairs, i_base, j_base in case.calls:
+            with DeviceArray(eng, as_edges(pairs)) as d_edges:
+                eng.union_find_labels_dev(d_edges.ptr if len(pairs) else None, len(pairs), d_labels.ptr, case.n, i_base, j_base)
+                eng.synchronize()
+        got = d_labels.download(np.uint32)
+        assert np.array_equal(got, case.want)
+        groups = eng.groups_from_labels_dev(d_labels.ptr, case.n)
+    assert groups == lc.groups_of(case.want)
+
+
+@pytest.mark.parametrize("which", [0, 1], ids=["G+77", "2G+1"])
+@pytest.mark.parametrize("family", [0, 1, 2, 3], ids=["singletons", "one-component", "pairs", "interleaved"])
+def test_export_beyond_one_grid(eng, grid, family, which):
+    n = lc.grid_sizes(grid)[which]
+    name, labels = list(lc.label_families(n))[family]
+    with DeviceArray(eng, labels) as d_labels:
+        assert eng.groups_from_labels_dev(d_labels.ptr, n) == lc.groups_of(labels), name
+
+
+def test_refusals_beyond_the_first_pass(eng, grid):
+    from rupphash_amd import RphError, _lib
+
+    # a bad edge at index G + 5: the range check's second pass finds it, nothing is written
+    n = grid + 77
+    edges, _ = lc.blocks_of_four(n)
+    assert len(edges) > grid + 5
+    edges[grid + 5] = (7, n)
+    start = np.arange(n, dtype=np.uint32)
+    with DeviceArray(eng, start) as d_labels, DeviceArray(eng, as_edges(edges)) as d_edges:
+        with pytest.raises(RphError) as err:
+            eng.union_find_labels_dev(d_edges.ptr, len(edges), d_labels.ptr, n)
+        assert err.value.status == _lib.RPH_ERR_INVALID_ARG
+        eng.synchronize()
+        assert np.array_equal(d_labels.download(np.uint32), start)
+    # a label outside n at the last index of a large array: the export refuses, the outputs are untouched
+    for n in lc.grid_sizes(grid):
+        labels = np.arange(n, dtype=np.uint32) & ~np.uint32(1)
+        labels[n - 1] = 0xFFFFFFFF
+        with DeviceArray(eng, labels) as d_labels:
+            members, offsets = np.full(n, 77, np.uint32), np.full(n // 2 + 2, 77, np.uint32)
+            ng = C.c_uint32(77)
+            rc = eng.L.rph_groups_from_labels_dev(eng.ctx, d_labels.ptr, n, members.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p),
+                                                  C.byref(ng), None)
+            assert rc == _lib.RPH_ERR_INVALID_ARG and ng.value == 0 and (members == 77).all()
+
+
 def test_an_edge_outside_n_is_refused_and_nothing_is_written(eng):
     from rupphash_amd import RphError, _lib
 

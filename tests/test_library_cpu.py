@@ -88,6 +88,43 @@ def test_label_cases_are_flattened_min_labels():
     assert seen == {1, 2, 255, 256, 257, 4099}
 
 
+@pytest.mark.parametrize("case", list(lc.large_edge_lists(4 * 256)), ids=lambda c: c.name)
+def test_closed_form_labels_of_the_large_cases_are_the_min_labels(case):
+    assert lc.grid_sizes(1024) == (4 * 256 + 77, 2049)
+    g = lc.global_edges(case)
+    assert len(g) and (g < case.n).all()
+    assert case.want.dtype == np.uint32 and np.array_equal(case.want, lc.min_labels(case.n, g))
+    for edges, i_base, j_base in case.calls:  # what the device's range check demands of every call
+        assert edges.dtype == np.uint32 and ((edges[:, 0].astype(np.int64) + i_base < case.n) & (edges[:, 1].astype(np.int64) + j_base < case.n)).all()
+    if "two-calls" in case.name:
+        assert all(len(e) >= 48 for e, _, _ in case.calls) and case.calls[1][1:] == (case.n // 2, case.n // 2)
+    if case.name.startswith("star-forest") and "8-times" not in case.name:
+        e = g[g[:, 0] != g[:, 1]]
+        hub_is_j = (e[:, 1] % 1000 == 0).mean()
+        assert 0.4 < hub_is_j < 0.6 and len(e) == case.n - (case.n + 999) // 1000
+    if case.name.startswith("clique"):
+        assert len(case.calls[0][0]) == 1500 * 1499 // 2 == 1124250
+    if case.name.startswith("chain"):
+        assert (case.labels <= np.arange(case.n)).all() and (case.labels[case.labels] != case.labels)[2:].all()  # legal, not flattened
+
+
+def test_label_families_and_dense_sets(oracle):
+    for n in lc.grid_sizes(1024):
+        for name, labels in lc.label_families(n):
+            assert (labels <= np.arange(n)).all() and (labels[labels] == labels).all(), name
+    hashes, common = lc.dense_hashes(1500)
+    assert len(hashes) == 1500 + 37 and common.sum() == 1500 and not common[40] and common[41]
+    others = hashes[~common]
+    for k, h in enumerate(others):  # the unrelated hashes are more than 63 bits from the common one and from each other
+        assert oracle.hamming256(h, hashes[0]) > 63
+        assert all(oracle.hamming256(h, o) > 63 for o in others[:k])
+    labels, groups, cmp_count = lc.dense_expectation(common)
+    edges, ref_groups = oracle.group_pdq(hashes[:300], 31)
+    want = lc.dense_expectation(common[:300])
+    assert (ref_groups, len(edges)) == want[1:] and np.array_equal(want[0], lc.min_labels(300, edges))
+    assert cmp_count == 1124250 and groups[0][:41] == list(range(40)) + [41]
+
+
 @pytest.fixture(scope="module")
 def files(oracle):
     return lc.corpus()

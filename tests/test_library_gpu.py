@@ -143,6 +143,127 @@ def test_the_bridge_file_merges_two_resident_groups(eng, files):
         assert list(lib.labels(b["b"], 2)) == [b["a"]] * 2 and len(lib.groups()) == n_before - 1
 
 
+# ---------------------------------------------------------------- dense libraries: the edge buffer's retry loop
+# identical files resident, identical files appended, eight rows per file (coefficients all +0.0: eight all-zero variants)
+DENSE = {"within-overflows": (0, 1500, False), "cross-overflows": (1100, 1000, False), "sum-overflows": (700, 1000, False),
+         "eight-rows-per-file": (300, 400, True)}
+DENSE_SIM = 31
+
+
+def dense_premise(name, cross, inner, cap):
+    """the inequality of the case: which sweep runs the edge buffer over"""
+    if name == "within-overflows":
+        return cross == 0 and inner > cap
+    if name == "cross-overflows":
+        return cross > cap
+    return cross <= cap < cross + inner
+
+
+def same_state(lib, labels, groups, comparisons):
+    assert lib.groups() == groups
+    assert np.array_equal(lib.labels(), labels)
+    assert lib.comparisons == comparisons
+
+
+def run_dense(eng, oracle, name):
+    from rupphash_amd import EDGE_DTYPE, RphError, _lib
+
+    resident, appended, eight = DENSE[name]
+    rows = 8 if eight else 1
+    hashes, common = lc.dense_hashes(resident + appended, common=np.zeros(32, np.uint8) if eight else None)
+    n = len(hashes)
+    cut = int(np.nonzero(common)[0][resident]) if resident else 0
+    assert common[:cut].sum() == resident and common[cut:].sum() == appended
+    hf = common.astype(np.uint8) if eight else np.zeros(n, np.uint8)  # the unrelated files keep to their hash
+    coeffs = np.zeros((n, 256), np.float32)
+    variants = np.repeat(hashes[:, None, :], 8, axis=1)  # what zero coefficients hash to is the all-zero hash, eight times
+    files = lambda a, b: dict(coeffs=coeffs[a:b], has_features=hf[a:b]) if eight else {}  # noqa: E731
+
+    def by_oracle(stop, features):
+        if stop == 0:
+            return [], 0
+        edges, groups = oracle.group_pdq(hashes[:stop], DENSE_SIM, variants=variants[:stop] if eight else None, has_features=features[:stop] if eight else None)
+        return groups, len(edges)
+
+    # the premise, on numbers that do not come from the library
+    cross, inner = rows * resident * appended, rows * appended * (appended - 1) // 2
+    assert by_oracle(n, hf)[1] - by_oracle(cut, hf)[1] == cross + inner
+    assert dense_premise(name, cross, inner, lc.library_first_cap(n - cut)), (name, cross, inner, lc.library_first_cap(n - cut))
+    want_labels, want_groups, want_cmp = lc.dense_expectation(common, rows)
+    assert (want_groups, want_cmp) == by_oracle(n, hf)
+    old_groups, old_cmp = lc.dense_expectation(common[:cut], rows)[1:]
+
+    with eng.library(DENSE_SIM) as lib:
+        if cut:
+            assert lib.append(hashes[:cut], **files(0, cut))[1] == old_cmp
+            same_state(lib, lc.dense_expectation(common[:cut], rows)[0], old_groups, old_cmp)
+        labels, new_cmp = lib.append(hashes[cut:], **files(cut, n))
+        assert new_cmp == cross + inner and np.array_equal(labels, want_labels[cut:])
+        same_state(lib, want_labels, want_groups, want_cmp)
+        kw = dict(old_coeffs=coeffs[:cut], old_has_features=hf[:cut], new_coeffs=coeffs[cut:], new_has_features=hf[cut:]) if eight else {}
+        if cut:
+            assert eng.group_files_pdq_append(hashes[:cut], old_groups, hashes[cut:], DENSE_SIM, **kw) == (want_groups, cross + inner)
+        else:  # nothing resident: the split is the one-shot call
+            assert eng.group_files_pdq(hashes, DENSE_SIM) == (want_groups, cross + inner)
+
+        # the state after a retry is healthy: ten more files (without coefficients), a query that fits and one that does not
+        more = np.concatenate([np.repeat(hashes[:1], 5, axis=0), np.random.default_rng(7).integers(0, 256, (5, 32), dtype=np.uint8)])
+        all_hashes, all_common = np.concatenate([hashes, more]), np.concatenate([common, [True] * 5 + [False] * 5])
+        all_hf = np.concatenate([hf, np.zeros(10, np.uint8)])
+        variants = np.concatenate([variants, np.repeat(more[:, None, :], 8, axis=1)])
+        hashes = all_hashes
+        ref_groups, ref_cmp = by_oracle(n + 10, all_hf)
+        state = (lc.dense_expectation(all_common)[0], ref_groups, ref_cmp)
+        assert ref_groups == lc.dense_expectation(all_common)[1] and ref_cmp == want_cmp + rows * (resident + appended) * 5 + 10
+        labels, new_cmp = lib.append(more)
+        assert new_cmp == ref_cmp - want_cmp and np.array_equal(labels, state[0][n:])
+        same_state(lib, *state)
+        total = rows * (resident + appended) + 5
+        got = lib.query(hashes[:1], cap=total)
+        assert len(got) == total and (got["d"] == 0).all() and sorted(set(got["i"].tolist())) == np.nonzero(all_common)[0].tolist()
+        same_state(lib, *state)
+        edges, found = np.zeros(10, EDGE_DTYPE), C.c_uint64()
+        rc = eng.L.rph_library_query(lib.handle, hashes[:1].ctypes.data_as(C.c_void_p), None, 1, edges.ctypes.data_as(C.c_void_p), 10, C.byref(found))
+        assert rc == _lib.RPH_ERR_CAPACITY and found.value == total
+        with pytest.raises(RphError) as err:
+            lib.query(hashes[:1], cap=10)
+        assert err.value.status == _lib.RPH_ERR_CAPACITY
+        same_state(lib, *state)
+
+
+@pytest.mark.parametrize("name", list(DENSE))
+def test_dense_append_overflows_the_edge_buffer_and_still_equals_the_oracle(eng, oracle, name):
+    run_dense(eng, oracle, name)
+
+
+@pytest.mark.parametrize("kernel", [0, 1])  # (2 is the default: the test above)
+def test_the_sum_overflow_under_the_other_hamming_kernels(eng, oracle, kernel):
+    try:
+        eng.set_hamming_kernel(kernel)
+        run_dense(eng, oracle, "sum-overflows")
+    finally:
+        eng.set_hamming_kernel(2)
+
+
+def test_reserve_with_files_resident(eng, files):
+    f = files
+    want_groups, want_cmp = expected(eng, f, 40, lc.N_FILES, f.has_features)
+    with eng.library(40) as lib:
+        lib.append(f.hashes[:300], f.coeffs[:300], f.has_features[:300], f.quality[:300])
+        state = (lib.groups(), lib.labels().tolist(), lib.comparisons)
+        assert state[0] == expected(eng, f, 40, 300, f.has_features)[0]
+        lib.reserve(3000)  # the resident files move to the new buffers
+        assert (lib.groups(), lib.labels().tolist(), lib.comparisons) == state and len(lib) == 300
+        lib.reserve(100)  # below the current size: nothing changes
+        assert (lib.groups(), lib.labels().tolist(), lib.comparisons) == state and len(lib) == 300
+        labels, _ = lib.append(f.hashes[300:], f.coeffs[300:], f.has_features[300:], f.quality[300:])
+        assert lib.groups() == want_groups and lib.comparisons == want_cmp
+        assert np.array_equal(labels, first_members(want_groups, 300, lc.N_FILES))
+        assert np.array_equal(lib.labels(), first_members(want_groups, 0, lc.N_FILES))
+        lib.reserve(0)
+        assert lib.groups() == want_groups and lib.comparisons == want_cmp
+
+
 # ---------------------------------------------------------------- restore
 @pytest.mark.parametrize("sim", (16, 40))
 @pytest.mark.parametrize("n_old", (0, 1, 1500, 1901))
