@@ -394,9 +394,10 @@ int rph_groups_from_labels_dev(rph_ctx *ctx, const void *d_labels, uint64_t n, u
 /*
  * A grouped library that stays on the device: hashes, the 8 variant rows of every file, flags and component labels live in HBM
  * between calls (294 bytes per file), so that an append moves and sweeps the new files only and a query moves the queries only.
- * The result is rph_group_files_pdq on everything appended so far, in order.  One similarity per library; at most 2^31 - 1 files;
- * files cannot be removed (a union-find does not split).  One library serves one call at a time (calls from several threads
- * queue); several libraries on one context are independent.  Destroy every library before rph_shutdown of its context.
+ * The result is rph_group_files_pdq on the files it holds, in order.  One similarity per library; at most 2^31 - 1 files;
+ * files leave through rph_library_remove, which renumbers the ones that stay.  One library serves one call at a time (calls
+ * from several threads queue); several libraries on one context are independent.  Destroy every library before rph_shutdown
+ * of its context.
  */
 typedef struct rph_library rph_library;
 int rph_library_create(rph_ctx *ctx, uint32_t similarity, rph_library **lib_out);   /* similarity > RPH_MAX_SIMILARITY_256: RPH_ERR_INVALID_ARG */
@@ -416,7 +417,22 @@ int rph_library_append(rph_library *lib, const uint8_t *hashes32, const float *c
 int rph_library_restore(rph_library *lib, const uint8_t *hashes32, const float *coeffs, const uint8_t *has_features,
                         const int32_t *quality, uint64_t n, const uint32_t *members, const uint32_t *offsets, uint32_t n_groups,
                         uint64_t comparisons);
-/* members capacity size, offsets capacity size / 2 + 2: identical to rph_group_files_pdq on everything appended so far, in order. */
+/* Remove files (deleted duplicates, files gone at the next scan).  indices: n_remove current file numbers in any order.  The files that
+ * stay keep their order and are renumbered densely: new number = old number - removed files below it; new_index_out (nullable, one entry
+ * per file of the OLD size) gives the new number of every old file, 0xFFFFFFFF for a removed one -- the caller renumbers whatever it keeps
+ * by file number through it.  Afterwards the library is what rph_group_files_pdq gives on the remaining files in order: groups, labels,
+ * queries, every later append, and the comparison count, which goes down by the edges that had a removed file at either end
+ * (*dropped_comparisons_out, nullable; a count restored too low stops at 0).  A union-find does not split, so the components that lost a
+ * file are regrouped: their members are swept again among themselves and everything else keeps its labels.  The cost is one pass over the
+ * resident arrays plus 8 * m^2 / 2 pairs for m members of such components -- a full regroup when one component holds the library.
+ * Memory: the new state is built beside the old one, so for the length of the call a second copy of the library is allocated (294 bytes x
+ * capacity, which does not shrink) plus 290 bytes per regrouped member and 16 per resident file of work space, which are kept.
+ * All or nothing, with no exception: a null indices with n_remove > 0, an index >= size or an index listed twice (RPH_ERR_INVALID_ARG), an
+ * allocation or a HIP call that fails -- each leaves groups, labels, size and count exactly as they were.  n_remove == 0: RPH_OK, nothing
+ * changes.  Removing every file leaves an empty library that rph_library_restore accepts. */
+int rph_library_remove(rph_library *lib, const uint32_t *indices, uint64_t n_remove, uint32_t *new_index_out,
+                       uint64_t *dropped_comparisons_out);
+/* members capacity size, offsets capacity size / 2 + 2: identical to rph_group_files_pdq on the files the library holds, in order. */
 int rph_library_groups(rph_library *lib, uint32_t *members, uint32_t *offsets, uint32_t *n_groups_out);
 /* first + count <= size */
 int rph_library_labels(rph_library *lib, uint64_t first, uint64_t count, uint32_t *labels_out);

@@ -124,6 +124,7 @@ SIGNATURES = {
     "rph_library_reserve": (C.c_int, [_vp, C.c_uint64]),
     "rph_library_size": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "rph_library_append": (C.c_int, [_vp, _u8p, _f32p, _u8p, _i32p, C.c_uint64, _u32p, C.POINTER(C.c_uint64)]),
+    "rph_library_remove": (C.c_int, [_vp, _u32p, C.c_uint64, _u32p, C.POINTER(C.c_uint64)]),
     "rph_library_restore": (C.c_int, [_vp, _u8p, _f32p, _u8p, _i32p, C.c_uint64, _u32p, _u32p, C.c_uint32, C.c_uint64]),
     "rph_library_groups": (C.c_int, [_vp, _u32p, _u32p, C.POINTER(C.c_uint32)]),
     "rph_library_labels": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _u32p]),
@@ -210,6 +211,8 @@ DEBUG_SIGNATURES = {
                                               C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "rph_debug_file_chunks": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "rph_debug_library_stages": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_float)]),
+    "rph_debug_library_remove_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "rph_debug_library_remove_stages": (C.c_int, [_vp, C.POINTER(C.c_float)]),
 }
 
 _lib = None

@@ -106,12 +106,6 @@ __global__ void __launch_bounds__(256) cc_flags_kernel(const uint32_t *__restric
     }
 }
 
-unsigned grid_for(const rph_ctx *ctx, uint64_t items)
-{
-    const uint64_t want = (items + 255) / 256, most = (uint64_t)std::max(ctx->compute_units, 1) * 8;
-    return (unsigned)std::max<uint64_t>(1, std::min(want, most));
-}
-
 int bad_argument(const char *who, const char *what)
 {
     rph_set_error("%s: %s", who, what);
@@ -155,7 +149,7 @@ int rph_union_find_labels(rph_ctx *ctx, const rph_union_edges *sets, uint32_t n_
         RPH_HIP_CHECK(hipMemsetAsync(d_bad, 0, 4, s));
         for (uint32_t k = 0; k < n_sets || k == 0; k++) {  // (no list at all: the forest is still checked)
             const rph_union_edges none{}, &q = n_sets ? sets[k] : none;
-            hipLaunchKernelGGL(uf_check_kernel, dim3(grid_for(ctx, std::max<uint64_t>(q.n_edges, k == 0 ? n : 0))), dim3(256), 0, s, q.edges, q.n_edges, q.i_base, q.j_base,
+            hipLaunchKernelGGL(uf_check_kernel, dim3(rph_stride_grid(ctx, std::max<uint64_t>(q.n_edges, k == 0 ? n : 0))), dim3(256), 0, s, q.edges, q.n_edges, q.i_base, q.j_base,
                                d_labels, n, k == 0, d_bad);
             RPH_HIP_CHECK(hipGetLastError());
         }
@@ -166,11 +160,11 @@ int rph_union_find_labels(rph_ctx *ctx, const rph_union_edges *sets, uint32_t n_
     if (bad) return bad_argument("union-find", "an edge names a file outside n, or a label lies above its file");
     for (uint32_t k = 0; k < n_sets; k++) {
         if (!sets[k].n_edges) continue;
-        hipLaunchKernelGGL(uf_union_kernel, dim3(grid_for(ctx, sets[k].n_edges)), dim3(256), 0, s, sets[k].edges, sets[k].n_edges, sets[k].i_base, sets[k].j_base,
+        hipLaunchKernelGGL(uf_union_kernel, dim3(rph_stride_grid(ctx, sets[k].n_edges)), dim3(256), 0, s, sets[k].edges, sets[k].n_edges, sets[k].i_base, sets[k].j_base,
                            d_labels);
         RPH_HIP_CHECK(hipGetLastError());
     }
-    hipLaunchKernelGGL(uf_flatten_kernel, dim3(grid_for(ctx, n)), dim3(256), 0, s, d_labels, n);
+    hipLaunchKernelGGL(uf_flatten_kernel, dim3(rph_stride_grid(ctx, n)), dim3(256), 0, s, d_labels, n);
     RPH_HIP_CHECK(hipGetLastError());
     return RPH_OK;
 }
@@ -234,7 +228,7 @@ extern "C" int rph_groups_from_labels_dev(rph_ctx *ctx, const void *d_labels, ui
                  *nums = (uint32_t *)(base + o_nums);  // nums: members selected, groups, bad labels
         uint8_t *mflag = base + o_mflag, *rflag = base + o_rflag;
         void *temp = base + o_temp;
-        const unsigned grid = grid_for(ctx, n);
+        const unsigned grid = rph_stride_grid(ctx, n);
         RPH_HIP_CHECK(hipMemsetAsync(count, 0, n * 4, s));
         RPH_HIP_CHECK(hipMemsetAsync(gcount, 0, ((size_t)scan_n + 1) * 4, s));
         RPH_HIP_CHECK(hipMemsetAsync(nums, 0, 16, s));

@@ -1,7 +1,8 @@
 // library.cpp -- rph_library: a grouped set of files that stays on the device (include/rupphash.h).  What rph_group_files_pdq_append
 // moves, expands and re-unions on every call -- the library's hashes, its variants, its flags and its components -- is kept in HBM
 // between calls: an append uploads the new files only, sweeps the pairs they add and unites the edges where the sweep left them
-// (components.hip); a query sweeps without changing anything.
+// (components.hip); a query sweeps without changing anything; a removal compacts the survivors into a second set of arrays and regroups
+// the components that lost a file (library_kernels.hip).
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -22,6 +23,12 @@ struct rph_library {
     // rph_debug_library_stages: events around the stages of the last append (created on the first request)
     bool profile = false, staged = false;  // armed; an append has recorded all six since
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    // rph_library_remove: the uploaded indices; flags, index lists and hipCUB workspace; the gathered rows of the components that lost a
+    // file.  What the last removal did (rph_debug_library_remove_stats) and the events around its stages, armed with the append's
+    DevBuf d_rm_idx, d_rm_work, d_rm_rows;
+    uint64_t rm_stats[3] = {0, 0, 0};  // members regrouped, edges found among them, first edge capacity tried
+    bool rm_staged = false;
+    hipEvent_t rm_ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 };
 
 namespace {
@@ -33,6 +40,13 @@ int fail(const char *who, const char *what)
     rph_set_error("%s: %s", who, what);
     return RPH_ERR_INVALID_ARG;
 }
+
+// Declared behind the host variables that asynchronous copies write and the buffers that kernels in flight use: on every way out of the
+// scope, an error's included, the stream is through with them before they go.  On the ordinary way out the stream is already idle.
+struct StreamDrain {
+    hipStream_t s;
+    ~StreamDrain() { (void)hipStreamSynchronize(s); }
+};
 
 // room for `need` files: geometric growth, device-to-device copy of the resident part, old buffers freed once the stream is through
 // with them.  The new buffers are all allocated before anything is replaced: a failure leaves the library as it was.
@@ -115,6 +129,8 @@ int append(rph_library *lib, const uint8_t *hashes32, const float *coeffs, const
     if (!lib->d_cnt.data()) RPH_TRY(lib->d_cnt.alloc(8));
     uint64_t cap = std::max<uint64_t>(1u << 20, 32 * n_new);
     unsigned long long found[2] = {0, 0};  // behind the cross sweep, behind both
+    std::vector<uint32_t> own(n_new);
+    StreamDrain drain{s};
     for (int attempt = 0;; attempt++) {
         if (attempt == RPH_GROW_GROUP_FILES.attempts) {
             rph_set_error("rph_library_append: edge list kept growing (%llu)", found[1]);
@@ -142,7 +158,6 @@ int append(rph_library *lib, const uint8_t *hashes32, const float *coeffs, const
     // fail after it is a HIP call, that is a device that is lost to this context anyway.
     const rph_edge *e = lib->d_edges.as<rph_edge>();
     uint32_t *lab = lib->d_lab.as<uint32_t>();
-    std::vector<uint32_t> own(n_new);
     for (uint64_t i = 0; i < n_new; i++) own[i] = (uint32_t)(n + i);
     RPH_HIP_CHECK(hipMemcpyAsync(lab + n, own.data(), n_new * 4, hipMemcpyHostToDevice, s));
     RPH_HIP_CHECK(hipStreamSynchronize(s));
@@ -156,6 +171,127 @@ int append(rph_library *lib, const uint8_t *hashes32, const float *coeffs, const
     lib->n = n + n_new;
     lib->comparisons += found[1];
     if (new_comparisons_out) *new_comparisons_out = found[1];
+    return RPH_OK;
+}
+
+int mark_removal(rph_library *lib, int k, hipStream_t s)
+{
+    if (lib->profile) RPH_HIP_CHECK(hipEventRecord(lib->rm_ev[k], s));
+    return RPH_OK;
+}
+
+// `indices` are checked (below the size, none twice) and `sorted` holds them ascending.  Three facts make this exact: an edge (i, j), i < j,
+// depends on the two files and their order alone; every edge lies inside one component; a stable compaction keeps the order.  So the
+// survivors' graph is the old one minus the edges of the removed files, components that lost nobody keep their labels (renumbered), and
+// only the members of the others are swept again.  The new state is built beside the old one and moved in last: whatever fails before
+// that, an allocation or a HIP call, leaves the library as it was.
+int remove(rph_library *lib, const uint32_t *indices, const std::vector<uint32_t> &sorted, uint32_t *new_index_out, uint64_t *dropped_out)
+{
+    rph_ctx *ctx = lib->ctx;
+    hipStream_t s = ctx->stream;
+    const uint64_t n = lib->n, n_remove = sorted.size(), kept = n - n_remove;
+    // every buffer whose size is known now: the resident twins at the same capacity, the indices, flags / lists / workspace
+    const size_t width[5] = {32, 256, 1, 1, 4};
+    DevBuf *cur[5] = {&lib->d_h, &lib->d_var, &lib->d_lc, &lib->d_hf, &lib->d_lab};
+    DevBuf next[5];
+    uint32_t host_nums[2] = {0, 0};  // what comes back from the device: survivors and members, edges found, edges dropped
+    unsigned long long found = 0, dropped = 0;
+    StreamDrain drain{s};
+    for (int k = 0; k < 5; k++) RPH_TRY(next[k].alloc(lib->cap * width[k]));
+    size_t temp_bytes = 0;
+    RPH_TRY(rph_library_select_temp_bytes(n, &temp_bytes));
+    Layout L;
+    const size_t o_removed = L.add(n, 256), o_touched = L.add(n, 256), o_keep = L.add(n, 256), o_regroup = L.add(n, 256), o_new = L.add(n * 4, 256),
+                 o_survivors = L.add(n * 4, 256), o_members = L.add(n * 4, 256), o_nums = L.add(16, 256), o_temp = L.add(temp_bytes + 16, 256);
+    RPH_TRY(lib->d_rm_work.reserve(L.end(), s));
+    RPH_TRY(lib->d_rm_idx.reserve(n_remove * 4, s));
+    if (!lib->d_cnt.data()) RPH_TRY(lib->d_cnt.alloc(8));
+    uint8_t *w = lib->d_rm_work.data();
+    uint8_t *removed = w + o_removed, *touched = w + o_touched, *keep = w + o_keep, *regroup = w + o_regroup;
+    uint32_t *new_index = (uint32_t *)(w + o_new), *survivors = (uint32_t *)(w + o_survivors), *members = (uint32_t *)(w + o_members);
+    uint32_t *nums = (uint32_t *)(w + o_nums);  // survivors, members; behind them the dropped edges (8 bytes)
+    unsigned long long *d_dropped = (unsigned long long *)(w + o_nums + 8);
+    const uint32_t *lab = lib->d_lab.as<uint32_t>();
+
+    RPH_TRY(mark_removal(lib, 0, s));
+    RPH_HIP_CHECK(hipMemcpyAsync(lib->d_rm_idx.data(), indices, n_remove * 4, hipMemcpyHostToDevice, s));
+    RPH_TRY(rph_library_launch_mark(ctx, lib->d_rm_idx.as<uint32_t>(), n_remove, lab, n, removed, touched, keep, regroup, s));
+    RPH_TRY(rph_library_launch_select(keep, regroup, n, new_index, survivors, members, nums, w + o_temp, temp_bytes, s));
+    RPH_HIP_CHECK(hipMemcpyAsync(host_nums, nums, 8, hipMemcpyDeviceToHost, s));
+    RPH_TRY(mark_removal(lib, 1, s));
+    RPH_HIP_CHECK(hipStreamSynchronize(s));
+    const uint64_t m = host_nums[1];
+    if (host_nums[0] != kept || m < n_remove || m > n) {
+        rph_set_error("rph_library_remove: the selection kept %u files and regroups %u (%llu of %llu stay)", host_nums[0], host_nums[1], (unsigned long long)kept,
+                      (unsigned long long)n);
+        return RPH_ERR_HIP;
+    }
+
+    // the members of the components that lost a file, removed ones included (their edges are what the count goes down by), in order
+    Layout R;
+    const size_t r_h = R.add(m * 32, 256), r_var = R.add(m * 256, 256), r_lc = R.add(m, 256), r_hf = R.add(m, 256);
+    RPH_TRY(lib->d_rm_rows.reserve(R.end(), s));
+    uint8_t *r = lib->d_rm_rows.data();
+    const rph_library_rows resident{lib->d_h.data(), lib->d_var.data(), lib->d_lc.data(), lib->d_hf.data()}, part{r + r_h, r + r_var, r + r_lc, r + r_hf},
+        twin{next[0].data(), next[1].data(), next[2].data(), next[3].data()};
+    RPH_TRY(rph_library_launch_gather(ctx, members, m, resident, part, s));
+    RPH_TRY(mark_removal(lib, 2, s));
+
+    // their pairs again: the triangular variant sweep, i < j among the members being i < j in the library.  The capacity asked for is what
+    // the sweep may fill, not what the buffer happens to hold: which attempt succeeds then depends on this call alone.
+    rph_sweep again;
+    again.rows = part.variants, again.n_variants = 8, again.n = m;
+    again.low_conf = part.low_conf, again.has_features = part.has_features;
+    again.cols = part.hashes;
+    again.threshold = lib->similarity;
+    uint64_t edge_cap = std::max<uint64_t>(1u << 20, 32 * m);
+    const uint64_t first_cap = edge_cap;
+    for (int attempt = 0;; attempt++) {
+        if (attempt == RPH_GROW_GROUP_FILES.attempts) {
+            rph_set_error("rph_library_remove: edge list kept growing (%llu)", found);
+            return RPH_ERR_CAPACITY;
+        }
+        RPH_TRY(lib->d_edges.reserve(edge_cap * sizeof(rph_edge), s));
+        RPH_HIP_CHECK(hipMemsetAsync(lib->d_cnt.data(), 0, 8, s));
+        again.edges = lib->d_edges.as<rph_edge>(), again.cap = edge_cap, again.count = lib->d_cnt.as<unsigned long long>();
+        RPH_TRY(rph_launch_hamming_sweep(ctx, again, s, ctx->hamming_kernel));
+        RPH_HIP_CHECK(hipMemcpyAsync(&found, lib->d_cnt.data(), 8, hipMemcpyDeviceToHost, s));
+        RPH_TRY(mark_removal(lib, 3, s));
+        RPH_HIP_CHECK(hipStreamSynchronize(s));
+        if (found <= edge_cap) break;
+        edge_cap = RPH_GROW_GROUP_FILES.next_cap(found);
+    }
+
+    // edges of removed files counted and disarmed, the rest renumbered; the survivors' rows and starting labels into the twins; the kept
+    // edges united over the new labels (one range check first, then union and flatten)
+    RPH_TRY(rph_library_launch_split_edges(ctx, lib->d_edges.as<rph_edge>(), found, members, removed, new_index, d_dropped, s));
+    RPH_HIP_CHECK(hipMemcpyAsync(&dropped, d_dropped, 8, hipMemcpyDeviceToHost, s));
+    RPH_TRY(mark_removal(lib, 4, s));
+    RPH_TRY(rph_library_launch_gather(ctx, survivors, kept, resident, twin, s));
+    RPH_TRY(rph_library_launch_labels(ctx, lab, removed, touched, new_index, n, next[4].as<uint32_t>(), s));
+    RPH_TRY(mark_removal(lib, 5, s));
+    if (kept) {
+        const rph_union_edges all{lib->d_edges.as<rph_edge>(), found, 0, 0};
+        RPH_TRY(rph_union_find_labels(ctx, &all, 1, next[4].as<uint32_t>(), kept, s));
+    }
+    RPH_TRY(mark_removal(lib, 6, s));
+    RPH_HIP_CHECK(hipStreamSynchronize(s));
+
+    // the swap: nothing can fail from here, and the stream is through with the old arrays
+    for (int k = 0; k < 5; k++) *cur[k] = std::move(next[k]);
+    lib->n = kept;
+    lib->comparisons -= std::min<uint64_t>(dropped, lib->comparisons);  // (a restored count may have been lower than the files' edges)
+    lib->rm_stats[0] = m, lib->rm_stats[1] = found, lib->rm_stats[2] = first_cap;
+    lib->rm_staged = lib->profile;
+    if (dropped_out) *dropped_out = dropped;
+    if (new_index_out) {
+        uint64_t gone = 0;
+        for (uint64_t x = 0; x < n; x++) {
+            const bool out = gone < n_remove && sorted[gone] == x;
+            gone += out;
+            new_index_out[x] = out ? 0xFFFFFFFFu : (uint32_t)(x - gone);
+        }
+    }
     return RPH_OK;
 }
 }  // namespace
@@ -184,6 +320,8 @@ int rph_library_destroy(rph_library *lib)
         (void)hipSetDevice(lib->ctx->device);
         (void)hipStreamSynchronize(lib->ctx->stream);
         for (hipEvent_t e : lib->ev)
+            if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : lib->rm_ev)
             if (e) (void)hipEventDestroy(e);
     }
     delete lib;
@@ -225,6 +363,26 @@ int rph_library_append(rph_library *lib, const uint8_t *hashes32, const float *c
         if (n_new > MAX_FILES || lib->n + n_new > MAX_FILES) return fail("rph_library_append", "at most 2^31 - 1 files");
         RPH_HIP_CHECK(hipSetDevice(lib->ctx->device));
         return append(lib, hashes32, coeffs, has_features, quality, n_new, labels_out, new_comparisons_out);
+    });
+}
+
+int rph_library_remove(rph_library *lib, const uint32_t *indices, uint64_t n_remove, uint32_t *new_index_out, uint64_t *dropped_comparisons_out)
+{
+    return rph_guarded("rph_library_remove", [&]() -> int {
+        if (!lib || (!indices && n_remove)) return fail("rph_library_remove", "null argument");
+        std::lock_guard<std::mutex> lock(lib->mu);
+        if (n_remove > lib->n) return fail("rph_library_remove", "more indices than files: one is listed twice or lies outside the library");
+        std::vector<uint32_t> sorted(indices, indices + n_remove);
+        std::sort(sorted.begin(), sorted.end());
+        if (n_remove && sorted.back() >= lib->n) return fail("rph_library_remove", "an index is not below the size");
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return fail("rph_library_remove", "an index is listed twice");
+        if (n_remove == 0) {  // nothing changes; the map is the identity
+            if (dropped_comparisons_out) *dropped_comparisons_out = 0;
+            for (uint64_t x = 0; x < lib->n && new_index_out; x++) new_index_out[x] = (uint32_t)x;
+            return RPH_OK;
+        }
+        RPH_HIP_CHECK(hipSetDevice(lib->ctx->device));
+        return remove(lib, indices, sorted, new_index_out, dropped_comparisons_out);
     });
 }
 
@@ -337,8 +495,32 @@ int rph_debug_library_stages(rph_library *lib, int on, float *ms_out)
             for (int k = 0; k < 5; k++) RPH_HIP_CHECK(hipEventElapsedTime(&ms_out[k], lib->ev[k], lib->ev[k + 1]));
         }
         for (int k = 0; k < 6 && on && !lib->ev[k]; k++) RPH_HIP_CHECK(hipEventCreate(&lib->ev[k]));
+        for (int k = 0; k < 7 && on && !lib->rm_ev[k]; k++) RPH_HIP_CHECK(hipEventCreate(&lib->rm_ev[k]));
         lib->profile = on != 0;
-        lib->staged = false;
+        lib->staged = lib->rm_staged = false;
+        return RPH_OK;
+    });
+}
+
+// What the last removal did (exported for the tests, not in the header; rph_internal.h says what the four numbers are)
+int rph_debug_library_remove_stats(rph_library *lib, uint64_t *out)
+{
+    if (!lib || !out) return fail("rph_debug_library_remove_stats", "null argument");
+    std::lock_guard<std::mutex> lock(lib->mu);
+    for (int k = 0; k < 3; k++) out[k] = lib->rm_stats[k];
+    out[3] = rph_stride_lanes_per_pass(lib->ctx);
+    return RPH_OK;
+}
+
+// The stages of the last removal in device time, armed by rph_debug_library_stages (exported for tools/library_remove_rate.py)
+int rph_debug_library_remove_stages(rph_library *lib, float *ms_out)
+{
+    return rph_guarded("rph_debug_library_remove_stages", [&]() -> int {
+        if (!lib || !ms_out) return fail("rph_debug_library_remove_stages", "null argument");
+        std::lock_guard<std::mutex> lock(lib->mu);
+        if (!lib->rm_staged) return fail("rph_debug_library_remove_stages", "no removal has run with the events armed");
+        RPH_HIP_CHECK(hipSetDevice(lib->ctx->device));
+        for (int k = 0; k < 6; k++) RPH_HIP_CHECK(hipEventElapsedTime(&ms_out[k], lib->rm_ev[k], lib->rm_ev[k + 1]));
         return RPH_OK;
     });
 }

@@ -203,9 +203,44 @@ struct rph_union_edges {
 // What rph_union_find_labels_dev does, for several lists at once: one range check of all of them and of the entry forest (it waits for
 // that: RPH_ERR_INVALID_ARG with nothing written), then one union launch per list and ONE flatten, asynchronous on `stream`
 int rph_union_find_labels(rph_ctx *ctx, const rph_union_edges *sets, uint32_t n_sets, uint32_t *d_labels, uint64_t n, hipStream_t stream);
+// The grid of the grid-stride kernels of components.hip and library_kernels.hip: blocks of 256 lanes, at most 8 per compute unit, the
+// loops stride over the rest.  rph_stride_lanes_per_pass is what one pass of such a loop covers (rph_debug_library_remove_stats).
+inline uint64_t rph_stride_lanes_per_pass(const rph_ctx *ctx) { return (uint64_t)(ctx->compute_units > 1 ? ctx->compute_units : 1) * 8 * 256; }
+inline unsigned rph_stride_grid(const rph_ctx *ctx, uint64_t items)
+{
+    const uint64_t want = (items + 255) / 256, most = rph_stride_lanes_per_pass(ctx) / 256;
+    return (unsigned)(want < 1 ? 1 : want < most ? want : most);
+}
 // library.cpp: the stages of a library's last append in device time (exported for tools/library_rate.py, not in the header)
 struct rph_library;
 extern "C" int rph_debug_library_stages(rph_library *lib, int on, float *ms_out);
+// library.cpp: what the last rph_library_remove did (exported for the tests and tools/library_remove_rate.py, not in the header).
+// out[0..3]: members of the components that lost a file (m), edges the regroup sweep found among them, the first edge capacity it tried,
+// lanes of one pass of the removal kernels' grid-stride loops (the gather kernel moves a sixteenth as many files per pass).
+extern "C" int rph_debug_library_remove_stats(rph_library *lib, uint64_t *out);
+// its stages in device time, armed by rph_debug_library_stages(lib, 1, NULL) like the append's (6 floats): mark and select, gather of
+// the members, regroup sweep, edge split, compaction and labels, union and flatten
+extern "C" int rph_debug_library_remove_stages(rph_library *lib, float *ms_out);
+// library_kernels.hip: the steps of rph_library_remove, asynchronous on `stream`.  One file's rows in the four per-file arrays:
+struct rph_library_rows {
+    uint8_t *hashes = nullptr, *variants = nullptr, *low_conf = nullptr, *has_features = nullptr;  // [32], [8][32], [1], [1] per file; 16-byte aligned
+};
+// removed[x] and touched[label[x]] for the listed files (d_labels: flattened min-labels), then keep[x] = !removed[x] and
+// regroup[x] = touched[label[x]]; n bytes each
+int rph_library_launch_mark(rph_ctx *ctx, const uint32_t *d_indices, uint64_t n_remove, const uint32_t *d_labels, uint64_t n, uint8_t *d_removed, uint8_t *d_touched,
+                            uint8_t *d_keep, uint8_t *d_regroup, hipStream_t stream);
+int rph_library_select_temp_bytes(uint64_t n, size_t *bytes_out);
+// d_new_index[x] = kept files below x; d_survivors / d_members: the files with keep / regroup set, ascending; d_counts[0], [1]: how many
+int rph_library_launch_select(const uint8_t *d_keep, const uint8_t *d_regroup, uint64_t n, uint32_t *d_new_index, uint32_t *d_survivors, uint32_t *d_members,
+                              uint32_t *d_counts, void *d_temp, size_t temp_bytes, hipStream_t stream);
+// rows d_list[0 .. count) of src become rows 0 .. count-1 of dst
+int rph_library_launch_gather(rph_ctx *ctx, const uint32_t *d_list, uint64_t count, const rph_library_rows &src, const rph_library_rows &dst, hipStream_t stream);
+// edges local to d_members, in place: one that touches a removed file is counted in *d_dropped and becomes (0, 0), the others get new numbers
+int rph_library_launch_split_edges(rph_ctx *ctx, rph_edge *d_edges, uint64_t n_edges, const uint32_t *d_members, const uint8_t *d_removed, const uint32_t *d_new_index,
+                                   unsigned long long *d_dropped, hipStream_t stream);
+// new_labels[new(x)] for every kept x: itself if its component lost a file, else the new number of its (kept) root
+int rph_library_launch_labels(rph_ctx *ctx, const uint32_t *d_labels, const uint8_t *d_removed, const uint8_t *d_touched, const uint32_t *d_new_index, uint64_t n,
+                              uint32_t *d_new_labels, hipStream_t stream);
 int rph_launch_mih_build256(rph_ctx *ctx, const uint8_t *d_hashes, uint64_t n, uint32_t *d_offsets, uint32_t *d_values,
                             hipStream_t stream);
 int rph_launch_mih_build64(rph_ctx *ctx, const uint64_t *d_hashes, uint64_t n, uint32_t *d_offsets, uint32_t *d_values,

@@ -933,7 +933,8 @@ class Engine:
 
 class Library:
     """rph_library: files appended so far stay on the device with their variants, flags and component labels.  groups() equals
-    Engine.group_files_pdq on everything appended, in order.  One similarity, at most 2^31 - 1 files, no removal.  Close it before its engine."""
+    Engine.group_files_pdq on the files it holds, in order.  One similarity, at most 2^31 - 1 files; remove() renumbers the files that
+    stay.  Close it before its engine."""
 
     def __init__(self, engine, similarity):
         self.engine, self.L, self.similarity = engine, engine.L, similarity
@@ -991,6 +992,16 @@ class Library:
         check(self.L.rph_library_append(self.handle, _ptr(h), _ptr(c), _ptr(hf), _ptr(q), len(h), _ptr(labels), C.byref(cmp_count)),
               "rph_library_append")
         return labels, cmp_count.value
+
+    def remove(self, indices):
+        """Remove the files with these (current, distinct) numbers.  The others keep their order and are renumbered densely.  Returns
+        (new_index, dropped): the new number of every old file (0xFFFFFFFF for a removed one) and the comparisons that went with the
+        removed files.  Afterwards the library equals Engine.group_files_pdq on the remaining files; a refused call changes nothing."""
+        idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        new_index = np.zeros(len(self), np.uint32)
+        dropped = C.c_uint64()
+        check(self.L.rph_library_remove(self.handle, _ptr(idx), len(idx), _ptr(new_index), C.byref(dropped)), "rph_library_remove")
+        return new_index, dropped.value
 
     def restore(self, hashes, groups, comparisons=0, coeffs=None, has_features=None, quality=None):
         """Start an empty library from files an earlier run grouped at the same similarity (`groups` as it returned them): no sweep."""

@@ -173,7 +173,8 @@ class ScannerLibrary(Library):
 
 def open_library(similarity, engine=None):
     """A grouped library that stays on the device between scans (ScannerLibrary): append(...) -> (labels, new_comparisons), restore(...),
-    groups(), labels(), query(...).  groups() is group_with_pdqhash on everything appended so far, in order."""
+    groups(), labels(), query(...).  groups() is group_with_pdqhash on the files the library holds, in order.
+    remove(indices) -> (new_index, dropped) takes files out (deleted, or gone at the next scan) and renumbers the rest through new_index."""
     return ScannerLibrary(engine or default_engine(), similarity)
 
 
