@@ -133,6 +133,55 @@ def lzw_decode(stream, m, n):
     return np.array(out[:n], np.uint8)
 
 
+def lzw_events(stream, m, n):
+    """a trace of the rule over the same stream: one (kind, at, src, length, written, distinct, clipped) per code that gives bytes, in
+    order, or None for a stream lzw_decode refuses.  kind: "literal", "copy" (a table entry) or "kwkwk" (the next free entry); at: the
+    position in the frame's indices the string begins at; src: where the string it copies begins (an entry is the string before it and
+    the byte behind that string; None for a literal); length: the string's bytes; written: those that fit the frame; distinct: the
+    number of different bytes among the written ones; clipped: length > written.  Written for the tests' coverage claims, apart from
+    lzw_decode: the table holds (position, length) as the device's does."""
+    cl, eoi, first = 1 << m, (1 << m) + 1, (1 << m) + 2
+    bits = int.from_bytes(stream, "little")
+    avail, used = 8 * len(stream), 0
+    pos, length = {}, {}
+    nxt, width, prev = first, m + 1, None  # prev: (position, length) of the string before
+    out, events = [], []
+    while len(out) < n:
+        if used + width > avail:
+            return None
+        code = (bits >> used) & ((1 << width) - 1)
+        used += width
+        if code == cl:
+            pos, length, nxt, width, prev = {}, {}, first, m + 1, None
+            continue
+        if code == eoi:
+            return None
+        at, room = len(out), n - len(out)
+        if code < cl:
+            kind, src, ln = "literal", None, 1
+            out.append(code)
+        elif prev is None:
+            return None
+        elif code < nxt:
+            kind, src, ln = "copy", pos[code], length[code]
+        elif code == nxt:
+            kind, src, ln = "kwkwk", prev[0], prev[1] + 1
+        else:
+            return None
+        written = min(ln, room)
+        if src is not None:
+            for i in range(written):  # (forward, byte by byte: an overlapping copy repeats its period)
+                out.append(out[src + i])
+        events.append((kind, at, src, ln, written, len(set(out[at:at + written])), ln > written))
+        if prev is not None and nxt < ENTRIES:
+            pos[nxt], length[nxt] = prev[0], prev[1] + 1
+            nxt += 1
+            if nxt == 1 << width and width < 12:
+                width += 1
+        prev = (at, ln)
+    return events
+
+
 # ---- the pixel rule ----
 def pass_order(h):
     return list(range(0, h, 8)) + list(range(4, h, 8)) + list(range(2, h, 4)) + list(range(1, h, 2))
@@ -232,6 +281,24 @@ def image_gif(idx, pal, m=None, screen=None, pos=(0, 0), interlace=False, trans=
     screen = screen or (fw, fh)
     data = write_gif(screen, pos, (fw, fh), m, stream, gct=gct if local else pal, lct=pal if local else None, interlace=interlace, trans=trans, **kw)
     return data, render(screen, pos, idx, pal, trans)
+
+
+def frame_stream(data):
+    """a file of this writer taken apart again: (m, (fw, fh), the joined LZW bytes of its first frame)"""
+    pos = 13 + (3 * (2 << (data[10] & 7)) if data[10] & 0x80 else 0)
+    while data[pos] == 0x21:
+        pos += 2
+        while data[pos]:
+            pos += 1 + data[pos]
+        pos += 1
+    assert data[pos] == 0x2C
+    fw, fh, flags = struct.unpack_from("<HHB", data, pos + 5)
+    pos += 10 + (3 * (2 << (flags & 7)) if flags & 0x80 else 0)
+    m, pos, stream = data[pos], pos + 1, bytearray()
+    while pos < len(data) and data[pos]:
+        stream += data[pos + 1:pos + 1 + data[pos]]
+        pos += 1 + data[pos]
+    return m, (fw, fh), bytes(stream)
 
 
 def raw_gif(codes, m, size, pal=None, **kw):

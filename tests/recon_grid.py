@@ -3,13 +3,20 @@ transforms and table slots.  Every grid puts the sizes where wave-shaped code go
 129, units of 1 to 8 bytes, every sample layout, every filter or predictor mode) under noise, so that running sums wrap, Paeth takes
 all three branches, the clamping modes saturate at both ends and select meets ties (a share of every image holds only 0 and the
 maximum).  Seeded, built once per process, (name, bytes) lists per group; references() decodes each file once with the plain Python
-decoders and hashes what the pixel hash hashes."""
+decoders and hashes what the pixel hash hashes.
+
+GIF and BMP have no stage behind an entropy decoder; their grids put the device kernels they do have on their seams: the GIF expand
+kernel's row loop past one trip of its grid and its frame edges on the 64-pixel steps, the GIF LZW kernel's switch between LDS and
+global memory and its 64-byte copies under noise, the BMP expand kernel's walk through a band of rows.  Their references are the
+pixels gif_streams and bmp_streams state for what they write."""
 import os
 import re
 
 import numpy as np
 
 import blake3_util as b3
+import bmp_streams as bs
+import gif_streams as gs
 import png_util as pu
 import tiff_util as tu
 import webp_util as wu
@@ -225,13 +232,223 @@ def webp_grid():
     return _CACHE["webp"]
 
 
+# ------------------------------------------------------------------ GIF
+# The expand kernel gives one wave a screen row and a block four of them; the launch has at most 256 blocks, so one trip of a wave's row
+# loop covers 1024 rows.  The LZW kernel builds a frame of at most 16 384 indices in LDS and a longer one in global memory.
+GIF_ROWS_PER_TRIP, GIF_LDS_FRAME = 1024, 16384
+GIF_TALL = (1023, 1024, 1025, 1028, 2047, 2049)
+GIF_COPY_LENGTHS = (63, 64, 65, 127, 128, 129)
+GIF_OVERRUNS = (1, 63, 64, 65)
+GIF_SMALL = "small-5x5"  # the file the tall screens are mixed with (test_recon_grid_gpu.py)
+
+
+class _Built:
+    """a format whose builders (gif_streams, bmp_streams) hand out the pixels the rule gives together with the file: references() takes
+    them from _PIXELS and decodes nothing"""
+    to_rgba16 = staticmethod(b3.rgba16_bytes)
+
+
+_PIXELS = {}
+
+
+def _gif_content(rng, shape, colours, opaque):
+    """noise over `colours` indices and what it is shown with: (indices, m, palette, transparent index).  Not opaque: a palette half as
+    long as the index range (indices past the palette) and a transparent index in the palette's middle, so that noise falls on both
+    sides of it; opaque: the whole palette and no transparency, what Pillow decodes by the same rule."""
+    m = max(2, (colours - 1).bit_length())
+    idx = rng.integers(0, colours, shape).astype(np.uint8)
+    if opaque:
+        return idx, m, gs.colour_palette(1 << m, colours + 1), None
+    n = max(2, (1 << m) // 2)
+    return idx, m, gs.colour_palette(n, colours), n // 2
+
+
+def _gif_image(rng, fw, fh, colours=32, opaque=False, **kw):
+    idx, m, pal, trans = _gif_content(rng, (fh, fw), colours, opaque)
+    return gs.image_gif(idx, pal, m=m, trans=trans, **kw)
+
+
+class _Codes:
+    """a raw code list that keeps count of what the decoder's table will hold: emit() returns the entry the code adds (the string
+    before it and its first byte), or None"""
+
+    def __init__(self, m):
+        self.m, self.codes, self.out = m, [], 0
+        self.clear()
+
+    def clear(self):
+        self.codes.append(1 << self.m)
+        self.next, self.prev = (1 << self.m) + 2, False
+
+    def emit(self, code, length):
+        added = None
+        if self.prev and self.next < gs.ENTRIES:
+            added, self.next = self.next, self.next + 1
+        self.prev = True
+        self.codes.append(code)
+        self.out += length
+        return added
+
+
+def _staircase(c, s, kwkwk=(), last=None):
+    """After S[0], S[1] the pair (code of S[:j], literal S[j]) adds the entry S[:j + 1]: every pair begins with a plain copy of j bytes of
+    noise.  Before the pair of j = L - 1 for L in kwkwk: (code of S[:L - 1], the next free entry), the copy of L bytes that overlaps its
+    own output by one byte.  last = ("copy", L) or ("kwkwk", L): stop with that code (the caller clips it)."""
+    c.emit(int(s[0]), 1)
+    code = None
+    for j in range(1, len(s)):
+        if code is not None:
+            if j + 1 in kwkwk or last == ("kwkwk", j + 1):
+                c.emit(code, j)
+                c.emit(c.next, j + 1)
+                if last == ("kwkwk", j + 1):
+                    return
+            c.emit(code, j)
+            if last == ("copy", j):
+                return
+        code = c.emit(int(s[j]), 1)
+    assert last is None
+
+
+def _gif_raw(name, c, m, w, h, pal, trans):
+    stream = gs.pack_codes(c.codes, m)
+    idx = gs.lzw_decode(stream, m, w * h)
+    assert idx is not None, name
+    return name, gs.write_gif((w, h), (0, 0), (w, h), m, stream, gct=pal, trans=trans), gs.render((w, h), (0, 0), idx.reshape(h, w), pal, trans)
+
+
+def _gif_copies(rng):
+    """raw code streams whose copies carry noise, each in a frame built in LDS (one staircase) and in one built in global memory (two,
+    a Clear between them; three where the last one is cut short by a clipped string); literals in front fill the frame to a whole
+    number of rows"""
+    out = []
+    for m, steps in ((4, 140), (8, 140)):
+        pal, trans = gs.colour_palette(max(2, (1 << m) // 2), 50 + m), (1 << m) // 4
+        for form, stairs in (("lds", 1), ("global", 2)):
+            w = 97 if form == "lds" else 131
+            # clipped last strings: the frame ends `room` bytes into them, room and length - room each 1, 63, 64 and 65 where they fit
+            tails = [(kind, L, room) for kind, L in (("copy", 130), ("kwkwk", 65), ("kwkwk", 129)) if m == 4
+                     for room in sorted({r for o in GIF_OVERRUNS for r in (o, L - o) if 0 < r < L})]
+            for tail in [None] + tails:
+                s = [rng.integers(0, 1 << m, steps) for _ in range(stairs + (tail is not None and form == "global"))]
+                lits = rng.integers(0, 1 << m, w)
+
+                def build(pad):
+                    c = _Codes(m)
+                    for v in lits[:pad]:
+                        c.emit(int(v), 1)
+                    for k in range(len(s)):
+                        if k:
+                            c.clear()
+                        _staircase(c, s[k], GIF_COPY_LENGTHS, tail[:2] if tail and k == len(s) - 1 else None)
+                    return c, c.out if tail is None else c.out - tail[1] + tail[2]  # (a clipped last string gives `room` bytes)
+
+                c, total = build(-build(0)[1] % w)
+                assert total % w == 0 and (total <= GIF_LDS_FRAME) == (form == "lds"), (m, form, tail, total)
+                name = f"stairs-m{m}-{form}" + (f"-{tail[0]}{tail[1]}-room{tail[2]}" if tail else "")
+                out.append(_gif_raw(name, c, m, w, total // w, pal, trans))
+    return out
+
+
+def gif_grid():
+    """{'expand_rows': screens 5 .. 9 px wide and 1023 .. 2049 rows tall, plain and interlaced, the frame on the screen, one row down and
+    1020 rows down (clipped at the bottom), and interlaced frames of 1024 .. 1031 rows (every residue mod 8); 'expand_cols': screens of
+    127 .. 130 px with the frame's left edge at 0, 1, 63, 64, 65 and its right edge at 63, 64, 65, 128, 129 and past the screen;
+    'lzw_switch': frames of 16 383, 16 384 and 16 385 indices, of 16 369 .. 16 383 (every residue of the last 16-byte store) and of
+    1 .. 33; 'lzw_copies': raw streams whose plain and KwKwK copies of 63 .. 129 bytes carry noise, on both sides of the switch, and
+    last strings clipped by the frame's end}"""
+    if "gif" not in _CACHE:
+        rng = np.random.default_rng(2104)
+        rows, cols, switch = [], [], []
+        add = lambda group, name, pair: group.append((name, pair[0], pair[1]))
+        add(rows, GIF_SMALL, _gif_image(rng, 5, 5))
+        for k, h in enumerate(GIF_TALL):
+            w = 5 + k % 5
+            for il in (False, True):
+                kind = "interlaced" if il else "plain"
+                add(rows, f"rows-{kind}-{w}x{h}" + ("-opaque" if il == (k % 2 == 0) else ""), _gif_image(rng, w, h, opaque=il == (k % 2 == 0), interlace=il))
+                for fy in (1, 1020):  # (the frame as tall as the screen: it reaches fy rows past the bottom)
+                    add(rows, f"rows-{kind}-{w}x{h}-fy{fy}", _gif_image(rng, w, h, screen=(w, h), pos=(0, fy), interlace=il))
+        for fh in range(1024, 1032):
+            add(rows, f"rows-interlaced-frame5x{fh}-fy0", _gif_image(rng, 5, fh, interlace=True))
+            add(rows, f"rows-interlaced-frame5x{fh}-fy3", _gif_image(rng, 5, fh, screen=(5, fh + 5), pos=(0, 3), interlace=True))
+        for w in (127, 128, 129, 130):
+            for fx in (0, 1, 63, 64, 65):
+                for k, right in enumerate((63, 64, 65, 128, 129, w + 3)):
+                    if right > fx:
+                        add(cols, f"cols-{w}x6-fx{fx}-right{right}", _gif_image(rng, right - fx, 6, screen=(w, 6), pos=(fx, 0), interlace=k % 2 == 1))
+        exact = [(127, 129), (128, 128), (16384, 1), (1, 16384), (145, 113)]
+        below = [(n, 1) if n % 2 else (1, n) for n in range(16369, 16383)]
+        small = [(n, 1) if n % 2 else (1, n) for n in range(1, 34)]
+        for k, (w, h) in enumerate(exact + below + small):
+            for j, (colours, clear) in enumerate(((4, "never"), (256, "full"), (4, "full"), (256, "never"))):
+                if (w, h) in exact or (k + j) % 4 == 0:  # the exact sizes take all four contents, the others one each in turn
+                    opaque = (k + j) % 2 == 0
+                    add(switch, f"switch-{w}x{h}-c{colours}-{clear}" + ("-opaque" if opaque else ""), _gif_image(rng, w, h, colours, opaque, clear=clear))
+        grid = dict(expand_rows=rows, expand_cols=cols, lzw_switch=switch, lzw_copies=_gif_copies(rng))
+        for files in grid.values():
+            for name, _, px in files:
+                _PIXELS[("gif", name)] = px
+        _CACHE["gif"] = {g: [(n, d) for n, d, _ in files] for g, files in grid.items()}
+    return _CACHE["gif"]
+
+
+# ------------------------------------------------------------------ BMP
+# The expand kernel's work item is a band of max(1, 2048 / G) rows of an image, G = ceil(w / 4) groups of four pixels; its 256 threads
+# walk the band's rows * G groups flattened, stepping by (256 / G, 256 % G) and carrying a group overflow into the row.
+BMP_GROUPS_PER_ITEM, BMP_THREADS = 2048, 256
+BMP_KEPT = ((1, 2049), (9, 683), (1025, 15), (8193, 3))  # every variant and row order
+BMP_THINNED = ((4, 2048), (5, 1025), (10, 1365), (17, 410), (25, 293), (1021, 9), (1024, 8), (8192, 3))  # size k: the variants with (k + variant) % 4 == 0
+
+
+def bmp_walk(w, h):
+    """the kernel's formulas restated: G, band, (dr, dg), the rows of every work item, the trips of thread 0 through a full item and
+    the carries (g >= G) of all threads in it"""
+    G = (w + 3) // 4
+    band = max(1, BMP_GROUPS_PER_ITEM // G)
+    dr, dg = BMP_THREADS // G, BMP_THREADS % G
+    items = [min(band, h - row0) for row0 in range(0, h, band)]
+    total = items[0] * G
+    carries = 0
+    for t in range(min(BMP_THREADS, total)):
+        g = t % G
+        for _ in range(t, total, BMP_THREADS):
+            g += dg
+            if g >= G:
+                g, carries = g - G, carries + 1
+    return dict(G=G, band=band, clamped=BMP_GROUPS_PER_ITEM // G == 0, dr=dr, dg=dg, items=items, trips=-(-total // BMP_THREADS), carries=carries)
+
+
+def bmp_name(variant, top_down, w, h):
+    return f"{variant}-{'topdown' if top_down else 'bottomup'}-{w}x{h}"
+
+
+def bmp_grid():
+    """{'bands': the 16 variants in both row orders (RLE: bottom-up) at the sizes where the band walk of the expand kernel changes:
+    one group per row and eight trips, a last item of one row, steps that carry on every third trip, more groups than threads, more
+    groups than an item holds}"""
+    if "bmp" not in _CACHE:
+        bands = []
+        for v, variant in enumerate(bs.VARIANTS):
+            sizes = list(BMP_KEPT) + [s for k, s in enumerate(BMP_THINNED) if (k + v) % 4 == 0]
+            for w, h in sizes:
+                for td in bs.ROW_ORDERS:
+                    if td and variant.startswith("rle"):
+                        continue
+                    data, px = bs.make(variant, w, h, td, seed=2105)
+                    bands.append((bmp_name(variant, td, w, h), data))
+                    _PIXELS[("bmp", bands[-1][0])] = px
+        _CACHE["bmp"] = dict(bands=bands)
+    return _CACHE["bmp"]
+
+
 # ------------------------------------------------------------------ references
-GRIDS = dict(png=(png_grid, pu), tiff=(tiff_grid, tu), webp=(webp_grid, wu))
+GRIDS = dict(png=(png_grid, pu), tiff=(tiff_grid, tu), webp=(webp_grid, wu), gif=(gif_grid, _Built), bmp=(bmp_grid, _Built))
 
 
 def references(fmt, group, hashes=True, layout=None):
     """[(name, file, reference pixels, BLAKE3 of their to_rgba16 or None)] of one group, or of the files of one layout in it (the
-    first part of their names); each file is decoded and hashed once per process"""
+    first part of their names); each file is decoded (GIF and BMP: rendered by its builder) and hashed once per process"""
     grid, util = GRIDS[fmt]
     out = []
     for name, data in grid()[group]:
@@ -239,8 +456,10 @@ def references(fmt, group, hashes=True, layout=None):
             continue
         item = _REFS.get((fmt, name))
         if item is None:
-            st, ref = util.decode(data)
-            assert st == 0, name
+            ref = _PIXELS.get((fmt, name))
+            if ref is None:
+                st, ref = util.decode(data)
+                assert st == 0, name
             ref.setflags(write=False)
             item = _REFS[(fmt, name)] = [name, data, ref, None]
         out.append(item)

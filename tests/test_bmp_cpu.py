@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import bmp_streams as bs
+import recon_grid as rg
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -141,7 +142,7 @@ def test_capacity_and_null_arguments():
 
 def test_host_parser_is_clean_under_asan_and_ubsan(tmp_path):
     """tools/fuzz_bmp_host.cpp, a program of its own built from bmp_host.cpp with -fsanitize=address,undefined: the valid, Pillow and
-    damaged corpora, every prefix and 300 single-byte mutations of three small files"""
+    damaged corpora and the files of the reconstruction grid, every prefix and 300 single-byte mutations of three small files"""
     cxx = shutil.which("g++") or shutil.which("clang++")
     assert cxx, "a host C++ compiler is needed"
     exe = tmp_path / "fuzz_bmp_host"
@@ -149,7 +150,10 @@ def test_host_parser_is_clean_under_asan_and_ubsan(tmp_path):
                            os.path.join(ROOT, "tools", "fuzz_bmp_host.cpp"), os.path.join(ROOT, "rupphash_amd", "csrc", "bmp_host.cpp"), "-o", str(exe)])
     corpus = tmp_path / "corpus"
     assert bs.dump(str(corpus)) >= 250
-    small = ["rle8_delta_and_skipped_pixels_palette_of_9", "bf4444a_header_40_compression_6", "pal4_header_12"]
+    # the reconstruction grid (recon_grid.py): every file
+    for k, (name, data) in enumerate(x for files in rg.bmp_grid().values() for x in files):
+        (corpus / f"grid{k:04d}.bmp").write_bytes(data)
+    small =["rle8_delta_and_skipped_pixels_palette_of_9", "bf4444a_header_40_compression_6", "pal4_header_12"]
     r = subprocess.run([str(exe), str(corpus), "300"] + small, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "no sanitizer report" in r.stdout

@@ -1,12 +1,19 @@
 """The GIF decoder on the host (rph_gif_decode_host, rph_gif_info; no GPU): files Pillow writes against Pillow's own decode of them, files of
-tests/gif_streams.py against its numpy restatement of the rule (include/rupphash.h, GIF section), and one damaged file per line of the
-rule with its exact status."""
+tests/gif_streams.py against its numpy restatement of the rule (include/rupphash.h, GIF section), one damaged file per line of the
+rule with its exact status, and the host decoder as a stand-alone program under ASan + UBSan over the corpora, the files of the
+reconstruction grid and damaged variants of all of them."""
 import io
+import os
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
 
 import gif_streams as gs
+import recon_grid as rg
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _pillow_rgba(data):
@@ -163,3 +170,21 @@ def test_capacity_and_null_arguments():
     assert L.rph_gif_decode_host(data, len(data), buf.ctypes.data_as(C.c_void_p), 8) == _lib.RPH_ERR_CAPACITY
     assert L.rph_gif_decode_host(None, 0, buf.ctypes.data_as(C.c_void_p), 8) == _lib.RPH_ERR_INVALID_ARG
     assert L.rph_gif_info(data, len(data), None, None, None, None) == 0
+
+
+def test_host_decoder_is_clean_under_asan_and_ubsan(tmp_path):
+    """tools/fuzz_gif_host.cpp, a program of its own built from gif_host.cpp with -fsanitize=address,undefined: the valid, Pillow and
+    damaged corpora and every file of the reconstruction grid (recon_grid.py), each intact and with 10 random damages"""
+    cxx = shutil.which("g++") or shutil.which("clang++")
+    assert cxx, "a host C++ compiler is needed"
+    exe = tmp_path / "fuzz_gif_host"
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "rupphash_amd", "csrc"),
+                           os.path.join(ROOT, "tools", "fuzz_gif_host.cpp"), os.path.join(ROOT, "rupphash_amd", "csrc", "gif_host.cpp"), "-o", str(exe)])
+    corpus = tmp_path / "corpus"
+    assert gs.dump(str(corpus)) >= 120
+    grid = [x for files in rg.gif_grid().values() for x in files]
+    for k, (name, data) in enumerate(grid):
+        (corpus / f"grid{k:04d}.gif").write_bytes(data)
+    r = subprocess.run([str(exe), str(corpus), "10"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "no sanitizer report" in r.stdout and int(r.stdout.split()[0]) >= 120 + len(grid)
