@@ -70,6 +70,9 @@ struct Geo {
     // (kernel head; col_pass of the band before).  The 128-px build sits at 256 VGPRs and answers either with a spilled register, so
     // it keeps the serial prologue and loads a band's edge pixels at the band's start.
     static constexpr bool AHEAD = SW == 64;
+    // The frame bands' quotient for two columns per instruction (div_small2).  The scan of a 128-px strip is 16 octets long and that
+    // build sits at 256 VGPRs: the register pairs cost it 55 spilled VGPRs (92 B of scratch), so it keeps one column per instruction.
+    static constexpr bool PAIR_QUOT = SW == 64;
     static_assert(64 * 33 * 4 <= TILE_BYTES, "sample transpose buffer must fit in the dead V tile");
     static_assert((NG - 1) * 7 * CL * 16 <= (NH == 2 ? 32 : 64) * TILE_PITCH, "exchange area must fit");
     static_assert(rph::TAIL_LDS_FLOATS * 4 <= TILE_BYTES, "tail scratch must fit in the dead V tile");
@@ -248,6 +251,20 @@ __device__ __forceinline__ float div_small(float N, float d, float dinv)
     return __builtin_fmaf(r, dinv, q0);
 }
 
+// The same for two columns at once (the frame bands' scan): the two quotients do not depend on each other, so the two fused
+// multiply-adds of a pair of columns are one v_pk_fma_f32 each -- per element the same IEEE operations on the same operands as
+// div_small, hence the same bits.  The two multiplies are left to the compiler, which pairs them as well (v_pk_mul_f32 costs what two
+// full-rate v_mul_f32 cost, profiles/r02_valu_rate.txt: 13.2 x 2 against 28.3 lanes per clock, in one issue slot).
+typedef float f2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f2 div_small2(f2 N, f2 d, f2 dinv)
+{
+    f2 q0;
+    q0.x = N.x * dinv.x;
+    q0.y = N.y * dinv.y;
+    const f2 r = __builtin_elementwise_fma(-q0, d, N);
+    return __builtin_elementwise_fma(r, dinv, q0);
+}
+
 // Phase separator inside the wave.  The workgroup IS one wave and the LDS executes a wave's DS instructions in
 // issue order, so a later ds_read sees an earlier ds_write of any lane without waiting; all that is needed is
 // that the compiler keeps the program order.  (__syncthreads() would also drain vmcnt and so serialise the
@@ -283,33 +300,41 @@ struct Wave {
 
 // luma row of lane group g, local row k, in half h of band b
 template <class G>
-__device__ __forceinline__ int half_row(int b, int h, int g, int k) { return 64 * b + 4 + (G::NG * 8) * h + 8 * g + k; }
+constexpr __device__ __forceinline__ int half_row(int b, int h, int g, int k) { return 64 * b + 4 + (G::NG * 8) * h + 8 * g + k; }
 
-// Byte offset (from the image base, < 2^32: the launcher checks 512 * row_stride) of the first of the 8 rows this lane loads in
-// half tile (b, s, h), and the largest offset it may use (row 511 of its columns: rows beyond the image are re-reads of row 511
-// and are zeroed in luma_row)
+// The eight rows a lane loads in half tile (b, s, h) are one 32-bit lane offset (below) on top of a row base, image + k * row_stride,
+// that the scalar unit forms: no vector instruction per row.  Only the last build step of band 7 reaches below the image: rows 4..7 of
+// its last lane group are rows 512..515.  They are zeroed in luma_row, so any row of the image will do for them, and the offset of
+// those lanes steps back by four rows once, before row 4 (half_row_fold): they read their own rows 508..511 again.
 template <class G>
-__device__ __forceinline__ void half_offsets(const Wave &w, int b, int s, int h, uint32_t &off0, uint32_t &off_max)
+__device__ __forceinline__ uint32_t half_offset(const Wave &w, int b, int s, int h)
 {
     const int c = w.lane & (G::CL - 1), g = w.lane / G::CL;
     const uint32_t col = (uint32_t)(G::SW * s + 8 * c) * (uint32_t)G::CH;
-    off0 = (uint32_t)half_row<G>(b, h, g, 0) * w.rs32 + col;
-    off_max = 511u * w.rs32 + col;
+    return (uint32_t)half_row<G>(b, h, g, 0) * w.rs32 + col;  // < 2^32: the launcher checks 512 * row_stride
+}
+template <class G>
+__device__ __forceinline__ uint32_t half_row_fold(const Wave &w, int b, int h)
+{
+    static_assert(half_row<G>(7, G::NH - 1, G::NG - 1, 4) == 512 && half_row<G>(7, G::NH - 1, G::NG - 2, 7) < 512, "rows >= 512: last lane group, rows 4..7");
+    const int g = w.lane / G::CL;
+    return (b == 7 && h == G::NH - 1 && g == G::NG - 1) ? 4u * w.rs32 : 0u;
 }
 template <int CH>
-__device__ __forceinline__ Px8 load_px8_at(const Wave &w, uint32_t off) { return load_px8<CH>(w.img + off); }  // uniform base + 32-bit lane offset
+__device__ __forceinline__ Px8 load_px8_row(const Wave &w, int k, uint32_t off)  // uniform row base + 32-bit lane offset
+{
+    return load_px8<CH>(w.img + (size_t)k * w.row_stride + off);
+}
 
 // LOAD phase 1 (only for the very first tile of the image): issue the 16 loads of half tile (b, s, h)
 template <class G>
 __device__ __forceinline__ void half_issue(const Wave &w, int b, int s, int h, Px8 (&pre)[8])
 {
-    uint32_t off, off_max;
-    half_offsets<G>(w, b, s, h, off, off_max);
+    uint32_t off = half_offset<G>(w, b, s, h);
 #pragma unroll
     for (int k = 0; k < 8; k++) {
-        pre[k] = load_px8_at<G::CH>(w, off);
-        off = off + w.rs32;
-        off = off < off_max ? off : off_max;
+        if (k == 4) off -= half_row_fold<G>(w, b, h);
+        pre[k] = load_px8_row<G::CH>(w, k, off);
     }
 }
 
@@ -319,24 +344,21 @@ template <class G, bool LAST_BAND>
 __device__ __forceinline__ void half_luma(const Wave &w, int b, int h, Px8 (&pre)[8], Row8 (&L)[8], bool has_next, int nb, int ns, int nh)
 {
     const int g = w.lane / G::CL;
-    uint32_t off, off_max;
-    half_offsets<G>(w, nb, ns, nh, off, off_max);
+    uint32_t off = half_offset<G>(w, nb, ns, nh);
     uint32_t order = 0;
 #pragma unroll
     for (int k = 0; k < 8; k++) {
+        if (k == 4) off -= half_row_fold<G>(w, nb, nh);
+        const bool zero = LAST_BAND && (half_row<G>(b, h, g, k) >= 512);
         if (G::CH == 1) {
             const Px8 cur = pre[k];
-            if (has_next) pre[k] = load_px8_at<1>(w, off);
-            off = off + w.rs32;
-            off = off < off_max ? off : off_max;
-            L[k] = luma_row_gray(cur, LAST_BAND && (half_row<G>(b, h, g, k) >= 512), order);
+            if (has_next) pre[k] = load_px8_row<1>(w, k, off);
+            L[k] = luma_row_gray(cur, zero, order);
             continue;
         }
         const Pairs12 pr = byte_pairs(pre[k]);
-        if (has_next) pre[k] = load_px8_at<3>(w, off);
-        off = off + w.rs32;
-        off = off < off_max ? off : off_max;
-        L[k] = luma_row(pr, LAST_BAND && (half_row<G>(b, h, g, k) >= 512), order);
+        if (has_next) pre[k] = load_px8_row<3>(w, k, off);
+        L[k] = luma_row(pr, zero, order);
     }
 }
 
@@ -452,6 +474,7 @@ __device__ __forceinline__ void scan_strip(Wave &w)
     const uint8_t *tp = w.lds + G::OFF_TILE + r * G::TILE_PITCH;
     const float *edge = reinterpret_cast<const float *>(w.lds + G::OFF_EDGE);
     float fresh[G::NOCT];
+    const f2 d2 = {w.row_d8, w.row_d8}, dinv2 = {w.row_dinv8, w.row_dinv8};
 #pragma unroll
     for (int q = 0; q < G::NOCT; q++) {
         const uint4 cur = *reinterpret_cast<const uint4 *>(tp + 16 * q);
@@ -472,10 +495,27 @@ __device__ __forceinline__ void scan_strip(Wave &w)
         if (first_octet && (E) == 6) in2 = e2;                                   \
         if (!(first_octet && (E) < 4)) row_step<E>(w, in2); /* ri = xv - 4 >= 0 */ \
     }
-        RPH_STEP(0) RPH_STEP(1) RPH_STEP(2) RPH_STEP(3) RPH_STEP(4)
-        // output o = xv - 8 = 8j + 4 right after element 4 of octet j + 1
-        fresh[q] = w.sum * 0.125f;  // sample slot G::NOCT * s + q (slot 0 of the image = octet 0 is a dummy)
-        RPH_STEP(5) RPH_STEP(6) RPH_STEP(7)
+        // frame bands: Hs of columns E and E + 1 lands in the two halves of a register pair, which the packed quotient reads as it is
+#define RPH_PAIR(E, BETWEEN)                                                     \
+    {                                                                            \
+        f2 hp;                                                                   \
+        hp.x = hs_step<0>(w.hs, dq[(E) >> 1]);                                   \
+        hp.y = hs_step<1>(hp.x, dq[(E) >> 1]);                                   \
+        w.hs = hp.y;                                                             \
+        const f2 in2 = div_small2(hp, d2, dinv2);                                \
+        row_step<(E)>(w, in2.x);                                                 \
+        BETWEEN;                                                                 \
+        row_step<(E) + 1>(w, in2.y);                                             \
+    }
+        // output o = xv - 8 = 8j + 4 right after element 4 of octet j + 1: sample slot G::NOCT * s + q (slot 0 of the image = octet 0 is a dummy)
+        if (G::PAIR_QUOT && EDGE_ROWS && !first_octet) {
+            RPH_PAIR(0, (void)0) RPH_PAIR(2, (void)0) RPH_PAIR(4, fresh[q] = w.sum * 0.125f) RPH_PAIR(6, (void)0)
+        } else {
+            RPH_STEP(0) RPH_STEP(1) RPH_STEP(2) RPH_STEP(3) RPH_STEP(4)
+            fresh[q] = w.sum * 0.125f;
+            RPH_STEP(5) RPH_STEP(6) RPH_STEP(7)
+        }
+#undef RPH_PAIR
 #undef RPH_STEP
         w.pv = cur;
     }

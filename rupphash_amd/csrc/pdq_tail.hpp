@@ -50,23 +50,38 @@ __device__ __forceinline__ float key_to_float(uint32_t k)
 }
 
 // 128th smallest (0-based rank 127) of the wave's 256 keys (4 per lane): MSB-first radix select.
+// Per bit and key one v_and and one v_cmp: with bit b already in the mask, a key that matches the prefix and has bit b clear is one
+// with (key & mask) == prefix, and the compare's result is the ballot.  `cand` counts the keys that still match the prefix; once a single one is left it is the
+// answer (its rank among the candidates, k, is then 0) and is fetched from its lane.  Sets with ties at the median never get down to
+// one candidate and walk all 32 bits.
 __device__ __forceinline__ uint32_t select_rank127(const uint32_t (&key)[4])
 {
     uint32_t prefix = 0, mask = 0;
-    int k = 127;
+    int k = 127, cand = 256;
 #pragma unroll 1
     for (int bit = 31; bit >= 0; --bit) {
         const uint32_t b = 1u << bit;
+        mask |= b;
         int cnt = 0;
 #pragma unroll
-        for (int m = 0; m < 4; m++) cnt += __popcll(__ballot(((key[m] & mask) == prefix) && !(key[m] & b)));
+        for (int m = 0; m < 4; m++) cnt += __popcll(__ballot((key[m] & mask) == prefix));
         if (k >= cnt) {
             k -= cnt;
+            cand -= cnt;
             prefix |= b;
+        } else {
+            cand = cnt;
         }
-        mask |= b;
+        if (cand == 1) break;
     }
-    return prefix;
+    if (cand != 1) return prefix;
+    uint32_t found = prefix;
+#pragma unroll
+    for (int m = 0; m < 4; m++) {
+        const unsigned long long hit = __ballot((key[m] & mask) == prefix);
+        if (hit) found = (uint32_t)__builtin_amdgcn_readlane((int)key[m], __ffsll(hit) - 1);
+    }
+    return found;
 }
 
 // bits of one 16x16 sign pattern -> 32 hash bytes; lanes 0..31 each store one byte.
