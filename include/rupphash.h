@@ -333,7 +333,8 @@ int rph_find_groups_from_edges(const rph_edge *edges, uint64_t n_edges, uint64_t
 /*
  * group_files_generic with PdqStrategy (scanner.rs:1640-1823) up to and
  * including the union-find (merge_groups_by_stem / process_raw_groups are
- * file-name logic and stay in the caller).
+ * file-name logic and stay in the caller; the one data-parallel step of
+ * process_raw_groups, max_dist, is rph_group_max_dist below).
  *   hashes32 n x 32; coeffs n x 256 floats or NULL (then every file has the one
  *   variant out[0] = hash, scanner.rs:1624-1627); has_features n bytes or NULL
  *   (all 1 when coeffs != NULL); quality n x int32, <0 = None (scanner.rs:1592), or NULL.
@@ -440,6 +441,52 @@ int rph_library_labels(rph_library *lib, uint64_t first, uint64_t count, uint32_
  * capacity protocol of rph_hamming_variant_cross_pairs (e.i library, e.j query); quality_q nullable. */
 int rph_library_query(rph_library *lib, const uint8_t *hashes32_q, const int32_t *quality_q, uint64_t n_q, rph_edge *edges,
                       uint64_t cap, uint64_t *n_edges_out);
+
+/*
+ * max_dist of every group (process_raw_groups -> analyze_group_with_features, scanner.rs:1986-2022 and :2214-2241): the maximum, over the
+ * group's members, of the minimum Hamming distance to the rows of the group's pivot file.  One rule for every form below.
+ *   Group g is members[offsets[g] .. offsets[g + 1]) in the caller's order (the reference sorts a group by file name first: that stays
+ *   with the caller), over n files.  pivots[g] is a file number or RPH_NO_PIVOT; a pivot need not be a member of its group, a file may be
+ *   listed more than once, groups of one member and empty groups are legal.
+ *   dist(m) = min over the pivot's rows of hamming256(row, hash[m]).  The rows of a pivot WITH features are its 8 dihedral hashes, exactly
+ *   what rph_pdq_hashes_from_coeffs gives for its coefficients; the rows of a pivot without are its hash alone.  "With features":
+ *   coeffs != NULL and has_features is NULL or 1 for that file.
+ *   max_dist_out[g] (n_groups x uint32, required) = max of dist over the listed members; member_dist_out (nullable) gets dist for every
+ *   member slot.  An empty group or RPH_NO_PIVOT gives max_dist 0 and member_dist 0 in that group's slots.
+ *   pivots == NULL selects the reference's find_map pair (scanner.rs:2219-2232): the first listed member that has features, else the
+ *   first listed member.
+ * RPH_ERR_INVALID_ARG with NO output written: offsets[0] != 0, offsets that do not ascend, a member >= n, a pivot >= n that is not
+ * RPH_NO_PIVOT, a null required argument.  n_groups == 0: RPH_OK.  n at most 2^32 - 2.
+ */
+#define RPH_NO_PIVOT 0xFFFFFFFFu
+/* On the host, no context: the pivots' rows through rph_pdq_dihedral_one.  The rule's restatement for callers' own tests and the
+ * fallback without a device, like rph_image_luma601_host. */
+int rph_group_max_dist_host(const uint8_t *hashes32, const float *coeffs, const uint8_t *has_features, uint64_t n,
+                            const uint32_t *members, const uint32_t *offsets, uint32_t n_groups, const uint32_t *pivots,
+                            uint32_t *max_dist_out, uint32_t *member_dist_out);
+/* Host arrays in, host arrays out: the hashes cross PCIe, and of the coefficients only the pivots' rows (in bounded pieces). */
+int rph_group_max_dist(rph_ctx *ctx, const uint8_t *hashes32, const float *coeffs, const uint8_t *has_features, uint64_t n,
+                       const uint32_t *members, const uint32_t *offsets, uint32_t n_groups, const uint32_t *pivots,
+                       uint32_t *max_dist_out, uint32_t *member_dist_out);
+/* The core, everything on the device.  d_hashes32: n x 32.  row_mode says what d_rows holds: RPH_ROWS_NONE nothing (plain distance to
+ * hash[pivot], d_rows ignored), RPH_ROWS_PER_GROUP n_groups x 8 x 32 bytes (block g: the rows of pivot g), RPH_ROWS_PER_FILE n x 8 x 32
+ * bytes (the library's layout).  d_has_features (n bytes, nullable; it only counts next to rows, as has_features next to coeffs): a pivot
+ * with 0 there has its hash as its only row whatever d_rows holds.  d_hashes32 and d_rows are read 16 bytes at a time and must be aligned so.  d_members holds d_offsets[n_groups] entries,
+ * d_offsets n_groups + 1.  d_pivots nullable: the default pair is then resolved on the device from d_has_features (if that is null too:
+ * the first listed member).  The device arrays are range-checked by a pass of their own before anything is read through them -- the call
+ * waits for that (it synchronises `stream` once) and a bad index is RPH_ERR_INVALID_ARG, never a read out of range; the rest is
+ * asynchronous on `stream`.  d_member_dist nullable. */
+#define RPH_ROWS_NONE 0
+#define RPH_ROWS_PER_GROUP 1
+#define RPH_ROWS_PER_FILE 2
+int rph_group_max_dist_dev(rph_ctx *ctx, const void *d_hashes32, uint64_t n, const void *d_rows, int row_mode,
+                           const void *d_has_features, const void *d_members, const void *d_offsets, uint32_t n_groups,
+                           const void *d_pivots, void *d_max_dist, void *d_member_dist, void *stream);
+/* Against the files a library holds (their hashes, variant rows and flags never leave the device): host group arrays in the library's
+ * current numbering, e.g. what rph_library_groups returned, re-ordered by the caller as it likes; checked on the host against the
+ * library's size.  The library is not changed. */
+int rph_library_group_max_dist(rph_library *lib, const uint32_t *members, const uint32_t *offsets, uint32_t n_groups,
+                               const uint32_t *pivots, uint32_t *max_dist_out, uint32_t *member_dist_out);
 
 /* is_low_pdq_quality (scanner.rs:1592-1594); quality < 0 encodes None. */
 int rph_is_low_pdq_quality(int32_t quality);

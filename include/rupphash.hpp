@@ -505,6 +505,69 @@ inline AppendResult group_with_pdqhash_append(const std::vector<ScannedFile> &li
     r.new_comparisons = (size_t)cmp;
     return r;
 }
+
+// max_dist of every group (process_raw_groups -> analyze_group_with_features, scanner.rs:1986-2022, :2214-2241): `groups` are indices
+// into `files` in the caller's order (the reference sorts a group by file name first), `pivots` one file per group or nullopt, or no
+// vector at all for the reference's find_map pair (the first listed file with features, else the first listed file).  Files without a
+// hash are skipped as the reference's filter_map(|f| f.pdqhash) skips them, as members and as pivots.
+namespace detail {
+template <class Call>
+inline std::vector<uint32_t> groups_max_dist_with(const std::vector<ScannedFile> &files, const std::vector<std::vector<uint32_t>> &groups,
+                                                  const std::optional<std::vector<std::optional<uint32_t>>> &pivots, const char *where, Call &&call)
+{
+    if (pivots && pivots->size() != groups.size()) throw std::runtime_error("groups_max_dist: one pivot per group");
+    std::vector<uint32_t> sparse_to_dense(files.size(), RPH_NO_PIVOT);
+    std::vector<uint8_t> hashes, has;
+    std::vector<float> coeffs;
+    bool any_features = false;
+    uint32_t n = 0;
+    for (size_t i = 0; i < files.size(); i++) {
+        const auto &f = files[i];
+        if (!f.pdqhash) continue;
+        sparse_to_dense[i] = n++;
+        hashes.insert(hashes.end(), f.pdqhash->begin(), f.pdqhash->end());
+        has.push_back(f.pdq_features ? 1 : 0);
+        any_features |= f.pdq_features.has_value();
+        const size_t at = coeffs.size();
+        coeffs.resize(at + 256, 0.0f);
+        if (f.pdq_features) std::memcpy(&coeffs[at], f.pdq_features->coefficients.data(), 1024);
+    }
+    std::vector<uint32_t> members, offsets{0}, dense_pivots;
+    for (size_t g = 0; g < groups.size(); g++) {
+        for (uint32_t i : groups[g]) {
+            if (i >= files.size()) throw std::runtime_error("groups_max_dist: a member is not a file");
+            if (sparse_to_dense[i] != RPH_NO_PIVOT) members.push_back(sparse_to_dense[i]);
+        }
+        offsets.push_back((uint32_t)members.size());
+        if (!pivots) continue;
+        const std::optional<uint32_t> &p = (*pivots)[g];
+        if (p && *p >= files.size()) throw std::runtime_error("groups_max_dist: a pivot is not a file");
+        dense_pivots.push_back(p ? sparse_to_dense[*p] : RPH_NO_PIVOT);
+    }
+    if (members.empty()) members.push_back(0);  // (a non-null pointer for groups that are all empty)
+    std::vector<uint32_t> out(groups.size(), 0);
+    check(call(hashes.data(), any_features ? coeffs.data() : nullptr, any_features ? has.data() : nullptr, (uint64_t)n, members.data(), offsets.data(),
+               (uint32_t)groups.size(), pivots ? dense_pivots.data() : nullptr, out.data()),
+          where);
+    return out;
+}
+}  // namespace detail
+
+inline std::vector<uint32_t> groups_max_dist(const std::vector<ScannedFile> &files, const std::vector<std::vector<uint32_t>> &groups,
+                                             const std::optional<std::vector<std::optional<uint32_t>>> &pivots = std::nullopt)
+{
+    return detail::groups_max_dist_with(files, groups, pivots, "groups_max_dist",
+                                        [](const uint8_t *h, const float *c, const uint8_t *hf, uint64_t n, const uint32_t *m, const uint32_t *o, uint32_t ng,
+                                           const uint32_t *p, uint32_t *out) { return rph_group_max_dist(Context::get(), h, c, hf, n, m, o, ng, p, out, nullptr); });
+}
+// the same on the host: no device, no context (rph_group_max_dist_host)
+inline std::vector<uint32_t> groups_max_dist_host(const std::vector<ScannedFile> &files, const std::vector<std::vector<uint32_t>> &groups,
+                                                  const std::optional<std::vector<std::optional<uint32_t>>> &pivots = std::nullopt)
+{
+    return detail::groups_max_dist_with(files, groups, pivots, "groups_max_dist_host",
+                                        [](const uint8_t *h, const float *c, const uint8_t *hf, uint64_t n, const uint32_t *m, const uint32_t *o, uint32_t ng,
+                                           const uint32_t *p, uint32_t *out) { return rph_group_max_dist_host(h, c, hf, n, m, o, ng, p, out, nullptr); });
+}
 }  // namespace scanner
 
 }  // namespace rupphash

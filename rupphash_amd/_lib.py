@@ -43,6 +43,10 @@ RPH_EDGE_PROBE_MASK = 0x01FF
 RPH_EDGE_VARIANT_SHIFT = 9
 RPH_EDGE_VARIANT_MASK = 0x0E00
 
+# rph_group_max_dist: a group without a pivot; what d_rows of the _dev form holds
+RPH_NO_PIVOT = 0xFFFFFFFF
+RPH_ROWS_NONE, RPH_ROWS_PER_GROUP, RPH_ROWS_PER_FILE = 0, 1, 2
+
 
 class RphEdge(C.Structure):
     _fields_ = [("i", C.c_uint32), ("j", C.c_uint32), ("d", C.c_uint16), ("flags", C.c_uint16)]
@@ -129,6 +133,10 @@ SIGNATURES = {
     "rph_library_groups": (C.c_int, [_vp, _u32p, _u32p, C.POINTER(C.c_uint32)]),
     "rph_library_labels": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _u32p]),
     "rph_library_query": (C.c_int, [_vp, _u8p, _i32p, C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "rph_group_max_dist_host": (C.c_int, [_u8p, _f32p, _u8p, C.c_uint64, _u32p, _u32p, C.c_uint32, _u32p, _u32p, _u32p]),
+    "rph_group_max_dist": (C.c_int, [_vp, _u8p, _f32p, _u8p, C.c_uint64, _u32p, _u32p, C.c_uint32, _u32p, _u32p, _u32p]),
+    "rph_group_max_dist_dev": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_int, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp]),
+    "rph_library_group_max_dist": (C.c_int, [_vp, _u32p, _u32p, C.c_uint32, _u32p, _u32p, _u32p]),
     "rph_is_low_pdq_quality": (C.c_int, [C.c_int32]),
     "rph_mih_build256": (C.c_int, [_vp, _u8p, C.c_uint64, _u32p, _u32p]),
     "rph_mih_build64": (C.c_int, [_vp, _u64p, C.c_uint64, _u32p, _u32p]),
@@ -213,6 +221,7 @@ DEBUG_SIGNATURES = {
     "rph_debug_library_stages": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_float)]),
     "rph_debug_library_remove_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "rph_debug_library_remove_stages": (C.c_int, [_vp, C.POINTER(C.c_float)]),
+    "rph_debug_group_max_dist_events": (C.c_int, [_vp, _vp, _vp]),
 }
 
 _lib = None

@@ -111,29 +111,6 @@ int bad_argument(const char *who, const char *what)
     rph_set_error("%s: %s", who, what);
     return RPH_ERR_INVALID_ARG;
 }
-
-// One use of the context's sweep scratch on `s`, under ctx->mu: published on every way out of the scope, an error's included, so that
-// the next user on another stream is ordered behind whatever this one had enqueued.  done() is the ordinary end and reports.
-struct ScratchUse {
-    SharedScratch &scratch;
-    hipStream_t s;
-    bool held = false;
-    int acquire(size_t need, size_t bytes)
-    {
-        RPH_TRY(scratch.acquire(s, need, bytes));
-        held = true;
-        return RPH_OK;
-    }
-    int done()
-    {
-        held = false;
-        return scratch.publish(s);
-    }
-    ~ScratchUse()
-    {
-        if (held) (void)scratch.publish(s);
-    }
-};
 }  // namespace
 
 // Several edge lists over one label array: ONE range check of all of them and of the entry forest (the call waits for it: nothing has

@@ -257,3 +257,65 @@ int rph_host_find_groups(const rph_edge *edges, uint64_t n_edges, uint64_t n, ui
     *n_groups_out = ng;
     return RPH_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// max_dist of every group (scanner.rs:1986-2022, :2214-2241): the rule on the host
+// ---------------------------------------------------------------------------------------------
+int rph_host_group_lists_check(const char *who, const uint8_t *hashes32, uint64_t n, const uint32_t *members, const uint32_t *offsets, uint32_t n_groups,
+                               const uint32_t *pivots, const uint32_t *max_dist_out)
+{
+    const auto refuse = [&](const char *what) {
+        rph_set_error("%s: %s", who, what);
+        return RPH_ERR_INVALID_ARG;
+    };
+    if (n_groups == 0) return RPH_OK;
+    if (!offsets || !max_dist_out || (!hashes32 && n)) return refuse("null argument");
+    if (n >= RPH_NO_PIVOT) return refuse("at most 2^32 - 2 files");
+    if (offsets[0] != 0) return refuse("offsets do not start at 0");
+    for (uint32_t g = 0; g < n_groups; g++)
+        if (offsets[g + 1] < offsets[g]) return refuse("offsets do not ascend");
+    const uint32_t total = offsets[n_groups];
+    if (total && !members) return refuse("null argument");
+    for (uint32_t t = 0; t < total; t++)
+        if (members[t] >= n) return refuse("a member is not below n");
+    for (uint32_t g = 0; g < n_groups && pivots; g++)
+        if (pivots[g] != RPH_NO_PIVOT && pivots[g] >= n) return refuse("a pivot is neither below n nor RPH_NO_PIVOT");
+    return RPH_OK;
+}
+
+uint32_t rph_host_default_pivot(const uint32_t *members, const uint32_t *offsets, uint32_t g, const float *coeffs, const uint8_t *has_features)
+{
+    if (offsets[g] == offsets[g + 1]) return RPH_NO_PIVOT;
+    for (uint32_t t = offsets[g]; t < offsets[g + 1] && coeffs; t++)
+        if (!has_features || has_features[members[t]]) return members[t];
+    return members[offsets[g]];
+}
+
+extern "C" int rph_group_max_dist_host(const uint8_t *hashes32, const float *coeffs, const uint8_t *has_features, uint64_t n, const uint32_t *members,
+                                       const uint32_t *offsets, uint32_t n_groups, const uint32_t *pivots, uint32_t *max_dist_out, uint32_t *member_dist_out)
+{
+    return rph_guarded("rph_group_max_dist_host", [&]() -> int {
+        RPH_TRY(rph_host_group_lists_check("rph_group_max_dist_host", hashes32, n, members, offsets, n_groups, pivots, max_dist_out));
+        uint8_t rows[8 * 32];
+        for (uint32_t g = 0; g < n_groups; g++) {
+            const uint32_t p = pivots ? pivots[g] : rph_host_default_pivot(members, offsets, g, coeffs, has_features);
+            uint32_t n_rows = 0;
+            if (p != RPH_NO_PIVOT && coeffs && (!has_features || has_features[p])) {
+                rph_pdq_dihedral_one(coeffs + (size_t)p * 256, rows);
+                n_rows = 8;
+            } else if (p != RPH_NO_PIVOT) {
+                std::memcpy(rows, hashes32 + (size_t)p * 32, 32);
+                n_rows = 1;
+            }
+            uint32_t most = 0;
+            for (uint32_t t = offsets[g]; t < offsets[g + 1]; t++) {
+                uint32_t d = n_rows ? 256 : 0;
+                for (uint32_t k = 0; k < n_rows; k++) d = std::min(d, rph_hamming_distance256(rows + k * 32, hashes32 + (size_t)members[t] * 32));
+                if (member_dist_out) member_dist_out[t] = d;
+                most = std::max(most, d);
+            }
+            max_dist_out[g] = most;
+        }
+        return RPH_OK;
+    });
+}

@@ -26,6 +26,7 @@ struct rph_library {
     // rph_library_remove: the uploaded indices; flags, index lists and hipCUB workspace; the gathered rows of the components that lost a
     // file.  What the last removal did (rph_debug_library_remove_stats) and the events around its stages, armed with the append's
     DevBuf d_rm_idx, d_rm_work, d_rm_rows;
+    rph_group_lists_dev group_lists;  // rph_library_group_max_dist: the caller's group arrays and its outputs
     uint64_t rm_stats[3] = {0, 0, 0};  // members regrouped, edges found among them, first edge capacity tried
     bool rm_staged = false;
     hipEvent_t rm_ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -40,13 +41,6 @@ int fail(const char *who, const char *what)
     rph_set_error("%s: %s", who, what);
     return RPH_ERR_INVALID_ARG;
 }
-
-// Declared behind the host variables that asynchronous copies write and the buffers that kernels in flight use: on every way out of the
-// scope, an error's included, the stream is through with them before they go.  On the ordinary way out the stream is already idle.
-struct StreamDrain {
-    hipStream_t s;
-    ~StreamDrain() { (void)hipStreamSynchronize(s); }
-};
 
 // room for `need` files: geometric growth, device-to-device copy of the resident part, old buffers freed once the stream is through
 // with them.  The new buffers are all allocated before anything is replaced: a failure leaves the library as it was.
@@ -478,6 +472,27 @@ int rph_library_query(rph_library *lib, const uint8_t *hashes32_q, const int32_t
             return RPH_ERR_CAPACITY;
         }
         return RPH_OK;
+    });
+}
+
+int rph_library_group_max_dist(rph_library *lib, const uint32_t *members, const uint32_t *offsets, uint32_t n_groups, const uint32_t *pivots,
+                               uint32_t *max_dist_out, uint32_t *member_dist_out)
+{
+    return rph_guarded("rph_library_group_max_dist", [&]() -> int {
+        if (!lib) return fail("rph_library_group_max_dist", "null argument");
+        std::lock_guard<std::mutex> lock(lib->mu);
+        RPH_TRY(rph_host_group_lists_check("rph_library_group_max_dist", lib->d_h.data(), lib->n, members, offsets, n_groups, pivots, max_dist_out));
+        if (n_groups == 0) return RPH_OK;
+        RPH_HIP_CHECK(hipSetDevice(lib->ctx->device));
+        hipStream_t s = lib->ctx->stream;
+        StreamDrain drain{s};
+        RPH_TRY(lib->group_lists.upload(members, offsets, n_groups, pivots, member_dist_out != nullptr, s));
+        // the resident rows as they are: a file without features repeats its hash in all 8, which is the plain distance
+        rph_group_dist q;
+        q.hashes = lib->d_h.data(), q.n = lib->n, q.rows = lib->d_var.data(), q.row_mode = RPH_ROWS_PER_FILE, q.has_features = lib->d_hf.data();
+        lib->group_lists.fill(q);
+        RPH_TRY(rph_group_max_dist_run(lib->ctx, q, lib->group_lists.total, s));
+        return lib->group_lists.download(max_dist_out, member_dist_out, s);
     });
 }
 

@@ -162,6 +162,36 @@ class SharedScratch {
     bool used_ = false;
 };
 
+// One use of a context's shared scratch on `s`, under ctx->mu: published on every way out of the scope, an error's included, so that
+// the next user on another stream is ordered behind whatever this one had enqueued.  done() is the ordinary end and reports.
+struct ScratchUse {
+    SharedScratch &scratch;
+    hipStream_t s;
+    bool held = false;
+    int acquire(size_t need, size_t bytes)
+    {
+        RPH_TRY(scratch.acquire(s, need, bytes));
+        held = true;
+        return RPH_OK;
+    }
+    int done()
+    {
+        held = false;
+        return scratch.publish(s);
+    }
+    ~ScratchUse()
+    {
+        if (held) (void)scratch.publish(s);
+    }
+};
+
+// Declared behind the host variables that asynchronous copies write and the buffers that kernels in flight use: on every way out of the
+// scope, an error's included, the stream is through with them before they go.  On the ordinary way out the stream is already idle.
+struct StreamDrain {
+    hipStream_t s;
+    ~StreamDrain() { (void)hipStreamSynchronize(s); }
+};
+
 // Host threads when the caller does not say: what this process may actually use (its affinity mask, and the cgroup CPU quota a
 // container runs under -- hardware_concurrency() reports the machine's 256 threads inside a 16-CPU container); rph_api.cpp
 unsigned rph_host_threads();

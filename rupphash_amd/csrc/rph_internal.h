@@ -111,6 +111,8 @@ struct rph_ctx {
     // PCIe as they are, RLE streams are the host's.  Their chunk limits (tests only: read once, by rph_init)
     rph_file_slot file[RPH_FILE_FORMATS];
     rph_file_limits file_limits;
+    // rph_debug_group_max_dist_events: the caller's events around the distance kernel of group_info.hip (null: none), under mu
+    hipEvent_t group_dist_ev[2] = {nullptr, nullptr};
 };
 
 // ---- launchers implemented in the .hip files (all asynchronous on `stream`) ----
@@ -241,6 +243,37 @@ int rph_library_launch_split_edges(rph_ctx *ctx, rph_edge *d_edges, uint64_t n_e
 // new_labels[new(x)] for every kept x: itself if its component lost a file, else the new number of its (kept) root
 int rph_library_launch_labels(rph_ctx *ctx, const uint32_t *d_labels, const uint8_t *d_removed, const uint8_t *d_touched, const uint32_t *d_new_index, uint64_t n,
                               uint32_t *d_new_labels, hipStream_t stream);
+// group_info.hip: one rph_group_max_dist_dev request in device pointers (include/rupphash.h says what each array is)
+struct rph_group_dist {
+    const uint8_t *hashes = nullptr, *rows = nullptr, *has_features = nullptr;
+    uint64_t n = 0;
+    int row_mode = RPH_ROWS_NONE;
+    const uint32_t *members = nullptr, *offsets = nullptr, *pivots = nullptr;
+    uint32_t n_groups = 0;
+    uint32_t *max_dist = nullptr, *member_dist = nullptr;
+};
+// known_total: offsets[n_groups], from a caller that holds the group arrays on the host and has checked them there
+// (rph_host_group_lists_check).  RPH_GROUP_TOTAL_ON_DEVICE: the arrays are only on the device; they are range-checked by a pass of their
+// own before anything is read through them, and the call waits for that (RPH_ERR_INVALID_ARG with nothing written).  The rest is
+// asynchronous on `stream`.
+constexpr uint64_t RPH_GROUP_TOTAL_ON_DEVICE = ~0ull;
+int rph_group_max_dist_run(rph_ctx *ctx, const rph_group_dist &q, uint64_t known_total, hipStream_t stream);
+// the group arrays of a host caller on the device and room for its outputs, kept by whoever calls often (rph_library)
+struct rph_group_lists_dev {
+    DevBuf d_groups, d_out;
+    uint32_t *members = nullptr, *offsets = nullptr, *pivots = nullptr, *max_dist = nullptr, *member_dist = nullptr;
+    uint64_t total = 0;
+    uint32_t n_groups = 0;
+    int upload(const uint32_t *members, const uint32_t *offsets, uint32_t n_groups, const uint32_t *pivots, bool want_member_dist, hipStream_t stream);
+    void fill(rph_group_dist &q) const { q.members = members, q.offsets = offsets, q.pivots = pivots, q.n_groups = n_groups, q.max_dist = max_dist, q.member_dist = member_dist; }
+    int download(uint32_t *max_dist_out, uint32_t *member_dist_out, hipStream_t stream);  // waits for the stream
+};
+// host_grouping.cpp: what every form of rph_group_max_dist refuses, checked before anything is written: a null required argument,
+// offsets that do not start at 0 or do not ascend, a member >= n, a pivot >= n that is not RPH_NO_PIVOT
+int rph_host_group_lists_check(const char *who, const uint8_t *hashes32, uint64_t n, const uint32_t *members, const uint32_t *offsets, uint32_t n_groups,
+                               const uint32_t *pivots, const uint32_t *max_dist_out);
+// find_map (scanner.rs:2219-2232): the first listed member of group g that has features, else the first listed member, else RPH_NO_PIVOT
+uint32_t rph_host_default_pivot(const uint32_t *members, const uint32_t *offsets, uint32_t g, const float *coeffs, const uint8_t *has_features);
 int rph_launch_mih_build256(rph_ctx *ctx, const uint8_t *d_hashes, uint64_t n, uint32_t *d_offsets, uint32_t *d_values,
                             hipStream_t stream);
 int rph_launch_mih_build64(rph_ctx *ctx, const uint64_t *d_hashes, uint64_t n, uint32_t *d_offsets, uint32_t *d_values,

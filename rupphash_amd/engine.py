@@ -832,6 +832,57 @@ class Engine:
               "rph_groups_from_labels_dev")
         return self._groups(members, offsets, ng.value)
 
+    @staticmethod
+    def _group_lists(groups, pivots):
+        """(members, offsets, n_groups, pivots or None) as the rph_group_max_dist forms take them.  groups: a list of index lists, or the
+        raw (members, offsets) arrays; pivots: one file number or None (RPH_NO_PIVOT) per group, or None for the default pivots."""
+        members, offsets = groups if isinstance(groups, tuple) else Engine._flatten_groups(groups)
+        members, offsets = np.ascontiguousarray(members, np.uint32), np.ascontiguousarray(offsets, np.uint32)
+        ng = max(len(offsets) - 1, 0)
+        if pivots is not None:
+            pivots = np.array([_lib.RPH_NO_PIVOT if p is None else int(p) for p in pivots], np.uint32)
+            if len(pivots) != ng:
+                raise ValueError(f"{len(pivots)} pivots for {ng} groups")
+        return members, offsets, ng, pivots
+
+    @staticmethod
+    def _group_dist_result(max_dist, member_dist, offsets, ng):
+        if member_dist is None:
+            return max_dist.tolist()
+        return max_dist.tolist(), [member_dist[offsets[g]:offsets[g + 1]].tolist() for g in range(ng)]
+
+    @staticmethod
+    def _group_max_dist_call(call, where, groups, pivots, want_member_dist):
+        members, offsets, ng, piv = Engine._group_lists(groups, pivots)
+        max_dist = np.zeros(ng, np.uint32)
+        member_dist = np.zeros(len(members), np.uint32) if want_member_dist else None
+        check(call(_ptr(members), _ptr(offsets), ng, _ptr(piv), _ptr(max_dist), _ptr(member_dist)), where)
+        return Engine._group_dist_result(max_dist, member_dist, offsets, ng)
+
+    def group_max_dist(self, groups, hashes, pivots=None, coeffs=None, has_features=None, want_member_dist=False):
+        """max_dist of every group (process_raw_groups, scanner.rs:2214-2241) on the device: the maximum over a group's members of the
+        minimum distance to its pivot's 8 dihedral hashes, or to its plain hash when the pivot has no features.  groups: index lists as
+        group_files_pdq returns them, in the caller's order; pivots: a file number or None per group, or None for the reference's
+        default (the first listed member with features, else the first).  Returns the list of max_dist, with want_member_dist
+        (max_dist, per-group lists of the members' distances)."""
+        h, c, hf, _ = Library._files(hashes, coeffs, has_features, None)
+        return self._group_max_dist_call(lambda m, o, ng, p, out, md: self.L.rph_group_max_dist(self.ctx, _ptr(h), _ptr(c), _ptr(hf), len(h), m, o, ng, p, out, md),
+                                         "rph_group_max_dist", groups, pivots, want_member_dist)
+
+    @staticmethod
+    def group_max_dist_host(groups, hashes, pivots=None, coeffs=None, has_features=None, want_member_dist=False):
+        """group_max_dist on the host (rph_group_max_dist_host): no device, no context."""
+        L = _lib.load()
+        h, c, hf, _ = Library._files(hashes, coeffs, has_features, None)
+        return Engine._group_max_dist_call(lambda m, o, ng, p, out, md: L.rph_group_max_dist_host(_ptr(h), _ptr(c), _ptr(hf), len(h), m, o, ng, p, out, md),
+                                           "rph_group_max_dist_host", groups, pivots, want_member_dist)
+
+    def group_max_dist_dev(self, d_hashes, n, d_members, d_offsets, n_groups, d_max_dist, d_rows=None, row_mode=_lib.RPH_ROWS_NONE, d_has_features=None,
+                           d_pivots=None, d_member_dist=None, stream=None):
+        """rph_group_max_dist_dev: everything on the device; row_mode says what d_rows holds (RPH_ROWS_*); d_pivots None: default pivots."""
+        check(self.L.rph_group_max_dist_dev(self.ctx, d_hashes, n, d_rows, row_mode, d_has_features, d_members, d_offsets, n_groups, d_pivots, d_max_dist,
+                                            d_member_dist, stream), "rph_group_max_dist_dev")
+
     def library(self, similarity):
         """A grouped library that stays on this engine's device (rph_library): see Library."""
         return Library(self, similarity)
@@ -1025,12 +1076,21 @@ class Library:
         check(self.L.rph_library_labels(self.handle, first, count, _ptr(out)), "rph_library_labels")
         return out
 
+    def group_max_dist(self, groups, pivots=None, want_member_dist=False):
+        """Engine.group_max_dist against the resident files, in the library's current numbering: no hash or coefficient leaves the device.
+        The library is not changed."""
+        return self.engine._group_max_dist_call(lambda m, o, ng, p, out, md: self.L.rph_library_group_max_dist(self.handle, m, o, ng, p, out, md),
+                                                "rph_library_group_max_dist", groups, pivots, want_member_dist)
+
     def query(self, hashes, quality=None, cap=None):
         """Edges (library file i, query j, d, variant in flags) of the queries against the resident files; the library is not changed.
         With cap given, RPH_ERR_CAPACITY raises (RphError)."""
         h, _, _, q = self._files(hashes, None, None, quality)
         return Engine._sweep_growing(lambda e, c, f: self.L.rph_library_query(self.handle, _ptr(h), _ptr(q), len(h), e, c, f),
                                      max(1 << 16, 8 * len(h)) if cap is None else cap, cap is None, "rph_library_query")
+
+
+group_max_dist_host = Engine.group_max_dist_host  # needs no engine
 
 
 _default = None

@@ -208,3 +208,10 @@ def group_max_dist(groups, hashes, pivots, coefficients=None, has_features=None,
             d = (mb != bits[p][None, :]).sum(axis=1)
         out[g] = int(d.max())
     return out
+
+
+def groups_max_dist(groups, hashes, pivots=None, coefficients=None, has_features=None, want_member_dist=False, engine=None):
+    """group_max_dist for all groups in one device call (Engine.group_max_dist): same rule and arguments, and pivots=None selects the
+    reference's find_map pair per group (the first listed member that has features, else the first listed member).  A library that is
+    resident answers without the hashes: ScannerLibrary.group_max_dist(groups, pivots)."""
+    return (engine or default_engine()).group_max_dist(groups, hashes, pivots, coefficients, has_features, want_member_dist)
