@@ -488,6 +488,53 @@ int rph_group_max_dist_dev(rph_ctx *ctx, const void *d_hashes32, uint64_t n, con
 int rph_library_group_max_dist(rph_library *lib, const uint32_t *members, const uint32_t *offsets, uint32_t n_groups,
                                const uint32_t *pivots, uint32_t *max_dist_out, uint32_t *member_dist_out);
 
+/*
+ * The nearest files of a query: exact top-k Hamming search.  One rule for every form below; no threshold sweep, no capacity protocol --
+ * the output is n_q x k slots whatever the data holds.
+ *   Library side: n_lib files of n_variants (1 or 8) rows of 32 bytes, rows[n_lib][n_variants][32].  has_features (n_lib bytes,
+ *   nullable): a file whose byte is 0 owns row 0 only, whatever its other rows hold (the convention of the variant sweeps).
+ *   Query side: n_q hashes of 32 bytes.  skip (n_q x uint32, nullable): query q never reports library file skip[q]; RPH_NO_FILE skips
+ *   nothing.
+ *   dist(i, q) = min over the rows file i owns of hamming256(row, hash_q); variant(i, q) = the smallest row index that attains it.
+ *   Quality and low confidence play no part: this is a distance query, not the grouping rule.
+ *   Result of query q: the library files with i != skip[q] and dist(i, q) <= max_dist, ordered by the key (dist, i) ascending, the
+ *   first k of them.  max_dist >= 256 means no cutoff.  Ties in distance go to the smaller file number, so the result is unique: it
+ *   does not depend on launch geometry, on how the library is cut into segments or on the order in which anything was found.
+ *   out: n_q x k rph_edge.  Slot (q, r) holds the r-th entry: e.i = library file, e.j = q, e.d = distance (0..256),
+ *   e.flags = variant << RPH_EDGE_VARIANT_SHIFT.  Slots behind the end of the list are {RPH_NO_FILE, q, 0xFFFF, 0}.  counts_out
+ *   (nullable, n_q x uint32): the number of filled slots.
+ * k in 1 .. RPH_NEAREST_MAX_K, n_lib at most 2^32 - 2.  RPH_ERR_INVALID_ARG with NO output written: a k outside that range, an
+ * n_variants other than 1 or 8, an n_lib above the limit, a null required pointer with a non-zero count.  n_q == 0: RPH_OK.
+ * n_lib == 0: RPH_OK, every slot empty, counts 0.
+ * rph_hamming_set_kernel selects nothing here: there is one kernel (the full 256-bit distance of every pair on the fp4 matrix pipe,
+ * a running list of the k best per query and library segment, one merge per query).
+ */
+#define RPH_NO_FILE 0xFFFFFFFFu
+#define RPH_NEAREST_MAX_K 64
+/* On the host, no context and no device: the rule's restatement for callers' own tests and the fallback, like rph_group_max_dist_host
+ * (the queries are spread over the host's threads). */
+int rph_hamming_nearest_host(const uint8_t *rows, uint32_t n_variants, const uint8_t *has_features, uint64_t n_lib,
+                             const uint8_t *hashes32_q, const uint32_t *skip, uint64_t n_q, uint32_t k, uint32_t max_dist,
+                             rph_edge *out, uint32_t *counts_out);
+/* Host arrays in, host arrays out: rows, flags and queries cross PCIe, the slots come back. */
+int rph_hamming_nearest(rph_ctx *ctx, const uint8_t *rows, uint32_t n_variants, const uint8_t *has_features, uint64_t n_lib,
+                        const uint8_t *hashes32_q, const uint32_t *skip, uint64_t n_q, uint32_t k, uint32_t max_dist, rph_edge *out,
+                        uint32_t *counts_out);
+/* The core, everything on the device and asynchronous on `stream`.  d_rows and d_hashes_q are read 16 bytes at a time and must be
+ * aligned so.  The partial lists live in the context's kept scratch, at most 256 MiB of it: the queries are taken in chunks. */
+int rph_hamming_nearest_dev(rph_ctx *ctx, const void *d_rows, uint32_t n_variants, const void *d_has_features, uint64_t n_lib,
+                            const void *d_hashes_q, const void *d_skip, uint64_t n_q, uint32_t k, uint32_t max_dist, void *d_out,
+                            void *d_counts, void *stream);
+/* Against the files a library holds (8 rows each, with their flags, where they lie): only the queries go up and the slots come down.
+ * The library is not changed; e.i is in its current numbering. */
+int rph_library_nearest(rph_library *lib, const uint8_t *hashes32_q, uint64_t n_q, uint32_t k, uint32_t max_dist, rph_edge *out,
+                        uint32_t *counts_out);
+/* The queries are resident files, indices[q] in the library's current numbering: their hashes are gathered on the device, each with
+ * skip = itself ("the neighbours of file 4711" without a hash ever being on the host).  An index >= size: RPH_ERR_INVALID_ARG with
+ * nothing written. */
+int rph_library_nearest_files(rph_library *lib, const uint32_t *indices, uint64_t n_q, uint32_t k, uint32_t max_dist, rph_edge *out,
+                              uint32_t *counts_out);
+
 /* is_low_pdq_quality (scanner.rs:1592-1594); quality < 0 encodes None. */
 int rph_is_low_pdq_quality(int32_t quality);
 

@@ -46,6 +46,9 @@ RPH_EDGE_VARIANT_MASK = 0x0E00
 # rph_group_max_dist: a group without a pivot; what d_rows of the _dev form holds
 RPH_NO_PIVOT = 0xFFFFFFFF
 RPH_ROWS_NONE, RPH_ROWS_PER_GROUP, RPH_ROWS_PER_FILE = 0, 1, 2
+# rph_hamming_nearest: a skip entry that skips nothing and the file of an empty slot; the longest list
+RPH_NO_FILE = 0xFFFFFFFF
+RPH_NEAREST_MAX_K = 64
 
 
 class RphEdge(C.Structure):
@@ -137,6 +140,11 @@ SIGNATURES = {
     "rph_group_max_dist": (C.c_int, [_vp, _u8p, _f32p, _u8p, C.c_uint64, _u32p, _u32p, C.c_uint32, _u32p, _u32p, _u32p]),
     "rph_group_max_dist_dev": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_int, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp]),
     "rph_library_group_max_dist": (C.c_int, [_vp, _u32p, _u32p, C.c_uint32, _u32p, _u32p, _u32p]),
+    "rph_hamming_nearest_host": (C.c_int, [_u8p, C.c_uint32, _u8p, C.c_uint64, _u8p, _u32p, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _u32p]),
+    "rph_hamming_nearest": (C.c_int, [_vp, _u8p, C.c_uint32, _u8p, C.c_uint64, _u8p, _u32p, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _u32p]),
+    "rph_hamming_nearest_dev": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint64, _vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+    "rph_library_nearest": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _u32p]),
+    "rph_library_nearest_files": (C.c_int, [_vp, _u32p, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _u32p]),
     "rph_is_low_pdq_quality": (C.c_int, [C.c_int32]),
     "rph_mih_build256": (C.c_int, [_vp, _u8p, C.c_uint64, _u32p, _u32p]),
     "rph_mih_build64": (C.c_int, [_vp, _u64p, C.c_uint64, _u32p, _u32p]),
@@ -222,6 +230,8 @@ DEBUG_SIGNATURES = {
     "rph_debug_library_remove_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "rph_debug_library_remove_stages": (C.c_int, [_vp, C.POINTER(C.c_float)]),
     "rph_debug_group_max_dist_events": (C.c_int, [_vp, _vp, _vp]),
+    "rph_debug_nearest_layout": (None, [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "rph_debug_nearest_set_segment": (None, [C.c_uint32]),
 }
 
 _lib = None

@@ -319,3 +319,57 @@ extern "C" int rph_group_max_dist_host(const uint8_t *hashes32, const float *coe
         return RPH_OK;
     });
 }
+
+// ---------------------------------------------------------------------------------------------
+// The nearest files of a query (include/rupphash.h): the rule on the host
+// ---------------------------------------------------------------------------------------------
+int rph_nearest_check(const char *who, const void *rows, uint32_t n_variants, uint64_t n_lib, const void *hashes_q, uint64_t n_q, uint32_t k, const void *out)
+{
+    const auto refuse = [&](const char *what) {
+        rph_set_error("%s: %s", who, what);
+        return RPH_ERR_INVALID_ARG;
+    };
+    if (k < 1 || k > RPH_NEAREST_MAX_K) return refuse("k is not in 1 .. RPH_NEAREST_MAX_K");
+    if (n_variants != 1 && n_variants != 8) return refuse("n_variants is neither 1 nor 8");
+    if (n_lib >= RPH_NO_FILE) return refuse("at most 2^32 - 2 files");
+    if (n_q > 0xFFFFFFFFull) return refuse("at most 2^32 - 1 queries");
+    if ((!rows && n_lib) || ((!hashes_q || !out) && n_q)) return refuse("null argument");
+    return RPH_OK;
+}
+
+extern "C" int rph_hamming_nearest_host(const uint8_t *rows, uint32_t n_variants, const uint8_t *has_features, uint64_t n_lib, const uint8_t *hashes32_q,
+                                        const uint32_t *skip, uint64_t n_q, uint32_t k, uint32_t max_dist, rph_edge *out, uint32_t *counts_out)
+{
+    return rph_guarded("rph_hamming_nearest_host", [&]() -> int {
+        RPH_TRY(rph_nearest_check("rph_hamming_nearest_host", rows, n_variants, n_lib, hashes32_q, n_q, k, out));
+        // one query per task; its list is the k smallest keys (dist, file, variant) seen so far, ascending
+        parallel_for(0, n_q, rph_host_threads(), [&](size_t q) {
+            uint64_t best[RPH_NEAREST_MAX_K];
+            uint32_t filled = 0;
+            const uint8_t *h = hashes32_q + q * 32;
+            const uint32_t skipped = skip ? skip[q] : RPH_NO_FILE;
+            for (uint64_t i = 0; i < n_lib; i++) {
+                if (i == skipped) continue;
+                const uint32_t owned = (has_features && !has_features[i]) ? 1 : n_variants;
+                uint32_t d = 257, variant = 0;
+                for (uint32_t v = 0; v < owned; v++) {
+                    const uint32_t dv = rph_hamming_distance256(rows + (i * n_variants + v) * 32, h);
+                    if (dv < d) d = dv, variant = v;
+                }
+                if (d > max_dist) continue;
+                const uint64_t key = (uint64_t)d << 40 | i << 3 | variant;
+                if (filled == k && key > best[k - 1]) continue;
+                uint32_t at = filled < k ? filled++ : k - 1;
+                for (; at > 0 && best[at - 1] > key; at--) best[at] = best[at - 1];
+                best[at] = key;
+            }
+            for (uint32_t r = 0; r < k; r++) {
+                rph_edge e = {RPH_NO_FILE, (uint32_t)q, 0xFFFF, 0};
+                if (r < filled) e = {(uint32_t)(best[r] >> 3), (uint32_t)q, (uint16_t)(best[r] >> 40), (uint16_t)((best[r] & 7) << RPH_EDGE_VARIANT_SHIFT)};
+                out[q * k + r] = e;
+            }
+            if (counts_out) counts_out[q] = filled;
+        });
+        return RPH_OK;
+    });
+}

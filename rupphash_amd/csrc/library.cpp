@@ -27,6 +27,7 @@ struct rph_library {
     // file.  What the last removal did (rph_debug_library_remove_stats) and the events around its stages, armed with the append's
     DevBuf d_rm_idx, d_rm_work, d_rm_rows;
     rph_group_lists_dev group_lists;  // rph_library_group_max_dist: the caller's group arrays and its outputs
+    DevBuf d_near_idx, d_near_out;    // rph_library_nearest*: the query files' indices; the slots and, behind them, the counts
     uint64_t rm_stats[3] = {0, 0, 0};  // members regrouped, edges found among them, first edge capacity tried
     bool rm_staged = false;
     hipEvent_t rm_ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -493,6 +494,57 @@ int rph_library_group_max_dist(rph_library *lib, const uint32_t *members, const 
         lib->group_lists.fill(q);
         RPH_TRY(rph_group_max_dist_run(lib->ctx, q, lib->group_lists.total, s));
         return lib->group_lists.download(max_dist_out, member_dist_out, s);
+    });
+}
+
+// rph_library_nearest and rph_library_nearest_files: the queries are hashes of the caller's (uploaded into d_qh) or resident files
+// (their indices uploaded; the kernel gathers their hashes from d_h and skips each in its own list)
+static int library_nearest(const char *who, rph_library *lib, const uint8_t *hashes32_q, const uint32_t *indices, uint64_t n_q, uint32_t k, uint32_t max_dist,
+                           rph_edge *out, uint32_t *counts_out)
+{
+    if (!lib) return fail(who, "null argument");
+    std::lock_guard<std::mutex> lock(lib->mu);
+    const void *queries = indices ? (const void *)indices : (const void *)hashes32_q;
+    RPH_TRY(rph_nearest_check(who, lib->d_var.data(), 8, lib->n, queries, n_q, k, out));
+    for (uint64_t t = 0; t < n_q && indices; t++)
+        if (indices[t] >= lib->n) return fail(who, "an index is not below the size");
+    if (n_q == 0) return RPH_OK;
+    rph_ctx *ctx = lib->ctx;
+    RPH_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    StreamDrain drain{s};
+    const size_t slot_bytes = align_up(n_q * k * sizeof(rph_edge), 256);
+    RPH_TRY(lib->d_near_out.reserve(slot_bytes + n_q * 4, s));
+    rph_nearest q;
+    q.rows = lib->d_var.data(), q.has_features = lib->d_hf.data(), q.n_variants = 8, q.n_lib = lib->n;
+    q.k = k, q.max_dist = max_dist, q.n_q = n_q;
+    if (indices) {
+        RPH_TRY(lib->d_near_idx.reserve(n_q * 4, s));
+        RPH_HIP_CHECK(hipMemcpyAsync(lib->d_near_idx.data(), indices, n_q * 4, hipMemcpyHostToDevice, s));
+        q.hashes_q = lib->d_h.data(), q.gather = lib->d_near_idx.as<uint32_t>();
+    } else {
+        RPH_TRY(lib->d_qh.reserve(n_q * 32, s));
+        RPH_HIP_CHECK(hipMemcpyAsync(lib->d_qh.data(), hashes32_q, n_q * 32, hipMemcpyHostToDevice, s));
+        q.hashes_q = lib->d_qh.data();
+    }
+    q.out = lib->d_near_out.as<rph_edge>(), q.counts = (uint32_t *)(lib->d_near_out.data() + slot_bytes);
+    RPH_TRY(rph_nearest_run(ctx, q, s));
+    RPH_HIP_CHECK(hipMemcpyAsync(out, q.out, n_q * k * sizeof(rph_edge), hipMemcpyDeviceToHost, s));
+    if (counts_out) RPH_HIP_CHECK(hipMemcpyAsync(counts_out, q.counts, n_q * 4, hipMemcpyDeviceToHost, s));
+    RPH_HIP_CHECK(hipStreamSynchronize(s));
+    return RPH_OK;
+}
+
+int rph_library_nearest(rph_library *lib, const uint8_t *hashes32_q, uint64_t n_q, uint32_t k, uint32_t max_dist, rph_edge *out, uint32_t *counts_out)
+{
+    return rph_guarded("rph_library_nearest", [&]() -> int { return library_nearest("rph_library_nearest", lib, hashes32_q, nullptr, n_q, k, max_dist, out, counts_out); });
+}
+
+int rph_library_nearest_files(rph_library *lib, const uint32_t *indices, uint64_t n_q, uint32_t k, uint32_t max_dist, rph_edge *out, uint32_t *counts_out)
+{
+    return rph_guarded("rph_library_nearest_files", [&]() -> int {
+        if (!indices && n_q) return fail("rph_library_nearest_files", "null argument");
+        return library_nearest("rph_library_nearest_files", lib, nullptr, indices, n_q, k, max_dist, out, counts_out);
     });
 }
 

@@ -274,6 +274,26 @@ int rph_host_group_lists_check(const char *who, const uint8_t *hashes32, uint64_
                                const uint32_t *pivots, const uint32_t *max_dist_out);
 // find_map (scanner.rs:2219-2232): the first listed member of group g that has features, else the first listed member, else RPH_NO_PIVOT
 uint32_t rph_host_default_pivot(const uint32_t *members, const uint32_t *offsets, uint32_t g, const float *coeffs, const uint8_t *has_features);
+// nearest_kernels.hip: one rph_hamming_nearest_dev request in device pointers (include/rupphash.h says what each array is).  gather
+// (nullable, n_q x uint32): query q is the hash hashes_q[gather[q]] and skips that file (rph_library_nearest_files)
+struct rph_nearest {
+    const uint8_t *rows = nullptr, *has_features = nullptr, *hashes_q = nullptr;
+    const uint32_t *skip = nullptr, *gather = nullptr;
+    uint32_t n_variants = 1, k = 0, max_dist = 256;
+    uint64_t n_lib = 0, n_q = 0;
+    rph_edge *out = nullptr;
+    uint32_t *counts = nullptr;
+};
+// what every form of rph_hamming_nearest refuses, checked before anything is written (host_grouping.cpp)
+int rph_nearest_check(const char *who, const void *rows, uint32_t n_variants, uint64_t n_lib, const void *hashes_q, uint64_t n_q, uint32_t k, const void *out);
+// takes ctx->mu and the sweep scratch for the partial lists; asynchronous on `stream`
+int rph_nearest_run(rph_ctx *ctx, const rph_nearest &q, hipStream_t stream);
+// how a call is cut (exported for the tests, not in the header): out[0..3] = files per MFMA block, files per segment, queries per
+// tile, number of segments
+extern "C" void rph_debug_nearest_layout(uint64_t n_lib, uint32_t n_variants, uint64_t n_q, uint32_t k, uint32_t *out);
+// forces the segment length of the calls that follow, in files (rounded up to whole MFMA blocks); 0 restores the default.  It lets a
+// library of a few thousand files reach many segments (tests only)
+extern "C" void rph_debug_nearest_set_segment(uint32_t files);
 int rph_launch_mih_build256(rph_ctx *ctx, const uint8_t *d_hashes, uint64_t n, uint32_t *d_offsets, uint32_t *d_values,
                             hipStream_t stream);
 int rph_launch_mih_build64(rph_ctx *ctx, const uint64_t *d_hashes, uint64_t n, uint32_t *d_offsets, uint32_t *d_values,

@@ -883,6 +883,65 @@ class Engine:
         check(self.L.rph_group_max_dist_dev(self.ctx, d_hashes, n, d_rows, row_mode, d_has_features, d_members, d_offsets, n_groups, d_pivots, d_max_dist,
                                             d_member_dist, stream), "rph_group_max_dist_dev")
 
+    @staticmethod
+    def _nearest_inputs(rows, hashes_q, has_features, skip):
+        """The arrays of a nearest call as the C forms take them.  rows: [n_lib, 32] or [n_lib, n_variants, 32] uint8."""
+        rows = np.ascontiguousarray(rows, np.uint8)
+        if rows.ndim == 2:
+            rows = rows.reshape(len(rows), 1, 32)
+        if rows.ndim != 3 or rows.shape[2] != 32:
+            raise ValueError(f"rows of shape {rows.shape}: [n_lib, n_variants, 32] expected")
+        hq = np.ascontiguousarray(hashes_q, np.uint8).reshape(-1, 32)
+        hf = None if has_features is None else np.ascontiguousarray(has_features, np.uint8)
+        if hf is not None and len(hf) != len(rows):
+            raise ValueError(f"{len(hf)} has_features flags for {len(rows)} files")
+        sk = None if skip is None else np.array([_lib.RPH_NO_FILE if x is None else int(x) for x in skip], np.uint32)
+        if sk is not None and len(sk) != len(hq):
+            raise ValueError(f"{len(sk)} skip entries for {len(hq)} queries")
+        return rows, hq, hf, sk
+
+    @staticmethod
+    def _nearest_call(call, where, n_q, k):
+        k = int(k)
+        slots = max(k, 0) if 0 < k <= _lib.RPH_NEAREST_MAX_K else 0  # a refused k writes nothing
+        edges, counts = np.zeros((n_q, slots), EDGE_DTYPE), np.zeros(n_q, np.uint32)
+        check(call(k, _ptr(edges), _ptr(counts)), where)
+        return edges, counts
+
+    def hamming_nearest(self, rows, hashes_q, k, max_dist=256, has_features=None, skip=None):
+        """The k nearest library files of every query (rph_hamming_nearest): rows [n_lib, 32] or [n_lib, 8, 32]; a file whose
+        has_features byte is 0 owns row 0 only; skip[q] is a file query q never reports (None: none).  Returns (edges[n_q, k], counts[n_q]):
+        slot (q, r) = (file, q, distance, variant << 9), ordered by (distance, file); slots behind counts[q] hold file RPH_NO_FILE and
+        distance 0xFFFF.  max_dist >= 256: no cutoff."""
+        r, hq, hf, sk = self._nearest_inputs(rows, hashes_q, has_features, skip)
+        return self._nearest_call(lambda kk, out, cnt: self.L.rph_hamming_nearest(self.ctx, _ptr(r), r.shape[1], _ptr(hf), len(r), _ptr(hq), _ptr(sk), len(hq), kk,
+                                                                                  max_dist, out, cnt), "rph_hamming_nearest", len(hq), k)
+
+    @staticmethod
+    def hamming_nearest_host(rows, hashes_q, k, max_dist=256, has_features=None, skip=None):
+        """hamming_nearest on the host (rph_hamming_nearest_host): no device, no context."""
+        L = _lib.load()
+        r, hq, hf, sk = Engine._nearest_inputs(rows, hashes_q, has_features, skip)
+        return Engine._nearest_call(lambda kk, out, cnt: L.rph_hamming_nearest_host(_ptr(r), r.shape[1], _ptr(hf), len(r), _ptr(hq), _ptr(sk), len(hq), kk, max_dist,
+                                                                                    out, cnt), "rph_hamming_nearest_host", len(hq), k)
+
+    def hamming_nearest_dev(self, d_rows, n_variants, n_lib, d_hashes_q, n_q, k, d_out, max_dist=256, d_has_features=None, d_skip=None, d_counts=None, stream=None):
+        """rph_hamming_nearest_dev: everything on the device, asynchronous on `stream`; d_out: n_q x k edges, d_counts: n_q x uint32 or None."""
+        check(self.L.rph_hamming_nearest_dev(self.ctx, d_rows, n_variants, d_has_features, n_lib, d_hashes_q, d_skip, n_q, k, max_dist, d_out, d_counts, stream),
+              "rph_hamming_nearest_dev")
+
+    @staticmethod
+    def nearest_layout(n_lib, n_variants, n_q, k):
+        """How a nearest call is cut (tests): files per MFMA block, files per segment, queries per tile, number of segments."""
+        out = (C.c_uint32 * 4)()
+        _lib.load().rph_debug_nearest_layout(n_lib, n_variants, n_q, k, out)
+        return tuple(out)
+
+    @staticmethod
+    def nearest_set_segment(files):
+        """Forces the segment length of the nearest calls that follow (tests); 0 restores the default."""
+        _lib.load().rph_debug_nearest_set_segment(files)
+
     def library(self, similarity):
         """A grouped library that stays on this engine's device (rph_library): see Library."""
         return Library(self, similarity)
@@ -1090,7 +1149,22 @@ class Library:
                                      max(1 << 16, 8 * len(h)) if cap is None else cap, cap is None, "rph_library_query")
 
 
+    def nearest(self, hashes, k, max_dist=256):
+        """Engine.hamming_nearest of the queries against the resident files (their 8 rows and flags, where they lie): (edges[n_q, k],
+        counts[n_q]), files in the library's current numbering.  The library is not changed."""
+        hq = np.ascontiguousarray(hashes, np.uint8).reshape(-1, 32)
+        return Engine._nearest_call(lambda kk, out, cnt: self.L.rph_library_nearest(self.handle, _ptr(hq), len(hq), kk, max_dist, out, cnt), "rph_library_nearest",
+                                    len(hq), k)
+
+    def nearest_files(self, indices, k, max_dist=256):
+        """The neighbours of resident files (current numbering): nearest() of their hashes, gathered on the device, each skipping itself."""
+        idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        return Engine._nearest_call(lambda kk, out, cnt: self.L.rph_library_nearest_files(self.handle, _ptr(idx), len(idx), kk, max_dist, out, cnt),
+                                    "rph_library_nearest_files", len(idx), k)
+
+
 group_max_dist_host = Engine.group_max_dist_host  # needs no engine
+hamming_nearest_host = Engine.hamming_nearest_host
 
 
 _default = None

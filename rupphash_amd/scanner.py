@@ -174,7 +174,9 @@ class ScannerLibrary(Library):
 def open_library(similarity, engine=None):
     """A grouped library that stays on the device between scans (ScannerLibrary): append(...) -> (labels, new_comparisons), restore(...),
     groups(), labels(), query(...).  groups() is group_with_pdqhash on the files the library holds, in order.
-    remove(indices) -> (new_index, dropped) takes files out (deleted, or gone at the next scan) and renumbers the rest through new_index."""
+    remove(indices) -> (new_index, dropped) takes files out (deleted, or gone at the next scan) and renumbers the rest through new_index.
+    nearest(hashes, k, max_dist=256) -> (edges[n_q, k], counts[n_q]) is the exact k-nearest search of query hashes among the resident
+    files, ordered by (distance, file); nearest_files(indices, k, max_dist=256) asks it for resident files, each skipping itself."""
     return ScannerLibrary(engine or default_engine(), similarity)
 
 
