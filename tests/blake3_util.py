@@ -5,7 +5,7 @@ Two tree builders over the same chunk chaining values:
   blake3(...)        the pairwise fold: parents of neighbouring nodes level by level, an odd last node carried up a level
   blake3_stack(...)  the specification's incremental chaining-value stack (merge while the chunk count has trailing zero bits)
 They must agree at every length: that is what makes the fold a statement of BLAKE3's left-full tree.
-  blake3_many(...)   the pairwise fold over a list of messages at once (test_blake3_cpu.py holds it to blake3 at every length)
+  blake3_many(...)   the pairwise fold over a list of messages at once, keyed or not (test_blake3_cpu.py holds it to blake3 at every length)
 
 rgba16_bytes(image): the byte stream of the pixel hash (the `image` crate's to_rgba16() as little-endian bytes: u8 v -> u16 v * 257,
 Luma8 copied into R, G and B, alpha 65535 unless the input has four channels).
@@ -107,12 +107,13 @@ def blake3(data, key=None):
     return _digest(cv)
 
 
-def blake3_many(datas):
-    """[blake3(d) for d in datas] (unkeyed) with the chunks and the tree levels of all messages in the same array operations: many
+def blake3_many(datas, key=None):
+    """[blake3(d, key) for d in datas] with the chunks and the tree levels of all messages in the same array operations: many
     short messages cost what one long message costs"""
     datas = [bytes(d) for d in datas]
     if not datas:
         return []
+    kw, base = _key_words(key)
     nchs = np.array([max(1, -(-len(d) // CHUNK_LEN)) for d in datas], np.int64)
     offs = np.concatenate([[0], np.cumsum(nchs)])
     total = int(offs[-1])
@@ -125,13 +126,13 @@ def blake3_many(datas):
     clen = np.clip(np.array([len(d) for d in datas], np.int64)[which] - counter * CHUNK_LEN, 0, CHUNK_LEN)
     nblocks = np.maximum(1, -(-clen // BLOCK_LEN))
     single = nchs[which] == 1
-    cv = np.repeat(IV[:, None], total, axis=1)
+    cv = np.repeat(kw[:, None], total, axis=1)
     for b in range(16):
         act = b < nblocks
         if not act.any():
             break
         last = b + 1 == nblocks
-        flags = np.where(b == 0, CHUNK_START, 0) | np.where(last, CHUNK_END, 0) | np.where(last & single, ROOT, 0)
+        flags = base | np.where(b == 0, CHUNK_START, 0) | np.where(last, CHUNK_END, 0) | np.where(last & single, ROOT, 0)
         new = compress(cv, words[:, b, :].T, counter.astype(np.uint64), np.clip(clen - b * BLOCK_LEN, 0, BLOCK_LEN), flags)
         cv = np.where(act[None, :], new, cv)
     nodes = [cv[:, offs[k]:offs[k + 1]] for k in range(len(datas))]
@@ -142,8 +143,8 @@ def blake3_many(datas):
         pairs = [nodes[k].shape[1] // 2 for k in busy]
         left = np.concatenate([nodes[k][:, 0:2 * n:2] for k, n in zip(busy, pairs)], axis=1)
         right = np.concatenate([nodes[k][:, 1:2 * n:2] for k, n in zip(busy, pairs)], axis=1)
-        flags = np.concatenate([np.full(n, PARENT | (ROOT if nodes[k].shape[1] == 2 else 0)) for k, n in zip(busy, pairs)])
-        par = compress(np.repeat(IV[:, None], left.shape[1], axis=1), np.concatenate([left, right], axis=0), np.zeros(left.shape[1], np.uint64), BLOCK_LEN, flags)
+        flags = np.concatenate([np.full(n, base | PARENT | (ROOT if nodes[k].shape[1] == 2 else 0)) for k, n in zip(busy, pairs)])
+        par = compress(np.repeat(kw[:, None], left.shape[1], axis=1), np.concatenate([left, right], axis=0), np.zeros(left.shape[1], np.uint64), BLOCK_LEN, flags)
         o = 0
         for k, n in zip(busy, pairs):
             nodes[k] = np.concatenate([par[:, o:o + n], nodes[k][:, 2 * n:]], axis=1)  # (an odd last node is carried up a level)

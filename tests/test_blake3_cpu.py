@@ -36,6 +36,10 @@ def test_many_messages_at_once_agree_with_one_at_a_time():
     datas = [b3.test_input(n) for n in LENGTHS] + [rng.integers(0, 256, n, dtype=np.uint8).tobytes() for n in (0, 5, 1024, 3000, 3072, 70000)]
     assert b3.blake3_many(datas) == [b3.blake3(d) for d in datas]
     assert b3.blake3_many([]) == [] and b3.blake3_many([b"abc"]) == [b3.blake3(b"abc")]
+    for key in (KEY, bytes(range(32))):
+        assert b3.blake3_many(datas, key) == [b3.blake3(d, key) for d in datas]
+        assert b3.blake3_many([], key) == [] and b3.blake3_many([b""], key) == [b3.blake3(b"", key)]
+    assert b3.blake3_many(datas, key=None) == b3.blake3_many(datas) != b3.blake3_many(datas, KEY)
 
 
 @pytest.mark.parametrize("key", [None, KEY, bytes(range(32))], ids=["hash", "keyed", "key2"])
