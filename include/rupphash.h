@@ -583,6 +583,13 @@ int rph_multi_jpeg_hash_and_group(rph_multi *multi, const uint8_t *const *data, 
                                   uint32_t similarity, uint8_t *hash32_out, float *quality_out, float *coeffs_out, uint8_t *valid_out,
                                   int32_t *status_out, uint32_t *members, uint32_t *offsets, uint32_t *n_groups_out,
                                   uint64_t *comparison_count_out);
+/* The same from files of any mix of the six formats: device i runs rph_files_pdq_hash_batch (the files section below) on files
+ * [lo_i, hi_i) with their names, n_threads host threads in all; names, pixel_hash32_out and format_out as there (nullable).  The
+ * sharding, the exchange and the grouping are those of rph_multi_jpeg_hash_and_group. */
+int rph_multi_files_hash_and_group(rph_multi *multi, const uint8_t *const *data, const size_t *len, const char *const *names, uint32_t n,
+                                   int jpeg_flavour, uint32_t n_threads, uint32_t similarity, uint8_t *hash32_out, float *quality_out,
+                                   float *coeffs_out, uint8_t *valid_out, int32_t *status_out, uint8_t *pixel_hash32_out, uint8_t *format_out,
+                                   uint32_t *members, uint32_t *offsets, uint32_t *n_groups_out, uint64_t *comparison_count_out);
 /* rph_group_files_pdq across the devices: hashes / coefficients / quality from the cache (same arguments and results). */
 int rph_multi_group_files_pdq(rph_multi *multi, const uint8_t *hashes32, const float *coeffs, const uint8_t *has_features,
                               const int32_t *quality, uint64_t n, uint32_t similarity, uint32_t *members, uint32_t *offsets,
@@ -1085,6 +1092,60 @@ int rph_bmp_pdq_hash_batch(rph_ctx *ctx, const uint8_t *const *data, const size_
                            uint8_t *pixel_hash32_out);
 /* The BMP path keeps its staging and device buffers in the context between calls; this returns them. */
 int rph_bmp_release(rph_ctx *ctx);
+
+/* =====================================================================
+ * A mixed list of files in one call: the body of the scan loop's per-file closure (scanner.rs:1350-1417: decode, pixel hash, PDQ
+ * features, hash, quality, resolution) for a chunk of files of any of the six formats above.  The content hash stays with the host
+ * (INTEGRATION.md 7c).
+ * THE ROUTING RULE (rph_file_format): which pipeline takes a file, from its name and its first bytes; load_image_fast's routing
+ * (scanner.rs:461-735: extension first, then the bytes' magic, with a fall-through for a misnamed file) reduced to what it comes to.
+ *   `name`: a path or file name, UTF-8, or NULL.  Its extension is Rust's Path::extension of the last component after the last '/': none
+ *   when the component has no '.', or starts with its only '.'; else the part after the last '.' (which may be empty), compared ASCII
+ *   case-insensitively.
+ *   1. The extension is one of RAW_EXTS (scanner.rs:43-46: nef dng cr2 cr3 arw orf rw2 raf kdc dcr pef x3f srf 3fr), or jxl, or pdf:
+ *      RPH_FORMAT_NONE, the bytes are not looked at.  load_image_fast refuses the RAW names itself (the caller hashes the JPEG thumbnail it
+ *      extracts, and passes that with a .jpg name); the jxl and pdf arms return their decoder's error without falling through.
+ *   2. Otherwise the magic decides:   PNG 89 50 4E 47 0D 0A 1A 0A;  JPEG FF D8 FF;  GIF "GIF87a" or "GIF89a";  WebP "RIFF" at 0 and "WEBP"
+ *      at 8;  TIFF 4D 4D 00 2A or 49 49 2A 00;  BMP "BM".  Anything else, or a file too short for its magic: RPH_FORMAT_NONE.
+ *      This is image 0.25's guess_format restated from the published crate, which is not in the reference tree: PARITY UNPINNED.
+ *   3. The extension plays no further part: a .jpg or .tif whose bytes are another format fails the reference's dedicated arm and reaches
+ *      with_guessed_format (so it goes by its magic), and a known extension over an unknown magic fails in the crate's decoder (NONE).
+ *   A WebP goes to the WebP pipeline whatever its payload; that pipeline refuses a lossy one (RPH_ERR_UNSUPPORTED), as it does alone.
+ * ===================================================================== */
+#define RPH_FORMAT_NONE 0
+#define RPH_FORMAT_JPEG 1
+#define RPH_FORMAT_PNG 2
+#define RPH_FORMAT_TIFF 3
+#define RPH_FORMAT_WEBP 4
+#define RPH_FORMAT_GIF 5
+#define RPH_FORMAT_BMP 6
+/* Host code, no context: RPH_FORMAT_* by the rule above.  data may be NULL when len is 0. */
+int rph_file_format(const uint8_t *data, size_t len, const char *name);
+/* n files of any mix of formats -> the outputs of the per-format calls, in the caller's order.  names (n entries, or NULL; any entry may
+ * be NULL) feeds the rule; jpeg_flavour as rph_jpeg_pdq_hash_batch's flavour; every output behind hash32_out may be NULL.
+ *  - File i goes to the pipeline rph_file_format names and gets, byte for byte, what that format's own batch call returns for it alone
+ *    (JPEG: rph_jpeg_pdq_pixel_hash_batch when pixel_hash32_out is given, else rph_jpeg_pdq_hash_batch), the status of a refused or
+ *    damaged file and valid 0 with RPH_OK below 5 px included.  RPH_FORMAT_NONE: status RPH_ERR_UNSUPPORTED, valid 0, zero outputs (the
+ *    caller's own decoders take the file); a null or empty file: RPH_ERR_INVALID_ARG.  The call itself returns RPH_OK.
+ *  - format_out[i]: the pipeline that took the file (RPH_FORMAT_*), set even when it refused the file; 0 for NONE, null and empty files.
+ *    size_out[2 i], [2 i + 1]: width and height of the decoded image (the format's _info: the `resolution` of scanner.rs:1386-1390),
+ *    0, 0 when status != RPH_OK.
+ *  - The formats present run one after another on the calling thread, each with all n_threads host threads (0 = as many as the
+ *    process may use): the default, and RPH_FILES_SEQUENTIAL says so explicitly.  RPH_FILES_CONCURRENT: every format present runs on a
+ *    host thread of its own (a lane), so that one format's host decompression overlaps another's device work; the lanes are ordered by
+ *    the pipelines' own locks where they share scratch, and the call holds none of them.  The n_threads are then dealt to the lanes in
+ *    proportion to their compressed bytes weighted by the format's host cost, each lane at least one.  With 16 threads the lanes did
+ *    not beat the sequential route on the measured folder of 512x512 files (they won about 5 % at 1920x1080), which is
+ *    why they are not the default.
+ *  - A file's results depend neither on the other files of the call nor on n_threads, flags or the pipelines' mode settings.
+ *  - When a lane fails as a call (HIP error, allocation) every lane is still joined; the call returns the code of the first failing lane
+ *    in RPH_FORMAT_* order, rph_last_error() its message. */
+#define RPH_FILES_SEQUENTIAL 1u
+#define RPH_FILES_CONCURRENT 2u
+int rph_files_pdq_hash_batch(rph_ctx *ctx, const uint8_t *const *data, const size_t *len, const char *const *names, uint32_t n,
+                             int jpeg_flavour, uint32_t n_threads, uint32_t flags, uint8_t *hash32_out, float *quality_out, float *coeffs_out,
+                             uint8_t *dihedral_out, uint8_t *valid_out, int32_t *status_out, uint8_t *pixel_hash32_out, uint8_t *format_out,
+                             uint32_t *size_out);
 
 /* =====================================================================
  * BLAKE3 identity hashes (blake3 crate 1.x, 32-byte output): the two exact hashes the reference computes next to the PDQ hash.

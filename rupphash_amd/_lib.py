@@ -38,6 +38,12 @@ RPH_GIF_DECOMPRESS_HOST = 0
 RPH_GIF_DECOMPRESS_DEVICE = 1
 RPH_GIF_DECOMPRESS_AUTO = 2
 
+# rph_file_format / rph_files_pdq_hash_batch: the pipeline that takes a file
+RPH_FORMAT_NONE, RPH_FORMAT_JPEG, RPH_FORMAT_PNG, RPH_FORMAT_TIFF, RPH_FORMAT_WEBP, RPH_FORMAT_GIF, RPH_FORMAT_BMP = range(7)
+FORMAT_NAMES = (None, "jpeg", "png", "tiff", "webp", "gif", "bmp")
+RPH_FILES_SEQUENTIAL = 1
+RPH_FILES_CONCURRENT = 2
+
 RPH_EDGE_MIH_R1 = 0x8000
 RPH_EDGE_PROBE_MASK = 0x01FF
 RPH_EDGE_VARIANT_SHIFT = 9
@@ -157,8 +163,13 @@ SIGNATURES = {
                                            _u32p, _u32p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "rph_multi_jpeg_hash_and_group": (C.c_int, [_vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, _u8p, _f32p, _f32p, _u8p,
                                               _i32p, _u32p, _u32p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "rph_multi_files_hash_and_group": (C.c_int, [_vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(C.c_char_p), C.c_uint32, C.c_int, C.c_uint32, C.c_uint32,
+                                                 _u8p, _f32p, _f32p, _u8p, _i32p, _u8p, _u8p, _u32p, _u32p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "rph_multi_group_files_pdq": (C.c_int, [_vp, _u8p, _f32p, _u8p, _i32p, C.c_uint64, C.c_uint32, _u32p, _u32p, C.POINTER(C.c_uint32),
                                             C.POINTER(C.c_uint64)]),
+    "rph_file_format": (C.c_int, [C.c_char_p, _sz, C.c_char_p]),
+    "rph_files_pdq_hash_batch": (C.c_int, [_vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(C.c_char_p), C.c_uint32, C.c_int, C.c_uint32, C.c_uint32,
+                                           _u8p, _f32p, _f32p, _u8p, _u8p, _i32p, _u8p, _u8p, _u32p]),
     "rph_hash_record_encode": (None, [_u8p, _u8p]),
     "rph_hash_record_decode": (C.c_int, [_u8p, _sz, _u8p]),
     "rph_hash_records_encode": (None, [_u8p, _sz, _u8p]),
@@ -232,6 +243,9 @@ DEBUG_SIGNATURES = {
     "rph_debug_group_max_dist_events": (C.c_int, [_vp, _vp, _vp]),
     "rph_debug_nearest_layout": (None, [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32)]),
     "rph_debug_nearest_set_segment": (None, [C.c_uint32]),
+    "rph_debug_file_extension": (C.c_void_p, [C.c_char_p, C.POINTER(C.c_size_t)]),
+    "rph_debug_raw_ext": (C.c_char_p, [C.c_uint32]),
+    "rph_debug_files_lanes": (None, [C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
 }
 
 _lib = None

@@ -224,6 +224,36 @@ int sweep_all(rph_multi *m, const std::vector<const uint8_t *> &d_rows, uint32_t
     return RPH_ERR_CAPACITY;
 }
 
+// The grouping half of the scan-then-group calls from files: rph_multi_group_files_pdq over the files that produced a hash, members as
+// indices into the caller's file list
+int group_hashed_files(rph_multi *m, uint32_t n, const uint8_t *hash32, const float *quality, const float *coeffs, const uint8_t *valid, uint32_t similarity,
+                       uint32_t *members, uint32_t *offsets, uint32_t *n_groups_out, uint64_t *comparison_count_out)
+{
+    // dense ids over the files that have a hash; stored quality = (q * 100).round().clamp(0, 100) (scanner.rs:1416-1417)
+    std::vector<uint32_t> dense_to_file;
+    for (uint32_t i = 0; i < n; i++)
+        if (valid[i]) dense_to_file.push_back(i);
+    const uint64_t nd = dense_to_file.size();
+    if (nd < 2) return RPH_OK;
+    std::vector<uint8_t> h((size_t)nd * 32);
+    std::vector<float> c((size_t)nd * 256);
+    std::vector<int32_t> q(nd);
+    for (uint64_t d = 0; d < nd; d++) {
+        const uint32_t f = dense_to_file[d];
+        memcpy(&h[d * 32], hash32 + (size_t)f * 32, 32);
+        memcpy(&c[d * 256], coeffs + (size_t)f * 256, 1024);
+        const float s = quality[f] * 100.0f;
+        q[d] = (int32_t)std::min(100.0f, std::max(0.0f, floorf(s + 0.5f)));
+    }
+    std::vector<uint32_t> mem(nd), off(nd / 2 + 2);
+    uint32_t ng = 0;
+    RPH_TRY(rph_multi_group_files_pdq(m, h.data(), c.data(), nullptr, q.data(), nd, similarity, mem.data(), off.data(), &ng, comparison_count_out));
+    for (uint32_t g = 0; g <= ng; g++) offsets[g] = off[g];
+    for (uint32_t t = 0; t < off[ng]; t++) members[t] = dense_to_file[mem[t]];
+    *n_groups_out = ng;
+    return RPH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -449,29 +479,62 @@ int rph_multi_jpeg_hash_and_group(rph_multi *m, const uint8_t *const *data, cons
                     return rcs[i];
                 }
         }
-        // dense ids over the files that have a hash; stored quality = (q * 100).round().clamp(0, 100) (scanner.rs:1416-1417)
-        std::vector<uint32_t> dense_to_file;
-        for (uint32_t i = 0; i < n; i++)
-            if (valid[i]) dense_to_file.push_back(i);
-        const uint64_t nd = dense_to_file.size();
-        if (nd < 2) return RPH_OK;
-        std::vector<uint8_t> h((size_t)nd * 32);
-        std::vector<float> c((size_t)nd * 256);
-        std::vector<int32_t> q(nd);
-        for (uint64_t d = 0; d < nd; d++) {
-            const uint32_t f = dense_to_file[d];
-            memcpy(&h[d * 32], hash32_out + (size_t)f * 32, 32);
-            memcpy(&c[d * 256], coeffs + (size_t)f * 256, 1024);
-            const float s = quality[f] * 100.0f;
-            q[d] = (int32_t)std::min(100.0f, std::max(0.0f, floorf(s + 0.5f)));
+        return group_hashed_files(m, n, hash32_out, quality, coeffs, valid, similarity, members, offsets, n_groups_out, comparison_count_out);
+    });
+}
+
+// rph_multi_jpeg_hash_and_group for files of any mix of the six formats: the inner call is rph_files_pdq_hash_batch (files_batch.cpp) on
+// each device's range of the files and their names; the sharding and the grouping are the same.
+int rph_multi_files_hash_and_group(rph_multi *m, const uint8_t *const *data, const size_t *len, const char *const *names, uint32_t n, int jpeg_flavour,
+                                   uint32_t n_threads, uint32_t similarity, uint8_t *hash32_out, float *quality_out, float *coeffs_out, uint8_t *valid_out,
+                                   int32_t *status_out, uint8_t *pixel_hash32_out, uint8_t *format_out, uint32_t *members, uint32_t *offsets,
+                                   uint32_t *n_groups_out, uint64_t *comparison_count_out)
+{
+    return rph_guarded("rph_multi_files_hash_and_group", [&]() -> int {
+        if (!m || (n && (!data || !len)) || !hash32_out || !members || !offsets || !n_groups_out) {
+            rph_set_error("rph_multi_files_hash_and_group: null argument");
+            return RPH_ERR_INVALID_ARG;
         }
-        std::vector<uint32_t> mem(nd), off(nd / 2 + 2);
-        uint32_t ng = 0;
-        RPH_TRY(rph_multi_group_files_pdq(m, h.data(), c.data(), nullptr, q.data(), nd, similarity, mem.data(), off.data(), &ng, comparison_count_out));
-        for (uint32_t g = 0; g <= ng; g++) offsets[g] = off[g];
-        for (uint32_t t = 0; t < off[ng]; t++) members[t] = dense_to_file[mem[t]];
-        *n_groups_out = ng;
-        return RPH_OK;
+        if (similarity > RPH_MAX_SIMILARITY_256) {
+            rph_set_error("Similarity distances above %u require R=4 bit-flip checks, which are not implemented.", RPH_MAX_SIMILARITY_256);
+            return RPH_ERR_INVALID_ARG;
+        }
+        *n_groups_out = 0;
+        offsets[0] = 0;
+        if (comparison_count_out) *comparison_count_out = 0;
+        if (n == 0) return RPH_OK;
+        std::vector<float> q_tmp, c_tmp;
+        std::vector<uint8_t> v_tmp;
+        float *quality = quality_out, *coeffs = coeffs_out;
+        uint8_t *valid = valid_out;
+        if (!quality) q_tmp.resize(n), quality = q_tmp.data();
+        if (!coeffs) c_tmp.resize((size_t)n * 256), coeffs = c_tmp.data();
+        if (!valid) v_tmp.resize(n), valid = v_tmp.data();
+        {
+            std::lock_guard<std::mutex> lock(m->mu);
+            const int world = (int)m->ctx.size();
+            const uint32_t threads_each = n_threads ? std::max(1u, n_threads / (uint32_t)world) : 0;
+            std::vector<int> rcs(world, RPH_OK);
+            std::vector<std::string> errs(world);
+            std::vector<std::thread> th;
+            for (int i = 0; i < world; i++)
+                th.emplace_back([&, i] {
+                    uint64_t lo, hi;
+                    shard_range(n, i, world, lo, hi);
+                    if (hi == lo) return;
+                    rcs[i] = rph_files_pdq_hash_batch(m->ctx[i], data + lo, len + lo, names ? names + lo : nullptr, (uint32_t)(hi - lo), jpeg_flavour, threads_each, 0,
+                                                      hash32_out + lo * 32, quality + lo, coeffs + lo * 256, nullptr, valid + lo, status_out ? status_out + lo : nullptr,
+                                                      pixel_hash32_out ? pixel_hash32_out + lo * 32 : nullptr, format_out ? format_out + lo : nullptr, nullptr);
+                    if (rcs[i] != RPH_OK) errs[i] = rph_last_error();
+                });
+            for (auto &t : th) t.join();
+            for (int i = 0; i < world; i++)
+                if (rcs[i] != RPH_OK) {
+                    rph_set_error("device %d: %s", m->devices[i], errs[i].c_str());
+                    return rcs[i];
+                }
+        }
+        return group_hashed_files(m, n, hash32_out, quality, coeffs, valid, similarity, members, offsets, n_groups_out, comparison_count_out);
     });
 }
 

@@ -536,6 +536,58 @@ class Engine:
         outputs), valid[i] = 0 with status 0 for an image below 5 px (which still has its pixel hash)."""
         return self._file_hash_batch("bmp", files, threads, want_quality, want_coeffs, want_dihedral, want_pixel_hash)
 
+    # ---- a mixed list of files (include/rupphash.h, the files section) ----
+    @staticmethod
+    def file_format(data, name=None):
+        """The pipeline that takes a file (_lib.RPH_FORMAT_*: 0 none, 1 jpeg, 2 png, 3 tiff, 4 webp, 5 gif, 6 bmp) by the routing rule:
+        the extension of `name` (str, bytes or None) rules out RAW, jxl and pdf names, else the bytes' magic decides.  Host code."""
+        return _lib.load().rph_file_format(data, len(data) if data is not None else 0, Engine._name_bytes(name))
+
+    @staticmethod
+    def _name_bytes(name):
+        return None if name is None else (bytes(name) if isinstance(name, (bytes, bytearray)) else str(name).encode("utf-8", "surrogateescape"))
+
+    @staticmethod
+    def files_list(files, names=None):
+        """The (pointers, lengths, names, n) a C caller would hold; a file may be None (a null entry), names None or a list with None entries"""
+        n = len(files)
+        nm = None if names is None else (C.c_char_p * n)(*[Engine._name_bytes(x) for x in names])
+        return (C.c_char_p * n)(*files), (C.c_size_t * n)(*[len(f) if f is not None else 0 for f in files]), nm, n
+
+    def files_pdq_hash_batch(self, files, names=None, flavour=0, threads=0, sequential=False, want_quality=True, want_coeffs=False, want_dihedral=False,
+                             want_pixel_hash=False, concurrent=False):
+        """files: list of byte strings of any mix of the six formats (or the tuple files_list() made of one, names included).  Returns the
+        per-format dict(hash, quality, coeffs, dihedral, valid, status[, pixel_hash]) in the caller's order plus "format" (n uint8:
+        RPH_FORMAT_* of the pipeline that took the file, 0 for a file no pipeline takes -- status RPH_ERR_UNSUPPORTED) and "size"
+        (n x (w, h) of the decoded images, 0 where status != 0).  The formats run one after another (the default; `sequential` says so
+        explicitly) or, with `concurrent`, each on a host thread of its own."""
+        arr, lens, nm, n = files if isinstance(files, tuple) else self.files_list(files, names)
+        out = {
+            "hash": np.zeros((n, 32), np.uint8),
+            "quality": np.zeros(n, np.float32) if want_quality else None,
+            "coeffs": np.zeros((n, 256), np.float32) if want_coeffs else None,
+            "dihedral": np.zeros((n, 8, 32), np.uint8) if want_dihedral else None,
+            "valid": np.zeros(n, np.uint8),
+            "status": np.zeros(n, np.int32),
+            "format": np.zeros(n, np.uint8),
+            "size": np.zeros((n, 2), np.uint32),
+        }
+        if want_pixel_hash:
+            out["pixel_hash"] = np.zeros((n, 32), np.uint8)
+        check(self.L.rph_files_pdq_hash_batch(self.ctx, arr, lens, nm, n, int(flavour), int(threads),
+                                              (_lib.RPH_FILES_SEQUENTIAL if sequential else 0) | (_lib.RPH_FILES_CONCURRENT if concurrent else 0),
+                                              _ptr(out["hash"]), _ptr(out["quality"]), _ptr(out["coeffs"]), _ptr(out["dihedral"]), _ptr(out["valid"]),
+                                              _ptr(out["status"]), _ptr(out.get("pixel_hash")), _ptr(out["format"]), _ptr(out["size"])),
+              "rph_files_pdq_hash_batch")
+        return out
+
+    def debug_files_lanes(self):
+        """What the last files_pdq_hash_batch of the calling thread did: {format name: (wall ms, threads, files)} of the lanes it ran.
+        Debug / tools only."""
+        ms, th, nf = (C.c_double * 7)(), (C.c_uint32 * 7)(), (C.c_uint32 * 7)()
+        self.L.rph_debug_files_lanes(ms, th, nf)
+        return {_lib.FORMAT_NAMES[f]: (ms[f], th[f], nf[f]) for f in range(1, 7) if nf[f]}
+
     # ---- BLAKE3 identity hashes ----
     @staticmethod
     def blake3_host(data, key=None):
@@ -1260,6 +1312,26 @@ class MultiEngine:
         check(self.L.rph_multi_jpeg_hash_and_group(self.m, arr, lens, n, int(flavour), int(threads), similarity, _ptr(out["hash"]), _ptr(out["quality"]),
                                                    _ptr(out["coeffs"]), _ptr(out["valid"]), _ptr(out["status"]), _ptr(members), _ptr(offsets), C.byref(ng),
                                                    C.byref(cmp_count)), "rph_multi_jpeg_hash_and_group")
+        out["groups"] = Engine._groups(members, offsets, ng.value)
+        out["comparison_count"] = cmp_count.value
+        return out
+
+    def files_hash_and_group(self, files, similarity, names=None, flavour=0, threads=0, want_pixel_hash=False):
+        """files: list of byte strings of any mix of the six formats (Engine.files_pdq_hash_batch), names: their names or None.  Returns
+        dict(hash, quality, coeffs, valid, status, format[, pixel_hash], groups, comparison_count); groups hold indices into `files`."""
+        arr, lens, nm, n = files if isinstance(files, tuple) else Engine.files_list(files, names)
+        out = {"hash": np.zeros((n, 32), np.uint8), "quality": np.zeros(n, np.float32), "coeffs": np.zeros((n, 256), np.float32),
+               "valid": np.zeros(n, np.uint8), "status": np.zeros(n, np.int32), "format": np.zeros(n, np.uint8)}
+        if want_pixel_hash:
+            out["pixel_hash"] = np.zeros((n, 32), np.uint8)
+        members = np.zeros(max(n, 1), np.uint32)
+        offsets = np.zeros(n // 2 + 2, np.uint32)
+        ng = C.c_uint32()
+        cmp_count = C.c_uint64()
+        check(self.L.rph_multi_files_hash_and_group(self.m, arr, lens, nm, n, int(flavour), int(threads), similarity, _ptr(out["hash"]), _ptr(out["quality"]),
+                                                    _ptr(out["coeffs"]), _ptr(out["valid"]), _ptr(out["status"]), _ptr(out.get("pixel_hash")),
+                                                    _ptr(out["format"]), _ptr(members), _ptr(offsets), C.byref(ng), C.byref(cmp_count)),
+              "rph_multi_files_hash_and_group")
         out["groups"] = Engine._groups(members, offsets, ng.value)
         out["comparison_count"] = cmp_count.value
         return out

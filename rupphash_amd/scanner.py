@@ -10,6 +10,8 @@
     load_bmp (the image-crate arm for .bmp)        scanner.rs:713-734
     pixel_hash (--pixel-hash)                      scanner.rs:1393-1404
     hash_images (both hashes of decoded images)    scanner.rs:1386-1410
+    load_image_any (the routing over six formats)  scanner.rs:461-735
+    hash_files (the per-file closure, mixed files) scanner.rs:1350-1417
     identical_duplicates                           scanner.rs:1843-1864 (analyze_group steps 1-3)
 File-name logic after the union-find (merge_groups_by_stem, the sorting inside process_raw_groups) stays with the caller.
 """
@@ -109,6 +111,45 @@ def hash_images(images, pixel_hash=True, engine=None):
             res.append((out["hash"][i].tobytes(), float(out["quality"][i]), PdqFeatures(out["coeffs"][i]), ph))
         else:
             res.append((None, None, None, ph))
+    return res
+
+
+def load_image_any(path, data, engine=None, flavour=_lib.RPH_JPEG_ZUNE):
+    """load_image_fast's routing (scanner.rs:461-735) over the six formats the library decodes: the file goes to the pipeline the routing
+    rule names (Engine.file_format: RAW, jxl and pdf names to none, else by the bytes' magic, so a misnamed file falls through to its own
+    format) and comes back as that format's device decode -- what load_image_fast, load_png, load_tiff, load_gif and load_bmp return, and
+    Engine.webp_decode.  ValueError for a file no pipeline takes; RphError for one its pipeline refuses."""
+    eng = engine or default_engine()
+    fmt = eng.file_format(data, path)
+    if fmt == _lib.RPH_FORMAT_NONE:
+        raise ValueError(f"load_image_any: no pipeline of this library takes '{path}'")
+    if fmt == _lib.RPH_FORMAT_JPEG:
+        return eng.jpeg_decode(data, flavour)
+    return getattr(eng, _lib.FORMAT_NAMES[fmt] + "_decode")(data)
+
+
+def hash_files(names, datas=None, pixel_hash=True, engine=None):
+    """The body of the scan loop's per-file closure (scanner.rs:1350-1417) for a list of files of any mix of formats in one call
+    (Engine.files_pdq_hash_batch): [(pdq hash, quality, PdqFeatures or None, pixel hash, status, format, (w, h))] -- hash_images' tuples
+    extended by the file's status (0, or why no pipeline of the library hashed it: the caller's CPU path takes the file), the pipeline
+    that took it (_lib.RPH_FORMAT_*, 0: none) and the decoded image's resolution.  datas: the files' bytes; None reads the files."""
+    from .pdqhash import PdqFeatures
+
+    names = list(names)
+    if datas is None:
+        datas = []
+        for name in names:
+            with open(name, "rb") as f:
+                datas.append(f.read())
+    out = (engine or default_engine()).files_pdq_hash_batch(list(datas), names, want_coeffs=True, want_pixel_hash=pixel_hash)
+    res = []
+    for i in range(len(names)):
+        rest = (int(out["status"][i]), int(out["format"][i]), (int(out["size"][i][0]), int(out["size"][i][1])))
+        ph = out["pixel_hash"][i].tobytes() if pixel_hash and out["status"][i] == 0 else None
+        if out["valid"][i]:
+            res.append((out["hash"][i].tobytes(), float(out["quality"][i]), PdqFeatures(out["coeffs"][i]), ph) + rest)
+        else:
+            res.append((None, None, None, ph) + rest)
     return res
 
 
