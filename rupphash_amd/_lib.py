@@ -237,6 +237,8 @@ DEBUG_SIGNATURES = {
     "rph_debug_hamming_cross_layout": (None, [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                               C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "rph_debug_file_chunks": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "rph_debug_jpeg_segment_log": (C.c_int, [_vp, C.c_int]),
+    "rph_debug_jpeg_segments": (C.c_int, [_vp, _vp, C.c_uint32, C.POINTER(C.c_uint32), _vp, C.c_uint32, C.POINTER(C.c_uint32)]),
     "rph_debug_library_stages": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_float)]),
     "rph_debug_library_remove_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "rph_debug_library_remove_stages": (C.c_int, [_vp, C.POINTER(C.c_float)]),

@@ -148,6 +148,12 @@ int rph_jpeg_launch_prog(hipStream_t stream, const uint8_t *d_streams, const HIm
 // kernel, which writes the files' walk items (d_items[first_item ..]) -- n_segs of them per file, or one whole-file item and empty ones
 // when the file's chain did not verify.  d_work: rph_jpeg_segment_work_bytes(n_segs) (round 0's records, two `out` slots per segment, the segment -> file map).
 int rph_jpeg_launch_segments(hipStream_t stream, const uint8_t *d_streams, const HImage *d_images, const SegFile *d_files, uint32_t n_files, SegState *d_segs,
-                             uint32_t n_segs, uint32_t seg_bytes, void *d_work, int rounds, const rphj::DeviceLut *d_luts, uint32_t n_luts, HItem *d_items);
+                             uint32_t n_segs, uint32_t seg_bytes, void *d_work, int rounds, const rphj::DeviceLut *d_luts, uint32_t n_luts, HItem *d_items,
+                             bool count_decodes = false);  // count_decodes: the validation rounds also count their decodes and the bits they read (the log's)
 size_t rph_jpeg_segment_work_bytes(uint32_t n_segs);  // of d_work
 void rph_jpeg_debug_segment_stats(hipStream_t stream, const void *d_work, uint32_t n_segs);  // (RPH_JPEG_TRACE=1)
+// (rph_debug_jpeg_segment_log) behind rph_jpeg_launch_segments with the same d_work and rounds: waits for the stream and copies back, per
+// segment, the `out` the prefix kernel read, round 0's n and out, and the validation rounds' decodes and the bits they read (launched with
+// count_decodes; n_segs words each)
+int rph_jpeg_debug_copy_segments(hipStream_t stream, const void *d_work, uint32_t n_segs, int rounds, uint32_t *final_out, uint32_t *round0_n, uint32_t *round0_out,
+                                 uint32_t *decodes, uint32_t *decoded_bits);

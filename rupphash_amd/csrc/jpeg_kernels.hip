@@ -1211,7 +1211,7 @@ struct SegTable {
     uint32_t out;                 // round 0's exit (SEG_NONE: it broke off)
     uint32_t pos[SEG_MARKS];      // bit offsets from the boundary, ascending; the k-th is where round 0's k-th MCU began
     int32_t sum[SEG_MARKS][3];    // the DC sums when it began
-    uint32_t pad[2];
+    uint32_t decodes, decoded_bits;  // (rph_debug_jpeg_segment_log only) validation decodes begun in the segment, and the bits they read
 };
 static_assert(sizeof(SegTable) == 288, "segment tables are packed");
 // LDS_TABLES as in the walk: the table probe is on the critical path of every symbol (from global memory it is a cache round trip per symbol:
@@ -1221,7 +1221,7 @@ template <int LDS_TABLES, int MODE>
 __global__ void __launch_bounds__(SYNC_BLOCK) jpeg_sync_kernel(const uint8_t *__restrict__ streams, const HImage *__restrict__ imgs, const SegFile *__restrict__ files,
                                                        const uint32_t *__restrict__ seg_file, SegState *__restrict__ segs, SegOut2 *__restrict__ outs, uint32_t n_segs,
                                                        uint32_t seg_bytes, SegTable *__restrict__ tables, int round, const rphj::DeviceLut *__restrict__ g_luts,
-                                                       uint32_t n_luts)
+                                                       uint32_t n_luts, uint32_t count_decodes)
 {
     constexpr int mode = MODE;  // (a kernel per mode: round 0 carries nothing of the validation rounds' comparisons, and the other way round)
     __shared__ __attribute__((aligned(16))) rphj::DeviceLut s_luts[LDS_TABLES > 0 ? LDS_TABLES : 1];
@@ -1251,7 +1251,9 @@ __global__ void __launch_bounds__(SYNC_BLOCK) jpeg_sync_kernel(const uint8_t *__
             outs[u].v[wr] = own;  // unless this round finds another below
             if (e == SEG_NONE) return false;  // the predecessor has nothing to say yet
             st.entry = e;
-            if (e >= hi || e >= end_bits) {  // no MCU begins in this segment (or, in a damaged stream, the predecessor ran past the end of the scan: nothing is decoded from there): pass the position on
+            // no MCU begins in this segment: the entry lies behind it, or less than a byte is left -- the padding behind the last MCU, as at
+            // the exit below; decoded, it and the zeros behind the scan read as MCUs or break off, as the file's tables have it
+            if (e >= hi || e + 8 > end_bits) {  // (or, in a damaged stream, the predecessor ran past the end of the scan: nothing is decoded from there): pass the position on
                 st.from = e;
                 st.count = 0;
                 st.dc[0] = st.dc[1] = st.dc[2] = 0;
@@ -1285,7 +1287,7 @@ __global__ void __launch_bounds__(SYNC_BLOCK) jpeg_sync_kernel(const uint8_t *__
             }
             start = e;
         } else {
-            if (st.entry == SEG_NONE || st.entry >= hi || st.entry >= end_bits) {
+            if (st.entry == SEG_NONE || st.entry >= hi || st.entry + 8 > end_bits) {
                 st.count = 0;
                 st.dc[0] = st.dc[1] = st.dc[2] = 0;
                 st.out_check = st.entry;
@@ -1439,6 +1441,7 @@ __global__ void __launch_bounds__(SYNC_BLOCK) jpeg_sync_kernel(const uint8_t *__
     st.dc[0] = dc0, st.dc[1] = dc1, st.dc[2] = dc2;
     st.out_check = out;
     if (mode != 2) outs[u].v[mode == 0 ? 0 : wr] = out;
+    if (mode == 1 && count_decodes) tab->decodes += 1, tab->decoded_bits += pos - start;  // (the log's: what the validation rounds cost)
     if (mode == 0) {
         tab->n = n_marks;
         tab->count = count;
@@ -1602,10 +1605,22 @@ void rph_jpeg_debug_segment_stats(hipStream_t stream, const void *d_work, uint32
             SEG_MARKS - 1, full, SEG_MARKS);
 }
 
+int rph_jpeg_debug_copy_segments(hipStream_t stream, const void *d_work, uint32_t n_segs, int rounds, uint32_t *final_out, uint32_t *round0_n, uint32_t *round0_out,
+                                 uint32_t *decodes, uint32_t *decoded_bits)
+{
+    std::vector<SegTable> t(n_segs);
+    std::vector<SegOut2> o(n_segs);
+    RPH_HIP_CHECK(hipStreamSynchronize(stream));
+    RPH_HIP_CHECK(hipMemcpy(t.data(), d_work, (size_t)n_segs * sizeof(SegTable), hipMemcpyDeviceToHost));
+    RPH_HIP_CHECK(hipMemcpy(o.data(), reinterpret_cast<const SegTable *>(d_work) + n_segs, (size_t)n_segs * sizeof(SegOut2), hipMemcpyDeviceToHost));
+    for (uint32_t u = 0; u < n_segs; u++) final_out[u] = o[u].v[rounds & 1], round0_n[u] = t[u].n, round0_out[u] = t[u].out, decodes[u] = t[u].decodes, decoded_bits[u] = t[u].decoded_bits;
+    return RPH_OK;
+}
+
 size_t rph_jpeg_segment_work_bytes(uint32_t n_segs) { return (size_t)n_segs * (sizeof(SegTable) + sizeof(SegOut2) + 4) + 64; }
 
 int rph_jpeg_launch_segments(hipStream_t stream, const uint8_t *d_streams, const HImage *d_images, const SegFile *d_files, uint32_t n_files, SegState *d_segs,
-                             uint32_t n_segs, uint32_t seg_bytes, void *d_work, int rounds, const rphj::DeviceLut *d_luts, uint32_t n_luts, HItem *d_items)
+                             uint32_t n_segs, uint32_t seg_bytes, void *d_work, int rounds, const rphj::DeviceLut *d_luts, uint32_t n_luts, HItem *d_items, bool count_decodes)
 {
     if (n_files == 0 || n_segs == 0) return RPH_OK;
     // d_work: n_segs records of round 0 (SegTable), then n_segs double-buffered `out` positions, then the segment -> file map
@@ -1619,7 +1634,8 @@ int rph_jpeg_launch_segments(hipStream_t stream, const uint8_t *d_streams, const
     const dim3 grid((n_segs + SYNC_BLOCK - 1) / SYNC_BLOCK);
     auto sync = [&](int mode, int round) {
         auto launch = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, grid, dim3(SYNC_BLOCK), 0, stream, d_streams, d_images, d_files, d_seg_file, d_segs, d_outs, n_segs, seg_bytes, d_tables, round, d_luts, n_luts);
+            hipLaunchKernelGGL(kernel, grid, dim3(SYNC_BLOCK), 0, stream, d_streams, d_images, d_files, d_seg_file, d_segs, d_outs, n_segs, seg_bytes, d_tables, round, d_luts, n_luts,
+                               count_decodes ? 1u : 0u);
         };
         if (n_luts <= (uint32_t)HUFF_LDS_TABLES)
             mode == 0 ? launch(jpeg_sync_kernel<HUFF_LDS_TABLES, 0>) : (mode == 1 ? launch(jpeg_sync_kernel<HUFF_LDS_TABLES, 1>) : launch(jpeg_sync_kernel<HUFF_LDS_TABLES, 2>));

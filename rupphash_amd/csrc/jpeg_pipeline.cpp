@@ -998,6 +998,38 @@ int write_meta(JpegPipe &P, Jobs &jobs, const std::vector<uint32_t> &idx, const 
     return RPH_OK;
 }
 
+constexpr int SEG_ROUNDS = 8;  // validation rounds of the segment synchroniser
+
+// ---- rph_debug_jpeg_segment_log: behind the chunk's rph_jpeg_launch_segments, what it decided -- the segments' states, the `out` the
+// prefix kernel read, round 0's n and out, what the validation rounds decoded, and the items written for the segmented files -- appended to the context's log (rph_internal.h)
+int log_segments(rph_ctx *ctx, Slot &S, const Chunk &C, const std::vector<uint32_t> &idx, const SeqWork &W, const ChunkMeta &M)
+{
+    const uint32_t n = W.n_segs, first_item = W.seg_files[0].first_item;  // (the segments' items lie together behind the host's)
+    std::vector<uint32_t> final_out(n), r0_n(n), r0_out(n), decodes(n), decoded_bits(n);
+    std::vector<SegState> st(n);
+    std::vector<HItem> items(n);
+    RPH_TRY(rph_jpeg_debug_copy_segments(S.stream, S.segwork.data() + seg_states_bytes(n), n, SEG_ROUNDS, final_out.data(), r0_n.data(), r0_out.data(),
+                                         decodes.data(), decoded_bits.data()));
+    RPH_HIP_CHECK(hipMemcpy(st.data(), S.segwork.data(), (size_t)n * sizeof(SegState), hipMemcpyDeviceToHost));
+    RPH_HIP_CHECK(hipMemcpy(items.data(), M.items + first_item, (size_t)n * sizeof(HItem), hipMemcpyDeviceToHost));
+    std::vector<uint32_t> &lf = ctx->jpeg_seg_log_files, &ls = ctx->jpeg_seg_log_segs;
+    for (const SegFile &F : W.seg_files) {
+        const HItem *it = items.data() + (F.first_item - first_item);
+        const uint32_t rec[RPH_SEG_LOG_FILE_WORDS] = {idx[C.first + F.image], F.n_segs, F.total_mcus, F.scan_bits, it[0].scan == HITEM_ALL_SCANS ? 0u : 1u,
+                                                      (uint32_t)(ls.size() / RPH_SEG_LOG_SEG_WORDS), F.first_seg, M.n_luts};
+        lf.insert(lf.end(), rec, rec + RPH_SEG_LOG_FILE_WORDS);
+        for (uint32_t t = 0; t < F.n_segs; t++) {
+            const SegState &x = st[F.first_seg + t];
+            const uint32_t u = F.first_seg + t;
+            const uint32_t seg[RPH_SEG_LOG_SEG_WORDS] = {x.entry, final_out[u], x.count, (uint32_t)x.dc[0], (uint32_t)x.dc[1], (uint32_t)x.dc[2], x.from, x.out_check, r0_n[u],
+                                                         r0_out[u], it[t].mcu_first, it[t].mcu_count, it[t].stream_off, it[t].bit_skip, (uint32_t)it[t].dc[0],
+                                                         (uint32_t)it[t].dc[1], (uint32_t)it[t].dc[2], decodes[u], decoded_bits[u]};
+            ls.insert(ls.end(), seg, seg + RPH_SEG_LOG_SEG_WORDS);
+        }
+    }
+    return RPH_OK;
+}
+
 // ---- launch: streams and descriptors up, segments, zeroed coefficients, the walks, then reconstruction + hashing sub-batch by sub-batch.
 // RPH_JPEG_TRACE=1: synchronise after every phase and print where the time goes (stderr); t_host: start, prepared, descriptors written.
 int launch_chunk(rph_ctx *ctx, JpegPipe &P, const Chunk &C, int16_t *d_coef, Jobs &jobs, const std::vector<uint32_t> &idx, int flavour, const Outputs &out,
@@ -1015,9 +1047,11 @@ int launch_chunk(rph_ctx *ctx, JpegPipe &P, const Chunk &C, int16_t *d_coef, Job
     RPH_HIP_CHECK(hipMemcpyAsync(S.stream_bytes.d.data(), S.stream_bytes.h.data(), C.file_bytes + 64, hipMemcpyHostToDevice, s));
     RPH_HIP_CHECK(hipMemcpyAsync(S.meta.d.data(), S.meta.h.data(), M.upload_bytes, hipMemcpyHostToDevice, s));
     lap(t_up);
-    if (W.n_segs)  // streams without markers: their segments find their entries and become walk items
+    if (W.n_segs) {  // streams without markers: their segments find their entries and become walk items
         RPH_TRY(rph_jpeg_launch_segments(s, S.stream_bytes.d.data(), M.himgs, M.seg_files, (uint32_t)W.seg_files.size(), S.segwork.as<SegState>(), W.n_segs,
-                                         ctx->jpeg_seg_bytes, S.segwork.data() + seg_states_bytes(W.n_segs), 8, M.luts, M.n_luts, M.items));
+                                         ctx->jpeg_seg_bytes, S.segwork.data() + seg_states_bytes(W.n_segs), SEG_ROUNDS, M.luts, M.n_luts, M.items, ctx->jpeg_seg_log_on));
+        if (ctx->jpeg_seg_log_on) RPH_TRY(log_segments(ctx, S, C, idx, W, M));
+    }
     lap(t_seg);
     // The coefficients start from zero -- unless the walk writes whole blocks and covers every block of the chunk: sequential files of
     // one scan (interleaved, or one component), no progressive file.  (A file whose walk breaks off is reported as damaged; what its
@@ -1120,6 +1154,7 @@ int run_batch(rph_ctx *ctx, const uint8_t *const *data, const size_t *len, uint3
     threads = std::min(threads, 256u);
 
     g_trace_t0 = now_ms();
+    ctx->jpeg_seg_log_files.clear(), ctx->jpeg_seg_log_segs.clear();  // (rph_debug_jpeg_segment_log: the log holds one call)
     RPH_JPEG_STAMP("call: %u files", n);
     Jobs &jobs = prepared ? *prepared : P.jobs_cache;
     if (!prepared && jobs.size() < n) jobs.resize(n);  // (grown by this thread: first-touching the storage from the parsing threads is 5x slower, page faults under contention)
@@ -1265,6 +1300,26 @@ int rph_jpeg_set_segments(rph_ctx *ctx, uint32_t min_stream_bytes, uint32_t segm
     std::lock_guard<std::mutex> lock(ctx->jpeg_mu);
     ctx->jpeg_seg_min_bytes = min_stream_bytes;
     ctx->jpeg_seg_bytes = segment_bytes;
+    return RPH_OK;
+}
+
+int rph_debug_jpeg_segment_log(rph_ctx *ctx, int on)
+{
+    if (!ctx) return RPH_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lock(ctx->jpeg_mu);
+    ctx->jpeg_seg_log_on = on != 0;
+    return RPH_OK;
+}
+
+int rph_debug_jpeg_segments(rph_ctx *ctx, uint32_t *files_out, uint32_t file_cap, uint32_t *n_files_out, uint32_t *segs_out, uint32_t seg_cap, uint32_t *n_segs_out)
+{
+    if (!ctx) return RPH_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lock(ctx->jpeg_mu);
+    const std::vector<uint32_t> &lf = ctx->jpeg_seg_log_files, &ls = ctx->jpeg_seg_log_segs;
+    if (files_out) memcpy(files_out, lf.data(), std::min<size_t>((size_t)file_cap * RPH_SEG_LOG_FILE_WORDS, lf.size()) * 4);
+    if (segs_out) memcpy(segs_out, ls.data(), std::min<size_t>((size_t)seg_cap * RPH_SEG_LOG_SEG_WORDS, ls.size()) * 4);
+    if (n_files_out) *n_files_out = (uint32_t)(lf.size() / RPH_SEG_LOG_FILE_WORDS);
+    if (n_segs_out) *n_segs_out = (uint32_t)(ls.size() / RPH_SEG_LOG_SEG_WORDS);
     return RPH_OK;
 }
 

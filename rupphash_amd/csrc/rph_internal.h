@@ -98,6 +98,10 @@ struct rph_ctx {
     // device walk of streams without restart markers: from jpeg_seg_min_bytes of entropy data a stream is cut into segments of
     // jpeg_seg_bytes that synchronise on the device and are walked side by side (0 = never)
     uint32_t jpeg_seg_min_bytes = 8192, jpeg_seg_bytes = 1024;
+    // rph_debug_jpeg_segment_log: what the segment synchroniser decided in every chunk of the last batch call, as flat records of
+    // RPH_SEG_LOG_FILE_WORDS / RPH_SEG_LOG_SEG_WORDS words (under jpeg_mu; off: one branch per chunk)
+    bool jpeg_seg_log_on = false;
+    std::vector<uint32_t> jpeg_seg_log_files, jpeg_seg_log_segs;
     // rph_jpeg_pdq_hash_one: callers that arrive while a batch is on its way wait here and leave together as the next batch
     std::mutex jpeg_qmu;
     std::condition_variable jpeg_qcv;
@@ -196,6 +200,18 @@ extern "C" void rph_debug_hamming_cross_layout(uint64_t n_a, uint32_t n_variants
 // calls, the files of each (the first `cap` of them into sizes_out) and, for WebP, the number of parse windows (exported for the tests,
 // not in the header; any of the three outputs may be null)
 extern "C" int rph_debug_file_chunks(rph_ctx *ctx, int format, uint32_t *sizes_out, uint32_t cap, uint32_t *n_chunks_out, uint32_t *n_windows_out);
+// The JPEG segment synchroniser's decisions (jpeg_device.h), recorded chunk by chunk while the switch is on (off by default; every output
+// is the same either way) and cleared at the start of every JPEG batch call.  Per segmented file RPH_SEG_LOG_FILE_WORDS words: its index
+// in the caller's list, n_segs, total_mcus, scan_bits, verified (0: its first item is a whole-file walk), the index of its first segment
+// record, its first lane in the chunk's launch, the chunk's number of Huffman tables.  Per segment RPH_SEG_LOG_SEG_WORDS words: SegState's
+// entry, the final `out`, count, dc[3], from, out_check; round 0's n and out; its item's mcu_first, mcu_count, stream_off, bit_skip, dc[3];
+// the decodes the validation rounds began in the segment and the bits they read (counted only while the switch is on).
+// The reader copies the first file_cap / seg_cap records and reports how many there are (exported for the tests, not in the header; any
+// output may be null).
+constexpr uint32_t RPH_SEG_LOG_FILE_WORDS = 8, RPH_SEG_LOG_SEG_WORDS = 19;
+extern "C" int rph_debug_jpeg_segment_log(rph_ctx *ctx, int on);
+extern "C" int rph_debug_jpeg_segments(rph_ctx *ctx, uint32_t *files_out, uint32_t file_cap, uint32_t *n_files_out, uint32_t *segs_out, uint32_t seg_cap,
+                                       uint32_t *n_segs_out);
 // components.hip: one edge list of a union-find over a label array, e.i + i_base and e.j + j_base being the files an edge unites
 struct rph_union_edges {
     const rph_edge *edges = nullptr;

@@ -305,6 +305,28 @@ class Engine:
         """device walk of streams without restart markers: cut into segments from min_stream_bytes of entropy data (segment_bytes = 0: never)"""
         check(self.L.rph_jpeg_set_segments(self.ctx, int(min_stream_bytes), int(segment_bytes)), "rph_jpeg_set_segments")
 
+    def debug_jpeg_segment_log(self, on):
+        """Record what the segment synchroniser decides in every chunk of a JPEG batch call (off by default; the outputs are the same
+        either way).  Debug / tests only."""
+        check(self.L.rph_debug_jpeg_segment_log(self.ctx, int(bool(on))), "rph_debug_jpeg_segment_log")
+
+    SEG_LOG_FILE_FIELDS = ("index", "n_segs", "total_mcus", "scan_bits", "verified", "first_record", "first_seg", "n_luts")
+    SEG_LOG_SEG_FIELDS = ("entry", "out", "count", "dc0", "dc1", "dc2", "from", "out_check", "round0_n", "round0_out", "mcu_first", "mcu_count",
+                          "stream_off", "bit_skip", "item_dc0", "item_dc1", "item_dc2", "decodes", "decoded_bits")
+
+    def debug_jpeg_segments(self):
+        """The log of the last JPEG batch call made with debug_jpeg_segment_log(True): (files, segments), two dicts of arrays with one
+        entry per segmented file (SEG_LOG_FILE_FIELDS, uint32; a file's segments are records first_record .. first_record + n_segs - 1)
+        and per segment (SEG_LOG_SEG_FIELDS; positions uint32 with 0xFFFFFFFF = none, the DC sums int32).  Debug / tests only."""
+        nf, ns = C.c_uint32(), C.c_uint32()
+        check(self.L.rph_debug_jpeg_segments(self.ctx, None, 0, C.byref(nf), None, 0, C.byref(ns)), "rph_debug_jpeg_segments")
+        files = np.zeros((nf.value, len(self.SEG_LOG_FILE_FIELDS)), np.uint32)
+        segs = np.zeros((ns.value, len(self.SEG_LOG_SEG_FIELDS)), np.uint32)
+        check(self.L.rph_debug_jpeg_segments(self.ctx, _ptr(files), nf.value, C.byref(nf), _ptr(segs), ns.value, C.byref(ns)), "rph_debug_jpeg_segments")
+        f = {name: files[:, k].copy() for k, name in enumerate(self.SEG_LOG_FILE_FIELDS)}
+        s = {name: segs[:, k].copy().view(np.int32) if "dc" in name else segs[:, k].copy() for k, name in enumerate(self.SEG_LOG_SEG_FIELDS)}
+        return f, s
+
     def jpeg_release(self):
         """give the JPEG path's cached staging / device buffers back"""
         check(self.L.rph_jpeg_release(self.ctx), "rph_jpeg_release")

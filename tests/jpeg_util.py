@@ -184,7 +184,7 @@ def _real_blocks(w, h, sampling, ci, hmax, vmax):
 
 
 def encode_baseline_coefficients(blocks, qts, w, h, sampling=((1, 2), (1, 1), (1, 1)), restart_interval=0, interleaved=True, sixteen_bit_tables=False, gray=False,
-                                 tables="used", fault=None):
+                                 tables="used", fault=None, mcu_positions=False):
     """The entropy half of a baseline (SOF0) encoder.  blocks: per component an integer array (blocks high, blocks wide, 8, 8) or (.., 64) over
     the MCU-padded grid, natural order, quantised; qts: the quantisation tables (64 entries, natural order) of luma and chroma.
     AC values are int16 except -32768 (categories 1..15).  DC values are what the block is AIMED at: each is coded as the difference from the
@@ -193,7 +193,9 @@ def encode_baseline_coefficients(blocks, qts, w, h, sampling=((1, 2), (1, 1), (1
     tables: "used" = one table per class and slot, fixed-length codes for the symbols that occur (DC categories to 15 and AC sizes to 15 become
     codable); "annex_k" = T.81 K.3's tables.  fault: as encode_baseline (Annex K tables only).
     Returns (bytes, expected): expected = the (total blocks, 64) int16 coefficients a decoder holds afterwards, component-major, raster over the
-    padded grid, natural order -- plain int16 arithmetic on `blocks` (blocks a scan of one component does not cover stay 0)."""
+    padded grid, natural order -- plain int16 arithmetic on `blocks` (blocks a scan of one component does not cover stay 0).
+    mcu_positions: also return, per scan, the bit position (from the scan's first entropy bit, byte stuffing not counted) at which each of
+    its MCUs was written, and behind them the position behind the last one -- (bytes, expected, [positions of scan 0, ..])."""
     if gray:
         sampling = ((1, 1),)
     ncomp = len(sampling)
@@ -204,7 +206,7 @@ def encode_baseline_coefficients(blocks, qts, w, h, sampling=((1, 2), (1, 1), (1
     dc_l = DC_L_WIDE if fault and fault[0] in ("dc_cat", "dc_cat_16") else DC_L
     pred = [0] * ncomp
     luma_blocks = [0]
-    scans = []  # (component indices, tokens): ("s", "dc" | "ac", slot, symbol) | ("b", value, nbits) | ("rst", n)
+    scans = []  # (component indices, tokens): ("s", "dc" | "ac", slot, symbol) | ("b", value, nbits) | ("rst", n) | ("mcu",): an MCU begins
 
     def put_fault(toks, kind, arg):
         if kind == "dc_cat":  # the block's DC: the largest difference of the category, the prediction follows it
@@ -275,6 +277,7 @@ def encode_baseline_coefficients(blocks, qts, w, h, sampling=((1, 2), (1, 1), (1
                 toks.append(("rst", rst & 7))
                 rst += 1
                 pred = [0] * ncomp
+            toks.append(("mcu",))
             for ci, by, bx in unit:
                 put_block(toks, ci, by, bx)
         scans.append((cis, toks))
@@ -307,24 +310,34 @@ def encode_baseline_coefficients(blocks, qts, w, h, sampling=((1, 2), (1, 1), (1
     if restart_interval:
         seg(0xDD, restart_interval.to_bytes(2, "big"))
     codes = {key: _codes(*d) for key, d in defs.items()}
+    positions = []
     for cis, toks in scans:
         sos = bytes([len(cis)])
         for ci in cis:
             sos += bytes([ci + 1, 0x00 if ci == 0 else 0x11])
         seg(0xDA, sos + bytes([0, 63, 0]))
         bits = _Bits()
+        written, starts = 0, []  # bits put so far (padding before an RSTn included, markers and stuffing not)
         for k in toks:
             if k[0] == "s":
                 bits.put(*codes[k[1], k[2]][k[3]])
+                written += codes[k[1], k[2]][k[3]][1]
             elif k[0] == "b":
                 bits.put(k[1], k[2])
+                written += k[2]
+            elif k[0] == "mcu":
+                starts.append(written)
             else:
                 bits.flush()
+                written += -written % 8
                 bits.out.extend(bytes([0xFF, 0xD0 + k[1]]))
+        starts.append(written)
+        positions.append(starts)
         bits.flush()
         out.extend(bits.out)
     out.extend(b"\xff\xd9")
-    return bytes(out), np.concatenate([e.reshape(-1, 64) for e in expected])
+    result = bytes(out), np.concatenate([e.reshape(-1, 64) for e in expected])
+    return result + (positions,) if mcu_positions else result
 
 
 def encode_baseline(rgb, sampling=((1, 2), (1, 1), (1, 1)), quality_scale=1.0, restart_interval=0, gray=False, sixteen_bit_tables=False, interleaved=True,
