@@ -245,6 +245,7 @@ DEBUG_SIGNATURES = {
     "rph_debug_group_max_dist_events": (C.c_int, [_vp, _vp, _vp]),
     "rph_debug_nearest_layout": (None, [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32)]),
     "rph_debug_nearest_set_segment": (None, [C.c_uint32]),
+    "rph_debug_nearest_set_workspace": (None, [C.c_uint64]),
     "rph_debug_file_extension": (C.c_void_p, [C.c_char_p, C.POINTER(C.c_size_t)]),
     "rph_debug_raw_ext": (C.c_char_p, [C.c_uint32]),
     "rph_debug_files_lanes": (None, [C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

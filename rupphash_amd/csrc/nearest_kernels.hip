@@ -34,11 +34,13 @@ constexpr uint32_t EMPTY = 0xFFFFFFFFu;           // a list slot without a file 
 constexpr uint64_t EMPTY64 = ~0ull;
 constexpr uint32_t REL_BITS = 20;                 // a stage-1 key: distance << 23 | file relative to its segment << 3 | variant
 constexpr uint64_t MAX_SEG_FILES = 1ull << REL_BITS;
-constexpr uint64_t WORK_BYTES = (uint64_t)256 << 20;  // the partial lists never take more
+constexpr uint64_t WORK_BYTES = (uint64_t)256 << 20;  // the partial lists never take more (the default of g_work_bytes)
+constexpr uint64_t MIN_WORK_BYTES = QT * RPH_NEAREST_MAX_K * 4;  // one tile of the longest lists in one segment
 constexpr uint64_t TARGET_ITEMS = 2048;           // (segment, tile) items a call is cut into at least when the library allows: 8 workgroups on each of 256 CUs
 constexpr uint64_t MAX_CHUNK_QUERIES = 1u << 20;
 
 std::atomic<uint32_t> g_forced_segment{0};  // rph_debug_nearest_set_segment
+std::atomic<uint64_t> g_work_bytes{WORK_BYTES};  // rph_debug_nearest_set_workspace
 
 struct NearestLayout {
     uint32_t files_per_block, seg_files, n_segs, chunk_queries;
@@ -54,6 +56,7 @@ NearestLayout nearest_layout(uint64_t n_lib, uint32_t n_variants, uint64_t n_q, 
     const uint64_t fb = n_variants == 8 ? 4 : 32;
     const uint64_t n_tiles = std::max<uint64_t>(1, ceil_div(n_q, QT));
     const uint32_t forced = g_forced_segment.load();
+    const uint64_t work_bytes = g_work_bytes.load();
     uint64_t seg;
     if (forced) {
         seg = ceil_div(forced, fb) * fb;
@@ -61,14 +64,14 @@ NearestLayout nearest_layout(uint64_t n_lib, uint32_t n_variants, uint64_t n_q, 
         const uint64_t want = std::max<uint64_t>(1, ceil_div(TARGET_ITEMS, n_tiles));
         seg = std::max(ceil_div(ceil_div(std::max<uint64_t>(n_lib, 1), want), fb) * fb, 16 * fb);
     }
-    const uint64_t most_segs = WORK_BYTES / ((uint64_t)QT * k * 4);
+    const uint64_t most_segs = work_bytes / ((uint64_t)QT * k * 4);
     seg = std::max(seg, ceil_div(ceil_div(n_lib, most_segs), fb) * fb);
     seg = std::min(seg, MAX_SEG_FILES);
     L.files_per_block = (uint32_t)fb;
     L.seg_files = (uint32_t)seg;
     L.n_segs = (uint32_t)ceil_div(n_lib, seg);
     uint64_t chunk = MAX_CHUNK_QUERIES;
-    if (L.n_segs) chunk = std::min(chunk, WORK_BYTES / ((uint64_t)L.n_segs * k * 4) / QT * QT);
+    if (L.n_segs) chunk = std::min(chunk, work_bytes / ((uint64_t)L.n_segs * k * 4) / QT * QT);
     L.chunk_queries = (uint32_t)std::max<uint64_t>(chunk, QT);
     return L;
 }
@@ -302,7 +305,7 @@ int rph_nearest_run(rph_ctx *ctx, const rph_nearest &q, hipStream_t s)
     if (q.n_q == 0) return RPH_OK;
     const NearestLayout L = nearest_layout(q.n_lib, q.n_variants, q.n_q, q.k);
     const uint64_t chunk = std::min<uint64_t>(L.chunk_queries, q.n_q);
-    const size_t work = (size_t)L.n_segs * chunk * q.k * 4;  // <= WORK_BYTES by the layout
+    const size_t work = (size_t)L.n_segs * chunk * q.k * 4;  // <= the workspace limit by the layout
     std::lock_guard<std::mutex> lock(ctx->mu);
     ScratchUse use{ctx->sweep_scratch, s};
     RPH_TRY(use.acquire(std::max<size_t>(work, 256), std::max<size_t>(work, 4096)));
@@ -400,9 +403,11 @@ int rph_hamming_nearest(rph_ctx *ctx, const uint8_t *rows, uint32_t n_variants, 
 void rph_debug_nearest_layout(uint64_t n_lib, uint32_t n_variants, uint64_t n_q, uint32_t k, uint32_t *out)
 {
     const NearestLayout L = nearest_layout(n_lib, n_variants == 8 ? 8 : 1, n_q, k < 1 ? 1 : k > RPH_NEAREST_MAX_K ? RPH_NEAREST_MAX_K : k);
-    out[0] = L.files_per_block, out[1] = L.seg_files, out[2] = QT, out[3] = L.n_segs;
+    out[0] = L.files_per_block, out[1] = L.seg_files, out[2] = QT, out[3] = L.n_segs, out[4] = L.chunk_queries;
 }
 
 void rph_debug_nearest_set_segment(uint32_t files) { g_forced_segment.store(files); }
+
+void rph_debug_nearest_set_workspace(uint64_t bytes) { g_work_bytes.store(bytes == 0 ? WORK_BYTES : std::max(bytes, MIN_WORK_BYTES)); }
 
 }  // extern "C"

@@ -304,12 +304,15 @@ struct rph_nearest {
 int rph_nearest_check(const char *who, const void *rows, uint32_t n_variants, uint64_t n_lib, const void *hashes_q, uint64_t n_q, uint32_t k, const void *out);
 // takes ctx->mu and the sweep scratch for the partial lists; asynchronous on `stream`
 int rph_nearest_run(rph_ctx *ctx, const rph_nearest &q, hipStream_t stream);
-// how a call is cut (exported for the tests, not in the header): out[0..3] = files per MFMA block, files per segment, queries per
-// tile, number of segments
+// how a call is cut (exported for the tests, not in the header): out[0..4] = files per MFMA block, files per segment, queries per
+// tile, number of segments, queries per chunk
 extern "C" void rph_debug_nearest_layout(uint64_t n_lib, uint32_t n_variants, uint64_t n_q, uint32_t k, uint32_t *out);
 // forces the segment length of the calls that follow, in files (rounded up to whole MFMA blocks); 0 restores the default.  It lets a
 // library of a few thousand files reach many segments (tests only)
 extern "C" void rph_debug_nearest_set_segment(uint32_t files);
+// bounds the partial lists of the calls that follow, in bytes; 0 restores 256 MiB, anything below one tile of 64-key lists in one
+// segment (8192) is raised to that.  It lets a few dozen queries reach several chunks (tests only)
+extern "C" void rph_debug_nearest_set_workspace(uint64_t bytes);
 int rph_launch_mih_build256(rph_ctx *ctx, const uint8_t *d_hashes, uint64_t n, uint32_t *d_offsets, uint32_t *d_values,
                             hipStream_t stream);
 int rph_launch_mih_build64(rph_ctx *ctx, const uint64_t *d_hashes, uint64_t n, uint32_t *d_offsets, uint32_t *d_values,

@@ -1007,14 +1007,26 @@ class Engine:
     @staticmethod
     def nearest_layout(n_lib, n_variants, n_q, k):
         """How a nearest call is cut (tests): files per MFMA block, files per segment, queries per tile, number of segments."""
-        out = (C.c_uint32 * 4)()
+        out = (C.c_uint32 * 5)()
         _lib.load().rph_debug_nearest_layout(n_lib, n_variants, n_q, k, out)
-        return tuple(out)
+        return tuple(out)[:4]
+
+    @staticmethod
+    def nearest_chunk_queries(n_lib, n_variants, n_q, k):
+        """How many queries a nearest call takes at a time (tests): the fifth word of rph_debug_nearest_layout."""
+        out = (C.c_uint32 * 5)()
+        _lib.load().rph_debug_nearest_layout(n_lib, n_variants, n_q, k, out)
+        return out[4]
 
     @staticmethod
     def nearest_set_segment(files):
         """Forces the segment length of the nearest calls that follow (tests); 0 restores the default."""
         _lib.load().rph_debug_nearest_set_segment(files)
+
+    @staticmethod
+    def nearest_set_workspace(nbytes):
+        """Bounds the partial lists of the nearest calls that follow, in bytes (tests); 0 restores 256 MiB, less than 8192 is 8192."""
+        _lib.load().rph_debug_nearest_set_workspace(nbytes)
 
     def library(self, similarity):
         """A grouped library that stays on this engine's device (rph_library): see Library."""

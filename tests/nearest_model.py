@@ -1,5 +1,5 @@
 """The rule of rph_hamming_nearest (include/rupphash.h) in numpy, and builders of libraries whose answers are known in closed form.
-Shared by test_nearest_cpu.py and test_nearest_gpu.py; nothing here touches the library under test."""
+Shared by test_nearest_cpu.py, test_nearest_gpu.py and test_nearest_grid_gpu.py; nothing here touches the library under test."""
 import numpy as np
 
 from rupphash_amd import EDGE_DTYPE
@@ -26,7 +26,36 @@ def distances(rows, hashes_q):
     return d.astype(np.int32).reshape(n, nv, len(q))
 
 
-def file_distances(rows, hashes_q, has_features=None):
+_BYTE_ONES = np.unpackbits(np.arange(256, dtype=np.uint8)[:, None], axis=1).sum(axis=1).astype(np.uint8)
+POPCOUNT_TEMP_WORDS = 1 << 23  # uint64 words of XOR that distances_popcount holds at a time (64 MiB)
+
+
+def _ones64(x):
+    """set bits of every uint64, as uint8"""
+    if hasattr(np, "bitwise_count"):
+        return np.bitwise_count(x)
+    return _BYTE_ONES[x.view(np.uint8).reshape(x.shape + (8,))].sum(axis=-1, dtype=np.uint8)
+
+
+def distances_popcount(rows, hashes_q):
+    """distances() by XOR on uint64 views and a population count, in blocks of rows and queries (one query at a time against a large
+    library) so that the temporaries stay at POPCOUNT_TEMP_WORDS whatever the sizes: what the large libraries and the long query lists
+    are checked with"""
+    rows = as_rows(rows)
+    n, nv, _ = rows.shape
+    r = rows.reshape(n * nv, 32).view(np.uint64)                                     # [n nv, 4]
+    q = np.ascontiguousarray(hashes_q, np.uint8).reshape(-1, 32).view(np.uint64)     # [nq, 4]
+    d = np.empty((n * nv, len(q)), np.int32)
+    r_step = max(1, POPCOUNT_TEMP_WORDS // 4)
+    q_step = max(1, POPCOUNT_TEMP_WORDS // (4 * max(min(n * nv, r_step), 1)))
+    for r0 in range(0, n * nv, r_step):
+        for q0 in range(0, len(q), q_step):
+            x = r[r0:r0 + r_step, None, :] ^ q[None, q0:q0 + q_step, :]
+            d[r0:r0 + r_step, q0:q0 + q_step] = _ones64(x).sum(axis=2, dtype=np.int32)
+    return d.reshape(n, nv, len(q))
+
+
+def file_distances(rows, hashes_q, has_features=None, distances=distances):
     """(dist[i, q], variant[i, q]): minimum over the rows a file owns and the smallest row attaining it"""
     d = distances(rows, hashes_q)
     if has_features is not None and d.shape[1] > 1:
@@ -35,18 +64,51 @@ def file_distances(rows, hashes_q, has_features=None):
     return d.min(axis=1), d.argmin(axis=1)  # argmin: the first (smallest) index of the minimum
 
 
-def nearest(rows, hashes_q, k, max_dist=256, has_features=None, skip=None):
+def _empty_result(nq, k):
+    edges = np.zeros((nq, k), EDGE_DTYPE)
+    edges["i"], edges["d"] = NO_FILE, EMPTY_D
+    edges["j"] = np.arange(nq, dtype=np.uint32)[:, None]
+    return edges, np.zeros(nq, np.uint32)
+
+
+def nearest_vectorised(rows, hashes_q, k, max_dist=256, has_features=None, skip=None, distances=distances_popcount):
+    """nearest() without a Python loop over the queries, for thousands to a million of them: one sort along the file axis of the key
+    (dist, file), files that the cutoff or skip excludes pushed behind every real key"""
+    rows = as_rows(rows)
+    hq = np.ascontiguousarray(hashes_q, np.uint8).reshape(-1, 32)
+    n, nq = len(rows), len(hq)
+    edges, counts = _empty_result(nq, k)
+    if n == 0 or nq == 0:
+        return edges, counts
+    dist, variant = file_distances(rows, hq, has_features, distances)
+    out = dist > max_dist
+    if skip is not None:
+        sk = np.array([NO_FILE if x is None else int(x) for x in skip], np.int64)
+        has = np.flatnonzero(sk < n)
+        out[sk[has], has] = True
+    key = dist.astype(np.int64) << 32 | np.arange(n, dtype=np.int64)[:, None]
+    key[out] = np.iinfo(np.int64).max
+    m = min(k, n)
+    key = np.sort(key, axis=0)[:m].T                      # [nq, m]
+    filled = key != np.iinfo(np.int64).max
+    got = np.where(filled, key & 0xFFFFFFFF, 0)
+    at = np.arange(nq)[:, None]
+    edges["i"][:, :m] = np.where(filled, got, NO_FILE)
+    edges["d"][:, :m] = np.where(filled, key >> 32, EMPTY_D)
+    edges["flags"][:, :m] = np.where(filled, variant[got, at] << VARIANT_SHIFT, 0)
+    counts[:] = filled.sum(axis=1)
+    return edges, counts
+
+
+def nearest(rows, hashes_q, k, max_dist=256, has_features=None, skip=None, distances=distances):
     """(edges[n_q, k], counts[n_q]) as every form of the call must return them"""
     rows = as_rows(rows)
     hq = np.ascontiguousarray(hashes_q, np.uint8).reshape(-1, 32)
     n, nq = len(rows), len(hq)
-    edges = np.zeros((nq, k), EDGE_DTYPE)
-    edges["i"], edges["d"] = NO_FILE, EMPTY_D
-    edges["j"] = np.arange(nq, dtype=np.uint32)[:, None]
-    counts = np.zeros(nq, np.uint32)
+    edges, counts = _empty_result(nq, k)
     if n == 0 or nq == 0:
         return edges, counts
-    dist, variant = file_distances(rows, hq, has_features)
+    dist, variant = file_distances(rows, hq, has_features, distances)
     files = np.arange(n)
     for q in range(nq):
         ok = dist[:, q] <= max_dist

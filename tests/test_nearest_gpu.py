@@ -52,8 +52,9 @@ def check(eng, rows, hq, k, **kw):
     return got
 
 
-def dev_form(eng, rows, hq, k, max_dist=256, has_features=None, skip=None, nv=None, misalign=0):
-    """rph_hamming_nearest_dev on uploaded arrays, outputs prefilled with a sentinel: (status, edges, counts)"""
+def dev_form(eng, rows, hq, k, max_dist=256, has_features=None, skip=None, nv=None, misalign=0, with_counts=True):
+    """rph_hamming_nearest_dev on uploaded arrays, outputs prefilled with a sentinel: (status, edges, counts).  with_counts False: the
+    call gets no counts pointer, and the prefilled buffer, allocated next to the slots all the same, comes back as it is"""
     from rupphash_amd import EDGE_DTYPE, RphError
 
     rows, hq = nm.as_rows(rows), np.ascontiguousarray(hq, np.uint8).reshape(-1, 32)
@@ -77,7 +78,7 @@ def dev_form(eng, rows, hq, k, max_dist=256, has_features=None, skip=None, nv=No
         try:
             eng.hamming_nearest_dev((d_rows or 0) + misalign if misalign else d_rows, rows.shape[1] if nv is None else nv, len(rows), up(hq), len(hq), k, d_out,
                                     max_dist=max_dist, d_has_features=up(None if has_features is None else np.asarray(has_features, np.uint8)),
-                                    d_skip=up(None if skip is None else np.asarray(skip, np.uint32)), d_counts=d_counts)
+                                    d_skip=up(None if skip is None else np.asarray(skip, np.uint32)), d_counts=d_counts if with_counts else None)
         except RphError as e:
             status = e.status
         eng.synchronize()
