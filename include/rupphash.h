@@ -535,6 +535,65 @@ int rph_library_nearest(rph_library *lib, const uint8_t *hashes32_q, uint64_t n_
 int rph_library_nearest_files(rph_library *lib, const uint32_t *indices, uint64_t n_q, uint32_t k, uint32_t max_dist, rph_edge *out,
                               uint32_t *counts_out);
 
+/*
+ * Merge tree: the groups at EVERY similarity 0 .. top from one sweep at top.  The grouping of group_files_generic (scanner.rs:1640-1817)
+ * is connected components over the pairs within the limit -- single linkage -- so the groups at the similarities 0 .. top are nested, and
+ * one record per file holds them all.  One rule for every form below.
+ *   Files are 0 .. n-1; the arguments per file are those of rph_group_files_pdq (hashes32, nullable coeffs, has_features, quality).
+ *   For i < j, with the rows file i owns as the reference has them (scanner.rs:1692-1701: its 8 dihedral hashes if it has features, else
+ *   its hash): w(i, j) = min over those rows of hamming256(row, hash[j]).  lvl(i, j) = w(i, j) if neither file is low-confidence; if
+ *   either is, lvl(i, j) = 0 when w == 0 and the pair has no edge otherwise (scanner.rs:1699, 1721).
+ *   For 0 <= s <= top the components at s are the connected components of the pairs with lvl <= s, and label_s[x] is the smallest file
+ *   number of x's component: what rph_group_files_pdq(similarity = s) yields.
+ *   The tree is two arrays of n entries:
+ *     level[x] (uint8)  = the smallest s <= top with label_s[x] != x, or RPH_TREE_NEVER if there is none;
+ *     into[x]  (uint32) = label_{level[x]}[x], or x if level[x] is RPH_TREE_NEVER.
+ *   So into[x] < x whenever level[x] is not RPH_TREE_NEVER; level[into[x]] > level[x], strictly, or RPH_TREE_NEVER, so a chain has at most
+ *   top + 1 links (64 for the PDQ forms); label_s[x] is found by following `into` while level[current] <= s.  The tree is unique: it does
+ *   not depend on the order of the edges, on launch geometry or on which of several equal-weight edges did a merge, and every form
+ *   returns identical bytes.
+ *   edges_at[t], t = 0 .. top (uint64): the number of edges with d == t that the variant sweep at similarity `top` reports, one per
+ *   passing variant as in rph_hamming_variant_pairs.  The sweep at s reports exactly those with d <= s (a low-confidence pair only
+ *   ever d = 0), so the sum of edges_at[0 .. s] is rph_group_files_pdq's comparison count at similarity s (scanner.rs:1778).
+ */
+#define RPH_TREE_NEVER 255u
+/* The core, on any edge list a sweep left on the device (plain, variant, cross with bases, 64-bit): edge e joins e.i + i_base and
+ * e.j + j_base at level e.d.  d_into n x uint32, d_level n bytes, d_edges_at (top + 1) x uint64, d_labels (nullable) n x uint32: the
+ * flattened min-labels at `top`, as rph_union_find_labels_dev leaves them.  An edge that names a file >= n or has d > top:
+ * RPH_ERR_INVALID_ARG with nothing written; the call waits for that check (it synchronises `stream` once) and everything else is
+ * asynchronous on `stream`.  n at most 2^31 - 1; top at most 254, here and in the host form: a level of 255 could not be told from
+ * RPH_TREE_NEVER, so 255 and above are RPH_ERR_INVALID_ARG.  n == 0 without edges: RPH_OK.  Workspace: the context's kept scratch, 8 bytes
+ * per edge and 4 to 8 per file. */
+int rph_merge_tree_dev(rph_ctx *ctx, const void *d_edges, uint64_t n_edges, uint32_t i_base, uint32_t j_base, uint64_t n,
+                       uint32_t top, void *d_into, void *d_level, void *d_edges_at, void *d_labels, void *stream);
+/* The same on the host, no context: for edge lists gathered from several GPUs and for callers' own tests. */
+int rph_merge_tree_from_edges_host(const rph_edge *edges, uint64_t n_edges, uint64_t n, uint32_t top, uint32_t *into,
+                                   uint8_t *level, uint64_t *edges_at);
+/* Host arrays in, host arrays out: upload and variants as rph_group_files_pdq does them, ONE triangular variant sweep at `top` whose
+ * edges stay on the device, then the core.  top > RPH_MAX_SIMILARITY_256: RPH_ERR_INVALID_ARG (scanner.rs:1650-1655). */
+int rph_group_files_pdq_tree(rph_ctx *ctx, const uint8_t *hashes32, const float *coeffs, const uint8_t *has_features,
+                             const int32_t *quality, uint64_t n, uint32_t top, uint32_t *into, uint8_t *level,
+                             uint64_t *edges_at);
+/* The rule without a device: brute force over the host's threads, the rows through rph_pdq_dihedral_one as rph_group_max_dist_host
+ * derives them. */
+int rph_merge_tree_host(const uint8_t *hashes32, const float *coeffs, const uint8_t *has_features, const int32_t *quality,
+                        uint64_t n, uint32_t top, uint32_t *into, uint8_t *level, uint64_t *edges_at);
+/* Of the files a library holds, at `top` whatever the library's own similarity is.  The library is not changed: its labels, size and
+ * comparison count stay as they are. */
+int rph_library_merge_tree(rph_library *lib, uint32_t top, uint32_t *into, uint8_t *level, uint64_t *edges_at);
+/* Cutting a tree, on the host: O(n).  A malformed tree -- into[x] > x, into[x] == x with a level other than RPH_TREE_NEVER (or the
+ * reverse), a level that does not rise along a chain -- is RPH_ERR_INVALID_ARG with nothing written.
+ * labels_out[x] = label_s[x]. */
+int rph_merge_tree_labels(const uint32_t *into, const uint8_t *level, uint64_t n, uint32_t s, uint32_t *labels_out);
+/* The groups at s in the order and with the capacities of rph_union_find_groups: components with > 1 member, members ascending, groups
+ * by first member; members capacity n, offsets capacity n / 2 + 2. */
+int rph_merge_tree_groups(const uint32_t *into, const uint8_t *level, uint64_t n, uint32_t s, uint32_t *members,
+                          uint32_t *offsets, uint32_t *n_groups_out);
+/* For every s in 0 .. top (top + 1 entries each, top at most 254): the number of components with more than one member, and the number of
+ * files in them. */
+int rph_merge_tree_profile(const uint32_t *into, const uint8_t *level, uint64_t n, uint32_t top, uint64_t *n_groups_out,
+                           uint64_t *grouped_files_out);
+
 /* is_low_pdq_quality (scanner.rs:1592-1594); quality < 0 encodes None. */
 int rph_is_low_pdq_quality(int32_t quality);
 

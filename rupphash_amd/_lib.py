@@ -55,6 +55,8 @@ RPH_ROWS_NONE, RPH_ROWS_PER_GROUP, RPH_ROWS_PER_FILE = 0, 1, 2
 # rph_hamming_nearest: a skip entry that skips nothing and the file of an empty slot; the longest list
 RPH_NO_FILE = 0xFFFFFFFF
 RPH_NEAREST_MAX_K = 64
+# merge tree: the level of a file that no similarity up to `top` joins to a smaller one
+RPH_TREE_NEVER = 255
 
 
 class RphEdge(C.Structure):
@@ -151,6 +153,14 @@ SIGNATURES = {
     "rph_hamming_nearest_dev": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint64, _vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
     "rph_library_nearest": (C.c_int, [_vp, _u8p, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _u32p]),
     "rph_library_nearest_files": (C.c_int, [_vp, _u32p, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _u32p]),
+    "rph_merge_tree_dev": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
+    "rph_merge_tree_from_edges_host": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_uint32, _u32p, _u8p, _u64p]),
+    "rph_group_files_pdq_tree": (C.c_int, [_vp, _u8p, _f32p, _u8p, _i32p, C.c_uint64, C.c_uint32, _u32p, _u8p, _u64p]),
+    "rph_merge_tree_host": (C.c_int, [_u8p, _f32p, _u8p, _i32p, C.c_uint64, C.c_uint32, _u32p, _u8p, _u64p]),
+    "rph_library_merge_tree": (C.c_int, [_vp, C.c_uint32, _u32p, _u8p, _u64p]),
+    "rph_merge_tree_labels": (C.c_int, [_u32p, _u8p, C.c_uint64, C.c_uint32, _u32p]),
+    "rph_merge_tree_groups": (C.c_int, [_u32p, _u8p, C.c_uint64, C.c_uint32, _u32p, _u32p, C.POINTER(C.c_uint32)]),
+    "rph_merge_tree_profile": (C.c_int, [_u32p, _u8p, C.c_uint64, C.c_uint32, _u64p, _u64p]),
     "rph_is_low_pdq_quality": (C.c_int, [C.c_int32]),
     "rph_mih_build256": (C.c_int, [_vp, _u8p, C.c_uint64, _u32p, _u32p]),
     "rph_mih_build64": (C.c_int, [_vp, _u64p, C.c_uint64, _u32p, _u32p]),
@@ -243,6 +253,8 @@ DEBUG_SIGNATURES = {
     "rph_debug_library_remove_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "rph_debug_library_remove_stages": (C.c_int, [_vp, C.POINTER(C.c_float)]),
     "rph_debug_group_max_dist_events": (C.c_int, [_vp, _vp, _vp]),
+    "rph_debug_library_merge_tree_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "rph_debug_merge_tree_events": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "rph_debug_nearest_layout": (None, [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32)]),
     "rph_debug_nearest_set_segment": (None, [C.c_uint32]),
     "rph_debug_nearest_set_workspace": (None, [C.c_uint64]),

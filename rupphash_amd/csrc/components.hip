@@ -12,26 +12,9 @@
 #include <hipcub/hipcub.hpp>
 
 #include "rph_internal.h"
+#include "uf_device.h"  // uf_parent, uf_find: shared with merge_tree.hip
 
 namespace {
-#define UF_RELAXED __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-
-__device__ __forceinline__ uint32_t uf_parent(const uint32_t *parent, uint32_t x) { return __hip_atomic_load(parent + x, UF_RELAXED); }
-
-// The root of x, halving the path on the way.  The walk goes to strictly smaller indices, so it ends after at most x steps whatever
-// other lanes do.  fetch_min, not a store: two lanes that shorten the same pointer leave the smaller ancestor, so a pointer never rises.
-__device__ __forceinline__ uint32_t uf_find(uint32_t *parent, uint32_t x)
-{
-    uint32_t p = uf_parent(parent, x);
-    while (p != x) {
-        const uint32_t gp = uf_parent(parent, p);
-        if (gp != p) __hip_atomic_fetch_min(parent + x, gp, UF_RELAXED);
-        x = p;
-        p = gp;
-    }
-    return x;
-}
-
 // One lane per edge.  bad edges and a forest that points upwards are refused by uf_check_kernel before this one runs.
 __global__ void __launch_bounds__(256) uf_union_kernel(const rph_edge *__restrict__ edges, uint64_t n_edges, uint32_t i_base, uint32_t j_base, uint32_t *parent)
 {
@@ -141,6 +124,14 @@ int rph_union_find_labels(rph_ctx *ctx, const rph_union_edges *sets, uint32_t n_
                            d_labels);
         RPH_HIP_CHECK(hipGetLastError());
     }
+    hipLaunchKernelGGL(uf_flatten_kernel, dim3(rph_stride_grid(ctx, n)), dim3(256), 0, s, d_labels, n);
+    RPH_HIP_CHECK(hipGetLastError());
+    return RPH_OK;
+}
+
+// the flatten alone, for a forest another file's kernels built (merge_tree.hip)
+int rph_launch_uf_flatten(rph_ctx *ctx, uint32_t *d_labels, uint64_t n, hipStream_t s)
+{
     hipLaunchKernelGGL(uf_flatten_kernel, dim3(rph_stride_grid(ctx, n)), dim3(256), 0, s, d_labels, n);
     RPH_HIP_CHECK(hipGetLastError());
     return RPH_OK;

@@ -29,6 +29,8 @@ struct rph_library {
     rph_group_lists_dev group_lists;  // rph_library_group_max_dist: the caller's group arrays and its outputs
     DevBuf d_near_idx, d_near_out;    // rph_library_nearest*: the query files' indices; the slots and, behind them, the counts
     uint64_t rm_stats[3] = {0, 0, 0};  // members regrouped, edges found among them, first edge capacity tried
+    DevBuf d_tree;                     // rph_library_merge_tree: into, level and edges_at before they go to the host
+    uint64_t tree_stats[2] = {0, 0};   // edges its sweep found, first edge capacity it tried
     bool rm_staged = false;
     hipEvent_t rm_ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 };
@@ -166,6 +168,48 @@ int append(rph_library *lib, const uint8_t *hashes32, const float *coeffs, const
     lib->n = n + n_new;
     lib->comparisons += found[1];
     if (new_comparisons_out) *new_comparisons_out = found[1];
+    return RPH_OK;
+}
+
+// The resident files' rows against their own hashes (i < j) at `top`, whatever the library's similarity is, into the kept edge buffer
+// with append()'s retry loop; then the merge tree of those edges (merge_tree.hip).  Nothing resident is written.
+int merge_tree(rph_library *lib, uint32_t top, uint32_t *into, uint8_t *level, uint64_t *edges_at)
+{
+    rph_ctx *ctx = lib->ctx;
+    hipStream_t s = ctx->stream;
+    const uint64_t n = lib->n;
+    rph_sweep all = sweep_of(lib, 0, n, 0, n, false);
+    all.threshold = top;
+    if (!lib->d_cnt.data()) RPH_TRY(lib->d_cnt.alloc(8));
+    // (as in remove(): the capacity asked for is what the sweep may fill, not what the buffer happens to hold)
+    uint64_t edge_cap = std::max<uint64_t>(1u << 20, 32 * n);
+    const uint64_t first_cap = edge_cap;
+    unsigned long long found = 0;
+    StreamDrain drain{s};
+    for (int attempt = 0; n > 1; attempt++) {
+        if (attempt == RPH_GROW_GROUP_FILES.attempts) {
+            rph_set_error("rph_library_merge_tree: edge list kept growing (%llu)", found);
+            return RPH_ERR_CAPACITY;
+        }
+        RPH_TRY(lib->d_edges.reserve(edge_cap * sizeof(rph_edge), s));
+        RPH_HIP_CHECK(hipMemsetAsync(lib->d_cnt.data(), 0, 8, s));
+        all.edges = lib->d_edges.as<rph_edge>(), all.cap = edge_cap, all.count = lib->d_cnt.as<unsigned long long>();
+        RPH_TRY(rph_launch_hamming_sweep(ctx, all, s, ctx->hamming_kernel));
+        RPH_HIP_CHECK(hipMemcpyAsync(&found, lib->d_cnt.data(), 8, hipMemcpyDeviceToHost, s));
+        RPH_HIP_CHECK(hipStreamSynchronize(s));
+        if (found <= edge_cap) break;
+        edge_cap = RPH_GROW_GROUP_FILES.next_cap(found);
+    }
+    lib->tree_stats[0] = found, lib->tree_stats[1] = first_cap;
+    Layout L;
+    const size_t o_into = L.add(n * 4, 256), o_level = L.add(n, 256), o_at = L.add((size_t)(top + 1) * 8, 256);
+    RPH_TRY(lib->d_tree.reserve(L.end(), s));
+    uint8_t *t = lib->d_tree.data();
+    RPH_TRY(rph_merge_tree_run(ctx, lib->d_edges.as<rph_edge>(), found, 0, 0, n, top, (uint32_t *)(t + o_into), t + o_level, (uint64_t *)(t + o_at), nullptr, s));
+    RPH_HIP_CHECK(hipMemcpyAsync(into, t + o_into, n * 4, hipMemcpyDeviceToHost, s));
+    RPH_HIP_CHECK(hipMemcpyAsync(level, t + o_level, n, hipMemcpyDeviceToHost, s));
+    RPH_HIP_CHECK(hipMemcpyAsync(edges_at, t + o_at, (size_t)(top + 1) * 8, hipMemcpyDeviceToHost, s));
+    RPH_HIP_CHECK(hipStreamSynchronize(s));
     return RPH_OK;
 }
 
@@ -546,6 +590,30 @@ int rph_library_nearest_files(rph_library *lib, const uint32_t *indices, uint64_
         if (!indices && n_q) return fail("rph_library_nearest_files", "null argument");
         return library_nearest("rph_library_nearest_files", lib, nullptr, indices, n_q, k, max_dist, out, counts_out);
     });
+}
+
+int rph_library_merge_tree(rph_library *lib, uint32_t top, uint32_t *into, uint8_t *level, uint64_t *edges_at)
+{
+    return rph_guarded("rph_library_merge_tree", [&]() -> int {
+        if (!lib || !edges_at) return fail("rph_library_merge_tree", "null argument");
+        if (top > RPH_MAX_SIMILARITY_256) return fail("rph_library_merge_tree", "Similarity distances above 63 require R=4 bit-flip checks, which are not implemented.");
+        std::lock_guard<std::mutex> lock(lib->mu);
+        if ((!into || !level) && lib->n) return fail("rph_library_merge_tree", "null argument");
+        std::fill(edges_at, edges_at + top + 1, 0);
+        if (lib->n == 0) return RPH_OK;
+        RPH_HIP_CHECK(hipSetDevice(lib->ctx->device));
+        return merge_tree(lib, top, into, level, edges_at);
+    });
+}
+
+// What the last rph_library_merge_tree did (exported for the tests, not in the header): out[0..1] = edges its sweep found, the first
+// edge capacity it tried
+int rph_debug_library_merge_tree_stats(rph_library *lib, uint64_t *out)
+{
+    if (!lib || !out) return fail("rph_debug_library_merge_tree_stats", "null argument");
+    std::lock_guard<std::mutex> lock(lib->mu);
+    out[0] = lib->tree_stats[0], out[1] = lib->tree_stats[1];
+    return RPH_OK;
 }
 
 // The stages of the last append in device time (exported for tools/library_rate.py, not in the header): on != 0 arms the events for the

@@ -169,22 +169,31 @@ int sweep_host(const char *who, rph_ctx *ctx, const rph_sweep &q, uint64_t *n_ed
 // that `growth` sizes from what it counted.  launch(sink, cap) opens the sink for its request and queues its sweeps on `s`, all of
 // them appending through the one cursor.
 template <class F>
-int sweep_growing(const char *who, uint64_t cap, const rph_edge_growth &growth, hipStream_t s, std::vector<rph_edge> &edges, F &&launch)
+int sweep_growing_dev(const char *who, uint64_t cap, const rph_edge_growth &growth, hipStream_t s, EdgeSink &sink, unsigned long long *found_out, F &&launch)
 {
-    EdgeSink sink;
     unsigned long long found = 0;
     for (int attempt = 0; attempt < growth.attempts; attempt++) {
         RPH_TRY(launch(sink, cap));
         RPH_TRY(sink.read(&found, s));
         RPH_HIP_CHECK(hipStreamSynchronize(s));
         if (found <= cap) {
-            edges.resize(found);
-            return sink.take(who, found, edges.data());
+            *found_out = found;
+            return RPH_OK;
         }
         cap = growth.next_cap(found);
     }
     rph_set_error("%s: edge list kept growing (%llu)", who, found);
     return RPH_ERR_CAPACITY;
+}
+// ... and the edges brought to the host; sweep_growing_dev leaves them in `sink` on the device (rph_group_files_pdq_tree)
+template <class F>
+int sweep_growing(const char *who, uint64_t cap, const rph_edge_growth &growth, hipStream_t s, std::vector<rph_edge> &edges, F &&launch)
+{
+    EdgeSink sink;
+    unsigned long long found = 0;
+    RPH_TRY(sweep_growing_dev(who, cap, growth, s, sink, &found, launch));
+    edges.resize(found);
+    return sink.take(who, found, edges.data());
 }
 
 // One set of files of the grouping calls on the device: hashes, the variants its files own as rows (8 per file from the coefficients,
@@ -1038,6 +1047,51 @@ int rph_group_files_pdq(rph_ctx *ctx, const uint8_t *hashes32, const float *coef
                               }));
         if (comparison_count_out) *comparison_count_out = edges.size();
         return rph_host_union_find(edges.data(), edges.size(), n, members, offsets, n_groups_out);
+    });
+}
+
+// One sweep at `top`, its edges left on the device, then the merge tree of them (merge_tree.hip)
+int rph_group_files_pdq_tree(rph_ctx *ctx, const uint8_t *hashes32, const float *coeffs, const uint8_t *has_features, const int32_t *quality, uint64_t n,
+                             uint32_t top, uint32_t *into, uint8_t *level, uint64_t *edges_at)
+{
+    return rph_guarded("rph_group_files_pdq_tree", [&]() -> int {
+        if (!ctx || (!hashes32 && n) || ((!into || !level) && n) || !edges_at) {
+            rph_set_error("rph_group_files_pdq_tree: null argument");
+            return RPH_ERR_INVALID_ARG;
+        }
+        RPH_TRY(check_similarity(top));
+        if (n > 0x7FFFFFFFull) {
+            rph_set_error("rph_group_files_pdq_tree: at most 2^31 - 1 files");
+            return RPH_ERR_INVALID_ARG;
+        }
+        std::fill(edges_at, edges_at + top + 1, 0);
+        if (n == 0) return RPH_OK;
+        RPH_HIP_CHECK(hipSetDevice(ctx->device));
+        hipStream_t s = ctx->stream;
+        GroupSide set;
+        EdgeSink sink;
+        unsigned long long found = 0;
+        if (n > 1) {
+            RPH_TRY(set.upload(hashes32, coeffs, has_features, quality, n, true, s));
+            rph_sweep q = set.sweep(top);
+            RPH_TRY(sweep_growing_dev("rph_group_files_pdq_tree", std::max<uint64_t>(1u << 20, 32 * n), RPH_GROW_GROUP_FILES, s, sink, &found,
+                                      [&](EdgeSink &k, uint64_t cap) -> int {
+                                          RPH_TRY(k.open(cap, s, q));
+                                          return rph_launch_hamming_sweep(ctx, q, s, ctx->hamming_kernel);
+                                      }));
+        }
+        Layout L;
+        const size_t o_into = L.add(n * 4, 256), o_level = L.add(n, 256), o_at = L.add((size_t)(top + 1) * 8, 256);
+        DevBuf d_tree;
+        RPH_TRY(d_tree.alloc(L.end()));
+        StreamDrain drain{s};  // the tree's buffer and the sink's are in use until the stream is through
+        uint8_t *t = d_tree.data();
+        RPH_TRY(rph_merge_tree_run(ctx, sink.d_e.as<rph_edge>(), found, 0, 0, n, top, (uint32_t *)(t + o_into), t + o_level, (uint64_t *)(t + o_at), nullptr, s));
+        RPH_HIP_CHECK(hipMemcpyAsync(into, t + o_into, n * 4, hipMemcpyDeviceToHost, s));
+        RPH_HIP_CHECK(hipMemcpyAsync(level, t + o_level, n, hipMemcpyDeviceToHost, s));
+        RPH_HIP_CHECK(hipMemcpyAsync(edges_at, t + o_at, (size_t)(top + 1) * 8, hipMemcpyDeviceToHost, s));
+        RPH_HIP_CHECK(hipStreamSynchronize(s));
+        return RPH_OK;
     });
 }
 

@@ -117,6 +117,8 @@ struct rph_ctx {
     rph_file_limits file_limits;
     // rph_debug_group_max_dist_events: the caller's events around the distance kernel of group_info.hip (null: none), under mu
     hipEvent_t group_dist_ev[2] = {nullptr, nullptr};
+    // rph_debug_merge_tree_events: the caller's events between the stages of merge_tree.hip (null: none), under mu
+    hipEvent_t merge_tree_ev[4] = {nullptr, nullptr, nullptr, nullptr};
 };
 
 // ---- launchers implemented in the .hip files (all asynchronous on `stream`) ----
@@ -221,7 +223,16 @@ struct rph_union_edges {
 // What rph_union_find_labels_dev does, for several lists at once: one range check of all of them and of the entry forest (it waits for
 // that: RPH_ERR_INVALID_ARG with nothing written), then one union launch per list and ONE flatten, asynchronous on `stream`
 int rph_union_find_labels(rph_ctx *ctx, const rph_union_edges *sets, uint32_t n_sets, uint32_t *d_labels, uint64_t n, hipStream_t stream);
-// The grid of the grid-stride kernels of components.hip and library_kernels.hip: blocks of 256 lanes, at most 8 per compute unit, the
+// uf_flatten_kernel alone over a forest with d_labels[x] <= x (merge_tree.hip builds one with kernels of its own)
+int rph_launch_uf_flatten(rph_ctx *ctx, uint32_t *d_labels, uint64_t n, hipStream_t stream);
+// merge_tree.hip: rph_merge_tree_dev without its argument checks (n >= 1, top <= 255; d_labels nullable).  It takes ctx->mu and the
+// sweep scratch (8 bytes per edge, 4 to 8 per file), waits once for the range check and the per-level counts -- RPH_ERR_INVALID_ARG with
+// nothing written -- and queues the rest on `stream`
+int rph_merge_tree_run(rph_ctx *ctx, const rph_edge *d_edges, uint64_t n_edges, uint32_t i_base, uint32_t j_base, uint64_t n, uint32_t top, uint32_t *d_into,
+                       uint8_t *d_level, uint64_t *d_edges_at, uint32_t *d_labels, hipStream_t stream);
+// host_merge_tree.cpp: the tree of a host edge list whose edges have been checked (i, j < n, d <= top); edges_at is not touched
+void rph_host_merge_tree(const rph_edge *edges, uint64_t n_edges, uint64_t n, uint32_t top, uint32_t *into, uint8_t *level);
+// The grid of the grid-stride kernels of components.hip, merge_tree.hip and library_kernels.hip: blocks of 256 lanes, at most 8 per compute unit, the
 // loops stride over the rest.  rph_stride_lanes_per_pass is what one pass of such a loop covers (rph_debug_library_remove_stats).
 inline uint64_t rph_stride_lanes_per_pass(const rph_ctx *ctx) { return (uint64_t)(ctx->compute_units > 1 ? ctx->compute_units : 1) * 8 * 256; }
 inline unsigned rph_stride_grid(const rph_ctx *ctx, uint64_t items)
@@ -239,6 +250,12 @@ extern "C" int rph_debug_library_remove_stats(rph_library *lib, uint64_t *out);
 // its stages in device time, armed by rph_debug_library_stages(lib, 1, NULL) like the append's (6 floats): mark and select, gather of
 // the members, regroup sweep, edge split, compaction and labels, union and flatten
 extern "C" int rph_debug_library_remove_stages(rph_library *lib, float *ms_out);
+// library.cpp: what the last rph_library_merge_tree did (exported for the tests, not in the header): out[0..1] = edges its sweep found,
+// the first edge capacity it tried
+extern "C" int rph_debug_library_merge_tree_stats(rph_library *lib, uint64_t *out);
+// merge_tree.hip: the caller's events between the stages of the merge-tree calls that follow on this context (exported for
+// tools/merge_tree_rate.py, not in the header; nulls disarm)
+extern "C" int rph_debug_merge_tree_events(rph_ctx *ctx, void *e0, void *e1, void *e2, void *e3);
 // library_kernels.hip: the steps of rph_library_remove, asynchronous on `stream`.  One file's rows in the four per-file arrays:
 struct rph_library_rows {
     uint8_t *hashes = nullptr, *variants = nullptr, *low_conf = nullptr, *has_features = nullptr;  // [32], [8][32], [1], [1] per file; 16-byte aligned

@@ -906,6 +906,37 @@ class Engine:
               "rph_groups_from_labels_dev")
         return self._groups(members, offsets, ng.value)
 
+    def merge_tree_dev(self, d_edges, n_edges, n, top, d_into, d_level, d_edges_at, d_labels=None, i_base=0, j_base=0, stream=None):
+        """rph_merge_tree_dev: the merge tree of an edge list on the device (d_into n x uint32, d_level n bytes, d_edges_at (top + 1) x
+        uint64; d_labels, optional, the flattened min-labels at top)."""
+        check(self.L.rph_merge_tree_dev(self.ctx, d_edges, n_edges, i_base, j_base, n, top, d_into, d_level, d_edges_at, d_labels, stream), "rph_merge_tree_dev")
+
+    @staticmethod
+    def _tree_call(call, where, n, top):
+        into, level, edges_at = np.zeros(n, np.uint32), np.zeros(n, np.uint8), np.zeros(top + 1, np.uint64)
+        check(call(_ptr(into), _ptr(level), _ptr(edges_at)), where)
+        return MergeTree(into, level, edges_at)
+
+    @staticmethod
+    def merge_tree_from_edges_host(edges, n, top):
+        """rph_merge_tree_from_edges_host: the merge tree of a host edge list (no device, no context)."""
+        L = _lib.load()
+        edges = np.ascontiguousarray(edges, EDGE_DTYPE)
+        return Engine._tree_call(lambda i, l, e: L.rph_merge_tree_from_edges_host(_ptr(edges), len(edges), n, top, i, l, e), "rph_merge_tree_from_edges_host", n, top)
+
+    def group_files_pdq_tree(self, hashes, top, coeffs=None, has_features=None, quality=None):
+        """The groups of group_files_pdq at every similarity 0 .. top from one sweep at top: a MergeTree."""
+        h, c, hf, q = Library._files(hashes, coeffs, has_features, quality)
+        return self._tree_call(lambda i, l, e: self.L.rph_group_files_pdq_tree(self.ctx, _ptr(h), _ptr(c), _ptr(hf), _ptr(q), len(h), top, i, l, e),
+                               "rph_group_files_pdq_tree", len(h), top)
+
+    @staticmethod
+    def merge_tree_host(hashes, top, coeffs=None, has_features=None, quality=None):
+        """group_files_pdq_tree on the host (rph_merge_tree_host): brute force, no device, no context."""
+        L = _lib.load()
+        h, c, hf, q = Library._files(hashes, coeffs, has_features, quality)
+        return Engine._tree_call(lambda i, l, e: L.rph_merge_tree_host(_ptr(h), _ptr(c), _ptr(hf), _ptr(q), len(h), top, i, l, e), "rph_merge_tree_host", len(h), top)
+
     @staticmethod
     def _group_lists(groups, pivots):
         """(members, offsets, n_groups, pivots or None) as the rph_group_max_dist forms take them.  groups: a list of index lists, or the
@@ -1127,6 +1158,47 @@ class Engine:
         check(self.L.rph_event_destroy(self.ctx, e), "rph_event_destroy")
 
 
+class MergeTree:
+    """The groups at every similarity 0 .. top (include/rupphash.h, "Merge tree"): into (n x uint32), level (n x uint8) and edges_at
+    (top + 1 x uint64) as the C calls return them.  Cutting is host work, O(n) per call; none of it needs an engine."""
+
+    def __init__(self, into, level, edges_at):
+        self.into = np.ascontiguousarray(into, np.uint32)
+        self.level = np.ascontiguousarray(level, np.uint8)
+        self.edges_at = np.ascontiguousarray(edges_at, np.uint64)
+        self.top = len(self.edges_at) - 1
+
+    def __len__(self):
+        return len(self.into)
+
+    def labels(self, s):
+        """label_s: per file the smallest file number of its component at similarity s."""
+        out = np.zeros(len(self), np.uint32)
+        check(_lib.load().rph_merge_tree_labels(_ptr(self.into), _ptr(self.level), len(self), s, _ptr(out)), "rph_merge_tree_labels")
+        return out
+
+    def groups(self, s):
+        """What group_files_pdq(similarity=s) lists: components with > 1 member, members ascending, groups by first member."""
+        n = len(self)
+        members = np.zeros(max(n, 1), np.uint32)
+        offsets = np.zeros(n // 2 + 2, np.uint32)
+        ng = C.c_uint32()
+        check(_lib.load().rph_merge_tree_groups(_ptr(self.into), _ptr(self.level), n, s, _ptr(members), _ptr(offsets), C.byref(ng)), "rph_merge_tree_groups")
+        return Engine._groups(members, offsets, ng.value)
+
+    def comparisons(self, s):
+        """group_files_pdq's comparison count at similarity s <= top."""
+        if not 0 <= s <= self.top:
+            raise ValueError(f"similarity {s} outside 0 .. {self.top}")
+        return int(self.edges_at[:s + 1].sum())
+
+    def profile(self):
+        """(n_groups, grouped_files): for every s in 0 .. top the number of groups and the number of files in them."""
+        n_groups, files = np.zeros(self.top + 1, np.uint64), np.zeros(self.top + 1, np.uint64)
+        check(_lib.load().rph_merge_tree_profile(_ptr(self.into), _ptr(self.level), len(self), self.top, _ptr(n_groups), _ptr(files)), "rph_merge_tree_profile")
+        return n_groups, files
+
+
 class Library:
     """rph_library: files appended so far stay on the device with their variants, flags and component labels.  groups() equals
     Engine.group_files_pdq on the files it holds, in order.  One similarity, at most 2^31 - 1 files; remove() renumbers the files that
@@ -1227,6 +1299,10 @@ class Library:
         return self.engine._group_max_dist_call(lambda m, o, ng, p, out, md: self.L.rph_library_group_max_dist(self.handle, m, o, ng, p, out, md),
                                                 "rph_library_group_max_dist", groups, pivots, want_member_dist)
 
+    def merge_tree(self, top):
+        """The MergeTree of the resident files at `top`, whatever the library's own similarity is: one sweep, nothing resident changes."""
+        return Engine._tree_call(lambda i, l, e: self.L.rph_library_merge_tree(self.handle, top, i, l, e), "rph_library_merge_tree", len(self), top)
+
     def query(self, hashes, quality=None, cap=None):
         """Edges (library file i, query j, d, variant in flags) of the queries against the resident files; the library is not changed.
         With cap given, RPH_ERR_CAPACITY raises (RphError)."""
@@ -1251,6 +1327,8 @@ class Library:
 
 group_max_dist_host = Engine.group_max_dist_host  # needs no engine
 hamming_nearest_host = Engine.hamming_nearest_host
+merge_tree_host = Engine.merge_tree_host
+merge_tree_from_edges_host = Engine.merge_tree_from_edges_host
 
 
 _default = None

@@ -182,6 +182,13 @@ def group_with_pdqhash(hashes, similarity, coefficients=None, has_features=None,
     return (engine or default_engine()).group_files_pdq(hashes, similarity, coefficients, has_features, q)
 
 
+def merge_tree(hashes, top, coefficients=None, has_features=None, quality=None, engine=None):
+    """group_with_pdqhash at every similarity 0 .. top from ONE sweep at top: a MergeTree whose groups(s) and comparisons(s) are what
+    group_with_pdqhash(hashes, s, ...) returns, labels(s) the smallest file of every file's component, profile() the number of groups and
+    of grouped files per s.  Where the similarity changes, cut the tree instead of grouping again."""
+    return (engine or default_engine()).group_files_pdq_tree(hashes, top, coefficients, has_features, _quality32(quality))
+
+
 def group_with_pdqhash_append(old_hashes, old_groups, new_hashes, similarity, old_coefficients=None, old_has_features=None, old_quality=None,
                               new_coefficients=None, new_has_features=None, new_quality=None, engine=None):
     """group_with_pdqhash for a library that was grouped before (`old_groups`: the groups that call returned) plus new files.
