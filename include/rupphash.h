@@ -441,6 +441,36 @@ int rph_library_labels(rph_library *lib, uint64_t first, uint64_t count, uint32_
  * capacity protocol of rph_hamming_variant_cross_pairs (e.i library, e.j query); quality_q nullable. */
 int rph_library_query(rph_library *lib, const uint8_t *hashes32_q, const int32_t *quality_q, uint64_t n_q, rph_edge *edges,
                       uint64_t cap, uint64_t *n_edges_out);
+/* An edge-keeping library: beside everything above it holds, on the device, every edge the variant sweep at `top` reports among the
+ * resident files -- one rph_edge per passing variant exactly as rph_hamming_variant_pairs emits them, in the library's current numbering
+ * with i < j, in no particular order, 12 bytes each.  With that store rph_library_merge_tree(lib, t <= top) runs no sweep, so the
+ * similarity can change, or the groups at every similarity be counted, for milliseconds after every append and removal.
+ * similarity <= top <= RPH_MAX_SIMILARITY_256, else RPH_ERR_INVALID_ARG.  max_edges bounds the store; 0 means 2^28 edges (3 GiB).
+ * In every call above such a library gives what rph_library_create(ctx, similarity) gives when fed the same calls: its groups are the
+ * union-find of the stored edges with d <= similarity, its comparison count their number (the sweep at s reports exactly the edges with
+ * d <= s of the sweep at top: see "Merge tree").  What differs:
+ *  - an append sweeps at `top` (more edges than at `similarity`, and above 31 the slower sweep kernel).  One that would take the store
+ *    past max_edges is RPH_ERR_CAPACITY and, as every refused append, leaves size, labels, count and store as they were.  The store
+ *    grows geometrically; while it grows the old and the new allocation exist together.
+ *  - a removal also filters the store into a second one, which then replaces it: for the length of the call a second store of the same
+ *    capacity is allocated.  Still all or nothing.  The edges it drops within `similarity` must be the number the regroup counted; if
+ *    they are not (a store restored from edges that are not the files' own), RPH_ERR_HIP with both numbers and nothing changed.
+ *  - rph_library_restore is RPH_ERR_INVALID_ARG: groups alone cannot fill a store.  Use rph_library_restore_edges. */
+#define RPH_NO_EDGE_STORE 0xFFFFFFFFu
+int rph_library_create_tree(rph_ctx *ctx, uint32_t similarity, uint32_t top, uint64_t max_edges, rph_library **lib_out);
+/* Any output may be NULL.  *top_out: the store's top, RPH_NO_EDGE_STORE for a library made by rph_library_create (the counts are 0
+ * then); *n_edges_out: the edges the store holds; *capacity_out: the most it may hold (max_edges). */
+int rph_library_edge_info(rph_library *lib, uint32_t *top_out, uint64_t *n_edges_out, uint64_t *capacity_out);
+/* The store, downloaded.  *n_edges_out always receives the count; the records are written only if cap suffices, else RPH_ERR_CAPACITY
+ * with nothing written.  A library without a store: RPH_ERR_INVALID_ARG. */
+int rph_library_edges(rph_library *lib, rph_edge *edges_out, uint64_t cap, uint64_t *n_edges_out);
+/* Start an empty edge-keeping library from files plus the edges an earlier run downloaded from a library of the same top: no sweep.
+ * The labels are the union-find of the edges with d <= similarity (which may differ from the earlier run's), the comparison count
+ * their number.  The edges are the caller's word: each is checked for i < j < n and d <= top before anything is stored -- a violation
+ * is RPH_ERR_INVALID_ARG and the library stays empty -- and they are never trusted for indexing, but whether they are the files' edges
+ * is not checked.  A library that is not empty or has no store: RPH_ERR_INVALID_ARG. */
+int rph_library_restore_edges(rph_library *lib, const uint8_t *hashes32, const float *coeffs, const uint8_t *has_features,
+                              const int32_t *quality, uint64_t n, const rph_edge *edges, uint64_t n_edges);
 
 /*
  * max_dist of every group (process_raw_groups -> analyze_group_with_features, scanner.rs:1986-2022 and :2214-2241): the maximum, over the
@@ -579,8 +609,15 @@ int rph_group_files_pdq_tree(rph_ctx *ctx, const uint8_t *hashes32, const float 
 int rph_merge_tree_host(const uint8_t *hashes32, const float *coeffs, const uint8_t *has_features, const int32_t *quality,
                         uint64_t n, uint32_t top, uint32_t *into, uint8_t *level, uint64_t *edges_at);
 /* Of the files a library holds, at `top` whatever the library's own similarity is.  The library is not changed: its labels, size and
- * comparison count stay as they are. */
+ * comparison count stay as they are.  One triangular sweep of everything resident -- except on a library made by
+ * rph_library_create_tree with `top` at or below its store's: there no sweep runs, the core runs over the store and the result is cut
+ * down to `top`.  The bytes are the same either way: those of rph_group_files_pdq_tree(top) on the resident files in order. */
 int rph_library_merge_tree(rph_library *lib, uint32_t top, uint32_t *into, uint8_t *level, uint64_t *edges_at);
+/* The tree for t <= top from the tree for top, on the host, no context: level_out[x] = level[x] and into_out[x] = into[x] where
+ * level[x] <= t, RPH_TREE_NEVER and x elsewhere; edges_at_out = the first t + 1 entries of edges_at.  Exact, because level[x] does not
+ * depend on top.  The outputs may be the inputs.  t > top or a malformed tree (as below): RPH_ERR_INVALID_ARG with nothing written. */
+int rph_merge_tree_truncate(const uint32_t *into, const uint8_t *level, const uint64_t *edges_at, uint64_t n, uint32_t top,
+                            uint32_t t, uint32_t *into_out, uint8_t *level_out, uint64_t *edges_at_out);
 /* Cutting a tree, on the host: O(n).  A malformed tree -- into[x] > x, into[x] == x with a level other than RPH_TREE_NEVER (or the
  * reverse), a level that does not rise along a chain -- is RPH_ERR_INVALID_ARG with nothing written.
  * labels_out[x] = label_s[x]. */

@@ -57,6 +57,8 @@ RPH_NO_FILE = 0xFFFFFFFF
 RPH_NEAREST_MAX_K = 64
 # merge tree: the level of a file that no similarity up to `top` joins to a smaller one
 RPH_TREE_NEVER = 255
+# rph_library_edge_info: the top of a library that keeps no edges
+RPH_NO_EDGE_STORE = 0xFFFFFFFF
 
 
 class RphEdge(C.Structure):
@@ -144,6 +146,10 @@ SIGNATURES = {
     "rph_library_groups": (C.c_int, [_vp, _u32p, _u32p, C.POINTER(C.c_uint32)]),
     "rph_library_labels": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _u32p]),
     "rph_library_query": (C.c_int, [_vp, _u8p, _i32p, C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "rph_library_create_tree": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(C.c_void_p)]),
+    "rph_library_edge_info": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "rph_library_edges": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "rph_library_restore_edges": (C.c_int, [_vp, _u8p, _f32p, _u8p, _i32p, C.c_uint64, _vp, C.c_uint64]),
     "rph_group_max_dist_host": (C.c_int, [_u8p, _f32p, _u8p, C.c_uint64, _u32p, _u32p, C.c_uint32, _u32p, _u32p, _u32p]),
     "rph_group_max_dist": (C.c_int, [_vp, _u8p, _f32p, _u8p, C.c_uint64, _u32p, _u32p, C.c_uint32, _u32p, _u32p, _u32p]),
     "rph_group_max_dist_dev": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_int, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp]),
@@ -158,6 +164,7 @@ SIGNATURES = {
     "rph_group_files_pdq_tree": (C.c_int, [_vp, _u8p, _f32p, _u8p, _i32p, C.c_uint64, C.c_uint32, _u32p, _u8p, _u64p]),
     "rph_merge_tree_host": (C.c_int, [_u8p, _f32p, _u8p, _i32p, C.c_uint64, C.c_uint32, _u32p, _u8p, _u64p]),
     "rph_library_merge_tree": (C.c_int, [_vp, C.c_uint32, _u32p, _u8p, _u64p]),
+    "rph_merge_tree_truncate": (C.c_int, [_u32p, _u8p, _u64p, C.c_uint64, C.c_uint32, C.c_uint32, _u32p, _u8p, _u64p]),
     "rph_merge_tree_labels": (C.c_int, [_u32p, _u8p, C.c_uint64, C.c_uint32, _u32p]),
     "rph_merge_tree_groups": (C.c_int, [_u32p, _u8p, C.c_uint64, C.c_uint32, _u32p, _u32p, C.POINTER(C.c_uint32)]),
     "rph_merge_tree_profile": (C.c_int, [_u32p, _u8p, C.c_uint64, C.c_uint32, _u64p, _u64p]),
@@ -255,6 +262,8 @@ DEBUG_SIGNATURES = {
     "rph_debug_group_max_dist_events": (C.c_int, [_vp, _vp, _vp]),
     "rph_debug_library_merge_tree_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "rph_debug_merge_tree_events": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "rph_debug_library_edge_store": (C.c_int, [_vp, C.c_uint64]),
+    "rph_debug_library_edge_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "rph_debug_nearest_layout": (None, [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32)]),
     "rph_debug_nearest_set_segment": (None, [C.c_uint32]),
     "rph_debug_nearest_set_workspace": (None, [C.c_uint64]),

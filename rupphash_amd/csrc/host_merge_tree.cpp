@@ -84,6 +84,16 @@ void rph_host_merge_tree(const rph_edge *edges, uint64_t n_edges, uint64_t n, ui
     }
 }
 
+// The cut of rph_merge_tree_truncate on a checked tree: each output is written from the input at the same index, so the outputs may be the inputs
+void rph_host_merge_tree_cut(const uint32_t *into, const uint8_t *level, uint64_t n, uint32_t t, uint32_t *into_out, uint8_t *level_out)
+{
+    for (uint64_t x = 0; x < n; x++) {
+        const bool stays = level[x] <= t;  // (RPH_TREE_NEVER is above every t)
+        into_out[x] = stays ? into[x] : (uint32_t)x;
+        level_out[x] = stays ? level[x] : (uint8_t)RPH_TREE_NEVER;
+    }
+}
+
 extern "C" {
 
 int rph_merge_tree_from_edges_host(const rph_edge *edges, uint64_t n_edges, uint64_t n, uint32_t top, uint32_t *into, uint8_t *level, uint64_t *edges_at)
@@ -146,6 +156,24 @@ int rph_merge_tree_labels(const uint32_t *into, const uint8_t *level, uint64_t n
         if (!labels_out && n) return fail("rph_merge_tree_labels", "null argument");
         RPH_TRY(check_tree("rph_merge_tree_labels", into, level, n));
         cut_labels(into, level, n, s, labels_out);
+        return RPH_OK;
+    });
+}
+
+// level[x] is the smallest s at which x stops being its own label, whatever `top` the tree was built for: the tree for t keeps the
+// records with level <= t and turns the others into roots.  Each output is written from the input at the same index, so the outputs may
+// be the inputs.
+int rph_merge_tree_truncate(const uint32_t *into, const uint8_t *level, const uint64_t *edges_at, uint64_t n, uint32_t top, uint32_t t, uint32_t *into_out,
+                            uint8_t *level_out, uint64_t *edges_at_out)
+{
+    return rph_guarded("rph_merge_tree_truncate", [&]() -> int {
+        const char *who = "rph_merge_tree_truncate";
+        if (!edges_at || !edges_at_out || ((!into_out || !level_out) && n)) return fail(who, "null argument");
+        if (top >= RPH_TREE_NEVER) return fail(who, "top at most 254: level 255 is RPH_TREE_NEVER");
+        if (t > top) return fail(who, "t above the top the tree was built for");
+        RPH_TRY(check_tree(who, into, level, n));
+        rph_host_merge_tree_cut(into, level, n, t, into_out, level_out);
+        if (edges_at_out != edges_at) std::memmove(edges_at_out, edges_at, (size_t)(t + 1) * 8);
         return RPH_OK;
     });
 }

@@ -2,7 +2,8 @@
 // moves, expands and re-unions on every call -- the library's hashes, its variants, its flags and its components -- is kept in HBM
 // between calls: an append uploads the new files only, sweeps the pairs they add and unites the edges where the sweep left them
 // (components.hip); a query sweeps without changing anything; a removal compacts the survivors into a second set of arrays and regroups
-// the components that lost a file (library_kernels.hip).
+// the components that lost a file (library_kernels.hip).  A library made by rph_library_create_tree also keeps the edges its appends find,
+// swept at its `top`, in global numbering (library_edges.hip): rph_library_merge_tree then needs no sweep up to that top.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -33,6 +34,14 @@ struct rph_library {
     uint64_t tree_stats[2] = {0, 0};   // edges its sweep found, first edge capacity it tried
     bool rm_staged = false;
     hipEvent_t rm_ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    // rph_library_create_tree: every edge the variant sweep at `top` reports among the resident files, in the library's numbering, i < j,
+    // order unspecified; n_store of them, room for store_cap, never more than max_edges.  d_united: the edges of one append within
+    // `similarity`, for the union-find; d_store_nums: the store kernels' counters.  edge_stats: rph_debug_library_edge_stats
+    bool keeps_edges = false;
+    uint32_t top = 0;
+    uint64_t max_edges = 0, n_store = 0, store_cap = 0, store_first_cap = 0;
+    DevBuf d_store, d_united, d_store_nums;
+    uint64_t edge_stats[5] = {0, 0, 0, 0, 0};
 };
 
 namespace {
@@ -93,6 +102,53 @@ int upload_behind(rph_library *lib, const uint8_t *hashes32, const float *coeffs
     return RPH_OK;
 }
 
+constexpr uint64_t STORE_FIRST_CAP = 1u << 20;     // 12 MiB: where a store starts (rph_debug_library_edge_store overrides it)
+constexpr uint64_t STORE_MAX_EDGES = 1ull << 28;  // max_edges == 0: 3 GiB
+
+// room for `need` edges in the store: geometric growth, device-to-device copy of the edges it holds.  The new buffer is allocated before
+// anything is replaced: a failure leaves a valid store of the old length.  More than max_edges: RPH_ERR_CAPACITY, nothing changed.
+int grow_store(rph_library *lib, uint64_t need, hipStream_t s)
+{
+    if (need > lib->max_edges) {
+        rph_set_error("rph_library: the edge store would hold %llu edges, max_edges is %llu", (unsigned long long)need, (unsigned long long)lib->max_edges);
+        return RPH_ERR_CAPACITY;
+    }
+    if (need <= lib->store_cap) return RPH_OK;
+    uint64_t cap = std::max<uint64_t>(lib->store_first_cap ? lib->store_first_cap : STORE_FIRST_CAP, 1);
+    while (cap < need) cap *= 2;
+    cap = std::min(cap, lib->max_edges);
+    DevBuf next;
+    RPH_TRY(next.alloc(cap * sizeof(rph_edge)));
+    if (lib->n_store) RPH_HIP_CHECK(hipMemcpyAsync(next.data(), lib->d_store.data(), lib->n_store * sizeof(rph_edge), hipMemcpyDeviceToDevice, s));
+    RPH_HIP_CHECK(hipStreamSynchronize(s));
+    lib->edge_stats[0] += lib->store_cap != 0;  // (the first allocation is no growth)
+    lib->d_store = std::move(next);
+    lib->store_cap = cap;
+    return RPH_OK;
+}
+
+// What d_edges holds -- n_cross edges (resident file, new-local file), then (new-local, new-local) ones, over n resident and n_new new
+// files -- behind the store's end in the library's numbering and, within the similarity, into d_united (*united_out of them).  The
+// store's length does not advance: that is the caller's commit.  It waits for the stream.
+int stage_edges(rph_library *lib, uint64_t n_found, uint64_t n_cross, uint64_t n, uint64_t n_new, hipStream_t s, unsigned long long *united_out)
+{
+    RPH_TRY(grow_store(lib, lib->n_store + n_found, s));
+    RPH_TRY(lib->d_united.reserve(n_found * sizeof(rph_edge), s));
+    if (!lib->d_store_nums.data()) RPH_TRY(lib->d_store_nums.alloc(32));
+    unsigned long long nums[2] = {0, 0};
+    StreamDrain drain{s};
+    RPH_TRY(rph_library_launch_store_append(lib->ctx, lib->d_edges.as<rph_edge>(), n_found, n_cross, (uint32_t)n, (uint32_t)n_new, lib->similarity, lib->top,
+                                            lib->d_store.as<rph_edge>() + lib->n_store, lib->d_united.as<rph_edge>(), lib->d_store_nums.as<unsigned long long>(), s));
+    RPH_HIP_CHECK(hipMemcpyAsync(nums, lib->d_store_nums.data(), 16, hipMemcpyDeviceToHost, s));
+    RPH_HIP_CHECK(hipStreamSynchronize(s));
+    if (nums[1] || nums[0] > n_found) {
+        rph_set_error("rph_library: an edge for the store names a file outside its set, is not i < j or lies above top");
+        return RPH_ERR_INVALID_ARG;
+    }
+    *united_out = nums[0];
+    return RPH_OK;
+}
+
 int mark(rph_library *lib, int k, hipStream_t s)
 {
     if (lib->profile) RPH_HIP_CHECK(hipEventRecord(lib->ev[k], s));
@@ -123,6 +179,7 @@ int append(rph_library *lib, const uint8_t *hashes32, const float *coeffs, const
     RPH_TRY(upload_behind(lib, hashes32, coeffs, hf, quality, n_new, s));
     RPH_TRY(mark(lib, 1, s));
     rph_sweep cross = sweep_of(lib, 0, n, n, n_new, true), within = sweep_of(lib, n, n_new, n, n_new, false);
+    if (lib->keeps_edges) cross.threshold = within.threshold = lib->top;  // the store's edges; the unions below take those within `similarity`
     if (!lib->d_cnt.data()) RPH_TRY(lib->d_cnt.alloc(8));
     uint64_t cap = std::max<uint64_t>(1u << 20, 32 * n_new);
     unsigned long long found[2] = {0, 0};  // behind the cross sweep, behind both
@@ -153,21 +210,53 @@ int append(rph_library *lib, const uint8_t *hashes32, const float *coeffs, const
     // left them, the cross edges (library index, new-local index) and the inner ones (both new-local): one range check, which is the last
     // thing that can refuse, two union launches, one flatten.  From the first union launch the resident labels change; what can still
     // fail after it is a HIP call, that is a device that is lost to this context anyway.
+    // An edge-keeping library first writes all of them behind its store's end, rebased to the library's numbering, and unites the copy
+    // of those within `similarity`; a store that cannot take them (max_edges, an allocation) refuses here, before any label changes.
     const rph_edge *e = lib->d_edges.as<rph_edge>();
     uint32_t *lab = lib->d_lab.as<uint32_t>();
+    unsigned long long united = found[1];
+    if (lib->keeps_edges) RPH_TRY(stage_edges(lib, found[1], found[0], n, n_new, s, &united));
     for (uint64_t i = 0; i < n_new; i++) own[i] = (uint32_t)(n + i);
     RPH_HIP_CHECK(hipMemcpyAsync(lab + n, own.data(), n_new * 4, hipMemcpyHostToDevice, s));
     RPH_HIP_CHECK(hipStreamSynchronize(s));
     const rph_union_edges sets[2] = {{e, found[0], 0, (uint32_t)n}, {e + found[0], found[1] - found[0], (uint32_t)n, (uint32_t)n}};
-    RPH_TRY(rph_union_find_labels(ctx, sets, 2, lab, n + n_new, s));
+    const rph_union_edges kept{lib->d_united.as<rph_edge>(), united, 0, 0};
+    RPH_TRY(rph_union_find_labels(ctx, lib->keeps_edges ? &kept : sets, lib->keeps_edges ? 1 : 2, lab, n + n_new, s));
     RPH_TRY(mark(lib, 4, s));
     if (labels_out) RPH_HIP_CHECK(hipMemcpyAsync(labels_out, lab + n, n_new * 4, hipMemcpyDeviceToHost, s));
     RPH_TRY(mark(lib, 5, s));
     RPH_HIP_CHECK(hipStreamSynchronize(s));
     lib->staged = lib->profile;
     lib->n = n + n_new;
-    lib->comparisons += found[1];
-    if (new_comparisons_out) *new_comparisons_out = found[1];
+    lib->comparisons += united;
+    if (new_comparisons_out) *new_comparisons_out = united;
+    if (lib->keeps_edges) lib->n_store += found[1], lib->edge_stats[1] = found[1], lib->edge_stats[2] = united;
+    return RPH_OK;
+}
+
+// The tree of an edge-keeping library at t <= its top, without a sweep: the core over the store at `top`, then the cut of
+// rph_merge_tree_truncate (rph_host_merge_tree_cut, in place) on the arrays as they arrive: the tree is the core's own, nothing to check
+int merge_tree_from_store(rph_library *lib, uint32_t t, uint32_t *into, uint8_t *level, uint64_t *edges_at)
+{
+    rph_ctx *ctx = lib->ctx;
+    hipStream_t s = ctx->stream;
+    const uint64_t n = lib->n;
+    const uint32_t top = lib->top;
+    uint64_t at[RPH_MAX_SIMILARITY_256 + 1];  // rph_library_create_tree refuses a top above RPH_MAX_SIMILARITY_256
+    if (top > RPH_MAX_SIMILARITY_256) return fail("rph_library_merge_tree", "the store's top is above 63");
+    StreamDrain drain{s};
+    Layout L;
+    const size_t o_into = L.add(n * 4, 256), o_level = L.add(n, 256), o_at = L.add((size_t)(top + 1) * 8, 256);
+    RPH_TRY(lib->d_tree.reserve(L.end(), s));
+    uint8_t *d = lib->d_tree.data();
+    RPH_TRY(rph_merge_tree_run(ctx, lib->d_store.as<rph_edge>(), lib->n_store, 0, 0, n, top, (uint32_t *)(d + o_into), d + o_level, (uint64_t *)(d + o_at), nullptr, s));
+    RPH_HIP_CHECK(hipMemcpyAsync(into, d + o_into, n * 4, hipMemcpyDeviceToHost, s));
+    RPH_HIP_CHECK(hipMemcpyAsync(level, d + o_level, n, hipMemcpyDeviceToHost, s));
+    RPH_HIP_CHECK(hipMemcpyAsync(at, d + o_at, (size_t)(top + 1) * 8, hipMemcpyDeviceToHost, s));
+    RPH_HIP_CHECK(hipStreamSynchronize(s));
+    rph_host_merge_tree_cut(into, level, n, t, into, level);
+    std::copy(at, at + t + 1, edges_at);
+    lib->edge_stats[4] = 0;
     return RPH_OK;
 }
 
@@ -201,6 +290,7 @@ int merge_tree(rph_library *lib, uint32_t top, uint32_t *into, uint8_t *level, u
         edge_cap = RPH_GROW_GROUP_FILES.next_cap(found);
     }
     lib->tree_stats[0] = found, lib->tree_stats[1] = first_cap;
+    lib->edge_stats[4] = 1;
     Layout L;
     const size_t o_into = L.add(n * 4, 256), o_level = L.add(n, 256), o_at = L.add((size_t)(top + 1) * 8, 256);
     RPH_TRY(lib->d_tree.reserve(L.end(), s));
@@ -235,8 +325,16 @@ int remove(rph_library *lib, const uint32_t *indices, const std::vector<uint32_t
     DevBuf next[5];
     uint32_t host_nums[2] = {0, 0};  // what comes back from the device: survivors and members, edges found, edges dropped
     unsigned long long found = 0, dropped = 0;
+    // an edge-keeping library: the twin of its store at the same capacity, and what the filter counted (kept, dropped within the
+    // similarity, dropped, out of range)
+    DevBuf store_twin;
+    unsigned long long store_nums[4] = {0, 0, 0, 0};
     StreamDrain drain{s};
     for (int k = 0; k < 5; k++) RPH_TRY(next[k].alloc(lib->cap * width[k]));
+    if (lib->keeps_edges) {
+        RPH_TRY(store_twin.alloc(lib->store_cap * sizeof(rph_edge)));
+        if (!lib->d_store_nums.data()) RPH_TRY(lib->d_store_nums.alloc(32));
+    }
     size_t temp_bytes = 0;
     RPH_TRY(rph_library_select_temp_bytes(n, &temp_bytes));
     Layout L;
@@ -314,10 +412,27 @@ int remove(rph_library *lib, const uint32_t *indices, const std::vector<uint32_t
         RPH_TRY(rph_union_find_labels(ctx, &all, 1, next[4].as<uint32_t>(), kept, s));
     }
     RPH_TRY(mark_removal(lib, 6, s));
+    // the store through the same flags and numbers into its twin.  What it drops within the similarity is what the regroup counted: both
+    // are the edges of the removed files, found by two different routes
+    if (lib->keeps_edges) {
+        RPH_TRY(rph_library_launch_store_filter(ctx, lib->d_store.as<rph_edge>(), lib->n_store, n, removed, new_index, lib->similarity, store_twin.as<rph_edge>(),
+                                                lib->d_store_nums.as<unsigned long long>(), s));
+        RPH_HIP_CHECK(hipMemcpyAsync(store_nums, lib->d_store_nums.data(), 32, hipMemcpyDeviceToHost, s));
+    }
     RPH_HIP_CHECK(hipStreamSynchronize(s));
+    if (lib->keeps_edges && (store_nums[3] || store_nums[1] != dropped || store_nums[0] + store_nums[2] != lib->n_store)) {
+        rph_set_error("rph_library_remove: the edge store drops %llu edges within the similarity (%llu of %llu in all, %llu kept), the regroup counted %llu",
+                      store_nums[1], store_nums[2], (unsigned long long)lib->n_store, store_nums[0], dropped);
+        return RPH_ERR_HIP;
+    }
 
     // the swap: nothing can fail from here, and the stream is through with the old arrays
     for (int k = 0; k < 5; k++) *cur[k] = std::move(next[k]);
+    if (lib->keeps_edges) {
+        lib->d_store = std::move(store_twin);
+        lib->n_store = store_nums[0];
+        lib->edge_stats[3] = store_nums[2];
+    }
     lib->n = kept;
     lib->comparisons -= std::min<uint64_t>(dropped, lib->comparisons);  // (a restored count may have been lower than the files' edges)
     lib->rm_stats[0] = m, lib->rm_stats[1] = found, lib->rm_stats[2] = first_cap;
@@ -347,6 +462,91 @@ int rph_library_create(rph_ctx *ctx, uint32_t similarity, rph_library **lib_out)
         lib->ctx = ctx;
         lib->similarity = similarity;
         *lib_out = lib;
+        return RPH_OK;
+    });
+}
+
+int rph_library_create_tree(rph_ctx *ctx, uint32_t similarity, uint32_t top, uint64_t max_edges, rph_library **lib_out)
+{
+    return rph_guarded("rph_library_create_tree", [&]() -> int {
+        if (!ctx || !lib_out) return fail("rph_library_create_tree", "null argument");
+        *lib_out = nullptr;
+        if (top > RPH_MAX_SIMILARITY_256) return fail("rph_library_create_tree", "Similarity distances above 63 require R=4 bit-flip checks, which are not implemented.");
+        if (similarity > top) return fail("rph_library_create_tree", "similarity above top: the store would lack edges the groups need");
+        rph_library *lib = new rph_library;
+        lib->ctx = ctx;
+        lib->similarity = similarity;
+        lib->keeps_edges = true;
+        lib->top = top;
+        lib->max_edges = max_edges ? max_edges : STORE_MAX_EDGES;
+        *lib_out = lib;
+        return RPH_OK;
+    });
+}
+
+int rph_library_edge_info(rph_library *lib, uint32_t *top_out, uint64_t *n_edges_out, uint64_t *capacity_out)
+{
+    if (!lib) return fail("rph_library_edge_info", "null argument");
+    std::lock_guard<std::mutex> lock(lib->mu);
+    if (top_out) *top_out = lib->keeps_edges ? lib->top : RPH_NO_EDGE_STORE;
+    if (n_edges_out) *n_edges_out = lib->n_store;
+    if (capacity_out) *capacity_out = lib->max_edges;
+    return RPH_OK;
+}
+
+int rph_library_edges(rph_library *lib, rph_edge *edges_out, uint64_t cap, uint64_t *n_edges_out)
+{
+    return rph_guarded("rph_library_edges", [&]() -> int {
+        if (!lib || !n_edges_out || (!edges_out && cap)) return fail("rph_library_edges", "null argument");
+        *n_edges_out = 0;
+        std::lock_guard<std::mutex> lock(lib->mu);
+        if (!lib->keeps_edges) return fail("rph_library_edges", "the library keeps no edges: make it with rph_library_create_tree");
+        *n_edges_out = lib->n_store;
+        if (lib->n_store > cap) {
+            rph_set_error("rph_library_edges: %llu edges, capacity %llu", (unsigned long long)lib->n_store, (unsigned long long)cap);
+            return RPH_ERR_CAPACITY;
+        }
+        if (lib->n_store == 0) return RPH_OK;
+        RPH_HIP_CHECK(hipSetDevice(lib->ctx->device));
+        RPH_HIP_CHECK(hipMemcpyAsync(edges_out, lib->d_store.data(), lib->n_store * sizeof(rph_edge), hipMemcpyDeviceToHost, lib->ctx->stream));
+        RPH_HIP_CHECK(hipStreamSynchronize(lib->ctx->stream));
+        return RPH_OK;
+    });
+}
+
+int rph_library_restore_edges(rph_library *lib, const uint8_t *hashes32, const float *coeffs, const uint8_t *has_features, const int32_t *quality, uint64_t n,
+                              const rph_edge *edges, uint64_t n_edges)
+{
+    return rph_guarded("rph_library_restore_edges", [&]() -> int {
+        const char *who = "rph_library_restore_edges";
+        if (!lib || (!hashes32 && n) || (!edges && n_edges)) return fail(who, "null argument");
+        std::lock_guard<std::mutex> lock(lib->mu);
+        if (!lib->keeps_edges) return fail(who, "the library keeps no edges: make it with rph_library_create_tree");
+        if (lib->n) return fail(who, "the library is not empty");
+        if (n > MAX_FILES) return fail(who, "at most 2^31 - 1 files");
+        // the caller's word, checked here before anything is uploaded and again by the kernel that stores it
+        for (uint64_t e = 0; e < n_edges; e++)
+            if (edges[e].i >= edges[e].j || edges[e].j >= n || edges[e].d > lib->top) return fail(who, "an edge is not i < j < n with d <= top");
+        if (n == 0) return RPH_OK;
+        rph_ctx *ctx = lib->ctx;
+        RPH_HIP_CHECK(hipSetDevice(ctx->device));
+        hipStream_t s = ctx->stream;
+        std::vector<uint32_t> own(n);
+        for (uint64_t i = 0; i < n; i++) own[i] = (uint32_t)i;
+        StreamDrain drain{s};
+        RPH_TRY(grow(lib, n, s));
+        RPH_TRY(upload_behind(lib, hashes32, coeffs, has_features, quality, n, s));
+        RPH_TRY(lib->d_edges.reserve(n_edges * sizeof(rph_edge), s));
+        if (n_edges) RPH_HIP_CHECK(hipMemcpyAsync(lib->d_edges.data(), edges, n_edges * sizeof(rph_edge), hipMemcpyHostToDevice, s));
+        unsigned long long united = 0;
+        RPH_TRY(stage_edges(lib, n_edges, 0, 0, n, s, &united));  // as inner edges of an append to an empty library
+        RPH_HIP_CHECK(hipMemcpyAsync(lib->d_lab.data(), own.data(), n * 4, hipMemcpyHostToDevice, s));
+        const rph_union_edges kept{lib->d_united.as<rph_edge>(), united, 0, 0};
+        RPH_TRY(rph_union_find_labels(ctx, &kept, 1, lib->d_lab.as<uint32_t>(), n, s));
+        RPH_HIP_CHECK(hipStreamSynchronize(s));
+        lib->n = n;
+        lib->n_store = n_edges;
+        lib->comparisons = united;
         return RPH_OK;
     });
 }
@@ -431,6 +631,7 @@ int rph_library_restore(rph_library *lib, const uint8_t *hashes32, const float *
     return rph_guarded("rph_library_restore", [&]() -> int {
         if (!lib || (!hashes32 && n) || ((!members || !offsets) && n_groups)) return fail("rph_library_restore", "null argument");
         std::lock_guard<std::mutex> lock(lib->mu);
+        if (lib->keeps_edges) return fail("rph_library_restore", "groups alone cannot fill an edge store: use rph_library_restore_edges");
         if (lib->n) return fail("rph_library_restore", "the library is not empty");
         if (n > MAX_FILES) return fail("rph_library_restore", "at most 2^31 - 1 files");
         // the groups through the checks of rph_union_find_groups_append (no edges); what it lists has its smallest member first
@@ -602,8 +803,28 @@ int rph_library_merge_tree(rph_library *lib, uint32_t top, uint32_t *into, uint8
         std::fill(edges_at, edges_at + top + 1, 0);
         if (lib->n == 0) return RPH_OK;
         RPH_HIP_CHECK(hipSetDevice(lib->ctx->device));
+        if (lib->keeps_edges && top <= lib->top) return merge_tree_from_store(lib, top, into, level, edges_at);
         return merge_tree(lib, top, into, level, edges_at);
     });
+}
+
+// A store allocated or grown from now on starts at first_capacity_edges and doubles from there; 0 restores the default (exported for
+// the tests, not in the header)
+int rph_debug_library_edge_store(rph_library *lib, uint64_t first_capacity_edges)
+{
+    if (!lib) return fail("rph_debug_library_edge_store", "null argument");
+    std::lock_guard<std::mutex> lock(lib->mu);
+    lib->store_first_cap = first_capacity_edges;
+    return RPH_OK;
+}
+
+// What the edge store has done (exported for the tests, not in the header; rph_internal.h says what the five numbers are)
+int rph_debug_library_edge_stats(rph_library *lib, uint64_t *out)
+{
+    if (!lib || !out) return fail("rph_debug_library_edge_stats", "null argument");
+    std::lock_guard<std::mutex> lock(lib->mu);
+    for (int k = 0; k < 5; k++) out[k] = lib->edge_stats[k];
+    return RPH_OK;
 }
 
 // What the last rph_library_merge_tree did (exported for the tests, not in the header): out[0..1] = edges its sweep found, the first

@@ -232,6 +232,9 @@ int rph_merge_tree_run(rph_ctx *ctx, const rph_edge *d_edges, uint64_t n_edges, 
                        uint8_t *d_level, uint64_t *d_edges_at, uint32_t *d_labels, hipStream_t stream);
 // host_merge_tree.cpp: the tree of a host edge list whose edges have been checked (i, j < n, d <= top); edges_at is not touched
 void rph_host_merge_tree(const rph_edge *edges, uint64_t n_edges, uint64_t n, uint32_t top, uint32_t *into, uint8_t *level);
+// the one definition of rph_merge_tree_truncate's cut, on a tree that has been checked or is the core's own: level <= t stays, the rest
+// become roots; in place when the outputs are the inputs (library.cpp cuts the tree of its edge store with it)
+void rph_host_merge_tree_cut(const uint32_t *into, const uint8_t *level, uint64_t n, uint32_t t, uint32_t *into_out, uint8_t *level_out);
 // The grid of the grid-stride kernels of components.hip, merge_tree.hip and library_kernels.hip: blocks of 256 lanes, at most 8 per compute unit, the
 // loops stride over the rest.  rph_stride_lanes_per_pass is what one pass of such a loop covers (rph_debug_library_remove_stats).
 inline uint64_t rph_stride_lanes_per_pass(const rph_ctx *ctx) { return (uint64_t)(ctx->compute_units > 1 ? ctx->compute_units : 1) * 8 * 256; }
@@ -276,6 +279,24 @@ int rph_library_launch_split_edges(rph_ctx *ctx, rph_edge *d_edges, uint64_t n_e
 // new_labels[new(x)] for every kept x: itself if its component lost a file, else the new number of its (kept) root
 int rph_library_launch_labels(rph_ctx *ctx, const uint32_t *d_labels, const uint8_t *d_removed, const uint8_t *d_touched, const uint32_t *d_new_index, uint64_t n,
                               uint32_t *d_new_labels, hipStream_t stream);
+// library_edges.hip: the edge store of a library made by rph_library_create_tree, asynchronous on `stream`.  Both range-check every edge
+// before anything is indexed by it and write the lists in no particular order.
+// What an append's sweeps left in d_found -- n_cross edges (resident file, new-local file), then (new-local, new-local) ones with i < j,
+// over n resident and n_new new files -- rebased to the library's numbering: all n_found of them to d_store_end, the ones with
+// d <= similarity also to d_united.  d_nums (2 x u64, zeroed here): how many went to d_united; != 0 if an edge was out of range or had
+// d > top (it is written nowhere)
+int rph_library_launch_store_append(rph_ctx *ctx, const rph_edge *d_found, uint64_t n_found, uint64_t n_cross, uint32_t n, uint32_t n_new, uint32_t similarity,
+                                    uint32_t top, rph_edge *d_store_end, rph_edge *d_united, unsigned long long *d_nums, hipStream_t stream);
+// The store of n files without the edges of removed files, renumbered through d_new_index, into d_twin.  d_nums (4 x u64, zeroed here):
+// edges kept, edges dropped with d <= similarity, edges dropped, != 0 if an edge named a file >= n
+int rph_library_launch_store_filter(rph_ctx *ctx, const rph_edge *d_store, uint64_t n_store, uint64_t n, const uint8_t *d_removed, const uint32_t *d_new_index,
+                                    uint32_t similarity, rph_edge *d_twin, unsigned long long *d_nums, hipStream_t stream);
+// library.cpp: the edge store's debug hooks (exported for the tests and tools/library_tree_rate.py, not in the header).
+// rph_debug_library_edge_store: a store allocated or grown from now on starts at first_capacity_edges and doubles from there (0: the
+// default).  rph_debug_library_edge_stats, out[0..4]: growths of the store so far; edges the last append's sweeps found at `top`; how
+// many of them were united; edges the last removal dropped from the store; whether the last rph_library_merge_tree swept (0 or 1)
+extern "C" int rph_debug_library_edge_store(rph_library *lib, uint64_t first_capacity_edges);
+extern "C" int rph_debug_library_edge_stats(rph_library *lib, uint64_t *out);
 // group_info.hip: one rph_group_max_dist_dev request in device pointers (include/rupphash.h says what each array is)
 struct rph_group_dist {
     const uint8_t *hashes = nullptr, *rows = nullptr, *has_features = nullptr;

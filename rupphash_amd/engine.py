@@ -938,6 +938,15 @@ class Engine:
         return Engine._tree_call(lambda i, l, e: L.rph_merge_tree_host(_ptr(h), _ptr(c), _ptr(hf), _ptr(q), len(h), top, i, l, e), "rph_merge_tree_host", len(h), top)
 
     @staticmethod
+    def merge_tree_truncate(tree, t):
+        """rph_merge_tree_truncate: the MergeTree for t <= tree.top from `tree` (host, no device, no context); `tree` is not changed."""
+        L = _lib.load()
+        if t < 0:
+            raise ValueError(f"similarity {t} below 0")
+        return Engine._tree_call(lambda i, l, e: L.rph_merge_tree_truncate(_ptr(tree.into), _ptr(tree.level), _ptr(tree.edges_at), len(tree), tree.top, t, i, l, e),
+                                 "rph_merge_tree_truncate", len(tree), min(t, tree.top))
+
+    @staticmethod
     def _group_lists(groups, pivots):
         """(members, offsets, n_groups, pivots or None) as the rph_group_max_dist forms take them.  groups: a list of index lists, or the
         raw (members, offsets) arrays; pivots: one file number or None (RPH_NO_PIVOT) per group, or None for the default pivots."""
@@ -1059,9 +1068,9 @@ class Engine:
         """Bounds the partial lists of the nearest calls that follow, in bytes (tests); 0 restores 256 MiB, less than 8192 is 8192."""
         _lib.load().rph_debug_nearest_set_workspace(nbytes)
 
-    def library(self, similarity):
-        """A grouped library that stays on this engine's device (rph_library): see Library."""
-        return Library(self, similarity)
+    def library(self, similarity, top=None, max_edges=0):
+        """A grouped library that stays on this engine's device (rph_library): see Library.  With `top` it keeps its edges."""
+        return Library(self, similarity, top, max_edges)
 
     def mih_build256(self, hashes):
         hashes = np.ascontiguousarray(hashes, np.uint8).reshape(-1, 32)
@@ -1202,12 +1211,25 @@ class MergeTree:
 class Library:
     """rph_library: files appended so far stay on the device with their variants, flags and component labels.  groups() equals
     Engine.group_files_pdq on the files it holds, in order.  One similarity, at most 2^31 - 1 files; remove() renumbers the files that
-    stay.  Close it before its engine."""
+    stay.  Close it before its engine.
 
-    def __init__(self, engine, similarity):
-        self.engine, self.L, self.similarity = engine, engine.L, similarity
+    With `top` (similarity <= top <= 63) the library keeps its edges (rph_library_create_tree): every edge of the sweep at `top` among the
+    resident files stays on the device, at most max_edges of them (0: 2^28), so merge_tree(t) and groups_at(t) for t <= top run no sweep.
+    Everything else behaves as without `top`; appends sweep at `top` and cost accordingly.  edges() and restore_edges() persist it."""
+
+    def __init__(self, engine, similarity, top=None, max_edges=0):
+        if top is not None and not isinstance(top, (int, np.integer)):  # (an engine passed where open_library(similarity, engine) used to take it)
+            raise TypeError(f"top is a similarity (an int) or None, not {type(top).__name__}: pass the engine as engine=")
+        if top is not None and not similarity <= top <= 63:
+            raise ValueError(f"top {top} outside similarity .. 63 (similarity {similarity})")
+        if max_edges < 0:
+            raise ValueError("max_edges below 0")
+        self.engine, self.L, self.similarity, self.top = engine, engine.L, similarity, top
         h = C.c_void_p()
-        check(self.L.rph_library_create(engine.ctx, similarity, C.byref(h)), "rph_library_create")
+        if top is None:
+            check(self.L.rph_library_create(engine.ctx, similarity, C.byref(h)), "rph_library_create")
+        else:
+            check(self.L.rph_library_create_tree(engine.ctx, similarity, top, max_edges, C.byref(h)), "rph_library_create_tree")
         self.handle = h
 
     def close(self):
@@ -1300,8 +1322,35 @@ class Library:
                                                 "rph_library_group_max_dist", groups, pivots, want_member_dist)
 
     def merge_tree(self, top):
-        """The MergeTree of the resident files at `top`, whatever the library's own similarity is: one sweep, nothing resident changes."""
+        """The MergeTree of the resident files at `top`, whatever the library's own similarity is; nothing resident changes.  One sweep
+        -- none on a library that keeps its edges when `top` is at or below the library's."""
         return Engine._tree_call(lambda i, l, e: self.L.rph_library_merge_tree(self.handle, top, i, l, e), "rph_library_merge_tree", len(self), top)
+
+    def groups_at(self, s):
+        """What Engine.group_files_pdq(similarity=s) lists for the resident files: merge_tree(s) cut at s."""
+        return self.merge_tree(s).groups(s)
+
+    def edge_info(self):
+        """(top, n_edges, max_edges) of the edge store; top is None for a library that keeps no edges."""
+        top, n, cap = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        check(self.L.rph_library_edge_info(self.handle, C.byref(top), C.byref(n), C.byref(cap)), "rph_library_edge_info")
+        return None if top.value == _lib.RPH_NO_EDGE_STORE else top.value, n.value, cap.value
+
+    def edges(self):
+        """The store as a structured array (EDGE_DTYPE: i < j in the current numbering, d, flags), in no particular order."""
+        found = C.c_uint64()
+        rc = self.L.rph_library_edges(self.handle, None, 0, C.byref(found))
+        if rc != _lib.RPH_ERR_CAPACITY:
+            check(rc, "rph_library_edges")
+        out = np.zeros(found.value, EDGE_DTYPE)
+        check(self.L.rph_library_edges(self.handle, _ptr(out), len(out), C.byref(found)), "rph_library_edges")
+        return out
+
+    def restore_edges(self, hashes, edges, coeffs=None, has_features=None, quality=None):
+        """Start an empty edge-keeping library from files and the edges() of an earlier run with the same top: no sweep."""
+        h, c, hf, q = self._files(hashes, coeffs, has_features, quality)
+        e = np.ascontiguousarray(edges, EDGE_DTYPE).reshape(-1)
+        check(self.L.rph_library_restore_edges(self.handle, _ptr(h), _ptr(c), _ptr(hf), _ptr(q), len(h), _ptr(e), len(e)), "rph_library_restore_edges")
 
     def query(self, hashes, quality=None, cap=None):
         """Edges (library file i, query j, d, variant in flags) of the queries against the resident files; the library is not changed.
@@ -1329,6 +1378,7 @@ group_max_dist_host = Engine.group_max_dist_host  # needs no engine
 hamming_nearest_host = Engine.hamming_nearest_host
 merge_tree_host = Engine.merge_tree_host
 merge_tree_from_edges_host = Engine.merge_tree_from_edges_host
+merge_tree_truncate = Engine.merge_tree_truncate
 
 
 _default = None

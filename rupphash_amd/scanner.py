@@ -218,14 +218,21 @@ class ScannerLibrary(Library):
     def query(self, hashes, quality=None, cap=None):
         return super().query(hashes, _quality32(quality), cap)
 
+    def restore_edges(self, hashes, edges, coefficients=None, has_features=None, quality=None):
+        return super().restore_edges(hashes, edges, coefficients, has_features, _quality32(quality))
 
-def open_library(similarity, engine=None):
+
+def open_library(similarity, top=None, engine=None):
     """A grouped library that stays on the device between scans (ScannerLibrary): append(...) -> (labels, new_comparisons), restore(...),
     groups(), labels(), query(...).  groups() is group_with_pdqhash on the files the library holds, in order.
     remove(indices) -> (new_index, dropped) takes files out (deleted, or gone at the next scan) and renumbers the rest through new_index.
     nearest(hashes, k, max_dist=256) -> (edges[n_q, k], counts[n_q]) is the exact k-nearest search of query hashes among the resident
-    files, ordered by (distance, file); nearest_files(indices, k, max_dist=256) asks it for resident files, each skipping itself."""
-    return ScannerLibrary(engine or default_engine(), similarity)
+    files, ordered by (distance, file); nearest_files(indices, k, max_dist=256) asks it for resident files, each skipping itself.
+    With `top` (similarity <= top <= 63) the library keeps its edges on the device: groups_at(s) and merge_tree(s) for any s <= top then run
+    no sweep, and edges() / restore_edges(...) persist it in place of groups() / restore(...)."""
+    if top is not None and not isinstance(top, (int, np.integer)):  # open_library(similarity, engine) of before this argument existed
+        raise TypeError(f"top is a similarity (an int) or None, not {type(top).__name__}: pass the engine as engine=")
+    return ScannerLibrary(engine or default_engine(), similarity, top)
 
 
 def group_max_dist(groups, hashes, pivots, coefficients=None, has_features=None, engine=None):
